@@ -7,19 +7,21 @@ window: 50 KF / 5 000 inverse-depth landmarks / 30 000 EdgePRIDP + PRV + bias ed
 per GPU built from `--distinct` seeded windows whose sizes are drawn AROUND that configuration (40..60 keyframes, mean 50;
 `--uniform` = every window exactly 50 / 5 000 / 30 000).
 
-Three figures per run, all on the same batch:
+A plain run measures the headline figure only: it sets up, warms up, times `--steps` steps and prints the line.
   value             windows/s with the inputs already resident in HBM when the clock starts (vba_batch_upload before,
-                    K x vba_batch_run timed) -- the bench contract's `value`;
+                    K x vba_batch_run timed) -- the bench contract's `value`; `ms_per_step` = one timed step.
+`--full` adds, on the same batch, everything else the benchmark measures and checks:
+  verified          replicas agree bit for bit, the distinct windows match the CPU oracle;
   value_end_to_end  windows/s of FRESH windows: host arrays in, solved host arrays out (vba_batch_solve = H2D + structure
                     build + solve + D2H, chunks of the batch in flight concurrently) -- SURVEY 8(d) "copies included";
   single_window_ms  median latency of one vba_solve (upload + solve + download of ONE window, the way LocalMapping calls
-                    the reference) beside the 1-core CPU oracle on the same window.
+                    the reference) beside the 1-core CPU oracle on the same window;
+  roofline          dominant kernel class, HIP events on the backend's own stream, in a profiled run of its own;
+  cpu_baseline      the CPU oracle = restatement of the reference's g2o path, 1 core, bounded sample; PCG (c4 / gba).
+`--dump-outputs DIR` writes what the last timed step handed back to its caller as DIR/<name>.npy (dump_outputs below).
 Weak scaling: every rank solves its own batch, no data-path collective (windows are independent, SURVEY.md 8e);
 torch.distributed (RCCL) only carries the barrier and the max-over-ranks time.  `--gpus N` without torchrun starts the N
-ranks itself (mc_slam_amd/launch.py); under torchrun every process is a rank already.
-
-One JSON line on rank 0, with `roofline` (dominant kernel class, HIP events on the backend's own stream) and
-`cpu_baseline` (the CPU oracle = restatement of the reference's g2o path, 1 core, bounded sample).
+ranks itself (mc_slam_amd/launch.py); under torchrun every process is a rank already.  One JSON line on rank 0.
 """
 import argparse
 import hashlib
@@ -63,6 +65,37 @@ def make_windows(specs, n_proc):
         return pool.map(_gen_window, specs, chunksize=1)
 
 
+def dump_outputs(out_dir, items, cap=56 << 20):
+    """items: one {name: array} per window (or frame) of the batch, what the timed call handed back for it.  Writes
+    out_dir/<name>.npy, every name concatenated over a fixed sample of the items -- all of them when they fit in `cap` bytes,
+    else items drawn in a seeded random order while they fit, kept in batch order -- and out_dir/sample.npy, the indices of
+    the items written.  Flags are written as float32, everything else as float64."""
+    import numpy as np
+    conv = [{k: np.asarray(v, dtype=np.float32 if np.asarray(v).dtype in (np.uint8, np.bool_) else np.float64).ravel()
+             for k, v in it.items() if v is not None} for it in items]
+    pick, size = [], 0
+    for i in np.random.default_rng(0).permutation(len(conv)):
+        b = sum(a.nbytes for a in conv[i].values())
+        if size + b > cap:
+            break
+        pick.append(int(i))
+        size += b
+    pick.sort()
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "sample.npy"), np.array(pick, dtype=np.float64))
+    for k in conv[0]:
+        np.save(os.path.join(out_dir, k + ".npy"), np.concatenate([conv[i][k] for i in pick]))
+
+
+def finish(dist, rank, out):
+    """end of a run: the ranks leave together, rank 0 prints the line"""
+    if dist is not None:
+        dist.barrier()
+        dist.destroy_process_group()
+    if rank == 0:
+        print(json.dumps(out))
+
+
 def bench_pose(args, rank, local_rank, world, dist, torch):
     """Extra measurement: frames/s of vba_pose_optimize on a batch of tracked frames (300 correspondences, last
     keyframe and last-frame variants alternating), end to end per call (host gather + H2D + the one kernel + D2H); the CPU
@@ -88,8 +121,18 @@ def bench_pose(args, rank, local_rank, world, dist, torch):
         total += n_step
         dt += t_step
     res = [b.get(s_) for b, s_ in zip(packed[2], packed[1])]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, [{"nav": r.nav, "its_done": r.its_done, "status": r.status, "n_inliers": r.n_inliers,
+                                          "outlier": r.outlier, "outlier_last": r.outlier_last, "chi2_round": r.chi2_round,
+                                          "marg_cov_inv": r.marg_cov_inv} for r in res])
     out = None
     if rank == 0:
+        out = {"metric": "IMU-aided PoseOptimization frames/sec (300 correspondences) [extra measurement]", "value": total / dt, "unit": "frames/s",
+               "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
+               "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+               "config": {"workload": "Optimizer::PoseOptimization(Frame*, KeyFrame*|Frame*, IMUPreintegrator, gw, bComputeMarg): 4 x optimize(10) LM + "
+                                      "reclassification + marginals per frame", "frames_per_gpu_per_step": nb, "distinct_frames": len(distinct)}}
+    if rank == 0 and args.full:
         cpu, verified = None, "batch self-consistent"
         for i, r in enumerate(res):
             j = i % len(distinct)
@@ -106,17 +149,8 @@ def bench_pose(args, rank, local_rank, world, dist, torch):
             verified += "; %d distinct frames == oracle (LM iterations, outlier bitmap, P 1e-6 m)" % len(distinct)
             cpu = {"value": len(distinct) / tc, "unit": "frames/s", "cores": 1, "kind": "port",
                    "sample": "%d frames, single thread, oracle/libvba_oracle.so" % len(distinct)}
-        out = {"metric": "IMU-aided PoseOptimization frames/sec (300 correspondences) [extra measurement]", "value": total / dt, "unit": "frames/s",
-               "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
-               "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-               "config": {"workload": "Optimizer::PoseOptimization(Frame*, KeyFrame*|Frame*, IMUPreintegrator, gw, bComputeMarg): 4 x optimize(10) LM + "
-                                      "reclassification + marginals per frame", "frames_per_gpu_per_step": nb, "distinct_frames": len(distinct)},
-               "roofline": None, "cpu_baseline": cpu, "verified": verified}
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
-    if rank == 0:
-        print(json.dumps(out))
+        out.update({"roofline": None, "cpu_baseline": cpu, "verified": verified})
+    finish(dist, rank, out)
 
 
 def matches_oracle(np, sol, res, qo, ro):
@@ -151,6 +185,9 @@ def main():
     ap.add_argument("--e2e-steps", type=int, default=4, help="timed vba_batch_solve calls over fresh copies of the batch (0: skip)")
     ap.add_argument("--gen-procs", type=int, default=None, help="worker processes that generate the synthetic windows (default: up to 16; 1 under a profiler)")
     ap.add_argument("--single-reps", type=int, default=21, help="vba_solve repetitions behind single_window_ms (0: skip)")
+    ap.add_argument("--full", action="store_true", help="beyond the headline figure: the checks against replicas and the CPU oracle, end to end, "
+                    "single window, roofline, CPU baselines, PCG and tile products (the options above that select among them apply here only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one handed back as DIR/<name>.npy")
     args = ap.parse_args()
     if args.batch is None:
         args.batch = {"c2": 2048, "c3": 4096, "c4": 256, "gba": 4, "pose": 4096, "c3s": 4096, "c2s": 2048}[args.workload]
@@ -226,6 +263,58 @@ def main():
     total_windows, dt = meter.stop(args.batch * args.steps, device="cuda")
     value = total_windows / dt
 
+    sol = res = None
+    if args.full or args.dump_outputs:
+        sol, res = ba.download()   # what the last timed run handed back: states, erase list and per-edge chi2 of every window
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, [{"kf_pose": s_.kf_pose, "kf_vel": s_.kf_vel, "kf_bias": s_.kf_bias, "pt": s_.pt,
+                                          "status": r.status, "its_done": r.its_done, "chi2_vis": r.chi2_vis, "chi2_prv": r.chi2_prv,
+                                          "chi2_bias": r.chi2_bias, "n_outliers": r.n_outliers, "lambda_final": r.lambda_final,
+                                          "lin_iterations": r.lin_iterations, "chi2_trace": r.chi2_trace, "obs_outlier": r.obs_outlier,
+                                          "obs_chi2": r.obs_chi2} for s_, r in zip(sol, res)])
+    rng = lambda f: [int(min(f(w) for w in wins)), int(max(f(w) for w in wins))]
+    out = None
+    if rank == 0:
+        out = {
+            "metric": {"c3": "LocalBA windows/sec (50 KF, 5k pts, 30k obs, IMU edges)",
+                       "c3s": "LocalBA windows/sec, scattered co-visibility (50 free + 8 fixed KF, 5k pts, 30k obs, IMU edges) [extra measurement]",
+                       "c2s": "vision-only LocalBundleAdjustment windows/sec, scattered co-visibility (20 KF, 2k pts, 12k obs) [extra measurement]",
+                       "c2": "vision-only LocalBundleAdjustment windows/sec (20 KF, 2k pts, 12k obs) [extra measurement]",
+                       "c4": "synthetic VI graph solves/sec (200 KF, 50k pts, 500k obs) [extra measurement]",
+                       "gba": "global BA solves/sec (300 KF, 30k pts, 180k obs, IMU chain) [extra measurement]"}[args.workload],
+            "value": value, "unit": "windows/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            # `value` = kernel-only rate: inputs resident in HBM when the clock starts (the bench contract's definition);
+            # `value_end_to_end` (--full) = the same windows handed over as fresh host arrays, PCIe both ways included
+            "value_kernel_only": value,
+            "config": {"workload": {"c3": "BASELINE configs[2]: LocalBAPRVIDP windows, 50 KF (49 free + fixed predecessor) / 5000 IDP landmarks / "
+                                          "30000 EdgePRIDP + 49 PRV + 49 bias edges, GN 5+10" + ("" if args.uniform else
+                                          "; sizes drawn per seed around it: 40..60 KF (mean 50), 100 landmarks per KF, 6 edges per landmark"),
+                                    "c2": "BASELINE configs[1]: vision-only LocalBundleAdjustment, 20 KF (18 free) / 2000 XYZ landmarks / "
+                                          "12000 EdgeSE3ProjectXYZ, LM 5+10",
+                                    "c3s": "BASELINE configs[2] with scattered co-visibility: 50 free + 8 fixed co-observer KF / 5000 IDP landmarks / 30000 "
+                                           "EdgePRIDP whose tracks are random subsets of the keyframes in view (gaps), ~20 % of the landmarks with a fixed "
+                                           "reference keyframe, GN 5+10",
+                                    "c2s": "BASELINE configs[1] with scattered co-visibility (tracks = random subsets of the keyframes in view), LM 5+10",
+                                    "c4": "BASELINE configs[3]: synthetic VI graph, 200 KF / 50000 IDP landmarks / 500000 EdgePRIDP + IMU "
+                                          "chain, GN 5+10",
+                                    "gba": "GlobalBundleAdjustmentNavStatePRV, 300 KF / 30000 XYZ landmarks / 180000 EdgeNavStatePRPointXYZ "
+                                           "+ IMU chain, LM optimize(10)"}[args.workload],
+                       "landmark_order": (args.landmark_order + (" (grouped by first local keyframe, as src/Optimizer.cpp:59-78 builds lLocalMapPoints)" if args.landmark_order == "caller" else
+                                                                 " (uncorrelated with the keyframes)")) if args.workload in ("c3", "c3s", "c4", "c2", "c2s") else None,
+                       "windows_per_gpu_per_step": args.batch, "distinct_windows": len(wins),
+                       "n_kf_range": rng(lambda w: w.n_kf), "n_pt_range": rng(lambda w: w.n_pt), "n_obs_range": rng(lambda w: w.n_obs),
+                       "mean_n_kf": float(np.mean([w.n_kf for w in batch])), "mean_n_obs": float(np.mean([w.n_obs for w in batch])),
+                       "parallelism": "independent windows sharded %d per GPU, no data-path collective" % args.batch,
+                       "value_is": "kernel-only (windows resident in HBM, no PCIe in the timed region)" + ("; value_end_to_end includes H2D + D2H" if args.full else ""),
+                       "host_threads": int(ba.lib.vba_host_threads()), "cpu_affinity": {"cores": len(my_cpus), "first": my_cpus[0], "last": my_cpus[-1]},
+                       "iteration_mix": args.iteration_mix if args.workload == "c3" and not args.uniform else None},
+        }
+    if not args.full:
+        return finish(dist, rank, out)
+
     # the timed work must be the real work: every window of the last timed run finished both stages, windows built from the
     # same seed agree bit for bit, and (rank 0) EVERY distinct window matches the CPU oracle
     def check_twins(sol, res, what):
@@ -234,7 +323,6 @@ def main():
             if r.status != 0 or r.its_done[0] < 1 or (min(r.its_done) < 1 and batch[0].protocol == 0) or r.its_done != res[j].its_done \
                     or r.chi2_vis != res[j].chi2_vis or (sol[i].kf_pose != sol[j].kf_pose).any():
                 raise SystemExit("bench (%s): window %d did not solve like its twin %d: %s vs %s" % (what, i, j, (r.status, r.its_done), res[j].its_done))
-    sol, res = ba.download()
     check_twins(sol, res, "resident")
     verified = "every window finished both stages; replicas agree bit for bit"
     oracle_res, oracle_ms = None, None
@@ -295,7 +383,6 @@ def main():
                        "back come states, landmarks and the erase list" + (" and the per-edge chi2" if args.e2e_chi2 else " (the optional per-edge chi2 is not requested: --e2e-chi2)")}
         del packed, sol_e, res_e
 
-    out = None
     if rank == 0:
         # ---- (3) one window at a time, the way LocalMapping calls the reference (src/LocalMapping.cpp:1026-1037) ----
         single = None
@@ -519,57 +606,17 @@ def main():
                                  "two_sided_mean": float(tp[:, 4].mean()) if (tp[:, 4] >= 0).all() else None,
                                  "windows_in_keyframe_order": int((tp[:, 2] == 1).sum()), "windows_two_sided": int((tp[:, 2] == 2).sum()),
                                  "chosen_mean": float(tp[:, 3].mean())}
-        rng = lambda f: [int(min(f(w) for w in wins)), int(max(f(w) for w in wins))]
-        out = {
-            "metric": {"c3": "LocalBA windows/sec (50 KF, 5k pts, 30k obs, IMU edges)",
-                       "c3s": "LocalBA windows/sec, scattered co-visibility (50 free + 8 fixed KF, 5k pts, 30k obs, IMU edges) [extra measurement]",
-                       "c2s": "vision-only LocalBundleAdjustment windows/sec, scattered co-visibility (20 KF, 2k pts, 12k obs) [extra measurement]",
-                       "c2": "vision-only LocalBundleAdjustment windows/sec (20 KF, 2k pts, 12k obs) [extra measurement]",
-                       "c4": "synthetic VI graph solves/sec (200 KF, 50k pts, 500k obs) [extra measurement]",
-                       "gba": "global BA solves/sec (300 KF, 30k pts, 180k obs, IMU chain) [extra measurement]"}[args.workload],
-            "value": value, "unit": "windows/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            # `value` = kernel-only rate: inputs resident in HBM when the clock starts (the bench contract's definition);
-            # `value_end_to_end` = the same windows handed over as fresh host arrays, PCIe both ways included
-            "value_kernel_only": value,
-            "value_end_to_end": None if e2e is None else e2e["value"],
-            "single_window_ms": None if single is None else single["ms"],
-            "config": {"workload": {"c3": "BASELINE configs[2]: LocalBAPRVIDP windows, 50 KF (49 free + fixed predecessor) / 5000 IDP landmarks / "
-                                          "30000 EdgePRIDP + 49 PRV + 49 bias edges, GN 5+10" + ("" if args.uniform else
-                                          "; sizes drawn per seed around it: 40..60 KF (mean 50), 100 landmarks per KF, 6 edges per landmark"),
-                                    "c2": "BASELINE configs[1]: vision-only LocalBundleAdjustment, 20 KF (18 free) / 2000 XYZ landmarks / "
-                                          "12000 EdgeSE3ProjectXYZ, LM 5+10",
-                                    "c3s": "BASELINE configs[2] with scattered co-visibility: 50 free + 8 fixed co-observer KF / 5000 IDP landmarks / 30000 "
-                                           "EdgePRIDP whose tracks are random subsets of the keyframes in view (gaps), ~20 % of the landmarks with a fixed "
-                                           "reference keyframe, GN 5+10",
-                                    "c2s": "BASELINE configs[1] with scattered co-visibility (tracks = random subsets of the keyframes in view), LM 5+10",
-                                    "c4": "BASELINE configs[3]: synthetic VI graph, 200 KF / 50000 IDP landmarks / 500000 EdgePRIDP + IMU "
-                                          "chain, GN 5+10",
-                                    "gba": "GlobalBundleAdjustmentNavStatePRV, 300 KF / 30000 XYZ landmarks / 180000 EdgeNavStatePRPointXYZ "
-                                           "+ IMU chain, LM optimize(10)"}[args.workload],
-                       "landmark_order": (args.landmark_order + (" (grouped by first local keyframe, as src/Optimizer.cpp:59-78 builds lLocalMapPoints)" if args.landmark_order == "caller" else
-                                                                 " (uncorrelated with the keyframes)")) if args.workload in ("c3", "c3s", "c4", "c2", "c2s") else None,
-                       "windows_per_gpu_per_step": args.batch, "distinct_windows": len(wins),
-                       "n_kf_range": rng(lambda w: w.n_kf), "n_pt_range": rng(lambda w: w.n_pt), "n_obs_range": rng(lambda w: w.n_obs),
-                       "mean_n_kf": float(np.mean([w.n_kf for w in batch])), "mean_n_obs": float(np.mean([w.n_obs for w in batch])),
-                       "its_done_histogram": its_hist, "tile_products_per_factorisation": tile_products,
-                       "parallelism": "independent windows sharded %d per GPU, no data-path collective" % args.batch,
-                       "value_is": "kernel-only (windows resident in HBM, no PCIe in the timed region); value_end_to_end includes H2D + D2H",
-                       "host_threads": int(ba.lib.vba_host_threads()), "cpu_affinity": {"cores": len(my_cpus), "first": my_cpus[0], "last": my_cpus[-1]},
-                       "iteration_mix": args.iteration_mix if args.workload == "c3" and not args.uniform else None,
-                       "mean_outer_iterations": float(np.mean(its))},
+        out["value_end_to_end"] = None if e2e is None else e2e["value"]
+        out["single_window_ms"] = None if single is None else single["ms"]
+        out["config"].update({"its_done_histogram": its_hist, "tile_products_per_factorisation": tile_products,
+                              "mean_outer_iterations": float(np.mean(its))})
+        out.update({
             # work-normalised: outer (Gauss-Newton / LM) iterations of all windows per second -- comparable across iteration mixes
             "window_iterations_per_s": value * float(np.mean(its)),
             "end_to_end": e2e, "single_window": single, "pcg": pcg,
             "roofline": roofline, "cpu_baseline": cpu, "verified": verified,
-        }
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
-    if rank == 0:
-        print(json.dumps(out))
+        })
+    finish(dist, rank, out)
 
 
 if __name__ == "__main__":

@@ -5,7 +5,7 @@ set -e
 tag=$1; shift
 root=$(cd "$(dirname "$0")/.." && pwd); out=$root/gpurun_out/tcc_$tag
 mkdir -p $out; cd /tmp; export TMPDIR=/tmp VBA_STREAMS=1
-args="$root/bench.py --workload c3 --steps 1 --warmup 0 --no-cpu-baseline --e2e-steps 0 --single-reps 0 --gen-procs 1 --distinct 32"
+args="$root/bench.py --workload c3 --steps 1 --warmup 0 --no-cpu-baseline --e2e-steps 0 --single-reps 0 --gen-procs 1 --distinct 32 --full"
 i=0
 for grp in "TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_128B_sum" "TCC_READ_sum TCC_READ_SECTORS_sum TCC_HIT_sum TCC_MISS_sum" "TCC_EA0_RDREQ_DRAM_sum TCC_REQ_sum TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum" "TCP_TCC_READ_REQ_sum TCP_TOTAL_CACHE_ACCESSES_sum TCP_TOTAL_READ_sum TCP_TCC_WRITE_REQ_sum"; do
   i=$((i+1))

@@ -6,7 +6,7 @@ tag=$1; root=$(cd "$(dirname "$0")/.." && pwd); out=$root/gpurun_out/prof_$tag
 cd /tmp; export TMPDIR=/tmp
 # one window group / one stream: every launch then covers the whole batch, as in the profiled run bench.py takes its roofline from
 export VBA_STREAMS=1
-args="$root/bench.py --steps 2 --warmup 1 --no-cpu-baseline --e2e-steps 0 --single-reps 0 --gen-procs 1 --distinct 32"
+args="$root/bench.py --steps 2 --warmup 1 --no-cpu-baseline --e2e-steps 0 --single-reps 0 --gen-procs 1 --distinct 32 --full"
 echo "pass 1: kernel trace"
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 $args > $out.bench_trace.json 2>/dev/null
 echo "pass 2: FETCH_SIZE"
