@@ -125,6 +125,13 @@ struct PinVec {
     }
 };
 
+// an A/B switch from the environment: 1 if the variable is set, read once per process (one instance per switch I)
+template <int I>
+int env_once(const char* name) {
+    static const int v = getenv(name) ? 1 : 0;
+    return v;
+}
+
 // pinned staging of vba_batch_upload (the concatenated arrays of a batch) and vba_batch_download
 struct Staging {
     PinVec<double> pose, vel, bias, pt, uv, ow, meas, info;
@@ -223,6 +230,17 @@ struct Handle {
     long long n_launch = 0;   // kernel launches enqueued through this handle so far
     int opt_no_chain = 0;     // test hook: 1 = one launch per block column everywhere (vba_debug_set_chain)
     int opt_stop_after = -1;  // test hook: >= 0 -- every window reads the stop flag as 1 from that terminate() poll on (poll_stop)
+    // A/B paths, per handle: each defaults to its environment variable (read once per process); vba_debug_set_path overrides it
+    int schur_split = env_once<0>("VBA_SCHUR_SPLIT");  // 1: inverse-depth Schur diagonal and off-diagonal pairs in two launches
+    int trsv_old = env_once<1>("VBA_TRSV_OLD");        // 1: k_trsv also for the row-major factor of the few-window regime
+    int pcg_jacobi = env_once<2>("VBA_PCG_JACOBI");    // 1: block-Jacobi PCG preconditioner instead of the block-tridiagonal one
+#ifdef VBA_TEST_HOOKS
+    // vba_debug_capture: at the cap_call-th enqueue_solve_iteration of the next run, device copies of the stage products
+    int cap_call = -1, cap_count = 0, cap_done = 0;
+    int cap_path[4] = {-1, -1, -1, -1};   // kernels that iteration enqueued: Schur, factor, triangular solve (CAP_SCHUR_* ...)
+    DevBuf cap[16];
+    size_t cap_bytes[16] = {0};
+#endif
     std::vector<ProfEvt> evts;
     std::vector<hipEvent_t> evt_pool;
     size_t evt_used = 0;
@@ -845,7 +863,7 @@ int do_upload(Handle* h, int n, vba_problem* const* probs, bool defer_sync = fal
     B.item_begin = dp<int>(h, BUF_ITEMBEG); B.items = dp<int>(h, BUF_ITEMS); B.item_mid = dp<int>(h, BUF_ITEMMID);
     B.kf_dir = dp<double>(h, BUF_KFDIR); B.slot_lm = dp<int>(h, BUF_SLOTOBS); B.slot_o = dp<int>(h, BUF_SLOTO); B.rec_lm = dp<int>(h, BUF_PTINV);
     B.adj_begin = dp<int>(h, BUF_ADJBEG); B.adj = dp<int>(h, BUF_ADJ); B.pcg_v = dp<double>(h, BUF_PCGV); B.pcg_m = dp<double>(h, BUF_PCGM); B.pcg_s = dp<double>(h, BUF_PCGS);
-    { static const int jac = getenv("VBA_PCG_JACOBI") ? 1 : 0; B.pcg_tri = jac ? 0 : 1; }
+    B.pcg_tri = h->pcg_jacobi ? 0 : 1;
     B.lmask = dp<unsigned long long>(h, BUF_LMASK); B.kf_seg = dp<int>(h, BUF_KFSEG); B.ref_seg = dp<int>(h, BUF_REFSEG);
     B.pimu_begin = dp<int>(h, BUF_PIMUBEG); B.pimu = dp<int>(h, BUF_PIMU);
     B.lin_blk = dp<int>(h, BUF_LINBLK);
@@ -941,26 +959,70 @@ hipError_t wait_event_forwarding(Handle* h, hipEvent_t ev, StopRef stop_flag) {
         std::this_thread::yield();
     }
 }
+#ifdef VBA_TEST_HOOKS
+// vba_debug_capture: the captured items (per window: vba_debug_capture_get) and the kernel paths an iteration took
+enum { CAP_POSE_A, CAP_VEL_A, CAP_BIAS_A, CAP_PT_A, CAP_CTRL_A, CAP_LVL_A, CAP_VARACT_A, CAP_S_B, CAP_VEC_B, CAP_LF_C, CAP_YV_C,
+       CAP_VEC_C, CAP_POSE_D, CAP_VEL_D, CAP_BIAS_D, CAP_PT_D, CAP_N };
+// the device buffer and the batch-wide byte count of every captured item
+void cap_source(Handle* h, int what, int& buf, size_t& bytes) {
+    static const int ids[CAP_N] = {BUF_POSE, BUF_VEL, BUF_BIAS, BUF_PT, BUF_CTRL, BUF_LVL, BUF_VARACT, BUF_S, BUF_VEC, BUF_LF, BUF_YV,
+                                   BUF_VEC, BUF_POSE, BUF_VEL, BUF_BIAS, BUF_PT};
+    const WinDesc& e = h->desc.back();
+    const size_t kf = (size_t)e.kf0 + e.n_kf, pt = (size_t)e.pt0 + e.n_pt, vec = (size_t)e.vec0 + e.nS;
+    const size_t sz[CAP_N] = {56 * kf, 24 * kf, 96 * kf, 24 * pt, sizeof(WinCtrl) * h->desc.size(), (size_t)e.obs0 + e.n_obs, 4 * vec,
+                              8 * ((size_t)e.S0 + (size_t)e.nS * e.nS), 8 * vec, 8 * ((size_t)e.S0 + (size_t)e.nS * e.nS), 8 * vec, 8 * vec,
+                              56 * kf, 24 * kf, 96 * kf, 24 * pt};
+    buf = ids[what];
+    bytes = sz[what];
+}
+// enqueue the device-to-device copies of items [first, last) on the run stream (the batch runs as one group: checked in do_run)
+void cap_copy(Handle* h, int first, int last) {
+    if (h->cap_call < 0 || h->cap_count != h->cap_call) return;
+    for (int q = first; q < last; q++) {
+        int id;
+        size_t bytes;
+        cap_source(h, q, id, bytes);
+        if (bytes > h->cap[q].cap) continue;   // (do_run sized every capture buffer)
+        (void)hipMemcpyAsync(h->cap[q].p, h->buf[id].ptr(), bytes, hipMemcpyDeviceToDevice, h->stream);
+        h->cap_bytes[q] = bytes;
+    }
+}
+#define CAP_COPY(h, a, b) cap_copy(h, a, b)
+#define CAP_PATH(h, i, v) do { if ((h)->cap_call >= 0 && (h)->cap_count == (h)->cap_call) (h)->cap_path[i] = (v); } while (0)
+#else
+#define CAP_COPY(h, a, b) do { } while (0)
+#define CAP_PATH(h, i, v) do { } while (0)
+#endif
+// kernel paths reported by the capture hook (vba_debug_window_layout)
+enum { CAP_SCHUR_ALL_W, CAP_SCHUR_ALL, CAP_SCHUR_SPLIT_W, CAP_SCHUR_SPLIT, CAP_SCHUR3_W, CAP_SCHUR3 };
+enum { CAP_FACTOR_STEP1 = 1, CAP_FACTOR_STEP4 = 4, CAP_FACTOR_STEP4_ONE = 5, CAP_FACTOR_LL = 6, CAP_FACTOR_PCG = 7, CAP_FACTOR_MIXED = 8 };
+enum { CAP_TRSV_P, CAP_TRSV };
+
 void enqueue_solve_iteration(Handle* h, StopRef stop_flag = StopRef()) {
     const Batch& B = h->B;
     const int n = h->n_win;         // windows of this group: grid sizes
     const int rn = h->regime_n;     // windows of the batch: kernel choice
     const bool idp = h->variant == VBA_VARIANT_PRV_IDP;
     const int ngrp = (n >= 8) ? 8 * ((n + 7) / 8) : n;   // grids whose workgroups schur_map() deals to the XCDs by window
+    CAP_COPY(h, CAP_POSE_A, CAP_VARACT_A + 1);
     {
         ProfScope ps(h, VBA_PROF_SCHUR);
         if (idp) {
-            static const int fused_schur = getenv("VBA_SCHUR_SPLIT") ? 0 : 1;
+            const int fused_schur = h->schur_split ? 0 : 1;
             if (rn >= 8 && fused_schur) {
+                CAP_PATH(h, 0, CAP_SCHUR_ALL);
                 VBA_LAUNCH(k_schur_all, dim3((h->max_free + h->max_quads) * ngrp), dim3(64), 0, h->stream, B, h->max_free, h->max_quads);
             } else if (fused_schur) {
+                CAP_PATH(h, 0, CAP_SCHUR_ALL_W);
                 VBA_LAUNCH(k_schur_all_w, dim3((h->max_free + h->max_offp) * ngrp), dim3(64), 0, h->stream, B, h->max_free, h->max_offp);
             } else {
+            CAP_PATH(h, 0, rn >= 8 ? CAP_SCHUR_SPLIT : CAP_SCHUR_SPLIT_W);
             VBA_LAUNCH(k_schur_diag, dim3(h->max_free * ngrp), dim3(64), 0, h->stream, B, h->max_free);
             if (rn >= 8) VBA_LAUNCH(k_schur_off, dim3(h->max_quads * ngrp), dim3(64), 0, h->stream, B, h->max_quads);
             else VBA_LAUNCH(k_schur_off_w, dim3(h->max_offp * ngrp), dim3(64), 0, h->stream, B, h->max_offp);
             }
         } else {
+            CAP_PATH(h, 0, rn >= 8 ? CAP_SCHUR3 : CAP_SCHUR3_W);
             VBA_LAUNCH(k_dinv, dim3(h->max_pt_blk, n), dim3(64), 0, h->stream, B);
             // (diagonal and off-diagonal pairs in two launches: fusing them as for the inverse-depth records gained nothing at C2)
             VBA_LAUNCH(k_schur_diag3, dim3(h->max_free * ngrp), dim3(64), 0, h->stream, B, h->max_free, 0);
@@ -968,6 +1030,7 @@ void enqueue_solve_iteration(Handle* h, StopRef stop_flag = StopRef()) {
             else VBA_LAUNCH(k_schur_off3_w, dim3(h->max_offp * ngrp), dim3(64), 0, h->stream, B, h->max_offp);
         }
     }
+    CAP_COPY(h, CAP_S_B, CAP_VEC_B + 1);
     if (h->solver == VBA_SOLVER_PCG) {
         // Two launches per CG iteration for all windows of the group; the host enqueues BATCHES of iterations and reads one pinned
         // word per batch (did any window go on?) two batches behind the device.  Converged windows exit at the first instruction.
@@ -994,6 +1057,8 @@ void enqueue_solve_iteration(Handle* h, StopRef stop_flag = StopRef()) {
             (void)hipEventRecord(ev.back(), h->stream);
         }
         VBA_LAUNCH(k_pcg_finish, dim3(n), dim3(256), 0, h->stream, B);
+        CAP_PATH(h, 1, CAP_FACTOR_PCG);
+        CAP_COPY(h, CAP_VEC_C, CAP_VEC_C + 1);
     } else {
     {
         ProfScope ps(h, VBA_PROF_FACTOR);
@@ -1016,6 +1081,7 @@ void enqueue_solve_iteration(Handle* h, StopRef stop_flag = StopRef()) {
             }
         }
         if (h->ll_mode) {
+            CAP_PATH(h, 1, CAP_FACTOR_LL);
             for (int k = k_first; k < h->max_nb; k++) {  // every tile read once, updated in registers, written once
                 VBA_LAUNCH(k_chol_diag_ll2, dim3(n), dim3(64), 0, h->stream, B, k);
                 if (h->pan_grid[k] > 0) VBA_LAUNCH(k_chol_panel_ll, dim3(h->pan_grid[k] * ngrp), dim3(64), 0, h->stream, B, k, h->pan_grid[k]);
@@ -1026,6 +1092,11 @@ void enqueue_solve_iteration(Handle* h, StopRef stop_flag = StopRef()) {
             static const int env_form = getenv("VBA_CHOL_STEP") ? atoi(getenv("VBA_CHOL_STEP")) : 0;
             const int step_form = h->opt_chol_step > 0 ? h->opt_chol_step : (env_form > 0 ? env_form : 4);
             for (int k = k_first; k < h->max_nb; k++) {
+                // (the capture reports the step kernel of the columns; columns that took different ones: CAP_FACTOR_MIXED)
+                const int form = step_form == 1 ? CAP_FACTOR_STEP1
+                               : (h->n_win == 1 && n == 1 && (int)h->one_sb.size() > k + 1) ? CAP_FACTOR_STEP4_ONE : CAP_FACTOR_STEP4;
+                CAP_PATH(h, 1, (k == k_first || h->cap_path[1] == form) ? form : CAP_FACTOR_MIXED);
+                (void)form;
                 if (step_form == 1) VBA_LAUNCH(k_chol_step, dim3(h->step_grid[k], n), dim3(64), 0, h->stream, B, k);
                 else if (h->n_win == 1 && n == 1 && (int)h->one_sb.size() > k + 1) {   // one window: descriptor and step table ride in the kernel arguments
                     const WinDesc& d0 = h->desc[0];
@@ -1039,21 +1110,27 @@ void enqueue_solve_iteration(Handle* h, StopRef stop_flag = StopRef()) {
     }
     {
         ProfScope ps(h, VBA_PROF_TRSV);
-        static const int trsv_old = getenv("VBA_TRSV_OLD") ? 1 : 0;
-        if (h->ll_mode || trsv_old) {
+        if (h->ll_mode || h->trsv_old) {
+            CAP_PATH(h, 2, CAP_TRSV);
             const size_t shm = ((size_t)h->max_nS + 256 + 32 * 33) * sizeof(double);
             VBA_LAUNCH(k_trsv, dim3(n), dim3(256), shm, h->stream, B);
         } else {   // row-major factor: a solving wave + seven waves that work one column ahead
+            CAP_PATH(h, 2, CAP_TRSV_P);
             const size_t shm = ((size_t)h->max_nS + 2 * TRSV_P_DW * 32 + 2 * 32 * 65 + 32) * sizeof(double) + ((size_t)h->max_pan + h->max_nb + 2) * sizeof(int);
             VBA_LAUNCH(k_trsv_p, dim3(n), dim3(512), shm, h->stream, B);
         }
     }
+    CAP_COPY(h, CAP_LF_C, CAP_VEC_C + 1);
     }
     {
         ProfScope ps(h, VBA_PROF_UPDATE);
         if (idp) VBA_LAUNCH(k_update, dim3(h->max_pt_blk + h->max_kf_blk, n), dim3(64), 0, h->stream, B, h->max_pt_blk);
         else VBA_LAUNCH(k_update_xyz, dim3(h->max_pt_blk + h->max_kf_blk, n), dim3(64), 0, h->stream, B, h->max_pt_blk);
     }
+    CAP_COPY(h, CAP_POSE_D, CAP_N);
+#ifdef VBA_TEST_HOOKS
+    if (h->cap_call >= 0 && h->cap_count++ == h->cap_call) h->cap_done = 1;
+#endif
 }
 
 void enqueue_lin(Handle* h, int mode) {
@@ -1310,6 +1387,7 @@ int do_run(Handle* h, StopRef stop_flag) {
     if (!h->uploaded) return fail(h, "vba_batch_run before vba_batch_upload");
     HIPCHK(h, hipSetDevice(h->device));
     h->B.dbg_stop_after = h->opt_stop_after;
+    h->B.pcg_tri = h->pcg_jacobi ? 0 : 1;
     const Batch B = h->B;
     const int n = h->n_win;
     *h->stop_host = stop_flag.set() ? 1 : 0;
@@ -1344,6 +1422,21 @@ int do_run(Handle* h, StopRef stop_flag) {
         HIPCHK(h, hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
         h->xstreams.push_back(st);
     }
+#ifdef VBA_TEST_HOOKS
+    h->cap_count = 0;
+    h->cap_done = 0;
+    for (int i = 0; i < 4; i++) h->cap_path[i] = -1;
+    for (int q = 0; q < CAP_N; q++) h->cap_bytes[q] = 0;
+    if (h->cap_call >= 0) {
+        if (ngroups > 1) { h->cap_call = -1; return fail(h, "vba_debug_capture: the batch runs as more than one window group (vba_debug_set_streams(h, 1))"); }
+        for (int q = 0; q < CAP_N; q++) {
+            int id;
+            size_t bytes;
+            cap_source(h, q, id, bytes);
+            HIPCHK(h, h->cap[q].ensure(bytes));
+        }
+    }
+#endif
     std::vector<Group> groups(ngroups);
     std::vector<hipEvent_t> done(ngroups);
     for (int g = 0; g < ngroups; g++) {
@@ -1434,6 +1527,9 @@ int do_run(Handle* h, StopRef stop_flag) {
         }
     }
     h->ran = true;
+#ifdef VBA_TEST_HOOKS
+    h->cap_call = -1;   // one capture per request
+#endif
     if (timing) fprintf(stderr, "[vba] %p t=%.1f run %d windows: %.3f ms\n", (void*)h, now_ms(), n, now_ms() - t_run0);
     return 0;
 }
@@ -1613,6 +1709,9 @@ int vba_destroy(void* handle) {
     h->up_arena.release();
     h->up_arena_host.release();
     for (auto& b : h->buf) b.release();
+#ifdef VBA_TEST_HOOKS
+    for (auto& b : h->cap) b.release();
+#endif
     h->preint.release();
     h->pose_arena.release();
     h->pose_host_in.release();
@@ -1747,6 +1846,9 @@ int batch_solve(void* handle, int32_t n, vba_problem* const* inout, vba_result* 
         l->opt_ll_min = h->opt_ll_min;
         l->opt_no_chain = h->opt_no_chain;
         l->opt_stop_after = h->opt_stop_after;
+        l->schur_split = h->schur_split;
+        l->trsv_old = h->trsv_old;
+        l->pcg_jacobi = h->pcg_jacobi;
         h->lanes.push_back(l);
     }
     const int n_chunks2 = (int)cbeg.size() - 1;
@@ -1907,6 +2009,120 @@ int vba_debug_set_chain(void* handle, int32_t on) {
     if (!h) return -1;
     h->opt_no_chain = on ? 0 : 1;
     for (Handle* l : h->lanes) l->opt_no_chain = h->opt_no_chain;
+    return 0;
+}
+
+// the A/B paths read from the environment, per handle: "schur_split", "trsv_old", "pcg_jacobi" (value 0 / 1)
+int vba_debug_set_path(void* handle, const char* name, int32_t value) {
+    Handle* h = reinterpret_cast<Handle*>(handle);
+    if (!h || !name) return -1;
+    int Handle::*f = !strcmp(name, "schur_split") ? &Handle::schur_split : !strcmp(name, "trsv_old") ? &Handle::trsv_old
+                   : !strcmp(name, "pcg_jacobi") ? &Handle::pcg_jacobi : nullptr;
+    if (!f) return -1;
+    h->*f = value ? 1 : 0;
+    for (Handle* l : h->lanes) l->*f = h->*f;
+    return 0;
+}
+
+// During the next vba_batch_run: at its call-th enqueue_solve_iteration (0-based, both stages), copy (a) the state and the control
+// blocks before the Schur launches, (b) S and the reduced rhs after them, (c) the factor, y and x_c after the triangular solves,
+// (d) the state after the update.  Refused (at the run) when the batch runs as more than one window group.
+int vba_debug_capture(void* handle, int32_t call) {
+    Handle* h = reinterpret_cast<Handle*>(handle);
+    if (!h || call < 0) return -1;
+    if (!h->uploaded || h->desc.empty()) return fail(h, "vba_debug_capture before vba_batch_upload");
+    h->cap_call = call;
+    h->cap_done = 0;
+    return 0;
+}
+// window w's slice of captured item `what` (CAP_*), nbytes exactly its size
+int vba_debug_capture_get(void* handle, int32_t what, int32_t w, void* dst, uint64_t nbytes) {
+    Handle* h = reinterpret_cast<Handle*>(handle);
+    if (!h || !dst || what < 0 || what >= CAP_N || w < 0 || w >= (int)h->desc.size() || !h->cap_done) return -1;
+    if (h->solver == VBA_SOLVER_PCG && (what == CAP_LF_C || what == CAP_YV_C)) return fail(h, "vba_debug_capture_get: PCG has no factor");
+    const WinDesc& d = h->desc[w];
+    size_t off = 0, len = 0;
+    switch (what) {
+        case CAP_POSE_A: case CAP_POSE_D: off = 56 * (size_t)d.kf0; len = 56 * (size_t)d.n_kf; break;
+        case CAP_VEL_A: case CAP_VEL_D: off = 24 * (size_t)d.kf0; len = 24 * (size_t)d.n_kf; break;
+        case CAP_BIAS_A: case CAP_BIAS_D: off = 96 * (size_t)d.kf0; len = 96 * (size_t)d.n_kf; break;
+        case CAP_PT_A: case CAP_PT_D: off = 24 * (size_t)d.pt0; len = 24 * (size_t)d.n_pt; break;
+        case CAP_CTRL_A: off = sizeof(WinCtrl) * (size_t)w; len = sizeof(WinCtrl); break;
+        case CAP_LVL_A: off = (size_t)d.obs0; len = (size_t)d.n_obs; break;
+        case CAP_VARACT_A: off = 4 * (size_t)d.vec0; len = 4 * (size_t)d.nS; break;
+        case CAP_S_B: case CAP_LF_C: off = 8 * (size_t)d.S0; len = 8 * (size_t)d.nS * d.nS; break;
+        default: off = 8 * (size_t)d.vec0; len = 8 * (size_t)d.nS; break;   // VEC_B, YV_C, VEC_C
+    }
+    if (nbytes != len || off + len > h->cap_bytes[what] || off + len > h->cap[what].cap) return -1;
+    (void)hipSetDevice(h->device);
+    return hipMemcpy(dst, reinterpret_cast<char*>(h->cap[what].p) + off, len, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
+}
+// Window w's layout of the reduced system, n_out int64 entries:
+//   [0] nS [1] nb [2] pdim [3] n_free [4] order [5] nc [6] nc_split [7] l_packed [8] regime_n [9] n_win
+//   [10..12] kernel paths of the captured iteration (Schur, factor, triangular solve: CAP_SCHUR_*, CAP_FACTOR_*, CAP_TRSV*)
+//   [13] sizeof(WinCtrl) [14] solver is PCG [15] pcg_tri
+//   [16..19] byte offsets in WinCtrl of stage, active, robust_vis (int) and lambda (double)
+//   [20, 20 + pdim n_free) row of S of dof r of free keyframe a at 20 + pdim a + r (vpos), then pad0[3], padn[3]
+int vba_debug_window_layout(void* handle, int32_t w, int64_t* out, int64_t n_out) {
+    Handle* h = reinterpret_cast<Handle*>(handle);
+    if (!h || !out || w < 0 || w >= (int)h->desc.size()) return -1;
+    const WinDesc& d = h->desc[w];
+    if (n_out < 20 + (int64_t)d.pdim * d.n_free + 6) return -1;
+    out[0] = d.nS; out[1] = d.nb; out[2] = d.pdim; out[3] = d.n_free; out[4] = d.order; out[5] = d.nc; out[6] = d.nc_split;
+    out[7] = h->B.l_packed; out[8] = h->regime_n; out[9] = h->n_win;
+    for (int i = 0; i < 3; i++) out[10 + i] = h->cap_path[i];
+    out[13] = sizeof(WinCtrl);
+    out[14] = h->solver == VBA_SOLVER_PCG; out[15] = h->B.pcg_tri;
+    out[16] = offsetof(WinCtrl, stage); out[17] = offsetof(WinCtrl, active); out[18] = offsetof(WinCtrl, robust_vis);
+    out[19] = offsetof(WinCtrl, lambda);
+    int64_t* vp = out + 20;
+    for (int a = 0; a < d.n_free; a++)
+        for (int r = 0; r < d.pdim; r++) {
+            const int v = r < 6 ? d.vp_pr0 + d.vp_prs * a + r : (a < d.vp_h ? d.vp_vb0 + d.vp_vbs * a : d.vp_vb1 - 9 * a) + (r - 6);   // vpos
+            vp[d.pdim * a + r] = v;
+        }
+    for (int q = 0; q < 3; q++) { vp[d.pdim * d.n_free + q] = d.pad0[q]; vp[d.pdim * d.n_free + 3 + q] = d.padn[q]; }
+    return 0;
+}
+// From the captured factor of window w: L (unit lower) with D on its diagonal, dense nS x nS row-major, exactly the tiles the
+// triangular solves read (the diagonal tiles and the panel tiles of every block column); zeros elsewhere and above the diagonal
+int vba_debug_factor_dense(void* handle, int32_t w, double* out, int64_t n_out) {
+    Handle* h = reinterpret_cast<Handle*>(handle);
+    if (!h || !out || w < 0 || w >= (int)h->desc.size() || !h->cap_done || h->solver == VBA_SOLVER_PCG) return -1;
+    const WinDesc& d = h->desc[w];
+    const size_t n = d.nS;
+    if (n_out != (int64_t)(n * n) || d.nb * VBA_NB != d.nS) return -1;
+    std::vector<double> lf(n * n);
+    std::vector<int> pb(d.nb + 1);
+    if (vba_debug_capture_get(handle, CAP_LF_C, w, lf.data(), n * n * 8)) return -1;
+    (void)hipSetDevice(h->device);
+    auto avail = [&](int id) { const DevBuf& b = h->buf[id]; return b.view ? b.view_bytes : b.cap; };
+    if (((size_t)d.tl_step0 + d.nb + 1) * 4 > avail(BUF_TLPANB)) return -1;
+    if (hipMemcpy(pb.data(), dp<int>(h, BUF_TLPANB) + d.tl_step0, (d.nb + 1) * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    for (int k = 0; k < d.nb; k++)
+        if (pb[k] < 0 || pb[k + 1] < pb[k]) return -1;
+    std::vector<int> pan(std::max(1, pb[d.nb]));
+    if (((size_t)d.tl_pan0 + pb[d.nb]) * 4 > avail(BUF_TLPAN)) return -1;
+    if (pb[d.nb] > 0 && hipMemcpy(pan.data(), dp<int>(h, BUF_TLPAN) + d.tl_pan0, (size_t)pb[d.nb] * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    std::fill(out, out + n * n, 0.0);
+    const bool pk = h->B.l_packed;
+    auto tile = [&](int I, int J) {
+        for (int r = 0; r < VBA_NB; r++)
+            for (int c = 0; c < VBA_NB; c++) {
+                const size_t gr = (size_t)I * VBA_NB + r, gc = (size_t)J * VBA_NB + c;
+                if (gc > gr) continue;
+                const int pr = (((((r >> 4) * 4 + (c >> 3)) * 64) + ((c & 3) * 16 + (r & 15))) * 2) + ((c >> 2) & 1);   // ll_pk
+                out[gr * n + gc] = pk ? lf[1024 * ((size_t)I * d.nb + J) + pr] : lf[gr * n + gc];
+            }
+    };
+    for (int k = 0; k < d.nb; k++) {
+        tile(k, k);
+        for (int i = pb[k]; i < pb[k + 1]; i++) {
+            const int I = pan[i];
+            if (I <= k || I >= d.nb) return -1;
+            tile(I, k);
+        }
+    }
     return 0;
 }
 #endif  // VBA_TEST_HOOKS

@@ -1,0 +1,281 @@
+"""Stage-level reference of one solve iteration: the Schur-reduced camera system, its solution and the state update, formed from the
+oracle's dense H and b in extended precision, with error bounds computed from the data.  TEST INFRASTRUCTURE ONLY.
+
+Rows follow the oracle's order (free keyframe a, local dof r at pdim a + r); `to_window` maps a matrix or vector into the row order of
+one window of the HIP backend (the layout that vba_debug_window_layout reports: vpos rows, identity pads).
+
+Bounds (eps = 2^-53, c a small constant):
+  S, r   |dS_ij| <= c eps (k + kappa) sqrt(h_i h_j): every edge term and every landmark's Schur term is PSD, so each term is at most
+         sqrt(t_ii t_jj) in entry ij and the terms of one entry add up to at most sqrt(h_i h_j); k terms at most per entry, kappa the
+         worst condition number of a landmark block.  r likewise with sqrt(h_i chi2) (Cauchy-Schwarz on J^T W e) plus |W| |Hpp^-1| |b_l|.
+  factor |L D L^T - S| <= c nS eps |L| |D| |L^T|                   (componentwise backward error of LDL^T)
+  solve  |r - L y| <= c nS eps |L| |y|,  |y - D L^T x| <= c nS eps (|D| |L^T| |x| + |y|)
+  x_c    |Ds (x - x_ref)|_2 <= (|E|_F |Ds x|_2 + |f|_2) / lambda_min(S^)   with S^ = Ds^-1 S Ds^-1 and E, f the scaled bounds above
+"""
+import numpy as np
+
+import oracle_lib
+from mc_slam_amd import abi
+
+EPS = np.finfo(np.float64).eps / 2
+LD = np.longdouble
+
+
+def dims(p):
+    pdim = 6 if p.variant == abi.VARIANT_SE3_XYZ else 15
+    ldim = 1 if p.variant == abi.VARIANT_PRV_IDP else 3
+    return pdim, ldim
+
+
+def active_sets(p, lvl):
+    """the oracle's index mapping (init_active): var_act per pose dof of H, pt_act per landmark"""
+    pdim, _ = dims(p)
+    nf = p.n_kf_free
+    fix = np.zeros(p.n_kf, np.uint8) if p.kf_fix is None else np.asarray(p.kf_fix, np.uint8)
+    var_act = np.zeros(pdim * nf, bool)
+    pt_act = np.zeros(p.n_pt, bool)
+
+    def col(kf, part):
+        if kf >= nf or (fix[kf] >> part) & 1:
+            return -1
+        return kf * pdim + (0, 6, 9)[part]
+
+    beg = np.asarray(p.pt_obs_begin)
+    for pi in range(p.n_pt):
+        for o in range(beg[pi], beg[pi + 1]):
+            if lvl[o]:
+                continue
+            pt_act[pi] = True
+            for kf in ([p.obs_kf[o], p.pt_ref_kf[pi]] if p.variant == abi.VARIANT_PRV_IDP else [p.obs_kf[o]]):
+                c = col(int(kf), 0)
+                if c >= 0:
+                    var_act[c:c + 6] = True
+    if p.variant != abi.VARIANT_SE3_XYZ:
+        for k in range(p.n_imu):
+            i, j = int(p.imu_kf_i[k]), int(p.imu_kf_j[k])
+            prv = max(col(i, 0), col(j, 0), col(i, 1), col(j, 1), col(i, 2)) >= 0
+            bias = max(col(i, 2), col(j, 2)) >= 0
+            for part, dim in ((0, 6), (1, 3), (2, 6)):
+                ci, cj = col(i, part), col(j, part)
+                if ci >= 0 and (prv or (part == 2 and bias)):
+                    var_act[ci:ci + dim] = True
+                if cj >= 0 and ((part < 2 and prv) or (part == 2 and bias)):
+                    var_act[cj:cj + dim] = True
+    return var_act, pt_act
+
+
+def _inv3(A):
+    """3x3 inverses by the adjugate, vectorised over the leading axis (any float dtype)"""
+    c = np.empty_like(A)
+    c[:, 0, 0] = A[:, 1, 1] * A[:, 2, 2] - A[:, 1, 2] * A[:, 2, 1]
+    c[:, 0, 1] = A[:, 0, 2] * A[:, 2, 1] - A[:, 0, 1] * A[:, 2, 2]
+    c[:, 0, 2] = A[:, 0, 1] * A[:, 1, 2] - A[:, 0, 2] * A[:, 1, 1]
+    c[:, 1, 0] = A[:, 1, 2] * A[:, 2, 0] - A[:, 1, 0] * A[:, 2, 2]
+    c[:, 1, 1] = A[:, 0, 0] * A[:, 2, 2] - A[:, 0, 2] * A[:, 2, 0]
+    c[:, 1, 2] = A[:, 0, 2] * A[:, 1, 0] - A[:, 0, 0] * A[:, 1, 2]
+    c[:, 2, 0] = A[:, 1, 0] * A[:, 2, 1] - A[:, 1, 1] * A[:, 2, 0]
+    c[:, 2, 1] = A[:, 0, 1] * A[:, 2, 0] - A[:, 0, 0] * A[:, 2, 1]
+    c[:, 2, 2] = A[:, 0, 0] * A[:, 1, 1] - A[:, 0, 1] * A[:, 1, 0]
+    det = A[:, 0, 0] * c[:, 0, 0] + A[:, 0, 1] * c[:, 1, 0] + A[:, 0, 2] * c[:, 2, 0]
+    return c / det[:, None, None]
+
+
+def lambda_init(H, var_act, pt_act, np_, ldim):
+    """computeLambdaInit (tau = 1e-5) over the active pose and landmark diagonals"""
+    d = np.abs(np.diag(H))
+    lm = d[np_:].reshape(-1, ldim)[pt_act]
+    return 1e-5 * max(d[:np_][var_act].max(initial=0.0), lm.max(initial=0.0))
+
+
+def linearize(p, robust_vis=True, lvl=None):
+    """the oracle's dense H, b and robust chi2 at p's state, with the stage's settings"""
+    lv = np.zeros(p.n_obs, np.uint8) if lvl is None else np.asarray(lvl, np.uint8)
+    H, b, chi2 = oracle_lib.linearize_ex(p, robust_vis, lv)
+    return H, b, chi2, lv
+
+
+def reduced(p, H, b, chi2, lvl, lam=0.0, dtype=LD):
+    """S = H_cc - H_cp H_pp^-1 H_pc and r = b_c - H_cp H_pp^-1 b_p in `dtype`, identity rows for dofs outside the index mapping,
+    landmarks without an active edge dropped, lam on the active diagonals (LM).  Returns a dict with the bound ingredients."""
+    pdim, L = dims(p)
+    np_ = pdim * p.n_kf_free
+    var_act, pt_act = active_sets(p, lvl)
+    bd = b.astype(dtype)
+    Hcc = H[:np_, :np_].astype(dtype)
+    Hcc[np.arange(np_)[var_act], np.arange(np_)[var_act]] += dtype(lam)
+    W = H[:np_, np_:].reshape(np_, p.n_pt, L)[:, pt_act, :].astype(dtype)
+    bl = bd[np_:].reshape(p.n_pt, L)[pt_act]
+    blk = np.stack([H[np_ + L * q: np_ + L * q + L, np_ + L * q: np_ + L * q + L] for q in np.flatnonzero(pt_act)]).astype(dtype) \
+        if pt_act.any() else np.zeros((0, L, L), dtype)
+    blk = blk + dtype(lam) * np.eye(L, dtype=dtype)
+    if L == 1:
+        Dinv = 1 / blk
+        kappa = 1.0
+    else:
+        Dinv = _inv3(blk)
+        kappa = float(np.linalg.cond(blk.astype(np.float64)).max(initial=1.0))
+    WD = np.einsum("cpa,pab->cpb", W, Dinv)
+    S = Hcc - WD.reshape(np_, -1) @ W.reshape(np_, -1).T
+    S = (S + S.T) / 2   # (exact: both triangles are the same sums in the same order up to the transposition)
+    r = bd[:np_] - np.einsum("cpb,pb->c", WD, bl)
+    out = ~var_act
+    S[out, :] = 0
+    S[:, out] = 0
+    S[np.flatnonzero(out), np.flatnonzero(out)] = 1
+    r[out] = 0
+    h = np.where(var_act, np.diag(Hcc).astype(np.float64), 1.0)
+    # terms per entry: per free keyframe, its active edges and landmarks (an IDP edge touches two keyframes) and IMU factors
+    deg = np.zeros(p.n_kf, np.int64)
+    beg = np.asarray(p.pt_obs_begin)
+    act_o = np.asarray(lvl) == 0
+    np.add.at(deg, np.asarray(p.obs_kf)[act_o], 2)
+    if p.variant == abi.VARIANT_PRV_IDP:
+        pid = np.repeat(np.arange(p.n_pt), np.diff(beg))
+        np.add.at(deg, np.asarray(p.pt_ref_kf)[pid[act_o]], 2)
+    if p.variant != abi.VARIANT_SE3_XYZ and p.n_imu:
+        np.add.at(deg, np.asarray(p.imu_kf_i), 2)
+        np.add.at(deg, np.asarray(p.imu_kf_j), 2)
+    k = int(deg.max()) + 2
+    aW = np.abs(W.astype(np.float64))
+    rabs = np.sqrt(h * max(chi2, 0.0)) + np.einsum("cpa,pab,pb->c", aW, np.abs(Dinv.astype(np.float64)), np.abs(bl.astype(np.float64)))
+    return dict(S=S, r=r, H=H, b=b, var_act=var_act, pt_act=pt_act, lam=lam, k=k, kappa=kappa, h=h, rabs=rabs,
+                Dinv=Dinv, W=W, bl=bl, np=np_, pdim=pdim, ldim=L)
+
+
+def tol_S(red, c=8.0):
+    h = red["h"]
+    return c * EPS * (red["k"] + red["kappa"]) * np.sqrt(np.outer(h, h))
+
+
+def tol_r(red, c=8.0):
+    return c * EPS * (red["k"] + red["kappa"]) * red["rabs"]
+
+
+def solve_c(red):
+    """keyframe part of the step: float64 solve of the reduced system, one refinement step with the residual in extended precision"""
+    S, r = red["S"], red["r"]
+    S64 = S.astype(np.float64)
+    x = np.linalg.solve(S64, r.astype(np.float64))
+    res = r - S @ x.astype(LD)
+    return x + np.linalg.solve(S64, res.astype(np.float64))
+
+
+def landmark_step(red, xc, dtype=LD):
+    """landmark back-substitution dl_p = Hpp_p^-1 (b_p - W_p^T x_c) for the active landmarks (in their order)"""
+    x = np.asarray(xc).astype(dtype)
+    W, Dinv, bl = red["W"].astype(dtype), red["Dinv"].astype(dtype), red["bl"].astype(dtype)
+    cl = bl - np.einsum("cpa,c->pa", W, x)
+    return np.einsum("pab,pb->pa", Dinv, cl)
+
+
+def landmark_step_tol(red, xc, c=8.0):
+    """bound of the float64 back-substitution: c eps (k + kappa) |Dinv| (|b_l| + |W|^T |x_c|)"""
+    aW, aD = np.abs(red["W"].astype(np.float64)), np.abs(red["Dinv"].astype(np.float64))
+    t = np.abs(red["bl"].astype(np.float64)) + np.einsum("cpa,c->pa", aW, np.abs(np.asarray(xc, np.float64)))
+    return c * EPS * (red["k"] + red["kappa"]) * np.einsum("pab,pb->pa", aD, t)
+
+
+def full_step(red, xc=None):
+    """the whole Delta x in the oracle's order (pose dofs, then L per landmark; zero for dropped landmarks)"""
+    if xc is None:
+        xc = solve_c(red)
+    dl = np.zeros((red["pt_act"].size, red["ldim"]))
+    dl[red["pt_act"]] = landmark_step(red, xc).astype(np.float64)
+    return np.concatenate([np.asarray(xc, np.float64), dl.reshape(-1)])
+
+
+def apply_step(p, state, dx, var_act, pt_act):
+    """state (pose, vel, bias, pt) + dx the way the oracle's apply_update does it"""
+    pose, vel, bias, pt = (a.copy() for a in state)
+    pdim, L = dims(p)
+    np_ = pdim * p.n_kf_free
+    for a in range(p.n_kf_free):
+        c = a * pdim
+        if p.variant == abi.VARIANT_SE3_XYZ:
+            if var_act[c]:
+                pose[a] = oracle_lib.oplus_se3(pose[a], dx[c:c + 6])
+            continue
+        if var_act[c]:
+            pose[a] = oracle_lib.oplus_pr(pose[a], dx[c:c + 6])
+        if var_act[c + 6]:
+            vel[a] += dx[c + 6:c + 9]
+        if var_act[c + 9]:
+            bias[a, 6:12] += dx[c + 9:c + 15]
+    dl = dx[np_:].reshape(-1, L)
+    for q in np.flatnonzero(pt_act):
+        if L == 1:
+            pt[q, 0] = max(pt[q, 0] + dl[q, 0], 1e-6)
+        else:
+            pt[q] += dl[q]
+    return pose, vel, bias, pt
+
+
+# ---- the row order of a window of the HIP backend ----------------------------------------------------------------------------
+def window_rows(layout):
+    """(rows of S for the oracle's dof order, pad rows)"""
+    nS, pdim, nf = layout["nS"], layout["pdim"], layout["n_free"]
+    rows = np.asarray(layout["vpos"], np.int64)
+    assert rows.size == pdim * nf and len(set(rows.tolist())) == rows.size and rows.max() < nS
+    pads = np.setdiff1d(np.arange(nS), rows)
+    want = np.concatenate([np.arange(a, a + n) for a, n in zip(layout["pad0"], layout["padn"]) if n > 0]) if any(layout["padn"]) \
+        else np.zeros(0, np.int64)
+    assert np.array_equal(np.sort(want), pads), ("pad ranges", want, pads)
+    return rows, pads
+
+
+def to_window(x, layout, pad_value=1.0):
+    """a matrix (nS x nS, identity on the pads) or a vector (zero on the pads) in the window's row order"""
+    rows, pads = window_rows(layout)
+    nS = layout["nS"]
+    if x.ndim == 1:
+        v = np.zeros(nS, x.dtype)
+        v[rows] = x
+        return v
+    M = np.zeros((nS, nS), x.dtype)
+    M[np.ix_(rows, rows)] = x
+    M[pads, pads] = pad_value
+    return M
+
+
+def from_window(v, layout):
+    rows, _ = window_rows(layout)
+    return np.asarray(v)[rows]
+
+
+def ratio(err, tol):
+    """worst |err| / tol over the entries (0 / 0 counts as 0, anything / 0 as inf)"""
+    err, tol = np.abs(np.asarray(err, np.float64)), np.asarray(tol, np.float64)
+    if err.size == 0:
+        return 0.0
+    q = np.divide(err, tol, out=np.where(err == 0, 0.0, np.inf), where=tol > 0)
+    return float(q.max())
+
+
+def solve_tols(L, d, y, x, c=8.0):
+    """bounds of the two triangular solves: |r - L y| and |y - D L^T x|"""
+    n = len(d)
+    return c * n * EPS * (np.abs(L) @ np.abs(y)), c * n * EPS * (np.abs(d) * (np.abs(L.T) @ np.abs(x)) + np.abs(y))
+
+
+# ---- bounds of the factor and the solves -------------------------------------------------------------------------------------
+def factor_parts(F):
+    """dense L D on the diagonal -> (unit lower L, d)"""
+    d = np.diag(F).copy()
+    L = np.tril(F, -1) + np.eye(F.shape[0])
+    return L, d
+
+
+def ldlt_tol(L, d, c=8.0):
+    n = L.shape[0]
+    aL = np.abs(L)
+    return c * n * EPS * (aL * np.abs(d)) @ aL.T
+
+
+def xc_bound(S_ref, E, f, x):
+    """|Ds (x - x_ref)|_2 bound for x solving (S_ref + dS) x = r + dr with |dS| <= E, |dr| <= f (componentwise)"""
+    ds = np.sqrt(np.abs(np.diag(S_ref)))
+    Sh = S_ref / np.outer(ds, ds)
+    lmin = np.linalg.eigvalsh(Sh).min()
+    Eh = E / np.outer(ds, ds)
+    fh = f / ds
+    return (np.linalg.norm(Eh) * np.linalg.norm(ds * x) + np.linalg.norm(fh)) / lmin, ds, lmin
