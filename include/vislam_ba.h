@@ -162,6 +162,34 @@ int vba_batch_run_b(void *handle, const volatile unsigned char *stop_flag);
 int vba_batch_solve_b(void *handle, int32_t n_windows, vba_problem *const *inout, vba_result *const *out,
                       const volatile unsigned char *stop_flag);
 
+/* Asynchronous form of vba_batch_solve, for a caller that produces one batch after another: batch k+1 is packed, copied and
+ * structured while batch k solves.
+ *   submit  returns at once with a ticket (strictly increasing per handle, from 1); it neither blocks nor reads the windows, and
+ *           tickets queue without bound.  The two pointer arrays are copied at submit; the vba_problem / vba_result structs, every
+ *           array they point to and the stop flag must stay valid and unmodified until vba_batch_wait of the ticket returns (or
+ *           vba_batch_poll returns 0).  The results land in the caller's arrays, as with vba_batch_solve.
+ *   order   batches are uploaded one at a time in ticket order and solved one at a time in ticket order, each as ONE run (never
+ *           chunked); a download may overlap the next solve.  At most `depth` batches hold device buffers at once; a batch whose
+ *           arena is not free yet waits inside the library.
+ *   results for any state of the stop flag, bit for bit what vba_batch_solve / _b gives for the same batch and flag (with no flag
+ *           set: what vba_batch_upload + run + download of the batch gives).
+ *   errors  wait returns 0 or -1; on -1 vba_last_error reads "vba_batch_submit, ticket T, windows 0..n-1: <message>".  A window
+ *           rejected by the upload fails that ticket only.  A HIP error (launch, copy, synchronisation) fails that ticket and
+ *           every later one, those submitted afterwards included, with the same message: no GPU work starts for them (earlier
+ *           tickets finish).  Waiting on an unknown or retired ticket returns -1.
+ *   handle  while any ticket is submitted and not yet waited for, every synchronous entry point of the handle (vba_solve*,
+ *           vba_batch_upload / run / download / solve*, vba_pose_optimize, vba_preintegrate, vba_set_profile,
+ *           vba_batch_set_depth) returns -1 with "asynchronous batches pending: wait for them first"; afterwards the handle
+ *           works synchronously as before.  vba_destroy finishes pending tickets (their results land) before it frees.
+ *           Profiling (vba_set_profile) covers synchronous calls only.  One caller thread at a time, as everywhere. */
+int vba_batch_set_depth(void *handle, int32_t depth);   /* batches resident on the device at once: 1..4, default 2 */
+int vba_batch_submit(void *handle, int32_t n_windows, vba_problem *const *inout, vba_result *const *out,
+                     const volatile int *stop_flag, int64_t *ticket);
+int vba_batch_submit_b(void *handle, int32_t n_windows, vba_problem *const *inout, vba_result *const *out,
+                       const volatile unsigned char *stop_flag, int64_t *ticket);
+int vba_batch_poll(void *handle, int64_t ticket);       /* 1 pending, 0 finished (wait will not block), -1 unknown ticket */
+int vba_batch_wait(void *handle, int64_t ticket);       /* the batch's return code; retires the ticket */
+
 /* On-device IMU preintegration: IMUPreintegrator::update (src/IMU/IMUPreintegrator.cpp:63-112) applied
  * over the samples of n_edges keyframe intervals, the way KeyFrame::ComputePreInt feeds it (src/KeyFrame.cpp:195-252:
  * the caller lists the samples and their dt, including the duplicated first sample).  gyr/acc are bias-corrected

@@ -17,7 +17,8 @@ _lib = None
 _libs = {}
 
 EXPORTS = ["vba_create", "vba_destroy", "vba_last_error", "vba_solve", "vba_batch_upload", "vba_batch_run",
-           "vba_batch_download", "vba_batch_solve", "vba_solve_b", "vba_batch_run_b", "vba_batch_solve_b", "vba_preintegrate", "vba_pose_optimize", "vba_problem_save", "vba_problem_load", "vba_problem_free", "vba_set_profile", "vba_get_profile", "vba_host_threads"]
+           "vba_batch_download", "vba_batch_solve", "vba_solve_b", "vba_batch_run_b", "vba_batch_solve_b", "vba_preintegrate", "vba_pose_optimize", "vba_problem_save", "vba_problem_load", "vba_problem_free", "vba_set_profile", "vba_get_profile", "vba_host_threads",
+           "vba_batch_set_depth", "vba_batch_submit", "vba_batch_submit_b", "vba_batch_poll", "vba_batch_wait"]
 
 
 def load_library(hooks=False):
@@ -49,6 +50,13 @@ def load_library(hooks=False):
     lib.vba_pose_optimize.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.POINTER(abi.vba_frame_problem)), C.POINTER(C.POINTER(abi.vba_frame_result))]
     lib.vba_set_profile.argtypes = [C.c_void_p, C.c_int32]
     lib.vba_get_profile.argtypes = [C.c_void_p, C.POINTER(abi.vba_profile)]
+    lib.vba_batch_set_depth.argtypes = [C.c_void_p, C.c_int32]
+    lib.vba_batch_submit.argtypes = [C.c_void_p, C.c_int32, PP, PR, C.c_void_p, C.POINTER(C.c_int64)]
+    lib.vba_batch_submit_b.argtypes = [C.c_void_p, C.c_int32, PP, PR, C.c_void_p, C.POINTER(C.c_int64)]
+    lib.vba_batch_poll.argtypes = [C.c_void_p, C.c_int64]
+    lib.vba_batch_wait.argtypes = [C.c_void_p, C.c_int64]
+    if hooks:
+        lib.vba_debug_async_hold.argtypes = [C.c_void_p, C.c_int32]
     for n in EXPORTS:
         if n != "vba_last_error":
             getattr(lib, n).restype = C.c_int
@@ -70,11 +78,15 @@ class LocalBA:
             raise RuntimeError("vba_create(device=%d) failed (rc=%d): no usable HIP device -- the backend has no CPU path"
                                % (device, rc))
         self._keep = None
+        self._tickets = {}   # ticket -> (packed copies, stop flag): what the library reads until the ticket is retired
 
     def close(self):
         if self.h:
+            for t in sorted(getattr(self, "_tickets", {})):   # pending batches finish first: their results land in the packed copies
+                self.lib.vba_batch_wait(self.h, t)
             self.lib.vba_destroy(self.h)
             self.h = C.c_void_p()
+            self._tickets = {}
 
     def __del__(self):
         try:
@@ -151,6 +163,45 @@ class LocalBA:
         packed = self.pack(probs)
         self.solve_packed(packed, stop)
         return self.pack_results(packed)
+
+    # ---- asynchronous batches (vba_batch_submit / poll / wait): batch k+1 is handed over while batch k solves ----
+    def submit_packed(self, packed, stop=None):
+        """vba_batch_submit of a pack(): returns the ticket.  The packed copies and the stop flag stay referenced by this object
+        until the ticket is retired (wait); stop: a one-byte ctypes flag (c_uint8, c_bool) goes through vba_batch_submit_b."""
+        t = C.c_int64(0)
+        fn = self.lib.vba_batch_submit_b if stop is not None and C.sizeof(stop) == 1 else self.lib.vba_batch_submit
+        if fn(self.h, packed["n"], packed["parr"], packed["rarr"], self._stop_ptr(stop), C.byref(t)) != 0:
+            raise self._err("vba_batch_submit")
+        self._tickets[t.value] = (packed, stop)
+        return t.value
+
+    def submit(self, probs, stop=None, want_chi2=True):
+        """vba_batch_submit on private copies of probs (pack): returns the ticket; wait(ticket) hands the solved copies back"""
+        return self.submit_packed(self.pack(probs, want_chi2), stop)
+
+    def poll(self, ticket):
+        """True once the ticket has finished (wait will not block), False while it is pending"""
+        rc = self.lib.vba_batch_poll(self.h, ticket)
+        if rc < 0:
+            raise self._err("vba_batch_poll")
+        return rc == 0
+
+    def wait_packed(self, ticket):
+        """vba_batch_wait: retires the ticket and returns its pack() (results in place); RuntimeError if the batch failed"""
+        rc = self.lib.vba_batch_wait(self.h, ticket)
+        packed = self._tickets.pop(ticket, (None, None))[0]
+        if rc != 0:
+            raise self._err("vba_batch_wait")
+        return packed
+
+    def wait(self, ticket):
+        """vba_batch_wait: (solved copies, Results) of the ticket"""
+        return self.pack_results(self.wait_packed(ticket))
+
+    def set_depth(self, n):
+        """vba_batch_set_depth: batches resident on the device at once (1..4)"""
+        if self.lib.vba_batch_set_depth(self.h, n) != 0:
+            raise self._err("vba_batch_set_depth")
 
     def preintegrate(self, sample_begin, gyr, acc, dt, want_info=True):
         """vba_preintegrate: (imu_meas [E,61], cov_PVphi [E,9,9], info_PphiV [E,9,9] or None)"""

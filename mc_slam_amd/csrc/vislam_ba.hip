@@ -27,6 +27,8 @@
 #include <atomic>
 #include <memory>
 #include <condition_variable>
+#include <deque>
+#include <map>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -171,6 +173,30 @@ struct ProfEvt {
     hipEvent_t a, b;
 };
 
+// Host threads that the stages of asynchronous batches (vba_batch_submit) share: the packing of one ticket may run while another
+// ticket's results are scattered.  A pool takes what is free when it starts (at least one thread: it waits for it) and gives it
+// back when it ends, so the stages together never use more than vba_host_threads().
+struct HostBudget {
+    std::mutex mu;
+    std::condition_variable cv;
+    int free = 0;
+    int take(int want) {
+        std::unique_lock<std::mutex> lk(mu);
+        cv.wait(lk, [&] { return free > 0; });
+        const int t = std::max(1, std::min(want, free));
+        free -= t;
+        return t;
+    }
+    void give(int t) {
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            free += t;
+        }
+        cv.notify_all();
+    }
+};
+struct AsyncState;   // the tickets, arenas and workers of vba_batch_submit (defined with it)
+
 struct Handle {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -194,6 +220,10 @@ struct Handle {
     Staging stg;   // pinned staging: upload arrays; download: one D2H per array, windows scattered to the callers' arrays by host threads
     std::vector<Handle*> lanes;   // sub-handles of vba_batch_solve (chunks of a large batch in flight concurrently)
     bool is_lane = false;
+    AsyncState* as = nullptr;     // vba_batch_submit: created at the first submit (its arenas are lanes too, kept apart from `lanes`)
+    int async_depth = 2;          // vba_batch_set_depth: batches resident on the device at once
+    HostBudget* budget = nullptr; // an arena of vba_batch_submit: its packing and scatter pools draw threads from the parent's budget
+    bool hip_failed = false;      // a HIP call of this handle failed (HIPCHK): tells a device error from a rejected window
     Batch B;
     std::vector<WinDesc> desc;
     PinVec<WinCtrl> hctrl;    // the control blocks after a run (pinned: the copy rides on the run's stream)
@@ -255,6 +285,7 @@ struct Handle {
         hipError_t _e = (call);                                                                   \
         if (_e != hipSuccess) {                                                                   \
             (h)->err = std::string(#call) + ": " + hipGetErrorString(_e);                         \
+            (h)->hip_failed = true;                                                               \
             return -1;                                                                            \
         }                                                                                         \
     } while (0)
@@ -490,10 +521,12 @@ int do_upload(Handle* h, int n, vba_problem* const* probs, bool defer_sync = fal
         auto work = [&]() {
             for (int q = next.fetch_add(1); q < cn; q = next.fetch_add(1)) job(q);
         };
+        const int nt = h->budget ? h->budget->take(std::min(n_threads, cn)) : std::min(n_threads, cn);
         std::vector<std::thread> pool;
-        for (int t = 1; t < std::min(n_threads, cn); t++) pool.emplace_back(work);
+        for (int t = 1; t < nt; t++) pool.emplace_back(work);
         work();
         for (auto& t : pool) t.join();
+        if (h->budget) h->budget->give(nt);
     };
     // The bulk of a window (observations, landmarks, masks: 1 MB of the 1.06 MB of a C3 window) crosses PCIe WHILE the host works on the
     // next windows: after every packing pass the freshly packed tail of these arrays is copied (their final sizes are known from
@@ -1617,16 +1650,23 @@ int do_download(Handle* h, int n, vba_problem* const* inout, vba_result* const* 
         }
     };
     {
-        const int nt = staged ? std::max(1, std::min(host_threads(), n / 8)) : 1;
+        int nt = staged ? std::max(1, std::min(host_threads(), n / 8)) : 1;
+        if (h->budget) nt = h->budget->take(nt);
         std::vector<std::thread> pool;
         for (int t = 1; t < nt; t++) pool.emplace_back(work);
         work();
         for (auto& t : pool) t.join();
+        if (h->budget) h->budget->give(nt);
     }
     if (bad.load()) return fail(h, "hipMemcpy (download) failed");
     if (timing) fprintf(stderr, "[vba] %p t=%.1f download %d windows: %.3f ms\n", (void*)h, now_ms(), n, now_ms() - t_dl0);
     return 0;
 }
+
+// vba_batch_submit (defined with it, below): the synchronous entry points refuse while a ticket is submitted and not retired
+int async_busy(Handle* h);
+// vba_destroy: the pending tickets finish (their results land in the callers' arrays), the workers are joined, the arenas freed
+void async_shutdown(Handle* h);
 
 }  // namespace
 
@@ -1697,6 +1737,7 @@ int vba_create(int device, void** handle) {
 int vba_destroy(void* handle) {
     Handle* h = reinterpret_cast<Handle*>(handle);
     if (!h) return -1;
+    if (h->as) async_shutdown(h);
     for (Handle* l : h->lanes) (void)vba_destroy(l);
     h->lanes.clear();
     (void)hipSetDevice(h->device);
@@ -1733,22 +1774,22 @@ const char* vba_last_error(void* handle) {
 
 int vba_batch_upload(void* handle, int32_t n, vba_problem* const* problems) {
     Handle* h = reinterpret_cast<Handle*>(handle);
-    if (!h) return -1;
+    if (!h || async_busy(h)) return -1;
     return do_upload(h, n, problems);
 }
 int vba_batch_run(void* handle, const volatile int* stop_flag) {
     Handle* h = reinterpret_cast<Handle*>(handle);
-    if (!h) return -1;
+    if (!h || async_busy(h)) return -1;
     return do_run(h, stop_int(stop_flag));
 }
 int vba_batch_run_b(void* handle, const volatile unsigned char* stop_flag) {
     Handle* h = reinterpret_cast<Handle*>(handle);
-    if (!h) return -1;
+    if (!h || async_busy(h)) return -1;
     return do_run(h, stop_byte(stop_flag));
 }
 int vba_batch_download(void* handle, int32_t n, vba_problem* const* inout, vba_result* const* out) {
     Handle* h = reinterpret_cast<Handle*>(handle);
-    if (!h) return -1;
+    if (!h || async_busy(h)) return -1;
     return do_download(h, n, inout, out);
 }
 
@@ -1757,6 +1798,7 @@ namespace {
 int solve_one(void* handle, vba_problem* inout, vba_result* out, StopRef stop_flag) {
     Handle* h = reinterpret_cast<Handle*>(handle);
     if (!h || !inout || !out) return -1;
+    if (async_busy(h)) return -1;
     if (stop_flag.set()) {  // src/Optimizer.cpp:453-455: return before anything is built
         out->status = VBA_ABORTED_BEFORE;
         out->its_done[0] = out->its_done[1] = 0;
@@ -1793,7 +1835,7 @@ int vba_batch_solve_b(void* handle, int32_t n, vba_problem* const* inout, vba_re
 namespace {
 int batch_solve(void* handle, int32_t n, vba_problem* const* inout, vba_result* const* out, StopRef stop_flag) {
     Handle* h = reinterpret_cast<Handle*>(handle);
-    if (!h) return -1;
+    if (!h || async_busy(h)) return -1;
     if (n <= 0 || !inout) return fail(h, "vba_batch_solve: bad arguments");
     // measured on MI355X, 4096 fresh C3 windows (scripts/e2e_sweep.py, resident 12.1-13.0k windows/s): chunk x lanes 512x4 7.8k windows/s,
     // 768x3 8.1k, 1024x2 9.05k, 1024x3 8.97k, 1365x2 9.3-9.4k, 1536x2 9.4k, 1700x2 9.6k, 2048x2 (no ramp) 7.7k -- one lane solves while
@@ -1924,9 +1966,220 @@ int batch_solve(void* handle, int32_t n, vba_problem* const* inout, vba_result* 
     for (auto& t : pool) t.join();
     return bad.load() ? -1 : 0;
 }
+
+// ---- asynchronous batches: vba_batch_submit / vba_batch_poll / vba_batch_wait -------------------------------------------------
+// A caller with one batch after another hands over batch k+1 while batch k solves.  Every ticket is ONE upload + run + download
+// on an arena -- a lane (make_handle) that owns its device buffers and pinned staging and shares the parent's four streams -- so
+// it gets bit for bit what vba_batch_upload + run + download of that batch gives (the kernel choice depends on the number of
+// windows in a run: thresholds 8 / 64 / 256; a chunked run would change it).  One persistent worker per arena, `depth` of them,
+// started at the first submit, takes the next ticket; uploads, runs and downloads each go one at a time in ticket order (the
+// turns of batch_solve), so the packing, H2D copies and structure build of ticket k+1 and the D2H copies and scatter of ticket
+// k-1 overlap the solve of ticket k.  A worker writes its arena's `err` and its ticket only; the parent's `err` is written on
+// the caller's thread (submit / poll / wait).
+struct AsyncTicket {
+    int64_t id = 0;
+    std::vector<vba_problem*> inout;   // the caller's pointer arrays, copied at submit
+    std::vector<vba_result*> out;      // empty: out == NULL
+    StopRef stop;
+    bool done = false;                 // rc, err, done: written by the worker under AsyncState::mu
+    int rc = 0;
+    std::string err;                   // the arena's message of the stage that failed
+    double t[6] = {0, 0, 0, 0, 0, 0};  // upload, run, download: start and end, ms from the first submit (VBA_TIMING)
+};
+struct AsyncState {
+    std::mutex mu;
+    std::condition_variable cv;        // every change of the fields below: notify_all
+    std::map<int64_t, std::shared_ptr<AsyncTicket>> tickets;   // submitted, not retired (caller's thread only)
+    std::deque<std::shared_ptr<AsyncTicket>> queue;            // submitted, not taken by a worker yet
+    int64_t next_id = 1;
+    int64_t up_turn = 1, run_turn = 1, dl_turn = 1;            // the ticket whose upload / run / download may start
+    bool hold = false;                 // vba_debug_async_hold: no upload starts
+    bool quit = false;                 // workers leave once the queue is empty
+    int64_t dead_at = 0;               // > 0: the ticket whose HIP error fails every later ticket with dead_msg
+    std::string dead_msg;
+    std::vector<Handle*> arenas;       // arenas[i] is worked by workers[i]
+    std::vector<std::thread> workers;
+    HostBudget budget;                 // vba_host_threads(), shared by the packing and scatter pools of the arenas
+    double t0 = 0;                     // first submit (timeline)
+};
+
+AsyncState& async_state(Handle* h) {
+    if (!h->as) {
+        h->as = new AsyncState();
+        h->as->t0 = now_ms();
+        h->as->budget.free = host_threads();
+    }
+    return *h->as;
+}
+
+void async_worker(Handle* h, Handle* arena) {
+    static const bool timing = getenv("VBA_TIMING") != nullptr;
+    AsyncState& A = *h->as;
+    (void)hipSetDevice(h->device);
+    for (;;) {
+        std::shared_ptr<AsyncTicket> t;
+        {
+            std::unique_lock<std::mutex> lk(A.mu);
+            A.cv.wait(lk, [&] { return A.quit || !A.queue.empty(); });
+            if (A.queue.empty()) return;
+            t = A.queue.front();
+            A.queue.pop_front();
+        }
+        const int64_t k = t->id;
+        const int n = (int)t->inout.size();
+        vba_problem* const* P = t->inout.data();
+        vba_result* const* R = t->out.empty() ? nullptr : t->out.data();
+        int rc = 0;
+        bool fatal = false;
+        std::string msg;
+        // one stage: wait for its turn, run it unless the ticket failed already or a HIP error of an earlier ticket forbids GPU work,
+        // pass the turn on -- a failed ticket passes it too, so that later tickets are not deadlocked.  A HIP error (every failure
+        // of a run or a download, a failed HIP call of an upload) fails this ticket and every later one; a rejected window only this one.
+        auto stage = [&](int64_t AsyncState::*turn, int slot, bool always_fatal, const std::function<int()>& body) {
+            {
+                std::unique_lock<std::mutex> lk(A.mu);
+                A.cv.wait(lk, [&] { return A.*turn == k && !(turn == &AsyncState::up_turn && A.hold); });
+                if (!rc && A.dead_at && A.dead_at < k) { rc = -1; msg = A.dead_msg; }
+            }
+            if (!rc) {
+                arena->hip_failed = false;
+                t->t[slot] = now_ms() - A.t0;
+                rc = body();
+                t->t[slot + 1] = now_ms() - A.t0;
+                if (rc) { msg = arena->err; fatal = always_fatal || arena->hip_failed; }
+            }
+            {
+                std::lock_guard<std::mutex> lk(A.mu);
+                if (fatal && !A.dead_at) { A.dead_at = k; A.dead_msg = msg; }
+                A.*turn = k + 1;
+            }
+            A.cv.notify_all();
+        };
+        stage(&AsyncState::up_turn, 0, false, [&] { return do_upload(arena, n, P); });
+        stage(&AsyncState::run_turn, 2, true, [&] { return do_run(arena, t->stop); });
+        stage(&AsyncState::dl_turn, 4, true, [&] { return do_download(arena, n, P, R); });
+        if (timing) fprintf(stderr, "[vba_batch_submit] ticket %lld (%d windows): upload %.1f..%.1f  run %.1f..%.1f  download %.1f..%.1f ms%s\n",
+                            (long long)k, n, t->t[0], t->t[1], t->t[2], t->t[3], t->t[4], t->t[5], rc ? "  FAILED" : "");
+        {
+            std::lock_guard<std::mutex> lk(A.mu);
+            t->rc = rc;
+            t->err = msg;
+            t->done = true;
+        }
+        A.cv.notify_all();
+    }
+}
+
+int async_busy(Handle* h) {
+    if (h->as && !h->as->tickets.empty()) return fail(h, "asynchronous batches pending: wait for them first");
+    return 0;
+}
+
+void async_stop_workers(AsyncState& A) {
+    {
+        std::lock_guard<std::mutex> lk(A.mu);
+        A.hold = false;
+        A.quit = true;
+    }
+    A.cv.notify_all();
+    for (auto& w : A.workers) w.join();   // (a worker leaves once the queue is empty: every ticket it took has finished)
+    A.workers.clear();
+    A.quit = false;
+}
+
+void async_shutdown(Handle* h) {
+    AsyncState* A = h->as;
+    async_stop_workers(*A);
+    for (Handle* a : A->arenas) (void)vba_destroy(a);
+    delete A;
+    h->as = nullptr;
+}
+
+int submit(Handle* h, int32_t n, vba_problem* const* inout, vba_result* const* out, StopRef stop, int64_t* ticket) {
+    if (!h) return -1;
+    if (!ticket || n <= 0 || !inout) return fail(h, "vba_batch_submit: bad arguments");
+    *ticket = 0;
+    AsyncState& A = async_state(h);
+    if (A.workers.empty()) {
+        while ((int)A.arenas.size() < h->async_depth) {
+            Handle* a = nullptr;
+            if (make_handle(h->device, h, &a) != 0) return fail(h, "vba_batch_submit: could not create an arena");
+            a->opt_ll_min = h->opt_ll_min;   // (the paths of the parent, as the lanes of vba_batch_solve take them)
+            a->opt_no_chain = h->opt_no_chain;
+            a->opt_stop_after = h->opt_stop_after;
+            a->opt_lin_fallback = h->opt_lin_fallback;
+            a->opt_chol_step = h->opt_chol_step;
+            a->schur_split = h->schur_split;
+            a->trsv_old = h->trsv_old;
+            a->pcg_jacobi = h->pcg_jacobi;
+            a->budget = &A.budget;
+            A.arenas.push_back(a);
+        }
+        for (int i = 0; i < h->async_depth; i++) A.workers.emplace_back(async_worker, h, A.arenas[i]);
+    }
+    auto t = std::make_shared<AsyncTicket>();
+    t->id = A.next_id++;
+    t->inout.assign(inout, inout + n);
+    if (out) t->out.assign(out, out + n);
+    t->stop = stop;
+    A.tickets[t->id] = t;
+    {
+        std::lock_guard<std::mutex> lk(A.mu);
+        A.queue.push_back(t);
+    }
+    A.cv.notify_all();
+    *ticket = t->id;
+    return 0;
+}
 }  // namespace
 
 extern "C" {
+int vba_batch_set_depth(void* handle, int32_t depth) {
+    Handle* h = reinterpret_cast<Handle*>(handle);
+    if (!h || async_busy(h)) return -1;
+    if (depth < 1 || depth > 4) return fail(h, "vba_batch_set_depth: depth must be 1..4");
+    if (h->as) {   // idle: the workers leave, arenas beyond the new depth free their device buffers and staging
+        AsyncState& A = *h->as;
+        async_stop_workers(A);
+        while ((int)A.arenas.size() > depth) {
+            (void)vba_destroy(A.arenas.back());
+            A.arenas.pop_back();
+        }
+    }
+    h->async_depth = depth;
+    return 0;
+}
+int vba_batch_submit(void* handle, int32_t n, vba_problem* const* inout, vba_result* const* out, const volatile int* stop_flag,
+                     int64_t* ticket) {
+    return submit(reinterpret_cast<Handle*>(handle), n, inout, out, stop_int(stop_flag), ticket);
+}
+int vba_batch_submit_b(void* handle, int32_t n, vba_problem* const* inout, vba_result* const* out,
+                       const volatile unsigned char* stop_flag, int64_t* ticket) {
+    return submit(reinterpret_cast<Handle*>(handle), n, inout, out, stop_byte(stop_flag), ticket);
+}
+int vba_batch_poll(void* handle, int64_t ticket) {
+    Handle* h = reinterpret_cast<Handle*>(handle);
+    if (!h) return -1;
+    if (!h->as || !h->as->tickets.count(ticket)) return fail(h, "vba_batch_poll: unknown or retired ticket " + std::to_string(ticket));
+    AsyncState& A = *h->as;
+    std::lock_guard<std::mutex> lk(A.mu);
+    return A.tickets[ticket]->done ? 0 : 1;
+}
+int vba_batch_wait(void* handle, int64_t ticket) {
+    Handle* h = reinterpret_cast<Handle*>(handle);
+    if (!h) return -1;
+    if (!h->as || !h->as->tickets.count(ticket)) return fail(h, "vba_batch_wait: unknown or retired ticket " + std::to_string(ticket));
+    AsyncState& A = *h->as;
+    std::shared_ptr<AsyncTicket> t = A.tickets[ticket];
+    {
+        std::unique_lock<std::mutex> lk(A.mu);
+        A.cv.wait(lk, [&] { return t->done; });
+    }
+    A.tickets.erase(ticket);
+    if (t->rc)
+        return fail(h, "vba_batch_submit, ticket " + std::to_string(ticket) + ", windows 0.." + std::to_string(t->inout.size() - 1) + ": " + t->err);
+    return 0;
+}
 
 // ---- test / diagnostic hooks: NOT part of include/vislam_ba.h and not in the shipped library.  `make` builds a second flavour,
 // libvislam_ba_hooks.so (-DVBA_TEST_HOOKS), that the tests load when they need to look inside (tests/test_abi_exports.py checks
@@ -1989,6 +2242,18 @@ int vba_debug_set_chunking(void* handle, int32_t chunk, int32_t lanes) {
     if (!h) return -1;
     h->opt_chunk = chunk;
     h->opt_lanes = lanes;
+    return 0;
+}
+// test hook: while on, the workers of vba_batch_submit start no upload (submitted tickets stay pending: observable without timing)
+int vba_debug_async_hold(void* handle, int32_t on) {
+    Handle* h = reinterpret_cast<Handle*>(handle);
+    if (!h) return -1;
+    AsyncState& A = async_state(h);
+    {
+        std::lock_guard<std::mutex> lk(A.mu);
+        A.hold = on != 0;
+    }
+    A.cv.notify_all();
     return 0;
 }
 int vba_debug_buf_id(const char* name) {
@@ -2134,7 +2399,7 @@ int vba_preintegrate(void* handle, int32_t n_edges, const int32_t* sample_begin,
                      const double* dt, double gyr_meas_cov, double acc_meas_cov, double* imu_meas, double* cov_pvphi,
                      double* imu_info_prv) {
     Handle* h = reinterpret_cast<Handle*>(handle);
-    if (!h) return -1;
+    if (!h || async_busy(h)) return -1;
     if (n_edges <= 0 || !sample_begin || !gyr || !acc || !dt || !imu_meas || !cov_pvphi) return fail(h, "vba_preintegrate: bad arguments");
     HIPCHK(h, hipSetDevice(h->device));
     const int ns = sample_begin[n_edges];
@@ -2202,7 +2467,7 @@ bool inverse_host(int n, const double* A, double* Ai) {
 
 int vba_pose_optimize(void* handle, int32_t n_frames, vba_frame_problem* const* inout, vba_frame_result* const* out) {
     Handle* h = reinterpret_cast<Handle*>(handle);
-    if (!h) return -1;
+    if (!h || async_busy(h)) return -1;
     if (n_frames <= 0 || !inout || !out) return fail(h, "vba_pose_optimize: bad arguments");
     HIPCHK(h, hipSetDevice(h->device));
     size_t n_tot = 0;
@@ -2317,7 +2582,7 @@ int vba_pose_optimize(void* handle, int32_t n_frames, vba_frame_problem* const* 
 
 int vba_set_profile(void* handle, int32_t enable) {
     Handle* h = reinterpret_cast<Handle*>(handle);
-    if (!h) return -1;
+    if (!h || async_busy(h)) return -1;
     h->profile = enable != 0;
     return 0;
 }
