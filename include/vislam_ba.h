@@ -123,7 +123,7 @@ typedef struct vba_profile {
     double total_ms;             /* first launch -> last launch of the run */
     double factor_flops;         /* FP64 flop the factorisation class executed on MFMA: 2*32^3 per tile product of the
                                     symbolic tile lists, per solve (structurally zero tiles are never touched) */
-    int64_t kernel_launches;     /* kernel launches the last vba_batch_run / vba_solve enqueued (filled with or without profiling) */
+    int64_t kernel_launches;     /* kernel launches the last vba_batch_run / vba_solve / vba_sim3_optimize enqueued (filled with or without profiling) */
 } vba_profile;
 
 /* One handle per host thread / GPU; owns device buffers and a stream.  Errors: nonzero return, message
@@ -178,7 +178,7 @@ int vba_batch_solve_b(void *handle, int32_t n_windows, vba_problem *const *inout
  *           every later one, those submitted afterwards included, with the same message: no GPU work starts for them (earlier
  *           tickets finish).  Waiting on an unknown or retired ticket returns -1.
  *   handle  while any ticket is submitted and not yet waited for, every synchronous entry point of the handle (vba_solve*,
- *           vba_batch_upload / run / download / solve*, vba_pose_optimize, vba_preintegrate, vba_set_profile,
+ *           vba_batch_upload / run / download / solve*, vba_pose_optimize, vba_sim3_optimize, vba_preintegrate, vba_set_profile,
  *           vba_batch_set_depth) returns -1 with "asynchronous batches pending: wait for them first"; afterwards the handle
  *           works synchronously as before.  vba_destroy finishes pending tickets (their results land) before it frees.
  *           Profiling (vba_set_profile) covers synchronous calls only.  One caller thread at a time, as everywhere. */
@@ -245,6 +245,45 @@ typedef struct vba_frame_result {
 } vba_frame_result;
 
 int vba_pose_optimize(void *handle, int32_t n_frames, vba_frame_problem *const *inout, vba_frame_result *const *out);
+
+/* ---- loop-closure Sim3 refinement ----
+ * Optimizer::OptimizeSim3(KeyFrame*, KeyFrame*, vector<MapPoint*>&, g2o::Sim3&, th2, bFixScale)   src/Optimizer.cpp:4579-4785
+ * Everything between the edge set-up (:4623-4720) and the write-back (:4727-4784): optimize(5) with Levenberg-Marquardt on the
+ * one VertexSim3Expmap (types_seven_dof_expmap.h:48-94), the chi2 > th2 test of EdgeSim3ProjectXYZ and EdgeInverseSim3ProjectXYZ
+ * (:130-171) of every matched pair, the early exit when fewer than 10 pairs are left, optimize(10 or 5) on the survivors, the
+ * inlier count.  The map points are fixed vertices, so the caller passes them in the two cameras' frames.  One call refines a
+ * batch of independent candidates (one workgroup per candidate, one kernel launch per call).  Jacobians are analytic; the
+ * reference differentiates both edges numerically (DESIGN.md gives the measured difference). */
+typedef struct vba_sim3_problem {
+    int32_t n_pairs;        /* matched map-point pairs that passed the reference's filters (:4640-4678); 0 is legal */
+    int32_t fix_scale;      /* bFixScale: VertexSim3Expmap::_fix_scale (update[6] = 0, types_seven_dof_expmap.h:64-65) */
+    double  S12[8];         /* in/out: g2o::Sim3 as t(3) q(4, xyzw) s, maps KF2-camera into KF1-camera coordinates (sim3.h:144-146).
+                             * Written back only when the candidate survives the first test (:4755-4756, :4781-4782) */
+    const double *p1c, *p2c;   /* [n_pairs][3] map points in KF1's / KF2's camera frame (P3D1c, P3D2c: :4659-4669) */
+    const double *uv1, *uv2;   /* [n_pairs][2] undistorted keypoints in KF1 / KF2 (kpUn1.pt, kpUn2.pt: :4682-4702) */
+    const double *w1,  *w2;    /* [n_pairs] invSigma2 of the keypoints' octaves (information = w * I2, :4692-4710) */
+    double K1[4], K2[4];    /* fx fy cx cy of each keyframe (:4612-4619; they may differ) */
+    double th2;             /* chi2 gate of both tests (10 at the reference's call site, src/LoopClosing.cpp:399) */
+    double huber;           /* Huber width of every edge: (double)(float)sqrt((float)th2), :4634 */
+    int32_t its_stage1, its_stage2_bad, its_stage2_clean;  /* 5, 10, 5 (:4724, :4749-4752); each at least 1 */
+    int32_t min_inliers;    /* 10 (:4755) */
+} vba_sim3_problem;
+
+typedef struct vba_sim3_result {
+    int32_t n_inliers;      /* the function's return value (0 when n_pairs - n_bad_stage1 < min_inliers) */
+    int32_t status;         /* VBA_OK */
+    int32_t n_bad_stage1;   /* nBad of the first test: tells which stage-2 budget was used */
+    int32_t its_done[2];    /* LM iterations of the two optimize() calls (0 for a stage that did not run) */
+    double  chi2_stage[2];  /* robust chi2 of the accepted estimate at the end of each optimize() (LM's currentChi) */
+    uint8_t *outlier;       /* [n_pairs] caller-allocated: 1 = the host nulls vpMatches1[idx] (:4738-4739, :4773-4774); set for the
+                             * pairs of the first test also when 0 is returned */
+    double  *chi2_12, *chi2_21; /* [n_pairs] caller-allocated or NULL: e12->chi2(), e21->chi2() as the last test of each pair read them */
+} vba_sim3_result;
+
+/* Synchronous, like vba_pose_optimize; -1 while asynchronous tickets are pending.  n_problems == 0 returns 0.  A bad problem
+ * (negative n_pairs, NULL array with n_pairs > 0, non-finite S12, scale <= 0, zero quaternion, a budget below 1) fails the whole
+ * call before any GPU work, message through vba_last_error.  No upper bound on n_pairs. */
+int vba_sim3_optimize(void *handle, int32_t n_problems, vba_sim3_problem *const *inout, vba_sim3_result *const *out);
 
 /* ---- on-disk problem format: one vba_problem per file, so that windows recorded from a live system can
  * be replayed as fixtures.  Little-endian; header "VBAP" u32 version(=2) then the scalar fields in struct order

@@ -373,3 +373,112 @@ def load_problem(path) -> "Problem":
                    imu_meas=meas, imu_info_prv=info, algo=algo, its_stage1=its1, its_stage2=its2, chi2_th=float(sc[5]),
                    depth_min=float(sc[6]), rho_min=float(sc[7]), huber_vis=float(sc[2]), huber_prv=float(sc[3]), huber_bias=float(sc[4]),
                    protocol=proto, robust=robust, kf_fix=fix, solver=solver)
+
+
+# ---- loop-closure Sim3 refinement (include/vislam_ba.h: vba_sim3_problem / vba_sim3_result) ----
+def huber_of(th2):
+    """const float deltaHuber = sqrt(th2) with th2 a float (src/Optimizer.cpp:4634)"""
+    return float(np.float32(np.sqrt(np.float32(th2))))
+
+
+class vba_sim3_problem(C.Structure):
+    _fields_ = [
+        ("n_pairs", C.c_int32), ("fix_scale", C.c_int32), ("S12", C.c_double * 8),
+        ("p1c", _pd), ("p2c", _pd), ("uv1", _pd), ("uv2", _pd), ("w1", _pd), ("w2", _pd),
+        ("K1", C.c_double * 4), ("K2", C.c_double * 4), ("th2", C.c_double), ("huber", C.c_double),
+        ("its_stage1", C.c_int32), ("its_stage2_bad", C.c_int32), ("its_stage2_clean", C.c_int32), ("min_inliers", C.c_int32),
+    ]
+
+
+class vba_sim3_result(C.Structure):
+    _fields_ = [
+        ("n_inliers", C.c_int32), ("status", C.c_int32), ("n_bad_stage1", C.c_int32), ("its_done", C.c_int32 * 2),
+        ("chi2_stage", C.c_double * 2), ("outlier", _pu8), ("chi2_12", _pd), ("chi2_21", _pd),
+    ]
+
+
+@dataclass
+class Sim3Problem:
+    """One Optimizer::OptimizeSim3 call (src/Optimizer.cpp:4579-4785) as flat arrays: the matched pairs that passed its filters."""
+    S12: np.ndarray                # [8] t(3) q(4, xyzw) s
+    p1c: np.ndarray                # [n,3]
+    p2c: np.ndarray                # [n,3]
+    uv1: np.ndarray                # [n,2]
+    uv2: np.ndarray                # [n,2]
+    w1: np.ndarray                 # [n]
+    w2: np.ndarray                 # [n]
+    K1: np.ndarray                 # [4]
+    K2: np.ndarray                 # [4]
+    fix_scale: int = 0
+    th2: float = 10.0
+    huber: Optional[float] = None  # default: huber_of(th2)
+    its_stage1: int = 5
+    its_stage2_bad: int = 10
+    its_stage2_clean: int = 5
+    min_inliers: int = 10
+    truth: dict = field(default_factory=dict)
+
+    def __post_init__(self):
+        self.S12 = _f64(self.S12, (8,))
+        self.p1c = _f64(self.p1c, (-1, 3)); self.p2c = _f64(self.p2c, (-1, 3))
+        self.uv1 = _f64(self.uv1, (-1, 2)); self.uv2 = _f64(self.uv2, (-1, 2))
+        self.w1 = _f64(self.w1, (-1,)); self.w2 = _f64(self.w2, (-1,))
+        self.K1 = _f64(self.K1, (4,)); self.K2 = _f64(self.K2, (4,))
+        if self.huber is None:
+            self.huber = huber_of(self.th2)
+
+    n_pairs = property(lambda self: self.p1c.shape[0])
+
+    def copy(self, **changes):
+        import copy as _c
+        q = _c.copy(self)
+        q.S12 = self.S12.copy()
+        for k, v in changes.items():
+            setattr(q, k, v)
+        return q
+
+    def as_struct(self) -> vba_sim3_problem:
+        s = vba_sim3_problem()
+        s.n_pairs, s.fix_scale = self.n_pairs, int(self.fix_scale)
+        s.S12[:] = self.S12.tolist()
+        p = lambda a: a.ctypes.data_as(_pd)
+        s.p1c, s.p2c, s.uv1, s.uv2, s.w1, s.w2 = p(self.p1c), p(self.p2c), p(self.uv1), p(self.uv2), p(self.w1), p(self.w2)
+        s.K1[:] = self.K1.tolist(); s.K2[:] = self.K2.tolist()
+        s.th2, s.huber = self.th2, self.huber
+        s.its_stage1, s.its_stage2_bad, s.its_stage2_clean = self.its_stage1, self.its_stage2_bad, self.its_stage2_clean
+        s.min_inliers = self.min_inliers
+        return s
+
+
+@dataclass
+class Sim3Result:
+    n_inliers: int
+    status: int
+    n_bad_stage1: int
+    its_done: tuple
+    chi2_stage: np.ndarray
+    outlier: np.ndarray
+    chi2_12: Optional[np.ndarray]
+    chi2_21: Optional[np.ndarray]
+    S12: np.ndarray
+
+
+class Sim3ResultBuf:
+    """Caller-allocated result storage of one candidate."""
+
+    def __init__(self, p: Sim3Problem, want_chi2: bool = True):
+        self.n = p.n_pairs
+        self.o = np.zeros(max(self.n, 1), dtype=np.uint8)
+        self.want_chi2 = want_chi2
+        self.s = vba_sim3_result()
+        self.s.outlier = self.o.ctypes.data_as(_pu8)
+        if want_chi2:
+            self.c12 = np.zeros(max(self.n, 1)); self.c21 = np.zeros(max(self.n, 1))
+            self.s.chi2_12 = self.c12.ctypes.data_as(_pd)
+            self.s.chi2_21 = self.c21.ctypes.data_as(_pd)
+
+    def get(self, st: vba_sim3_problem) -> Sim3Result:
+        s = self.s
+        return Sim3Result(s.n_inliers, s.status, s.n_bad_stage1, tuple(s.its_done), np.array(s.chi2_stage[:]), self.o[:self.n].copy(),
+                          self.c12[:self.n].copy() if self.want_chi2 else None, self.c21[:self.n].copy() if self.want_chi2 else None,
+                          np.array(st.S12[:]))

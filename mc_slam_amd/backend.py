@@ -18,7 +18,7 @@ _libs = {}
 
 EXPORTS = ["vba_create", "vba_destroy", "vba_last_error", "vba_solve", "vba_batch_upload", "vba_batch_run",
            "vba_batch_download", "vba_batch_solve", "vba_solve_b", "vba_batch_run_b", "vba_batch_solve_b", "vba_preintegrate", "vba_pose_optimize", "vba_problem_save", "vba_problem_load", "vba_problem_free", "vba_set_profile", "vba_get_profile", "vba_host_threads",
-           "vba_batch_set_depth", "vba_batch_submit", "vba_batch_submit_b", "vba_batch_poll", "vba_batch_wait"]
+           "vba_batch_set_depth", "vba_batch_submit", "vba_batch_submit_b", "vba_batch_poll", "vba_batch_wait", "vba_sim3_optimize"]
 
 
 def load_library(hooks=False):
@@ -48,6 +48,7 @@ def load_library(hooks=False):
     _pd, _pi = C.POINTER(C.c_double), C.POINTER(C.c_int32)
     lib.vba_preintegrate.argtypes = [C.c_void_p, C.c_int32, _pi, _pd, _pd, _pd, C.c_double, C.c_double, _pd, _pd, _pd]
     lib.vba_pose_optimize.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.POINTER(abi.vba_frame_problem)), C.POINTER(C.POINTER(abi.vba_frame_result))]
+    lib.vba_sim3_optimize.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.POINTER(abi.vba_sim3_problem)), C.POINTER(C.POINTER(abi.vba_sim3_result))]
     lib.vba_set_profile.argtypes = [C.c_void_p, C.c_int32]
     lib.vba_get_profile.argtypes = [C.c_void_p, C.POINTER(abi.vba_profile)]
     lib.vba_batch_set_depth.argtypes = [C.c_void_p, C.c_int32]
@@ -246,6 +247,31 @@ class LocalBA:
         """vba_pose_optimize on copies of the FrameProblems: list of abi.FrameResult (with the optimised nav)"""
         packed = self.pose_pack(frames)
         self.pose_run(packed)
+        return [b.get(s) for b, s in zip(packed[2], packed[1])]
+
+    # ---- loop-closure Sim3 refinement (vba_sim3_optimize): a batch of independent candidates per call ----
+    def sim3_pack(self, problems, want_chi2=True):
+        """ctypes views of a list of abi.Sim3Problem for vba_sim3_optimize (kept alive by the returned tuple)"""
+        n = len(problems)
+        structs = [p.as_struct() for p in problems]
+        bufs = [abi.Sim3ResultBuf(p, want_chi2) for p in problems]
+        pp = (C.POINTER(abi.vba_sim3_problem) * n)(*[C.pointer(s) for s in structs])
+        rr = (C.POINTER(abi.vba_sim3_result) * n)(*[C.pointer(b.s) for b in bufs])
+        return n, structs, bufs, pp, rr, problems
+
+    def sim3_reset(self, packed):
+        """vba_sim3_optimize updates S12 in place: put the initial estimates back before the next run"""
+        for s, p in zip(packed[1], packed[5]):
+            C.memmove(C.addressof(s) + abi.vba_sim3_problem.S12.offset, p.S12.ctypes.data, 64)
+
+    def sim3_call(self, packed):
+        if self.lib.vba_sim3_optimize(self.h, packed[0], packed[3], packed[4]) != 0:
+            raise self._err("vba_sim3_optimize")
+
+    def sim3_optimize(self, problems, want_chi2=True):
+        """vba_sim3_optimize on a list of abi.Sim3Problem (left untouched): list of abi.Sim3Result with the refined S12"""
+        packed = self.sim3_pack(problems, want_chi2)
+        self.sim3_call(packed)
         return [b.get(s) for b, s in zip(packed[2], packed[1])]
 
     def set_profile(self, on=True):

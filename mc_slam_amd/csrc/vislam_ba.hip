@@ -11,6 +11,7 @@
 #include "vba_kernels_lm.h"
 #include "vba_preint.h"
 #include "vba_pose.h"
+#include "vba_sim3.h"
 #include "vba_structure.h"
 #include "vba_pcg.h"
 #include "vba_chain.h"
@@ -210,6 +211,8 @@ struct Handle {
     DevBuf preint;  // arena of vba_preintegrate
     DevBuf pose_arena;  // arena of vba_pose_optimize
     PinnedBuf pose_host_in, pose_host_out;  // its pinned staging: one H2D and one D2H per call
+    DevBuf sim3_arena;  // arena of vba_sim3_optimize
+    PinnedBuf sim3_host_in, sim3_host_out;  // its pinned staging, same scheme
     // small batches (<= 8 windows): every host-built array of an upload goes through ONE pinned arena and ONE H2D copy into one
     // device arena (a single window is ~25 arrays of a few KB to a few 100 KB: 25 copies cost 0.4 ms of queue latency)
     struct Pending { int id; const void* src; size_t bytes; };
@@ -1757,6 +1760,9 @@ int vba_destroy(void* handle) {
     h->pose_arena.release();
     h->pose_host_in.release();
     h->pose_host_out.release();
+    h->sim3_arena.release();
+    h->sim3_host_in.release();
+    h->sim3_host_out.release();
     for (auto e : h->evt_pool) (void)hipEventDestroy(e);
     if (h->up_done) (void)hipEventDestroy(h->up_done);
     if (h->owns_streams)
@@ -2576,6 +2582,121 @@ int vba_pose_optimize(void* handle, int32_t n_frames, vba_frame_problem* const* 
         for (int i = 0; i < d.n_obs; i++) R->outlier[i] = lvl[d.obs0 + i];
         if (R->outlier_last)
             for (int i = 0; i < d.n_last; i++) R->outlier_last[i] = lvl[d.last0 + i];
+    }
+    return 0;
+}
+
+// Optimizer::OptimizeSim3 (src/Optimizer.cpp:4579-4785) between edge set-up and write-back, for a batch of independent loop
+// candidates: one arena [desc | points | keypoints | weights] goes up in one copy, k_sim3_opt runs one workgroup per candidate,
+// [out | flags (| chi2 of both edges, when a caller asked for them)] come back in one copy.
+int vba_sim3_optimize(void* handle, int32_t n_problems, vba_sim3_problem* const* inout, vba_sim3_result* const* out) {
+    Handle* h = reinterpret_cast<Handle*>(handle);
+    if (!h || async_busy(h)) return -1;
+    if (n_problems < 0 || (n_problems > 0 && (!inout || !out))) return fail(h, "vba_sim3_optimize: bad arguments");
+    if (n_problems == 0) return 0;
+    size_t n_tot = 0;
+    bool want_chi2 = false;
+    for (int f = 0; f < n_problems; f++) {
+        const vba_sim3_problem* P = inout[f];
+        const vba_sim3_result* R = out[f];
+        auto who = [f](const char* m) { return "vba_sim3_optimize: problem " + std::to_string(f) + ": " + m; };
+        if (!P || !R) return fail(h, who("NULL problem or result"));
+        if (P->n_pairs < 0) return fail(h, who("negative n_pairs"));
+        if (P->n_pairs > 0 && (!P->p1c || !P->p2c || !P->uv1 || !P->uv2 || !P->w1 || !P->w2 || !R->outlier))
+            return fail(h, who("NULL array with n_pairs > 0"));
+        for (int k = 0; k < 8; k++)
+            if (!std::isfinite(P->S12[k])) return fail(h, who("S12 is not finite"));
+        if (!(P->S12[7] > 0.0)) return fail(h, who("scale of S12 is not positive"));
+        if (!(P->S12[3] * P->S12[3] + P->S12[4] * P->S12[4] + P->S12[5] * P->S12[5] + P->S12[6] * P->S12[6] > 0.0))
+            return fail(h, who("zero quaternion in S12"));
+        if (P->its_stage1 < 1 || P->its_stage2_bad < 1 || P->its_stage2_clean < 1) return fail(h, who("iteration budgets must be at least 1"));
+        if (P->min_inliers < 0) return fail(h, who("negative min_inliers"));
+        if (!std::isfinite(P->th2) || !std::isfinite(P->huber) || !(P->huber > 0.0)) return fail(h, who("th2 / huber are not usable"));
+        n_tot += (size_t)P->n_pairs;
+        want_chi2 = want_chi2 || R->chi2_12 || R->chi2_21;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    // per-pair arrays with the two sides of a pair interleaved: p [6] = P1c P2c, uv [4] = uv1 uv2, w [2] = w1 w2
+    const size_t b_desc = up(sizeof(Sim3Desc) * n_problems), b_p = up((6 * n_tot + 6) * 8), b_uv = up((4 * n_tot + 4) * 8), b_w = up((2 * n_tot + 2) * 8);
+    const size_t b_in = b_desc + b_p + b_uv + b_w;
+    const size_t b_out = up(sizeof(Sim3Out) * n_problems), b_flag = up(n_tot + 1), b_c = up((2 * n_tot + 2) * 8);
+    const size_t b_back = b_out + b_flag + (want_chi2 ? b_c : 0);
+    HIPCHK(h, h->sim3_arena.ensure(b_in + b_out + b_flag + b_c));
+    HIPCHK(h, h->sim3_host_in.ensure(b_in));
+    HIPCHK(h, h->sim3_host_out.ensure(b_back));
+    char* hin = reinterpret_cast<char*>(h->sim3_host_in.p);
+    Sim3Desc* desc = reinterpret_cast<Sim3Desc*>(hin);
+    double* hp = reinterpret_cast<double*>(hin + b_desc);
+    double* huv = reinterpret_cast<double*>(hin + b_desc + b_p);
+    double* hw = reinterpret_cast<double*>(hin + b_desc + b_p + b_uv);
+    {
+        size_t o = 0;
+        for (int f = 0; f < n_problems; f++) {
+            desc[f].pair0 = (long long)o;
+            o += (size_t)inout[f]->n_pairs;
+        }
+    }
+    auto pack = [&](int f) {
+        const vba_sim3_problem* P = inout[f];
+        Sim3Desc& d = desc[f];
+        d.n_pairs = P->n_pairs;
+        d.fix_scale = P->fix_scale ? 1 : 0;
+        d.its1 = P->its_stage1; d.its2_bad = P->its_stage2_bad; d.its2_clean = P->its_stage2_clean;
+        d.min_inliers = P->min_inliers;
+        std::memcpy(d.S, P->S12, sizeof d.S);
+        std::memcpy(d.K1, P->K1, sizeof d.K1);
+        std::memcpy(d.K2, P->K2, sizeof d.K2);
+        d.th2 = P->th2; d.huber = P->huber;
+        const size_t o = (size_t)d.pair0, n = (size_t)d.n_pairs;
+        double *qp = hp + 6 * o, *quv = huv + 4 * o, *qw = hw + 2 * o;
+        for (size_t i = 0; i < n; i++) {
+            for (int k = 0; k < 3; k++) { qp[6 * i + k] = P->p1c[3 * i + k]; qp[6 * i + 3 + k] = P->p2c[3 * i + k]; }
+            for (int k = 0; k < 2; k++) { quv[4 * i + k] = P->uv1[2 * i + k]; quv[4 * i + 2 + k] = P->uv2[2 * i + k]; }
+            qw[2 * i] = P->w1[i];
+            qw[2 * i + 1] = P->w2[i];
+        }
+    };
+    {
+        const int nt = (n_problems >= 256) ? std::max(1, std::min(8, host_threads())) : 1;
+        std::atomic<int> next(0);
+        auto work = [&]() { for (int f = next.fetch_add(1); f < n_problems; f = next.fetch_add(1)) pack(f); };
+        std::vector<std::thread> pool;
+        for (int t = 1; t < nt; t++) pool.emplace_back(work);
+        work();
+        for (auto& t : pool) t.join();
+    }
+    char* base = reinterpret_cast<char*>(h->sim3_arena.p);
+    Sim3Batch B;
+    B.desc = reinterpret_cast<const Sim3Desc*>(base);
+    B.p = reinterpret_cast<const double*>(base + b_desc);
+    B.uv = reinterpret_cast<const double*>(base + b_desc + b_p);
+    B.w = reinterpret_cast<const double*>(base + b_desc + b_p + b_uv);
+    B.out = reinterpret_cast<Sim3Out*>(base + b_in);
+    B.flag = reinterpret_cast<unsigned char*>(base + b_in + b_out);
+    B.c = reinterpret_cast<double*>(base + b_in + b_out + b_flag);
+    const long long launch0 = h->n_launch;
+    HIPCHK(h, hipMemcpyAsync(base, hin, b_in, hipMemcpyHostToDevice, h->stream));
+    VBA_LAUNCH(k_sim3_opt, dim3(n_problems), dim3(64), 0, h->stream, B);
+    HIPCHK(h, hipGetLastError());
+    char* hout = reinterpret_cast<char*>(h->sim3_host_out.p);
+    HIPCHK(h, hipMemcpyAsync(hout, base + b_in, b_back, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->prof.kernel_launches = h->n_launch - launch0;
+    const Sim3Out* res = reinterpret_cast<const Sim3Out*>(hout);
+    const unsigned char* flag = reinterpret_cast<const unsigned char*>(hout + b_out);
+    const double* cc = reinterpret_cast<const double*>(hout + b_out + b_flag);
+    for (int f = 0; f < n_problems; f++) {
+        vba_sim3_problem* P = inout[f];
+        vba_sim3_result* R = out[f];
+        const Sim3Out& r = res[f];
+        const size_t o = (size_t)desc[f].pair0, n = (size_t)desc[f].n_pairs;
+        R->n_inliers = r.n_inliers; R->status = r.status; R->n_bad_stage1 = r.n_bad1;
+        for (int k = 0; k < 2; k++) { R->its_done[k] = r.its[k]; R->chi2_stage[k] = r.chi2_stage[k]; }
+        std::memcpy(P->S12, r.S, sizeof r.S);   // the input, bit for bit, when the candidate is rejected (:4755)
+        if (n) std::memcpy(R->outlier, flag + o, n);
+        for (size_t i = 0; i < n && R->chi2_12; i++) R->chi2_12[i] = cc[2 * (o + i)];
+        for (size_t i = 0; i < n && R->chi2_21; i++) R->chi2_21[i] = cc[2 * (o + i) + 1];
     }
     return 0;
 }

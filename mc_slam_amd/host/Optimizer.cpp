@@ -921,6 +921,75 @@ int Optimizer::PoseOptimization(Frame* pFrame, Frame* pLastFrame, const IMUPrein
     return R.n_inliers;
 }
 
+int Optimizer::OptimizeSim3(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoint*>& vpMatches1, g2o::Sim3& g2oS12, const float th2,
+                            const bool bFixScale) {                                                               // :4579-4785
+    const Mat4f& T1 = pKF1->GetPose();
+    const Mat4f& T2 = pKF2->GetPose();
+    // cv::Mat P3Dc = Rcw * P3Dw + tcw (:4659-4669): CV_32F arithmetic, widened by Converter::toVector3d
+    auto toCamera = [](const Mat4f& T, const float* Pw, double* Pc) {
+        for (int i = 0; i < 3; i++) {
+            float a = T[4 * i] * Pw[0];
+            a += T[4 * i + 1] * Pw[1];
+            a += T[4 * i + 2] * Pw[2];
+            a += T[4 * i + 3];
+            Pc[i] = (double)a;
+        }
+    };
+    const int N = (int)vpMatches1.size();
+    const std::vector<MapPoint*> vpMapPoints1 = pKF1->GetMapPointMatches();
+    std::vector<double> p1c, p2c, uv1, uv2, w1, w2;
+    std::vector<size_t> vnIndexEdge;
+    vnIndexEdge.reserve(N);
+    for (int i = 0; i < N; i++) {
+        if (!vpMatches1[i]) continue;                                                                             // :4640
+        MapPoint* pMP1 = vpMapPoints1[i];
+        MapPoint* pMP2 = vpMatches1[i];
+        const int i2 = pMP2->GetIndexInKeyFrame(pKF2);
+        if (!pMP1 || !pMP2) continue;                                                                             // :4653, :4677
+        if (pMP1->isBad() || pMP2->isBad() || i2 < 0) continue;                                                   // :4655, :4674
+        double P[3];
+        toCamera(T1, pMP1->mWorldPos, P);
+        p1c.insert(p1c.end(), P, P + 3);
+        toCamera(T2, pMP2->mWorldPos, P);
+        p2c.insert(p2c.end(), P, P + 3);
+        const KeyPoint& kpUn1 = pKF1->mvKeysUn[i];                                                                // :4683-4693
+        uv1.push_back(kpUn1.pt.x); uv1.push_back(kpUn1.pt.y);
+        w1.push_back(pKF1->mvInvLevelSigma2[kpUn1.octave]);
+        const KeyPoint& kpUn2 = pKF2->mvKeysUn[i2];                                                               // :4701-4710
+        uv2.push_back(kpUn2.pt.x); uv2.push_back(kpUn2.pt.y);
+        w2.push_back(pKF2->mvInvLevelSigma2[kpUn2.octave]);
+        vnIndexEdge.push_back(i);
+    }
+    const int nCorrespondences = (int)vnIndexEdge.size();
+    vba_sim3_problem P;
+    std::memset(&P, 0, sizeof P);
+    vba_sim3_result R;
+    std::memset(&R, 0, sizeof R);
+    std::vector<uint8_t> outl((size_t)nCorrespondences + 1, 0);
+    P.n_pairs = nCorrespondences;
+    P.fix_scale = bFixScale ? 1 : 0;
+    for (int k = 0; k < 3; k++) P.S12[k] = g2oS12.translation()[k];
+    for (int k = 0; k < 4; k++) P.S12[3 + k] = g2oS12.rotation()[k];
+    P.S12[7] = g2oS12.scale();
+    P.p1c = p1c.data(); P.p2c = p2c.data(); P.uv1 = uv1.data(); P.uv2 = uv2.data(); P.w1 = w1.data(); P.w2 = w2.data();
+    P.K1[0] = pKF1->fx; P.K1[1] = pKF1->fy; P.K1[2] = pKF1->cx; P.K1[3] = pKF1->cy;                               // :4612-4619
+    P.K2[0] = pKF2->fx; P.K2[1] = pKF2->fy; P.K2[2] = pKF2->cx; P.K2[3] = pKF2->cy;
+    P.th2 = th2;
+    P.huber = (double)std::sqrt(th2);                                                                             // const float deltaHuber = sqrt(th2), :4634
+    P.its_stage1 = 5; P.its_stage2_bad = 10; P.its_stage2_clean = 5; P.min_inliers = 10;                          // :4724, :4749-4755
+    R.outlier = outl.data();
+    void* h = handle();
+    if (!h) { std::cerr << "OptimizeSim3: no HIP device, Sim3 refinement skipped (the backend has no CPU path)" << std::endl; return 0; }
+    vba_sim3_problem* pp = &P;
+    vba_sim3_result* pr = &R;
+    if (vba_sim3_optimize(h, 1, &pp, &pr) != 0) { std::cerr << "OptimizeSim3: " << vba_last_error(h) << std::endl; return 0; }
+    for (int k = 0; k < nCorrespondences; k++)
+        if (outl[k]) vpMatches1[vnIndexEdge[k]] = static_cast<MapPoint*>(NULL);                                   // :4738-4739, :4773-4774
+    if (nCorrespondences - R.n_bad_stage1 < 10) return 0;                                                         // :4755-4756: g2oS12 untouched
+    g2oS12 = g2o::Sim3({{P.S12[3], P.S12[4], P.S12[5], P.S12[6]}}, {{P.S12[0], P.S12[1], P.S12[2]}}, P.S12[7]);   // :4781-4782
+    return R.n_inliers;
+}
+
 void Optimizer::GlobalBundleAdjustment(Map* pMap, int nIterations, bool* pbStopFlag, const unsigned long nLoopKF, const bool bRobust) {
     BundleAdjustment(pMap->GetAllKeyFrames(), pMap->GetAllMapPoints(), nIterations, pbStopFlag, nLoopKF, bRobust);   // :3346-3354
 }

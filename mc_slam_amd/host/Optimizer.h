@@ -66,6 +66,11 @@ public:
                                 const bool& bComputeMarg = false);
     static int PoseOptimization(Frame* pFrame, Frame* pLastFrame, const IMUPreintegrator& imupreint, const Vector3d& gw,
                                 const bool& bComputeMarg = false);
+    // include/Optimizer.h:90-91: refinement of a loop candidate's Sim3 (LoopClosing::ComputeSim3, src/LoopClosing.cpp:399).  Kept from
+    // the reference: the pair filters and the float32 camera-frame points (src/Optimizer.cpp:4623-4720), the nulling of
+    // vpMatches1 and the write-back of g2oS12 (:4727-4784).  Replaced: everything g2o did in between (vba_sim3_optimize).
+    static int OptimizeSim3(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoint*>& vpMatches1, g2o::Sim3& g2oS12, const float th2,
+                            const bool bFixScale);
     static bool PackLocalBundleAdjustment(KeyFrame* pKF, const std::list<KeyFrame*>* pList, PackedWindow& W);
     static void LocalBundleAdjustmentImpl(KeyFrame* pKF, const std::list<KeyFrame*>* pList, bool* pbStopFlag, Map* pMap, LocalMapping* pLM);
 

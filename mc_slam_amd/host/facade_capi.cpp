@@ -292,6 +292,52 @@ int fc_get_mappoint(void* m, long id, float* Pw, int* n_obs, int* n_updates) {
     *n_updates = p->nNormalUpdates;
     return 0;
 }
+// ---- loop-closure Sim3 refinement ----
+// one keypoint of a keyframe, with or without a map point (mp < 0: mvpMapPoints[i] = NULL); observe = 0 leaves the point's
+// observation map without the keyframe (GetIndexInKeyFrame < 0)
+int fc_kf_add_keypoint(void* m, long kf, long mp, float u, float v, int octave, int observe) {
+    FcMap* M = reinterpret_cast<FcMap*>(m);
+    KeyFrame* k = M->kfs.at(kf).get();
+    MapPoint* p = mp >= 0 ? M->mps.at(mp).get() : nullptr;
+    KeyPoint kp; kp.pt.x = u; kp.pt.y = v; kp.octave = octave;
+    k->mvKeysUn.push_back(kp);
+    k->mvuRight.push_back(-1.0f);
+    k->mvpMapPoints.push_back(p);
+    if (p && observe) p->mObservations[k] = k->mvKeysUn.size() - 1;
+    return (int)k->mvKeysUn.size() - 1;
+}
+int fc_set_mappoint_bad(void* m, long mp, int bad) {
+    reinterpret_cast<FcMap*>(m)->mps.at(mp)->mbBad = bad != 0;
+    return 0;
+}
+// Optimizer::OptimizeSim3(kf1, kf2, vpMatches1, g2oS12, th2, bFixScale): matches[i] = id of the map point matched to keypoint i
+// of kf1 (-1: NULL), rewritten in place (-1 where the call nulled the entry); S12 = t(3) q(4, xyzw) s in / out.  Returns the count.
+int fc_optimize_sim3(void* m, long kf1, long kf2, long* matches, int n, double* S12, float th2, int fix_scale) {
+    FcMap* M = reinterpret_cast<FcMap*>(m);
+    std::vector<MapPoint*> vpMatches1((size_t)n, nullptr);
+    for (int i = 0; i < n; i++)
+        if (matches[i] >= 0) vpMatches1[i] = M->mps.at(matches[i]).get();
+    g2o::Sim3 S({{S12[3], S12[4], S12[5], S12[6]}}, {{S12[0], S12[1], S12[2]}}, S12[7]);
+    const int nIn = Optimizer::OptimizeSim3(M->kfs.at(kf1).get(), M->kfs.at(kf2).get(), vpMatches1, S, th2, fix_scale != 0);
+    for (int i = 0; i < n; i++) matches[i] = vpMatches1[i] ? (long)vpMatches1[i]->mnId : -1;
+    for (int k = 0; k < 3; k++) S12[k] = S.translation()[k];
+    for (int k = 0; k < 4; k++) S12[3 + k] = S.rotation()[k];
+    S12[7] = S.scale();
+    return nIn;
+}
+// g2o::Sim3 members: out[0..2] = a.map(x), out[3..10] = a.inverse(), out[11..18] = a * b   (t, q, s each)
+void fc_sim3_ops(const double* a8, const double* b8, const double* x3, double* out19) {
+    const g2o::Sim3 A({{a8[3], a8[4], a8[5], a8[6]}}, {{a8[0], a8[1], a8[2]}}, a8[7]), B({{b8[3], b8[4], b8[5], b8[6]}}, {{b8[0], b8[1], b8[2]}}, b8[7]);
+    const Vector3d y = A.map({{x3[0], x3[1], x3[2]}});
+    auto put = [](const g2o::Sim3& S, double* o) {
+        for (int k = 0; k < 3; k++) o[k] = S.translation()[k];
+        for (int k = 0; k < 4; k++) o[3 + k] = S.rotation()[k];
+        o[7] = S.scale();
+    };
+    for (int k = 0; k < 3; k++) out19[k] = y[k];
+    put(A.inverse(), out19 + 3);
+    put(A * B, out19 + 11);
+}
 int fc_map_updated(void* m) { return reinterpret_cast<FcMap*>(m)->lm.mbMapUpdateFlagForTracking ? 1 : 0; }
 // last packed window (what the facade handed / would hand to vba_solve)
 const vba_problem* fc_last_problem() { return &Optimizer::LastWindow().P; }

@@ -256,3 +256,45 @@ inline void KeyFrame::EraseMapPointMatch(MapPoint* pMP) {
 }
 
 }  // namespace ORB_SLAM2
+
+// Thirdparty/g2o/g2o/types/sim3.h:41-292: the members LoopClosing uses (quaternion, translation, scale; map, inverse, operator*)
+namespace g2o {
+class Sim3 {
+public:
+    typedef ORB_SLAM2::Quaterniond Quaterniond;
+    typedef ORB_SLAM2::Vector3d Vector3d;
+    Sim3() {}
+    Sim3(const Quaterniond& r_, const Vector3d& t_, double s_) : r(r_), t(t_), s(s_) {}
+    const Quaterniond& rotation() const { return r; }
+    Quaterniond& rotation() { return r; }
+    const Vector3d& translation() const { return t; }
+    Vector3d& translation() { return t; }
+    const double& scale() const { return s; }
+    double& scale() { return s; }
+    Vector3d map(const Vector3d& xyz) const {   // s * (r * xyz) + t
+        const Vector3d v = rot(r, xyz);
+        return {{s * v[0] + t[0], s * v[1] + t[1], s * v[2] + t[2]}};
+    }
+    Sim3 inverse() const {                      // Sim3(r.conjugate(), r.conjugate() * ((-1. / s) * t), 1. / s)
+        const Quaterniond rc{{-r[0], -r[1], -r[2], r[3]}};
+        return Sim3(rc, rot(rc, {{(-1. / s) * t[0], (-1. / s) * t[1], (-1. / s) * t[2]}}), 1. / s);
+    }
+    Sim3 operator*(const Sim3& o) const {       // ret.r = r * o.r; ret.t = s * (r * o.t) + t; ret.s = s * o.s
+        Sim3 ret;
+        ret.r = {{r[3] * o.r[0] + r[0] * o.r[3] + r[1] * o.r[2] - r[2] * o.r[1], r[3] * o.r[1] + r[1] * o.r[3] + r[2] * o.r[0] - r[0] * o.r[2],
+                  r[3] * o.r[2] + r[2] * o.r[3] + r[0] * o.r[1] - r[1] * o.r[0], r[3] * o.r[3] - r[0] * o.r[0] - r[1] * o.r[1] - r[2] * o.r[2]}};
+        ret.t = map(o.t);
+        ret.s = s * o.s;
+        return ret;
+    }
+
+private:
+    static Vector3d rot(const Quaterniond& q, const Vector3d& v) {   // Eigen::Quaterniond * Vector3d
+        const ORB_SLAM2::Matrix3d R = ORB_SLAM2::QuatToMatrix(q);
+        return {{R[0] * v[0] + R[1] * v[1] + R[2] * v[2], R[3] * v[0] + R[4] * v[1] + R[5] * v[2], R[6] * v[0] + R[7] * v[1] + R[8] * v[2]}};
+    }
+    Quaterniond r{{0, 0, 0, 1}};
+    Vector3d t{{0, 0, 0}};
+    double s = 1.;
+};
+}  // namespace g2o

@@ -496,3 +496,49 @@ def make_frame_vision(seed=1, n_obs=200, noise=True, outlier_frac=0.1, pt_noise=
     gt = np.concatenate([f.truth["nav"][:7], np.zeros(3)])
     g.truth = dict(T_cw=tcw(gt), is_outlier=f.truth["is_outlier"])
     return g
+
+
+# ---------------------------------------------------------------- loop-closure Sim3 candidates (vba_sim3_optimize)
+def _sim3_exp(u):
+    """exp of a sim(3) tangent (omega, upsilon, sigma) as (R, t, s), through the series of the 4x4 generator
+    [[sigma I + [omega]x, upsilon], [0, 0]] (input synthesis only: not the closed form under test)"""
+    G = np.zeros((4, 4))
+    G[:3, :3] = hat(u[:3]) + u[6] * np.eye(3)
+    G[:3, 3] = u[3:6]
+    E, T = np.eye(4), np.eye(4)
+    for k in range(1, 40):
+        T = T @ G / k
+        E = E + T
+    s = float(np.exp(u[6]))
+    return _orthonormalise(E[:3, :3] / s), E[:3, 3].copy(), s
+
+
+def make_sim3_pair(seed, n_pairs, fix_scale=False, outlier_frac=0.1, noise=True, same_K=False):
+    """One loop candidate as Optimizer::OptimizeSim3 sees it (src/Optimizer.cpp:4579-4720): a true S12 (rotation ~0.2 rad,
+    translation ~0.3 m, log-scale sigma 0.15 unless fixed), points 3-10 m in front of KF2 mapped into KF1, pixel noise of one sigma
+    per octave (octaves 0-3, w = 1.2^(-2 octave)), gross errors of 8-40 px on outlier_frac of the pairs, K2 != K1 unless same_K,
+    and an initial S12 perturbed from the truth by (0.03 rad, 0.1 m, 0.05) as a RANSAC seed would be."""
+    r = np.random.default_rng(seed)
+    n = int(n_pairs)
+    K1 = EUROC_K.copy()
+    K2 = K1.copy() if same_K else K1 * np.array([1.02, 0.99, 1.01, 0.97])
+    R, _, _ = _sim3_exp(np.concatenate([r.normal(size=3) * 0.2, np.zeros(4)]))
+    t = r.normal(size=3) * 0.3
+    s = 1.0 if fix_scale else float(np.exp(r.normal() * 0.15))
+    p2 = np.stack([r.uniform(-2, 2, n), r.uniform(-1.5, 1.5, n), r.uniform(3, 10, n)], axis=1)
+    p1 = s * p2 @ R.T + t
+    lv1, lv2 = r.integers(0, 4, n), r.integers(0, 4, n)
+    w1, w2 = 1.2 ** (-2.0 * lv1), 1.2 ** (-2.0 * lv2)
+    uv1 = p1[:, :2] / p1[:, 2:3] * K1[:2] + K1[2:]
+    uv2 = p2[:, :2] / p2[:, 2:3] * K2[:2] + K2[2:]
+    if noise:
+        uv1 = uv1 + r.normal(size=(n, 2)) * (1.2 ** lv1)[:, None]
+        uv2 = uv2 + r.normal(size=(n, 2)) * (1.2 ** lv2)[:, None]
+    m = r.random(n) < outlier_frac
+    uv1[m] += r.uniform(8, 40, (int(m.sum()), 2)) * r.choice([-1.0, 1.0], (int(m.sum()), 2))
+    u0 = np.concatenate([r.normal(size=3) * 0.03, r.normal(size=3) * 0.1, [0.0 if fix_scale else r.normal() * 0.05]])
+    dR, dt, ds = _sim3_exp(u0)
+    R0, t0, s0 = dR @ R, ds * (dR @ t) + dt, (s if fix_scale else ds * s)
+    S12 = np.concatenate([t0, rot_to_quat(R0), [s0]])
+    return abi.Sim3Problem(S12=S12, p1c=p1, p2c=p2, uv1=uv1, uv2=uv2, w1=w1, w2=w2, K1=K1, K2=K2, fix_scale=int(bool(fix_scale)),
+                           truth=dict(S12=np.concatenate([t, rot_to_quat(R), [s]]), is_outlier=m))
