@@ -1,0 +1,91 @@
+// vba_layout.h -- the records the host describes a batch with and the device reads: window descriptor, control block and the
+// record-size constants.  Plain C / C++ (no HIP): included by vba_device.h for the kernels, and by the host code that lays a batch
+// out (vba_host_layout.h), which the tests compile with plain g++ under sanitizers.
+#pragma once
+#include <stdint.h>
+
+#define VBA_NB 32          // block size of the dense reduced-system factorisation
+#define VBA_EREC 18        // doubles per edge record, XYZ variants (144 B): Bi (2x6), g = -Bi^T r
+#define VBA_EREC1 8        // doubles per edge record, inverse-depth variant (64 B): P_c (3), sqrt(rho' w) (1), r (2); the
+                           // readers rebuild Bi = [A | B_rot] from it and the observer's rotation (rebuild_edge)
+#define VBA_PREC 32        // doubles per point record  (256 B)
+#define VBA_SLOT 8         // doubles per slot record   (64 B = one line), inverse-depth landmarks
+#define VBA_SLOT3 18       // doubles per slot record, XYZ landmarks (144 B): W = Bi^T A (6x3), independent of the damping
+#define VBA_IMUH 960       // doubles per IMU edge pair: 30x30 local Hessian + 30 rhs (+ pad)
+#define VBA_TRACE 64
+
+// Linearisation products kept in HBM between k_lin2 and its consumers (variant 2, EdgePRIDP).  A "slot" is one
+// (landmark, keyframe) incidence = one H_pl block: observation e -> slot e, reference keyframe of landmark p
+// -> slot n_obs + p.  Jacobians are pre-scaled by sqrt(rho' * invSigma2) and never stored unreduced.
+//   slot record  [0..5] U = W * sqrt(Dinv)  (W = H_pl block, 6x1)   [6] beta = sqrt(Dinv) * b_l   [7] sqrt(Dinv) (ref slot)
+//                -> Schur term of a keyframe pair is -U_a U_b^T, reduced rhs term -U_a beta, x_l = sD (beta - sum U.x_p)
+//   edge record  [0..11] Bi (2x6, d/d observing KF PR, g2otypes.cpp:139-145)  [12..23] Br (2x6, d/d reference KF PR,
+//                :128-134)  [24..29] g = -Bi^T r
+//   point record [0..20] G0 = sum Br^T Br (upper 6x6 packed)  [21..26] g0 = -sum Br^T r  [27] D
+struct WinDesc {
+    int variant, algo;
+    int n_kf, n_free, n_pt, n_obs, n_imu;
+    int pdim, np, nS, nb;
+    int its[2];
+    int kf0, pt0, obs0, imu0;
+    int pair0, n_pairs;
+    int item0;      // offset into the item array
+    int pimu0;      // offset into the pair-imu list
+    int vec0;       // offset into rhs/x vectors (nS slots per window)
+    int part0;      // offset into the chi2 partial array
+    int n_part_lin; // workgroups of this window in the linearise launch (= chi2 partials; XYZ: also the max-diagonal partials)
+    int n_part_pt;  // 64-landmark blocks of the window (= the computeScale partials of k_update_xyz)
+    int lin_runs;   // 1: the window has the work split of the edge-parallel linearisation (lin_blk); 0: thread-per-landmark fallback
+    int tl_step0;   // offset of this window's step_begin / pan_begin rows (nb + 1 entries each)
+    int tl_pair0;   // offset into the tile-pair list
+    int tl_pan0;    // offset into the panel-tile list
+    int lb0;        // first record of the window in the k_lin2 run table
+    int win;        // index of this window in the uploaded batch: the CSR-style tables (pt_obs_begin, item_begin,
+                    // pimu_begin) carry one extra entry per window, so their rows start at offset + win
+    int tl_kb0;     // offset of this window's column-entry table of the left-looking factorisation (pan entries + nb + 1)
+    int tl_k0;      // offset into its k lists
+    int order;      // elimination order: 0 = V/Bias blocks first, 1 = keyframe by keyframe
+    int nc;         // chain columns: block columns [0, nc) are factored by k_chol_chain, the per-column kernels start at nc
+    int ct0;        // offset (records of four ints) of the window's chain-column table (Structure::chain_tab)
+    int cu0, n_cu;  // few-window regime: the window's tiles that collect updates from chain columns (k_chol_chain_upd)
+    int vp_pr0, vp_prs, vp_vb0, vp_vbs;  // position of dof r of free keyframe a: r < 6 ? pr0 + prs a + r : vb0 + vbs a + r - 6
+    int vp_h, vp_vb1;   // order 2 (two-sided): the V/Bias block of keyframe a >= vp_h sits at vp_vb1 - 9 a (other orders: vp_h = INT_MAX)
+    int pad0[3], padn[3];  // rows of S that belong to no variable (identity): up to three ranges (order 2 pads each chain and the tail)
+    int nc_split;       // > 0: the chain columns [0, nc_split) and [nc_split, nc) are independent (k_chol_chain_rows walks them side by side)
+    long long S0;   // offset (doubles) into S
+    long long mask0; // offset (64-bit words) of the window's landmark masks (n_pt x mwords)
+    int mwords;      // 64-bit words per landmark mask = ceil(n_kf / 64)
+    int adj0;        // offset into the keyframe adjacency list (PCG)
+    double K[4];
+    double Rcb[9], tcb[3], g[3];
+    double inv_bg, inv_ba;
+    double hub_vis, hub_prv, hub_bias;
+    double chi2_th, depth_min, rho_min;
+    int protocol;    // VBA_PROTO_*: 1 = one optimize(its[0]) and no outlier pass (global BA)
+    int robust;      // protocol 1: Huber on every edge, or on none
+};
+
+struct WinCtrl {
+    int stage;        // 0,1
+    int it;           // outer iteration inside the stage
+    int active;       // 1 while the stage's optimize() loop is still running for this window
+    int status;
+    int its_done[2];
+    int robust_vis;   // Huber on vision edges (stage 1)
+    int chol_fail;    // set by the factorisation of the current iteration
+    int aborted;      // stop flag seen
+    int n_trace;
+    int n_outliers;
+    // LM state (levenberg.cpp)
+    int lm_trial;     // trials done in the current outer iteration (qmax)
+    int lm_need_trial;// 1: another trial must run in this outer iteration
+    int lm_restore;   // 1: the last trial was rejected, k_restore must pop the state
+    int nbad;
+    int lin_its;      // PCG iterations of all solves so far
+    int polls;        // terminate() polls of this window so far (test hook vba_debug_set_stop_after; oracle twin: stop_now)
+    double lambda, ni;
+    double chi_prev;  // GN: preChi2 of the last started iteration.  LM: currentChi
+    double chi_ini;   // LM: iniChi
+    double chi2_vis, chi2_prv, chi2_bias;
+    double trace[VBA_TRACE];
+};

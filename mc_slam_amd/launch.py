@@ -39,7 +39,7 @@ def cpu_share(local_rank: int, local_world: int, cpus=None):
 
 def host_threads_for(n_cores: int) -> int:
     """threads of the backend's host pool (packing, structure build, scatter) for a rank that owns n_cores: as many as it has
-    cores, at most 16, at least 2 (mirrors host_threads() in csrc/vislam_ba.hip, which applies the same rule when the variable
+    cores, at most 16, at least 2 (mirrors host_threads() in csrc/vba_host_handle.h, which applies the same rule when the variable
     is absent)"""
     return max(2, min(16, n_cores))
 

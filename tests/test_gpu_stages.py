@@ -18,7 +18,7 @@ from mc_slam_amd import abi, synth, backend
 
 pytestmark = pytest.mark.gpu
 
-# capture items (vislam_ba.hip, CAP_*)
+# capture items (vba_host_run.h, CAP_*)
 POSE_A, VEL_A, BIAS_A, PT_A, CTRL_A, LVL_A, VARACT_A, S_B, VEC_B, LF_C, YV_C, VEC_C, POSE_D, VEL_D, BIAS_D, PT_D = range(16)
 SCHUR = {0: "k_schur_all_w", 1: "k_schur_all", 2: "k_schur_diag+k_schur_off_w", 3: "k_schur_diag+k_schur_off",
          4: "k_dinv+k_schur_diag3+k_schur_off3_w", 5: "k_dinv+k_schur_diag3+k_schur_off3"}
