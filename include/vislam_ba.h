@@ -123,7 +123,7 @@ typedef struct vba_profile {
     double total_ms;             /* first launch -> last launch of the run */
     double factor_flops;         /* FP64 flop the factorisation class executed on MFMA: 2*32^3 per tile product of the
                                     symbolic tile lists, per solve (structurally zero tiles are never touched) */
-    int64_t kernel_launches;     /* kernel launches the last vba_batch_run / vba_solve / vba_sim3_optimize enqueued (filled with or without profiling) */
+    int64_t kernel_launches;     /* kernel launches the last vba_batch_run / vba_solve / vba_sim3_optimize / vba_posegraph_optimize enqueued (filled with or without profiling) */
 } vba_profile;
 
 /* One handle per host thread / GPU; owns device buffers and a stream.  Errors: nonzero return, message
@@ -178,7 +178,7 @@ int vba_batch_solve_b(void *handle, int32_t n_windows, vba_problem *const *inout
  *           every later one, those submitted afterwards included, with the same message: no GPU work starts for them (earlier
  *           tickets finish).  Waiting on an unknown or retired ticket returns -1.
  *   handle  while any ticket is submitted and not yet waited for, every synchronous entry point of the handle (vba_solve*,
- *           vba_batch_upload / run / download / solve*, vba_pose_optimize, vba_sim3_optimize, vba_preintegrate, vba_set_profile,
+ *           vba_batch_upload / run / download / solve*, vba_pose_optimize, vba_sim3_optimize, vba_posegraph_optimize, vba_preintegrate, vba_set_profile,
  *           vba_batch_set_depth) returns -1 with "asynchronous batches pending: wait for them first"; afterwards the handle
  *           works synchronously as before.  vba_destroy finishes pending tickets (their results land) before it frees.
  *           Profiling (vba_set_profile) covers synchronous calls only.  One caller thread at a time, as everywhere. */
@@ -284,6 +284,48 @@ typedef struct vba_sim3_result {
  * (negative n_pairs, NULL array with n_pairs > 0, non-finite S12, scale <= 0, zero quaternion, a budget below 1) fails the whole
  * call before any GPU work, message through vba_last_error.  No upper bound on n_pairs. */
 int vba_sim3_optimize(void *handle, int32_t n_problems, vba_sim3_problem *const *inout, vba_sim3_result *const *out);
+
+/* ---- essential-graph optimisation (Sim3 pose graph) ----
+ * Optimizer::OptimizeEssentialGraph(Map*, KeyFrame* pLoopKF, KeyFrame* pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections,
+ * bFixScale, LoopClosing*)   src/Optimizer.cpp:4243-4552
+ * Everything between the vertex / edge set-up (:4284-4478) and the write-back (:4488-4546): optimize(20) with Levenberg-Marquardt,
+ * setUserLambdaInit(1e-16) (:4256-4266, :4481-4482; schedule of optimization_algorithm_levenberg.cpp:61-164), over one
+ * VertexSim3Expmap per keyframe (types_seven_dof_expmap.h:48-94) and EdgeSim3 edges (:100-124) with identity information and no
+ * robust kernel; error log(Sji * Siw * Sjw^-1) (sim3.h:148-230); Jacobians by g2o's own central differences with delta = 1e-9
+ * through oplus (base_binary_edge.hpp:131-205: EdgeSim3 has no linearizeOplus); then every map point moved through its reference
+ * keyframe (:4511-4546).  The four pair rules that choose the edges (:4331-4478) are host work and stay with the caller.  One call
+ * takes any number of independent graphs (one workgroup per graph; one kernel launch per call, two with map points). */
+typedef struct vba_posegraph_problem {
+    int32_t n_vertices, n_edges;
+    int32_t fix_scale;            /* bFixScale: VertexSim3Expmap::_fix_scale (update[6] = 0, types_seven_dof_expmap.h:60-69) */
+    int32_t its;                  /* 20 (:4482); at least 1 */
+    double  lambda_init;          /* 1e-16 (:4260); must be > 0 */
+    double *S;                    /* [n_vertices][8] in/out: Siw as t(3) q(4, xyzw) s, the vba_sim3_problem.S12 layout (:4284-4325);
+                                   * the caller forms Tiw = [R, t/s] from it (:4488-4508) */
+    const uint8_t *fixed;         /* [n_vertices] 1 = setFixed(true): the loop keyframe (:4312-4313) */
+    const int32_t *edge_i, *edge_j; /* [n_edges] vertex 0 / vertex 1 of EdgeSim3 (:4349-4350 and the like); a pair may occur twice */
+    const double *edge_S;         /* [n_edges][8] measurement Sji, same layout (:4347, :4393, :4419, :4454) */
+    int32_t n_pt;                 /* 0 = no map-point correction */
+    double *pt;                   /* [n_pt][3] in/out world positions: correctedSwr.map(Srw.map(P)) (:4540-4543) */
+    const int32_t *pt_ref;        /* [n_pt] vertex whose pose change carries the point (:4518-4530) */
+} vba_posegraph_problem;
+
+typedef struct vba_posegraph_result {
+    int32_t status;               /* VBA_OK */
+    int32_t its_done;             /* cjIterations */
+    int32_t lm_trials;            /* LM trials summed over the iterations */
+    int32_t stop;                 /* 0 budget used up, 1 ten trials failed, 2 rho == 0, 3 _nBad >= 3 */
+    double chi2_initial, chi2_final, lambda_final;
+} vba_posegraph_result;
+
+/* Synchronous, like vba_sim3_optimize; -1 while asynchronous tickets are pending.  n_graphs == 0 returns 0.  Bad input fails the
+ * whole call before any GPU work, with a message naming the graph: negative counts, a NULL array with a non-zero count, an edge
+ * index out of range, edge_i == edge_j, an edge between two fixed vertices, a non-finite entry / zero quaternion / scale <= 0 in S
+ * or edge_S, its < 1, lambda_init <= 0, pt_ref out of range, a graph with no free vertex, and a call whose factors exceed 2^21
+ * 7x7 blocks (mc_slam_amd/csrc/vba_host_posegraph.h).  Duplicate edges and vertices without edges are legal.  A graph with a
+ * component that holds no fixed vertex is singular: it does what Levenberg-Marquardt does with it and its status stays VBA_OK. */
+int vba_posegraph_optimize(void *handle, int32_t n_graphs, vba_posegraph_problem *const *inout,
+                           vba_posegraph_result *const *out);
 
 /* ---- on-disk problem format: one vba_problem per file, so that windows recorded from a live system can
  * be replayed as fixtures.  Little-endian; header "VBAP" u32 version(=2) then the scalar fields in struct order

@@ -482,3 +482,81 @@ class Sim3ResultBuf:
         return Sim3Result(s.n_inliers, s.status, s.n_bad_stage1, tuple(s.its_done), np.array(s.chi2_stage[:]), self.o[:self.n].copy(),
                           self.c12[:self.n].copy() if self.want_chi2 else None, self.c21[:self.n].copy() if self.want_chi2 else None,
                           np.array(st.S12[:]))
+
+
+# ---- essential-graph optimisation (include/vislam_ba.h: vba_posegraph_problem / vba_posegraph_result) ----
+class vba_posegraph_problem(C.Structure):
+    _fields_ = [
+        ("n_vertices", C.c_int32), ("n_edges", C.c_int32), ("fix_scale", C.c_int32), ("its", C.c_int32),
+        ("lambda_init", C.c_double), ("S", _pd), ("fixed", _pu8), ("edge_i", _pi), ("edge_j", _pi), ("edge_S", _pd),
+        ("n_pt", C.c_int32), ("pt", _pd), ("pt_ref", _pi),
+    ]
+
+
+class vba_posegraph_result(C.Structure):
+    _fields_ = [
+        ("status", C.c_int32), ("its_done", C.c_int32), ("lm_trials", C.c_int32), ("stop", C.c_int32),
+        ("chi2_initial", C.c_double), ("chi2_final", C.c_double), ("lambda_final", C.c_double),
+    ]
+
+
+@dataclass
+class PoseGraphProblem:
+    """One Optimizer::OptimizeEssentialGraph call (src/Optimizer.cpp:4243-4552) as flat arrays: the Sim3 vertices, the EdgeSim3
+    edges its four pair rules chose, and the map points with their reference vertices."""
+    S: np.ndarray                  # [n,8] Siw as t(3) q(4, xyzw) s
+    fixed: np.ndarray              # [n] uint8
+    edge_i: np.ndarray             # [m] vertex 0
+    edge_j: np.ndarray             # [m] vertex 1
+    edge_S: np.ndarray             # [m,8] measurement Sji
+    fix_scale: int = 0
+    its: int = 20
+    lambda_init: float = 1e-16
+    pt: Optional[np.ndarray] = None      # [k,3]
+    pt_ref: Optional[np.ndarray] = None  # [k]
+    truth: dict = field(default_factory=dict)
+
+    def __post_init__(self):
+        self.S = _f64(self.S, (-1, 8))
+        self.fixed = np.ascontiguousarray(self.fixed, dtype=np.uint8).reshape(-1)
+        self.edge_i = _i32(self.edge_i).reshape(-1)
+        self.edge_j = _i32(self.edge_j).reshape(-1)
+        self.edge_S = _f64(self.edge_S, (-1, 8))
+        self.pt = _f64(self.pt if self.pt is not None else np.zeros((0, 3)), (-1, 3))
+        self.pt_ref = _i32(self.pt_ref if self.pt_ref is not None else []).reshape(-1)
+
+    n_vertices = property(lambda self: self.S.shape[0])
+    n_edges = property(lambda self: self.edge_i.shape[0])
+    n_pt = property(lambda self: self.pt.shape[0])
+
+    def copy(self, **changes):
+        import copy as _c
+        q = _c.copy(self)
+        q.S = self.S.copy()
+        q.pt = self.pt.copy()
+        for k, v in changes.items():
+            setattr(q, k, v)
+        return q
+
+    def as_struct(self) -> vba_posegraph_problem:
+        s = vba_posegraph_problem()
+        s.n_vertices, s.n_edges, s.fix_scale, s.its = self.n_vertices, self.n_edges, int(self.fix_scale), int(self.its)
+        s.lambda_init = self.lambda_init
+        s.S, s.fixed = self.S.ctypes.data_as(_pd), self.fixed.ctypes.data_as(_pu8)
+        s.edge_i, s.edge_j, s.edge_S = self.edge_i.ctypes.data_as(_pi), self.edge_j.ctypes.data_as(_pi), self.edge_S.ctypes.data_as(_pd)
+        s.n_pt = self.n_pt
+        s.pt, s.pt_ref = self.pt.ctypes.data_as(_pd), self.pt_ref.ctypes.data_as(_pi)
+        return s
+
+
+@dataclass
+class PoseGraphResult:
+    status: int
+    its_done: int
+    lm_trials: int
+    stop: int
+    chi2_initial: float
+    chi2_final: float
+    lambda_final: float
+    S: np.ndarray                  # [n,8] the optimised estimates
+    pt: np.ndarray                 # [k,3] the corrected map points

@@ -18,7 +18,8 @@ _libs = {}
 
 EXPORTS = ["vba_create", "vba_destroy", "vba_last_error", "vba_solve", "vba_batch_upload", "vba_batch_run",
            "vba_batch_download", "vba_batch_solve", "vba_solve_b", "vba_batch_run_b", "vba_batch_solve_b", "vba_preintegrate", "vba_pose_optimize", "vba_problem_save", "vba_problem_load", "vba_problem_free", "vba_set_profile", "vba_get_profile", "vba_host_threads",
-           "vba_batch_set_depth", "vba_batch_submit", "vba_batch_submit_b", "vba_batch_poll", "vba_batch_wait", "vba_sim3_optimize"]
+           "vba_batch_set_depth", "vba_batch_submit", "vba_batch_submit_b", "vba_batch_poll", "vba_batch_wait", "vba_sim3_optimize",
+           "vba_posegraph_optimize"]
 
 
 def load_library(hooks=False):
@@ -49,6 +50,8 @@ def load_library(hooks=False):
     lib.vba_preintegrate.argtypes = [C.c_void_p, C.c_int32, _pi, _pd, _pd, _pd, C.c_double, C.c_double, _pd, _pd, _pd]
     lib.vba_pose_optimize.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.POINTER(abi.vba_frame_problem)), C.POINTER(C.POINTER(abi.vba_frame_result))]
     lib.vba_sim3_optimize.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.POINTER(abi.vba_sim3_problem)), C.POINTER(C.POINTER(abi.vba_sim3_result))]
+    lib.vba_posegraph_optimize.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.POINTER(abi.vba_posegraph_problem)),
+                                           C.POINTER(C.POINTER(abi.vba_posegraph_result))]
     lib.vba_set_profile.argtypes = [C.c_void_p, C.c_int32]
     lib.vba_get_profile.argtypes = [C.c_void_p, C.POINTER(abi.vba_profile)]
     lib.vba_batch_set_depth.argtypes = [C.c_void_p, C.c_int32]
@@ -58,6 +61,8 @@ def load_library(hooks=False):
     lib.vba_batch_wait.argtypes = [C.c_void_p, C.c_int64]
     if hooks:
         lib.vba_debug_async_hold.argtypes = [C.c_void_p, C.c_int32]
+        lib.vba_debug_posegraph_system.argtypes = [C.c_void_p, C.POINTER(abi.vba_posegraph_problem), _pd, _pd, _pd]
+        lib.vba_debug_posegraph_system.restype = C.c_int
     for n in EXPORTS:
         if n != "vba_last_error":
             getattr(lib, n).restype = C.c_int
@@ -273,6 +278,47 @@ class LocalBA:
         packed = self.sim3_pack(problems, want_chi2)
         self.sim3_call(packed)
         return [b.get(s) for b, s in zip(packed[2], packed[1])]
+
+    # ---- essential-graph optimisation (vba_posegraph_optimize): a batch of independent Sim3 pose graphs per call ----
+    def posegraph_pack(self, problems):
+        """private copies of a list of abi.PoseGraphProblem and the ctypes views vba_posegraph_optimize needs (kept alive by the
+        returned tuple); the call updates the copies' S and pt in place"""
+        n = len(problems)
+        own = [p.copy() for p in problems]
+        structs = [p.as_struct() for p in own]
+        res = [abi.vba_posegraph_result() for _ in own]
+        pp = (C.POINTER(abi.vba_posegraph_problem) * n)(*[C.pointer(s) for s in structs])
+        rr = (C.POINTER(abi.vba_posegraph_result) * n)(*[C.pointer(r) for r in res])
+        return n, structs, res, pp, rr, problems, own
+
+    def posegraph_reset(self, packed):
+        """put the initial estimates and points back before the next run"""
+        for q, p in zip(packed[6], packed[5]):
+            q.S[...] = p.S
+            q.pt[...] = p.pt
+
+    def posegraph_call(self, packed):
+        if self.lib.vba_posegraph_optimize(self.h, packed[0], packed[3], packed[4]) != 0:
+            raise self._err("vba_posegraph_optimize")
+
+    def posegraph_optimize(self, problems):
+        """vba_posegraph_optimize on copies of a list of abi.PoseGraphProblem: list of abi.PoseGraphResult"""
+        packed = self.posegraph_pack(problems)
+        self.posegraph_call(packed)
+        return [abi.PoseGraphResult(r.status, r.its_done, r.lm_trials, r.stop, r.chi2_initial, r.chi2_final, r.lambda_final,
+                                    q.S.copy(), q.pt.copy()) for r, q in zip(packed[2], packed[6])]
+
+    def posegraph_system(self, problem):
+        """hooks flavour: (H dense, b, x of the first trial of the first iteration) as k_posegraph_opt formed them"""
+        import numpy as np
+        q = problem.copy()
+        s = q.as_struct()
+        n = 7 * int((q.fixed == 0).sum())
+        H, b, x = np.zeros((n, n)), np.zeros(n), np.zeros(n)
+        P = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        if self.lib.vba_debug_posegraph_system(self.h, C.byref(s), P(H), P(b), P(x)) != 0:
+            raise self._err("vba_debug_posegraph_system")
+        return H, b, x
 
     def set_profile(self, on=True):
         self.lib.vba_set_profile(self.h, 1 if on else 0)

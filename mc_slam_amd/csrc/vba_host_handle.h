@@ -204,6 +204,8 @@ struct Handle {
     PinnedBuf pose_host_in, pose_host_out;  // its pinned staging: one H2D and one D2H per call
     DevBuf sim3_arena;  // arena of vba_sim3_optimize
     PinnedBuf sim3_host_in, sim3_host_out;  // its pinned staging, same scheme
+    DevBuf pg_arena;    // arena of vba_posegraph_optimize
+    PinnedBuf pg_host_in, pg_host_out;      // its pinned staging, same scheme
     // small batches (<= 8 windows): every host-built array of an upload goes through ONE pinned arena and ONE H2D copy into one
     // device arena (a single window is ~25 arrays of a few KB to a few 100 KB: 25 copies cost 0.4 ms of queue latency)
     struct Pending { int id; const void* src; size_t bytes; };

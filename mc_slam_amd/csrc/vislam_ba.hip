@@ -1,5 +1,5 @@
 // vislam_ba.hip -- C-ABI (include/vislam_ba.h) of the MI355X local-BA backend, one translation unit: the kernel headers, the host
-// side by topic (vba_host_handle.h: handle and buffers, vba_host_upload.h: H2D + structure build, vba_host_run.h: the lock-step
+// side by topic (vba_host_structure.h / vba_host_posegraph.h: the plain-C++ structure builds, vba_host_handle.h: handle and buffers, vba_host_upload.h: H2D + structure build, vba_host_run.h: the lock-step
 // launch schedule of the two-stage solve and the download, vba_host_batch.h: lanes and tickets, vba_host_hooks.h), and below the
 // extern "C" entry points.
 //
@@ -9,11 +9,13 @@
 // point fails with an error.
 #include "../../include/vislam_ba.h"
 #include "vba_host_structure.h"
+#include "vba_host_posegraph.h"
 #include "vba_problem_io.h"
 #include "vba_kernels_lm.h"
 #include "vba_preint.h"
 #include "vba_pose.h"
 #include "vba_sim3.h"
+#include "vba_posegraph.h"
 #include "vba_structure.h"
 #include "vba_pcg.h"
 #include "vba_chain.h"
@@ -61,6 +63,9 @@ int vba_destroy(void* handle) {
     h->sim3_arena.release();
     h->sim3_host_in.release();
     h->sim3_host_out.release();
+    h->pg_arena.release();
+    h->pg_host_in.release();
+    h->pg_host_out.release();
     for (auto e : h->evt_pool) (void)hipEventDestroy(e);
     if (h->up_done) (void)hipEventDestroy(h->up_done);
     if (h->owns_streams)
@@ -438,6 +443,163 @@ int vba_sim3_optimize(void* handle, int32_t n_problems, vba_sim3_problem* const*
     }
     return 0;
 }
+
+namespace {
+// what vba_debug_posegraph_system asks of a run: graph 0 stops after the solve of its first trial, and H, b, x come back
+struct PgDebug { double *H, *b, *x; };
+
+// Optimizer::OptimizeEssentialGraph (src/Optimizer.cpp:4243-4552) between edge set-up and write-back, for a batch of independent
+// graphs: the host validates every graph and lays out its envelope (vba_host_posegraph.h), one staging block [desc | estimates |
+// measurements | index lists | points] goes up in one copy, k_posegraph_opt runs one workgroup per graph, k_posegraph_points moves
+// the map points when there are any, and [out | estimates | points] come back in one copy.
+static int posegraph_run(Handle* h, int32_t n_graphs, vba_posegraph_problem* const* inout, vba_posegraph_result* const* out, PgDebug* dbg) {
+    if (n_graphs < 0 || (n_graphs > 0 && (!inout || !out))) return fail(h, "vba_posegraph_optimize: bad arguments");
+    if (n_graphs == 0) return 0;
+    std::vector<vba_host::PoseGraphLayout> lay(n_graphs);
+    std::vector<PgDesc> hd(n_graphs);
+    size_t nv = 0, ne = 0, nf = 0, nenv = 0, ninc = 0, npair = 0, npe = 0, npt = 0;
+    for (int g = 0; g < n_graphs; g++) {
+        std::string err;
+        if (!inout[g] || !out[g]) return fail(h, "vba_posegraph_optimize: graph " + std::to_string(g) + ": NULL problem or result");
+        if (vba_host::build_posegraph(inout[g], lay[g], err, (long long)nenv))
+            return fail(h, "vba_posegraph_optimize: graph " + std::to_string(g) + ": " + err);
+        const vba_posegraph_problem* P = inout[g];
+        const vba_host::PoseGraphLayout& L = lay[g];
+        PgDesc& d = hd[g];
+        std::memset(&d, 0, sizeof d);
+        d.nv = P->n_vertices; d.ne = P->n_edges; d.nf = L.n_free; d.npair = (int)L.pair_lo.size();
+        d.fix_scale = P->fix_scale ? 1 : 0; d.its = P->its; d.n_pt = P->n_pt; d.debug = (dbg && g == 0) ? 1 : 0;
+        d.lambda_init = P->lambda_init;
+        d.v0 = (long long)nv; d.e0 = (long long)ne; d.f0 = (long long)nf; d.r0 = (long long)nf + g; d.env0 = (long long)nenv;
+        d.inc0 = (long long)ninc; d.pair0 = (long long)npair; d.pb0 = (long long)npair + g; d.pe0 = (long long)npe; d.pt0 = (long long)npt;
+        nv += (size_t)d.nv; ne += (size_t)d.ne; nf += (size_t)d.nf; nenv += (size_t)L.env_blocks; ninc += L.inc.size();
+        npair += L.pair_lo.size(); npe += L.pair_edge.size(); npt += (size_t)d.n_pt;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    // regions of the arena, each a multiple of 256 bytes: [upload | back | work]
+    size_t cur = 0;
+    auto take = [&cur](size_t bytes) { const size_t o = cur; cur += (bytes + 8 + 255) / 256 * 256; return o; };
+    const size_t G = (size_t)n_graphs;
+    const size_t o_desc = take(sizeof(PgDesc) * G), o_Sin = take(64 * nv), o_meas = take(64 * ne), o_ei = take(4 * ne), o_ej = take(4 * ne);
+    const size_t o_free = take(4 * nv), o_vert = take(4 * nf), o_first = take(4 * nf), o_last = take(4 * nf), o_roff = take(4 * (nf + G));
+    const size_t o_incb = take(4 * (nf + G)), o_inc = take(4 * ninc), o_plo = take(4 * npair), o_phi = take(4 * npair);
+    const size_t o_pb = take(4 * (npair + G)), o_pe = take(4 * npe), o_pt = take(24 * npt), o_ref = take(4 * npt);
+    const size_t b_in = cur;
+    const size_t o_out = take(sizeof(PgOut) * G), o_S = take(64 * nv), o_pto = take(24 * npt);
+    const size_t b_back = cur - b_in;
+    const size_t o_Sbk = take(64 * nv), o_err = take(56 * ne), o_J = take(784 * ne), o_H = take(392 * nenv), o_F = take(392 * nenv);
+    const size_t o_Ld = take(392 * nf), o_b = take(56 * nf), o_w = take(56 * nf), o_y = take(56 * nf), o_x = take(56 * nf);
+    HIPCHK(h, h->pg_arena.ensure(cur));
+    HIPCHK(h, h->pg_host_in.ensure(b_in));
+    HIPCHK(h, h->pg_host_out.ensure(b_back));
+    char* hin = reinterpret_cast<char*>(h->pg_host_in.p);
+    std::memcpy(hin + o_desc, hd.data(), sizeof(PgDesc) * G);
+    auto pack = [&](int g) {
+        const vba_posegraph_problem* P = inout[g];
+        const vba_host::PoseGraphLayout& L = lay[g];
+        const PgDesc& d = hd[g];
+        auto put = [hin](size_t o, size_t at, const void* src, size_t bytes) { if (bytes) std::memcpy(hin + o + at, src, bytes); };
+        put(o_Sin, 64 * (size_t)d.v0, P->S, 64 * (size_t)d.nv);
+        put(o_meas, 64 * (size_t)d.e0, P->edge_S, 64 * (size_t)d.ne);
+        put(o_ei, 4 * (size_t)d.e0, P->edge_i, 4 * (size_t)d.ne);
+        put(o_ej, 4 * (size_t)d.e0, P->edge_j, 4 * (size_t)d.ne);
+        put(o_free, 4 * (size_t)d.v0, L.free_of.data(), 4 * (size_t)d.nv);
+        put(o_vert, 4 * (size_t)d.f0, L.vert_of.data(), 4 * (size_t)d.nf);
+        put(o_first, 4 * (size_t)d.f0, L.first.data(), 4 * (size_t)d.nf);
+        put(o_last, 4 * (size_t)d.f0, L.last_row.data(), 4 * (size_t)d.nf);
+        put(o_roff, 4 * (size_t)d.r0, L.row_off.data(), 4 * ((size_t)d.nf + 1));
+        put(o_incb, 4 * (size_t)d.r0, L.inc_begin.data(), 4 * ((size_t)d.nf + 1));
+        put(o_inc, 4 * (size_t)d.inc0, L.inc.data(), 4 * L.inc.size());
+        put(o_plo, 4 * (size_t)d.pair0, L.pair_lo.data(), 4 * L.pair_lo.size());
+        put(o_phi, 4 * (size_t)d.pair0, L.pair_hi.data(), 4 * L.pair_hi.size());
+        put(o_pb, 4 * (size_t)d.pb0, L.pair_begin.data(), 4 * L.pair_begin.size());
+        put(o_pe, 4 * (size_t)d.pe0, L.pair_edge.data(), 4 * L.pair_edge.size());
+        put(o_pt, 24 * (size_t)d.pt0, P->pt, 24 * (size_t)d.n_pt);
+        int* ref = reinterpret_cast<int*>(hin + o_ref) + d.pt0;
+        for (int p = 0; p < d.n_pt; p++) ref[p] = (int)d.v0 + P->pt_ref[p];   // index into the concatenated vertices
+    };
+    for (int g = 0; g < n_graphs; g++) pack(g);
+    char* base = reinterpret_cast<char*>(h->pg_arena.p);
+    PgBatch B;
+    auto cd = [base](size_t o) { return reinterpret_cast<const double*>(base + o); };
+    auto ci = [base](size_t o) { return reinterpret_cast<const int*>(base + o); };
+    auto md = [base](size_t o) { return reinterpret_cast<double*>(base + o); };
+    B.desc = reinterpret_cast<const PgDesc*>(base + o_desc);
+    B.out = reinterpret_cast<PgOut*>(base + o_out);
+    B.Sin = cd(o_Sin); B.meas = cd(o_meas); B.ei = ci(o_ei); B.ej = ci(o_ej); B.free_of = ci(o_free);
+    B.vert_of = ci(o_vert); B.first = ci(o_first); B.last_row = ci(o_last); B.row_off = ci(o_roff); B.inc_begin = ci(o_incb);
+    B.inc = ci(o_inc); B.pair_lo = ci(o_plo); B.pair_hi = ci(o_phi); B.pair_begin = ci(o_pb); B.pair_edge = ci(o_pe);
+    B.pt_in = cd(o_pt); B.pt_ref = ci(o_ref);
+    B.S = md(o_S); B.Sbk = md(o_Sbk); B.err = md(o_err); B.J = md(o_J); B.H = md(o_H); B.F = md(o_F); B.Ld = md(o_Ld);
+    B.b = md(o_b); B.w = md(o_w); B.y = md(o_y); B.x = md(o_x); B.pt_out = md(o_pto);
+    B.n_pt_total = (long long)npt;
+    const long long launch0 = h->n_launch;
+    HIPCHK(h, hipMemcpyAsync(base, hin, b_in, hipMemcpyHostToDevice, h->stream));
+    VBA_LAUNCH(k_posegraph_opt, dim3(n_graphs), dim3(PG_NT), 0, h->stream, B);
+    HIPCHK(h, hipGetLastError());
+    if (npt > 0 && !dbg) {
+        VBA_LAUNCH(k_posegraph_points, dim3((unsigned)((npt + 255) / 256)), dim3(256), 0, h->stream, B);
+        HIPCHK(h, hipGetLastError());
+    }
+    char* hout = reinterpret_cast<char*>(h->pg_host_out.p);
+    HIPCHK(h, hipMemcpyAsync(hout, base + b_in, b_back, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->prof.kernel_launches = h->n_launch - launch0;
+    if (dbg) {   // graph 0 as the kernel formed it: the envelope expanded to a dense symmetric matrix, b, x
+        const vba_host::PoseGraphLayout& L = lay[0];
+        const size_t n = 7 * (size_t)L.n_free;
+        std::vector<double> env(49 * (size_t)L.env_blocks);
+        HIPCHK(h, hipMemcpy(env.data(), base + o_H, env.size() * 8, hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(dbg->b, base + o_b, n * 8, hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(dbg->x, base + o_x, n * 8, hipMemcpyDeviceToHost));
+        std::fill(dbg->H, dbg->H + n * n, 0.0);
+        for (int r = 0; r < L.n_free; r++)
+            for (int c = L.first[r]; c <= r; c++) {
+                const double* blk = env.data() + 49 * (size_t)(L.row_off[r] + c - L.first[r]);
+                for (int a = 0; a < 7; a++)
+                    for (int k = 0; k < 7; k++) {
+                        dbg->H[(7 * (size_t)r + a) * n + 7 * (size_t)c + k] = blk[7 * a + k];
+                        if (c < r) dbg->H[(7 * (size_t)c + k) * n + 7 * (size_t)r + a] = blk[7 * a + k];
+                    }
+            }
+        return 0;
+    }
+    const PgOut* res = reinterpret_cast<const PgOut*>(hout + (o_out - b_in));
+    const double* Sf = reinterpret_cast<const double*>(hout + (o_S - b_in));
+    const double* pf = reinterpret_cast<const double*>(hout + (o_pto - b_in));
+    for (int g = 0; g < n_graphs; g++) {
+        vba_posegraph_problem* P = inout[g];
+        vba_posegraph_result* R = out[g];
+        const PgDesc& d = hd[g];
+        const PgOut& r = res[g];
+        R->status = r.status; R->its_done = r.its_done; R->lm_trials = r.lm_trials; R->stop = r.stop;
+        R->chi2_initial = r.chi2_initial; R->chi2_final = r.chi2_final; R->lambda_final = r.lambda_final;
+        if (d.nv) std::memcpy(P->S, Sf + 8 * (size_t)d.v0, 64 * (size_t)d.nv);   // fixed vertices: the input, bit for bit
+        if (d.n_pt) std::memcpy(P->pt, pf + 3 * (size_t)d.pt0, 24 * (size_t)d.n_pt);
+    }
+    return 0;
+}
+}  // namespace
+
+int vba_posegraph_optimize(void* handle, int32_t n_graphs, vba_posegraph_problem* const* inout, vba_posegraph_result* const* out) {
+    Handle* h = reinterpret_cast<Handle*>(handle);
+    if (!h || async_busy(h)) return -1;
+    return posegraph_run(h, n_graphs, inout, out, nullptr);
+}
+
+#ifdef VBA_TEST_HOOKS
+// test hook (not part of include/vislam_ba.h): H (dense, [7 n_free]^2 row-major), b and the x of the first trial of the first
+// iteration of one graph, as k_posegraph_opt formed them; the graph's arrays are left untouched
+int vba_debug_posegraph_system(void* handle, vba_posegraph_problem* graph, double* H, double* b, double* x) {
+    Handle* h = reinterpret_cast<Handle*>(handle);
+    if (!h || async_busy(h)) return -1;
+    if (!graph || !H || !b || !x) return fail(h, "vba_debug_posegraph_system: bad arguments");
+    PgDebug dbg{H, b, x};
+    vba_posegraph_result r;
+    vba_posegraph_result* rp = &r;
+    return posegraph_run(h, 1, &graph, &rp, &dbg);
+}
+#endif
 
 int vba_set_profile(void* handle, int32_t enable) {
     Handle* h = reinterpret_cast<Handle*>(handle);

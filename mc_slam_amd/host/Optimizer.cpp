@@ -990,6 +990,168 @@ int Optimizer::OptimizeSim3(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoint
     return R.n_inliers;
 }
 
+namespace {
+thread_local PackedPoseGraph t_last_pg;
+void put_sim3(const g2o::Sim3& S, std::vector<double>& v) {
+    for (int k = 0; k < 3; k++) v.push_back(S.translation()[k]);
+    for (int k = 0; k < 4; k++) v.push_back(S.rotation()[k]);
+    v.push_back(S.scale());
+}
+}  // namespace
+PackedPoseGraph& Optimizer::LastPoseGraph() { return t_last_pg; }
+
+bool Optimizer::PackEssentialGraph(Map* pMap, KeyFrame* pLoopKF, KeyFrame* pCurKF, const LoopClosing::KeyFrameAndPose& NonCorrectedSim3,
+                                   const LoopClosing::KeyFrameAndPose& CorrectedSim3,
+                                   const std::map<KeyFrame*, std::set<KeyFrame*>>& LoopConnections, bool bFixScale, PackedPoseGraph& G) {
+    G = PackedPoseGraph();
+    const std::vector<KeyFrame*> vpKFs = pMap->GetAllKeyFrames();
+    const std::vector<MapPoint*> vpMPs = pMap->GetAllMapPoints();
+    const unsigned int nMaxKFid = pMap->GetMaxKFid();
+    std::vector<g2o::Sim3> vScw(nMaxKFid + 1);
+    std::vector<int> vVertex(nMaxKFid + 1, -1);       // optimizer.vertex(id): -1 where the reference has none (bad keyframes)
+    const int minFeat = 100;
+    for (size_t i = 0, iend = vpKFs.size(); i < iend; i++) {                                                      // :4284-4325
+        KeyFrame* pKF = vpKFs[i];
+        if (pKF->isBad()) continue;
+        const int nIDi = pKF->mnId;
+        LoopClosing::KeyFrameAndPose::const_iterator it = CorrectedSim3.find(pKF);
+        if (it != CorrectedSim3.end()) {
+            vScw[nIDi] = it->second;
+        } else {
+            double R[9], t[3];
+            pKF->GetRotation(R);
+            pKF->GetTranslation(t);
+            Matrix3d Rcw;
+            for (int k = 0; k < 9; k++) Rcw[k] = R[k];
+            vScw[nIDi] = g2o::Sim3(MatrixToQuat(Rcw), {{t[0], t[1], t[2]}}, 1.0);                                 // Sim3(Matrix3d, ...): Quaterniond(R)
+        }
+        vVertex[nIDi] = (int)G.vKF.size();
+        G.vKF.push_back(pKF);
+        put_sim3(vScw[nIDi], G.S);
+        G.fixed.push_back(pKF == pLoopKF ? 1 : 0);                                                                // :4314-4315
+    }
+    // an edge of the reference whose vertex does not exist is refused by addEdge; one between two fixed vertices cannot occur
+    // (there is one fixed vertex)
+    auto addEdge = [&](long unsigned int nIDi, long unsigned int nIDj, const g2o::Sim3& Sji) {
+        if (nIDi > nMaxKFid || nIDj > nMaxKFid || vVertex[nIDi] < 0 || vVertex[nIDj] < 0 || nIDi == nIDj) return;
+        G.ei.push_back(vVertex[nIDi]);
+        G.ej.push_back(vVertex[nIDj]);
+        put_sim3(Sji, G.edgeS);
+    };
+    std::set<std::pair<long unsigned int, long unsigned int>> sInsertedEdges;
+    for (std::map<KeyFrame*, std::set<KeyFrame*>>::const_iterator mit = LoopConnections.begin(), mend = LoopConnections.end(); mit != mend; mit++) {
+        KeyFrame* pKF = mit->first;                                                                               // :4331-4365
+        const long unsigned int nIDi = pKF->mnId;
+        const std::set<KeyFrame*>& spConnections = mit->second;
+        const g2o::Sim3 Siw = vScw[nIDi];
+        const g2o::Sim3 Swi = Siw.inverse();
+        for (std::set<KeyFrame*>::const_iterator sit = spConnections.begin(), send = spConnections.end(); sit != send; sit++) {
+            const long unsigned int nIDj = (*sit)->mnId;
+            if ((nIDi != pCurKF->mnId || nIDj != pLoopKF->mnId) && pKF->GetWeight(*sit) < minFeat) continue;
+            const g2o::Sim3 Sjw = vScw[nIDj];
+            addEdge(nIDi, nIDj, Sjw * Swi);
+            sInsertedEdges.insert(std::make_pair(std::min(nIDi, nIDj), std::max(nIDi, nIDj)));
+        }
+    }
+    for (size_t i = 0, iend = vpKFs.size(); i < iend; i++) {                                                      // :4368-4478
+        KeyFrame* pKF = vpKFs[i];
+        const int nIDi = pKF->mnId;
+        g2o::Sim3 Swi;
+        LoopClosing::KeyFrameAndPose::const_iterator iti = NonCorrectedSim3.find(pKF);
+        if (iti != NonCorrectedSim3.end()) Swi = (iti->second).inverse();
+        else Swi = vScw[nIDi].inverse();
+        KeyFrame* pParentKF = pKF->GetParent();
+        if (pParentKF) {                                                                                          // spanning tree
+            const int nIDj = pParentKF->mnId;
+            g2o::Sim3 Sjw;
+            LoopClosing::KeyFrameAndPose::const_iterator itj = NonCorrectedSim3.find(pParentKF);
+            if (itj != NonCorrectedSim3.end()) Sjw = itj->second;
+            else Sjw = vScw[nIDj];
+            addEdge(nIDi, nIDj, Sjw * Swi);
+        }
+        const std::set<KeyFrame*> sLoopEdges = pKF->GetLoopEdges();                                               // loop edges
+        for (std::set<KeyFrame*>::const_iterator sit = sLoopEdges.begin(), send = sLoopEdges.end(); sit != send; sit++) {
+            KeyFrame* pLKF = *sit;
+            if (pLKF->mnId < pKF->mnId) {
+                g2o::Sim3 Slw;
+                LoopClosing::KeyFrameAndPose::const_iterator itl = NonCorrectedSim3.find(pLKF);
+                if (itl != NonCorrectedSim3.end()) Slw = itl->second;
+                else Slw = vScw[pLKF->mnId];
+                addEdge(nIDi, pLKF->mnId, Slw * Swi);
+            }
+        }
+        const std::vector<KeyFrame*> vpConnectedKFs = pKF->GetCovisiblesByWeight(minFeat);                        // covisibility
+        for (std::vector<KeyFrame*>::const_iterator vit = vpConnectedKFs.begin(); vit != vpConnectedKFs.end(); vit++) {
+            KeyFrame* pKFn = *vit;
+            if (pKFn && pKFn != pParentKF && !pKF->hasChild(pKFn) && !sLoopEdges.count(pKFn)) {
+                if (!pKFn->isBad() && pKFn->mnId < pKF->mnId) {
+                    if (sInsertedEdges.count(std::make_pair(std::min(pKF->mnId, pKFn->mnId), std::max(pKF->mnId, pKFn->mnId)))) continue;
+                    g2o::Sim3 Snw;
+                    LoopClosing::KeyFrameAndPose::const_iterator itn = NonCorrectedSim3.find(pKFn);
+                    if (itn != NonCorrectedSim3.end()) Snw = itn->second;
+                    else Snw = vScw[pKFn->mnId];
+                    addEdge(nIDi, pKFn->mnId, Snw * Swi);
+                }
+            }
+        }
+    }
+    for (size_t i = 0, iend = vpMPs.size(); i < iend; i++) {                                                      // :4511-4530
+        MapPoint* pMP = vpMPs[i];
+        if (pMP->isBad()) continue;
+        long unsigned int nIDr;
+        if (pMP->mnCorrectedByKF == pCurKF->mnId) nIDr = pMP->mnCorrectedReference;
+        else nIDr = pMP->GetReferenceKeyFrame()->mnId;
+        if (nIDr > nMaxKFid || vVertex[nIDr] < 0) continue;   // no vertex: vScw and vCorrectedSwc are both the identity there, the point stays
+        double P[3];
+        pMP->GetWorldPos(P);
+        G.pt.insert(G.pt.end(), P, P + 3);
+        G.ptRef.push_back(vVertex[nIDr]);
+        G.vMP.push_back(pMP);
+    }
+    std::memset(&G.P, 0, sizeof G.P);
+    std::memset(&G.R, 0, sizeof G.R);
+    G.P.n_vertices = (int32_t)G.vKF.size(); G.P.n_edges = (int32_t)G.ei.size();
+    G.P.fix_scale = bFixScale ? 1 : 0;
+    G.P.its = 20;                                                                                                 // :4482
+    G.P.lambda_init = 1e-16;                                                                                      // :4265
+    G.P.S = G.S.data(); G.P.fixed = G.fixed.data(); G.P.edge_i = G.ei.data(); G.P.edge_j = G.ej.data(); G.P.edge_S = G.edgeS.data();
+    G.P.n_pt = (int32_t)G.vMP.size(); G.P.pt = G.pt.data(); G.P.pt_ref = G.ptRef.data();
+    return !G.vKF.empty();
+}
+
+void Optimizer::OptimizeEssentialGraph(Map* pMap, KeyFrame* pLoopKF, KeyFrame* pCurKF, const LoopClosing::KeyFrameAndPose& NonCorrectedSim3,
+                                       const LoopClosing::KeyFrameAndPose& CorrectedSim3,
+                                       const std::map<KeyFrame*, std::set<KeyFrame*>>& LoopConnections, const bool& bFixScale,
+                                       LoopClosing* pLC) {                                                        // :4243-4552
+    PackedPoseGraph& G = t_last_pg;
+    if (!PackEssentialGraph(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections, bFixScale, G)) return;
+    void* h = handle();
+    if (!h) { std::cerr << "OptimizeEssentialGraph: no HIP device, pose graph skipped (the backend has no CPU path)" << std::endl; return; }
+    vba_posegraph_problem* pp = &G.P;
+    vba_posegraph_result* pr = &G.R;
+    if (vba_posegraph_optimize(h, 1, &pp, &pr) != 0) { std::cerr << "OptimizeEssentialGraph: " << vba_last_error(h) << std::endl; return; }
+    std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);
+    for (size_t i = 0; i < G.vKF.size(); i++) {                                                                   // :4488-4508: Sim3 [sR t; 0 1] -> SE3 [R t/s; 0 1]
+        const double* Si = &G.S[8 * i];
+        const Matrix3d eigR = QuatToMatrix({{Si[3], Si[4], Si[5], Si[6]}});
+        const double s = Si[7];
+        Mat4f Tiw{};
+        for (int r = 0; r < 3; r++) {
+            for (int c = 0; c < 3; c++) Tiw[4 * r + c] = (float)eigR[3 * r + c];
+            Tiw[4 * r + 3] = (float)(Si[r] * (1.0 / s));
+        }
+        Tiw[15] = 1.0f;
+        G.vKF[i]->SetPose(Tiw);
+        G.vKF[i]->UpdateNavStatePVRFromTcw(Tiw, ConfigParam::Rbc(), ConfigParam::Pbc());
+    }
+    for (size_t i = 0; i < G.vMP.size(); i++) {                                                                   // :4537-4545
+        const float P[3] = {(float)G.pt[3 * i], (float)G.pt[3 * i + 1], (float)G.pt[3 * i + 2]};
+        G.vMP[i]->SetWorldPos(P);
+        G.vMP[i]->UpdateNormalAndDepth();
+    }
+    if (pLC) pLC->SetMapUpdateFlagInTracking(true);                                                               // :4548-4551
+}
+
 void Optimizer::GlobalBundleAdjustment(Map* pMap, int nIterations, bool* pbStopFlag, const unsigned long nLoopKF, const bool bRobust) {
     BundleAdjustment(pMap->GetAllKeyFrames(), pMap->GetAllMapPoints(), nIterations, pbStopFlag, nLoopKF, bRobust);   // :3346-3354
 }

@@ -6,6 +6,8 @@
 // set, Map::mMutexMapUpdate held during write-back only).  Replaced: everything g2o did in between.
 #pragma once
 #include <list>
+#include <map>
+#include <set>
 #include <vector>
 
 #include "../../include/vislam_ba.h"
@@ -30,6 +32,17 @@ struct PackedWindow {
     std::vector<uint8_t> outlier, kfFix;
     std::vector<double> chi2;
     vba_result R;
+};
+
+// flat arrays of one essential graph in the layout of vba_posegraph_problem, plus the bookkeeping the write-back needs
+struct PackedPoseGraph {
+    vba_posegraph_problem P;
+    std::vector<double> S, edgeS, pt;
+    std::vector<uint8_t> fixed;
+    std::vector<int32_t> ei, ej, ptRef;
+    std::vector<KeyFrame*> vKF;          // one per vertex
+    std::vector<MapPoint*> vMP;          // one per point row
+    vba_posegraph_result R;
 };
 
 class Optimizer {
@@ -71,6 +84,18 @@ public:
     // vpMatches1 and the write-back of g2oS12 (:4727-4784).  Replaced: everything g2o did in between (vba_sim3_optimize).
     static int OptimizeSim3(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoint*>& vpMatches1, g2o::Sim3& g2oS12, const float th2,
                             const bool bFixScale);
+    // include/Optimizer.h:84-88: the pose graph after a loop is accepted (LoopClosing::CorrectLoop).  Kept from the reference: the
+    // vertices (src/Optimizer.cpp:4284-4325), the four edge rules in their order with minFeat = 100 and sInsertedEdges
+    // (:4331-4478), the write-back of poses and map points (:4488-4546).  Replaced: optimize(20) and the arithmetic of the map-point
+    // correction (vba_posegraph_optimize).
+    static void OptimizeEssentialGraph(Map* pMap, KeyFrame* pLoopKF, KeyFrame* pCurKF, const LoopClosing::KeyFrameAndPose& NonCorrectedSim3,
+                                       const LoopClosing::KeyFrameAndPose& CorrectedSim3,
+                                       const std::map<KeyFrame*, std::set<KeyFrame*>>& LoopConnections, const bool& bFixScale,
+                                       LoopClosing* pLC = NULL);
+    static bool PackEssentialGraph(Map* pMap, KeyFrame* pLoopKF, KeyFrame* pCurKF, const LoopClosing::KeyFrameAndPose& NonCorrectedSim3,
+                                   const LoopClosing::KeyFrameAndPose& CorrectedSim3,
+                                   const std::map<KeyFrame*, std::set<KeyFrame*>>& LoopConnections, bool bFixScale, PackedPoseGraph& G);
+    static PackedPoseGraph& LastPoseGraph();    // of this thread's last OptimizeEssentialGraph / PackEssentialGraph
     static bool PackLocalBundleAdjustment(KeyFrame* pKF, const std::list<KeyFrame*>* pList, PackedWindow& W);
     static void LocalBundleAdjustmentImpl(KeyFrame* pKF, const std::list<KeyFrame*>* pList, bool* pbStopFlag, Map* pMap, LocalMapping* pLM);
 

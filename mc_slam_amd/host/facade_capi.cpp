@@ -1,6 +1,7 @@
 // facade_capi.cpp -- C entry points that let the test-suite build a KeyFrame / MapPoint map from flat arrays,
 // call the C++ facade (Optimizer.h) and read the map back.  Test harness of the facade, not part of the
 // product ABI (that is include/vislam_ba.h).
+#include <algorithm>
 #include <cstring>
 #include <map>
 #include <memory>
@@ -12,6 +13,7 @@ using namespace ORB_SLAM2;
 struct FcMap {
     Map map;
     LocalMapping lm;
+    LoopClosing lc;
     std::map<long, std::unique_ptr<KeyFrame>> kfs;
     std::map<long, std::unique_ptr<MapPoint>> mps;
     std::map<long, std::unique_ptr<Frame>> frames;
@@ -338,6 +340,64 @@ void fc_sim3_ops(const double* a8, const double* b8, const double* x3, double* o
     put(A.inverse(), out19 + 3);
     put(A * B, out19 + 11);
 }
+// ---- essential graph ----
+// spanning tree, loop edges and the ordered covisibility list (descending weights) of one keyframe
+int fc_kf_set_graph(void* m, long kf, long parent, const long* children, int n_children, const long* loop_edges, int n_loop,
+                    const long* cov_ids, const int* cov_w, int n_cov) {
+    FcMap* M = reinterpret_cast<FcMap*>(m);
+    KeyFrame* k = M->kfs.at(kf).get();
+    k->mpParent = parent >= 0 ? M->kfs.at(parent).get() : nullptr;
+    k->mspChildrens.clear(); k->mspLoopEdges.clear();
+    k->mvpOrderedConnectedKeyFrames.clear(); k->mvOrderedWeights.clear(); k->mConnectedKeyFrameWeights.clear();
+    for (int i = 0; i < n_children; i++) k->mspChildrens.insert(M->kfs.at(children[i]).get());
+    for (int i = 0; i < n_loop; i++) k->mspLoopEdges.insert(M->kfs.at(loop_edges[i]).get());
+    for (int i = 0; i < n_cov; i++) {
+        KeyFrame* o = M->kfs.at(cov_ids[i]).get();
+        k->mvpOrderedConnectedKeyFrames.push_back(o);
+        k->mvOrderedWeights.push_back(cov_w[i]);
+        k->mConnectedKeyFrameWeights[o] = cov_w[i];
+    }
+    return 0;
+}
+int fc_set_kf_bad(void* m, long kf, int bad) {
+    reinterpret_cast<FcMap*>(m)->kfs.at(kf)->mbBad = bad != 0;
+    return 0;
+}
+int fc_mappoint_set_corrected(void* m, long mp, long by_kf, long reference) {
+    MapPoint* p = reinterpret_cast<FcMap*>(m)->mps.at(mp).get();
+    p->mnCorrectedByKF = (long unsigned)by_kf;
+    p->mnCorrectedReference = (long unsigned)reference;
+    return 0;
+}
+// Optimizer::OptimizeEssentialGraph(map, loop_kf, cur_kf, NonCorrectedSim3, CorrectedSim3, LoopConnections, bFixScale, &lc).
+// nonc / corr: keyframe ids with their Sim3 (t, q xyzw, s each); conn: pairs (keyframe, connected keyframe).  mode 1: extraction
+// only (no GPU needed).  Returns the number of vertices packed.
+int fc_optimize_essential_graph(void* m, long loop_kf, long cur_kf, const long* nonc_ids, const double* nonc_S, int n_nonc,
+                                const long* corr_ids, const double* corr_S, int n_corr, const long* conn, int n_conn, int fix_scale, int mode) {
+    FcMap* M = reinterpret_cast<FcMap*>(m);
+    fill_map(M);
+    M->map.mnMaxKFid = 0;
+    for (auto& k : M->kfs) M->map.mnMaxKFid = std::max(M->map.mnMaxKFid, k.second->mnId);
+    auto sim3 = [](const double* a) { return g2o::Sim3({{a[3], a[4], a[5], a[6]}}, {{a[0], a[1], a[2]}}, a[7]); };
+    LoopClosing::KeyFrameAndPose NonCorrected, Corrected;
+    for (int i = 0; i < n_nonc; i++) NonCorrected[M->kfs.at(nonc_ids[i]).get()] = sim3(nonc_S + 8 * i);
+    for (int i = 0; i < n_corr; i++) Corrected[M->kfs.at(corr_ids[i]).get()] = sim3(corr_S + 8 * i);
+    std::map<KeyFrame*, std::set<KeyFrame*>> LoopConnections;
+    for (int i = 0; i < n_conn; i++) LoopConnections[M->kfs.at(conn[2 * i]).get()].insert(M->kfs.at(conn[2 * i + 1]).get());
+    KeyFrame *pLoop = M->kfs.at(loop_kf).get(), *pCur = M->kfs.at(cur_kf).get();
+    if (mode == 1) Optimizer::PackEssentialGraph(&M->map, pLoop, pCur, NonCorrected, Corrected, LoopConnections, fix_scale != 0, Optimizer::LastPoseGraph());
+    else Optimizer::OptimizeEssentialGraph(&M->map, pLoop, pCur, NonCorrected, Corrected, LoopConnections, fix_scale != 0, &M->lc);
+    return (int)Optimizer::LastPoseGraph().vKF.size();
+}
+const vba_posegraph_problem* fc_last_posegraph() { return &Optimizer::LastPoseGraph().P; }
+const vba_posegraph_result* fc_last_posegraph_result() { return &Optimizer::LastPoseGraph().R; }
+int fc_last_posegraph_ids(long* kf_ids, int cap_kf, long* mp_ids, int cap_mp) {   // mnId behind every vertex and every point row
+    const PackedPoseGraph& G = Optimizer::LastPoseGraph();
+    for (size_t i = 0; i < G.vKF.size() && (int)i < cap_kf; i++) kf_ids[i] = (long)G.vKF[i]->mnId;
+    for (size_t i = 0; i < G.vMP.size() && (int)i < cap_mp; i++) mp_ids[i] = (long)G.vMP[i]->mnId;
+    return (int)G.vMP.size();
+}
+int fc_loop_map_updated(void* m) { return reinterpret_cast<FcMap*>(m)->lc.mbMapUpdateFlagForTracking ? 1 : 0; }
 int fc_map_updated(void* m) { return reinterpret_cast<FcMap*>(m)->lm.mbMapUpdateFlagForTracking ? 1 : 0; }
 // last packed window (what the facade handed / would hand to vba_solve)
 const vba_problem* fc_last_problem() { return &Optimizer::LastWindow().P; }

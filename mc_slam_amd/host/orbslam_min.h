@@ -12,6 +12,7 @@
 #include <list>
 #include <map>
 #include <mutex>
+#include <set>
 #include <vector>
 
 namespace ORB_SLAM2 {
@@ -112,6 +113,8 @@ public:
     std::mutex mMutexMapUpdate;  // include/Map.h:72
     std::vector<KeyFrame*> GetAllKeyFrames() { return mspKeyFrames; }    // include/Map.h:44 (a std::set there: id order)
     std::vector<MapPoint*> GetAllMapPoints() { return mspMapPoints; }    // include/Map.h:45
+    long unsigned int GetMaxKFid() { return mnMaxKFid; }                 // include/Map.h:50
+    long unsigned int mnMaxKFid = 0;
     std::vector<KeyFrame*> mspKeyFrames;
     std::vector<MapPoint*> mspMapPoints;
 };
@@ -183,10 +186,33 @@ public:
     }
     void EraseMapPointMatch(MapPoint* pMP);   // src/KeyFrame.cpp:573-579: through pMP->GetIndexInKeyFrame(this) (below MapPoint)
     std::vector<KeyFrame*> GetVectorCovisibleKeyFrames() { return mvpOrderedConnectedKeyFrames; }
+    // spanning tree, loop edges and covisibility weights: what OptimizeEssentialGraph reads (include/KeyFrame.h:104-128)
+    KeyFrame* GetParent() { return mpParent; }
+    bool hasChild(KeyFrame* pKF) { return mspChildrens.count(pKF) != 0; }
+    std::set<KeyFrame*> GetLoopEdges() { return mspLoopEdges; }
+    int GetWeight(KeyFrame* pKF) {                                        // src/KeyFrame.cpp:548-555
+        const auto it = mConnectedKeyFrameWeights.find(pKF);
+        return it == mConnectedKeyFrameWeights.end() ? 0 : it->second;
+    }
+    // src/KeyFrame.cpp:525-544 as it stands: upper_bound over the descending weights; when EVERY connected keyframe has at least
+    // weight w the iterator is end() and the reference returns an empty vector
+    std::vector<KeyFrame*> GetCovisiblesByWeight(const int& w) {
+        if (mvpOrderedConnectedKeyFrames.empty()) return std::vector<KeyFrame*>();
+        size_t n = 0;
+        while (n < mvOrderedWeights.size() && !(w > mvOrderedWeights[n])) n++;
+        if (n == mvOrderedWeights.size()) return std::vector<KeyFrame*>();
+        return std::vector<KeyFrame*>(mvpOrderedConnectedKeyFrames.begin(), mvpOrderedConnectedKeyFrames.begin() + n);
+    }
+    // src/KeyFrame.cpp:19-36: P, R and V of the NavState from a new T_cw (float32 matrices like cv::Mat; bV1 = bV2)
+    void UpdateNavStatePVRFromTcw(const Mat4f& Tcw_, const Matrix3d& Rbc, const Vector3d& Pbc);
 
     // state (public here: the test harness fills it)
     std::vector<MapPoint*> mvpMapPoints;
     std::vector<KeyFrame*> mvpOrderedConnectedKeyFrames;
+    std::vector<int> mvOrderedWeights;                       // weights of mvpOrderedConnectedKeyFrames, descending
+    std::map<KeyFrame*, int> mConnectedKeyFrameWeights;
+    KeyFrame* mpParent = nullptr;
+    std::set<KeyFrame*> mspChildrens, mspLoopEdges;
     KeyFrame* mpPrevKeyFrame = nullptr;
     NavState mNavState;
     IMUPreintegrator mIMUPreInt;
@@ -203,6 +229,7 @@ public:
     long unsigned int mnId = 0;
     static long unsigned int nNextId;
     long unsigned int mnBALocalForKF = (long unsigned int)-1;
+    long unsigned int mnCorrectedByKF = 0, mnCorrectedReference = 0;      // include/MapPoint.h:86-87 (LoopClosing::CorrectLoop)
     bool isBad() { return mbBad; }
     void GetWorldPos(double P[3]) const { for (int i = 0; i < 3; i++) P[i] = mWorldPos[i]; }  // float32 -> double (Converter::toVector3d)
     void SetWorldPos(const float P[3]) { for (int i = 0; i < 3; i++) mWorldPos[i] = P[i]; }
@@ -250,6 +277,59 @@ public:
 };
 
 inline bool cmpKeyFrameId::operator()(const KeyFrame* a, const KeyFrame* b) const { return a->mnId < b->mnId; }
+inline Quaterniond MatrixToQuat(const Matrix3d& m) {   // Eigen::Quaterniond(Matrix3d)
+    Quaterniond q;
+    double t = m[0] + m[4] + m[8];
+    if (t > 0) {
+        t = std::sqrt(t + 1.0);
+        q[3] = 0.5 * t;
+        t = 0.5 / t;
+        q[0] = (m[7] - m[5]) * t; q[1] = (m[2] - m[6]) * t; q[2] = (m[3] - m[1]) * t;
+    } else {
+        int i = 0;
+        if (m[4] > m[0]) i = 1;
+        if (m[8] > m[4 * i]) i = 2;
+        const int j = (i + 1) % 3, k = (j + 1) % 3;
+        t = std::sqrt(m[4 * i] - m[4 * j] - m[4 * k] + 1.0);
+        q[i] = 0.5 * t;
+        t = 0.5 / t;
+        q[3] = (m[3 * k + j] - m[3 * j + k]) * t;
+        q[j] = (m[3 * j + i] + m[3 * i + j]) * t;
+        q[k] = (m[3 * k + i] + m[3 * i + k]) * t;
+    }
+    return q;
+}
+inline void KeyFrame::UpdateNavStatePVRFromTcw(const Mat4f& Tcw_, const Matrix3d& Rbc, const Vector3d& Pbc) {
+    // Tbc * Tcw in float32, then Converter::toCvMatInverse: Rwb = (Rbc Rcw)^T, Pwb = -Rwb (Rbc tcw + Pbc)
+    float Rbw[9], tbw[3];
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) {
+            float a = 0;
+            for (int k = 0; k < 3; k++) a += (float)Rbc[3 * i + k] * Tcw_[4 * k + j];
+            Rbw[3 * i + j] = a;
+        }
+        float a = 0;
+        for (int k = 0; k < 3; k++) a += (float)Rbc[3 * i + k] * Tcw_[4 * k + 3];
+        tbw[i] = a + (float)Pbc[i];
+    }
+    Matrix3d Rwb;
+    Vector3d Pwb;
+    for (int i = 0; i < 3; i++) {
+        float a = 0;
+        for (int k = 0; k < 3; k++) { Rwb[3 * i + k] = (double)Rbw[3 * k + i]; a += Rbw[3 * k + i] * tbw[k]; }
+        Pwb[i] = (double)(-a);
+    }
+    const Matrix3d Rw1 = mNavState.Get_RotMatrix();
+    const Vector3d Vw1 = mNavState.Get_V();
+    Vector3d b{{0, 0, 0}}, Vw2{{0, 0, 0}};
+    for (int i = 0; i < 3; i++)
+        for (int k = 0; k < 3; k++) b[i] += Rw1[3 * k + i] * Vw1[k];          // Rw1^T Vw1
+    for (int i = 0; i < 3; i++)
+        for (int k = 0; k < 3; k++) Vw2[i] += Rwb[3 * i + k] * b[k];
+    mNavState.Set_Pos(Pwb);
+    mNavState.Set_Rot(MatrixToQuat(Rwb));
+    mNavState.Set_Vel(Vw2);
+}
 inline void KeyFrame::EraseMapPointMatch(MapPoint* pMP) {
     const int idx = pMP->GetIndexInKeyFrame(this);
     if (idx >= 0) mvpMapPoints[idx] = nullptr;
@@ -298,3 +378,13 @@ private:
     double s = 1.;
 };
 }  // namespace g2o
+
+namespace ORB_SLAM2 {
+// include/LoopClosing.h:28-34, :60: what Optimizer::OptimizeEssentialGraph takes from it
+class LoopClosing {
+public:
+    typedef std::map<KeyFrame*, g2o::Sim3, std::less<KeyFrame*>> KeyFrameAndPose;
+    void SetMapUpdateFlagInTracking(bool b) { mbMapUpdateFlagForTracking = b; }
+    bool mbMapUpdateFlagForTracking = false;
+};
+}  // namespace ORB_SLAM2

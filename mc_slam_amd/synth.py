@@ -542,3 +542,84 @@ def make_sim3_pair(seed, n_pairs, fix_scale=False, outlier_frac=0.1, noise=True,
     S12 = np.concatenate([t0, rot_to_quat(R0), [s0]])
     return abi.Sim3Problem(S12=S12, p1c=p1, p2c=p2, uv1=uv1, uv2=uv2, w1=w1, w2=w2, K1=K1, K2=K2, fix_scale=int(bool(fix_scale)),
                            truth=dict(S12=np.concatenate([t, rot_to_quat(R), [s]]), is_outlier=m))
+
+
+# ---------------------------------------------------------------- essential graphs (vba_posegraph_optimize)
+def _s3_mul(a, b):
+    return a[0] @ b[0], a[2] * (a[0] @ b[1]) + a[1], a[2] * b[2]
+
+
+def _s3_inv(a):
+    return a[0].T, -(a[0].T @ a[1]) / a[2], 1.0 / a[2]
+
+
+def _s3_pack(a):
+    return np.concatenate([a[1], rot_to_quat(a[0]), [a[2]]])
+
+
+def make_posegraph(seed, n_kf, span=3, loops=None, fix_scale=False, fixed_at=0, rot_drift=2e-3, trans_drift=2e-2, scale_drift=2e-3,
+                   n_corrected=None, dup_edge=None, isolated=False, n_pt=0, loop_rot_err=0.0, noise=True, radius=5.0):
+    """One essential graph as Optimizer::OptimizeEssentialGraph sees it (src/Optimizer.cpp:4243-4478).
+    A closed trajectory of n_kf keyframes on a circle (Siw = camera-from-world, scale 1); odometry composes the true relative
+    motions with a drift in rotation, translation and (unless fix_scale) scale per step, starting from the truth at keyframe 0.
+    Edges (vertex 0 = i, vertex 1 = j, measurement Sji = Sjw Swi):
+      * from every keyframe i to its `span` predecessors, measured from the DRIFTED poses (what the reference does with
+        NonCorrectedSim3: spanning-tree and covisibility edges);
+      * `loops`: a list of (i, j) pairs that carry the TRUE relative pose (default: one loop, (n_kf - 1, 0)), turned by
+        loop_rot_err radians about a fixed axis when that is not 0 (a wrong loop measurement).
+    Initial estimates are the drifted poses, except for the last n_corrected keyframes (default span + 1), to which the loop
+    correction of the last keyframe is propagated (CorrectedSim3, src/LoopClosing.cpp:452-474): the input has the discontinuity
+    the real one has.  fixed_at: the fixed vertex (None: none).  dup_edge: index of an edge that is listed twice; isolated: one
+    more vertex without edges; n_pt: map points around the trajectory with random reference vertices.  noise=False: no drift at all
+    (the input is the truth).  truth['S']: the true Siw."""
+    r = np.random.default_rng(seed)
+    n = int(n_kf)
+    ang = 2 * np.pi * np.arange(n) / n
+    true = []
+    for k in range(n):
+        Rwc = so3_exp(np.array([0.0, 0.0, ang[k]])) @ so3_exp(0.05 * np.array([np.sin(3 * ang[k]), np.cos(2 * ang[k]), 0.0]))
+        c = np.array([radius * np.cos(ang[k]), radius * np.sin(ang[k]), 0.2 * np.sin(3 * ang[k])])
+        true.append((Rwc.T, -Rwc.T @ c, 1.0))
+    drift = [true[0]]
+    for k in range(1, n):
+        rel = _s3_mul(true[k], _s3_inv(true[k - 1]))
+        if noise:
+            u = np.concatenate([r.normal(size=3) * rot_drift, r.normal(size=3) * trans_drift,
+                                [0.0 if fix_scale else r.normal() * scale_drift]])
+            rel = _s3_mul(_sim3_exp(u), rel)
+        drift.append(_s3_mul(rel, drift[k - 1]))
+    ei, ej, meas = [], [], []
+    for i in range(1, n):
+        for j in range(max(0, i - span), i):
+            ei.append(i); ej.append(j); meas.append(_s3_mul(drift[j], _s3_inv(drift[i])))
+    if loops is None:
+        loops = [(n - 1, 0)]
+    wrong = (so3_exp(loop_rot_err * np.array([0.6, 0.0, 0.8])), np.zeros(3), 1.0)
+    for i, j in loops:
+        ei.append(int(i)); ej.append(int(j))
+        m = _s3_mul(true[j], _s3_inv(true[i]))
+        meas.append(_s3_mul(wrong, m) if loop_rot_err else m)
+    if dup_edge is not None:
+        ei.append(ei[dup_edge]); ej.append(ej[dup_edge]); meas.append(meas[dup_edge])
+    # CorrectedSim3: g2oCorrectedSiw = g2oSic * g2oCorrectedScw, Sic from the uncorrected poses
+    init = list(drift)
+    nc = span + 1 if n_corrected is None else int(n_corrected)
+    if noise and loops:
+        cur = n - 1
+        for i in range(max(1, n - nc), n):
+            init[i] = _s3_mul(_s3_mul(drift[i], _s3_inv(drift[cur])), true[cur])
+    S = np.stack([_s3_pack(a) for a in init])
+    St = np.stack([_s3_pack(a) for a in true])
+    fixed = np.zeros(n, dtype=np.uint8)
+    if fixed_at is not None:
+        fixed[fixed_at] = 1
+    if isolated:
+        extra = _s3_pack((so3_exp(r.normal(size=3) * 0.3), r.normal(size=3), 1.0 if fix_scale else 1.1))
+        S, St, fixed = np.vstack([S, extra]), np.vstack([St, extra]), np.append(fixed, np.uint8(0))
+    pt = pt_ref = None
+    if n_pt:
+        a = r.uniform(0, 2 * np.pi, n_pt)
+        pt = np.stack([(radius + r.uniform(1, 4, n_pt)) * np.cos(a), (radius + r.uniform(1, 4, n_pt)) * np.sin(a), r.uniform(-1, 1, n_pt)], axis=1)
+        pt_ref = r.integers(0, n, n_pt)
+    return abi.PoseGraphProblem(S=S, fixed=fixed, edge_i=ei, edge_j=ej, edge_S=np.stack([_s3_pack(m) for m in meas]),
+                                fix_scale=int(bool(fix_scale)), pt=pt, pt_ref=pt_ref, truth=dict(S=St))

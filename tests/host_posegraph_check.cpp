@@ -1,0 +1,117 @@
+// Sanitizer harness of the host half of vba_posegraph_optimize (mc_slam_amd/csrc/vba_host_posegraph.h): plain C++, built by
+// tests/test_host_posegraph.py with g++ -fsanitize=address,undefined.
+//   host_posegraph_check <file>...   -> one line per file: "ok <summary>" or "error <message>"
+// File (little-endian, written by the test): i32 n_vertices n_edges fix_scale its n_pt mutate, f64 lambda_init, f64 env_before,
+// then S [nv][8] f64, fixed [nv] u8, edge_i [ne] i32, edge_j [ne] i32, edge_S [ne][8] f64, pt [n_pt][3] f64, pt_ref [n_pt] i32.
+// mutate: 0 nothing, 1 n_vertices = -1, 2 n_edges = -1, 3 n_pt = -1, 4 S = NULL, 5 edge_S = NULL, 6 pt = NULL, 7 fixed = NULL.
+#include "../mc_slam_amd/csrc/vba_host_posegraph.h"
+
+#include <cstdio>
+#include <cstring>
+#include <set>
+
+template <class T>
+static bool take(FILE* f, std::vector<T>& v, size_t n) {
+    v.resize(n);
+    return n == 0 || fread(v.data(), sizeof(T), n, f) == n;
+}
+
+static const char* invariants(const vba_posegraph_problem& P, const vba_host::PoseGraphLayout& L) {
+    const int nf = L.n_free;
+    if ((int)L.free_of.size() != P.n_vertices || (int)L.vert_of.size() != nf || (int)L.first.size() != nf || (int)L.row_off.size() != nf + 1 ||
+        (int)L.last_row.size() != nf || (int)L.inc_begin.size() != nf + 1)
+        return "sizes";
+    int k = 0;
+    for (int v = 0; v < P.n_vertices; v++) {   // free vertices numbered in the caller's order
+        if (P.fixed[v] ? L.free_of[v] != -1 : (L.free_of[v] != k || L.vert_of[k] != v)) return "free numbering";
+        if (!P.fixed[v]) k++;
+    }
+    if (k != nf || L.row_off[0] != 0) return "free count";
+    for (int r = 0; r < nf; r++) {
+        if (L.first[r] < 0 || L.first[r] > r) return "first[r] <= r";
+        if (L.row_off[r + 1] - L.row_off[r] != r - L.first[r] + 1) return "offsets";
+        if (L.last_row[r] < r || L.last_row[r] >= nf) return "last_row range";
+        if (L.inc_begin[r] > L.inc_begin[r + 1]) return "inc_begin";
+    }
+    if (L.env_blocks != L.row_off[nf] || L.inc_begin[nf] != (int)L.inc.size()) return "totals";
+    for (int c = 0; c < nf; c++)
+        for (int r = c; r < nf; r++)
+            if ((L.first[r] <= c) != (r <= L.last_row[c]) && L.first[r] <= c) return "last_row misses a row";
+    std::vector<int> first_seen(nf);
+    for (int r = 0; r < nf; r++) first_seen[r] = r;
+    size_t n_inc = 0, n_pe = 0;
+    for (int e = 0; e < P.n_edges; e++) {   // every edge inside the envelope of its later row
+        const int a = L.free_of[P.edge_i[e]], b = L.free_of[P.edge_j[e]];
+        n_inc += (a >= 0) + (b >= 0);
+        if (a < 0 || b < 0) continue;
+        n_pe++;
+        const int hi = std::max(a, b), lo = std::min(a, b);
+        if (L.first[hi] > lo) return "edge outside the envelope";
+        first_seen[hi] = std::min(first_seen[hi], lo);
+    }
+    for (int r = 0; r < nf; r++)
+        if (first_seen[r] != L.first[r]) return "envelope wider than its edges";
+    if (n_inc != L.inc.size() || n_pe != L.pair_edge.size()) return "list totals";
+    for (int r = 0; r < nf; r++)   // incidence lists: the vertex' own edges, in edge order
+        for (int q = L.inc_begin[r]; q < L.inc_begin[r + 1]; q++) {
+            const int e = L.inc[q] >> 1, s = L.inc[q] & 1;
+            if (e < 0 || e >= P.n_edges || (s ? P.edge_j[e] : P.edge_i[e]) != L.vert_of[r]) return "incidence entry";
+            if (q > L.inc_begin[r] && L.inc[q - 1] >= L.inc[q]) return "incidence order";
+        }
+    const size_t np = L.pair_lo.size();
+    if (L.pair_hi.size() != np || L.pair_begin.size() != np + 1 || L.pair_begin[0] != 0 || L.pair_begin[np] != (int)L.pair_edge.size()) return "pair sizes";
+    std::set<std::pair<int, int>> seen;
+    for (size_t p = 0; p < np; p++) {
+        const int hi = L.pair_hi[p], lo = L.pair_lo[p];
+        if (lo < 0 || lo >= hi || hi >= nf || !seen.insert({hi, lo}).second) return "pair not distinct";
+        if (L.pair_begin[p] >= L.pair_begin[p + 1]) return "empty pair";
+        for (int q = L.pair_begin[p]; q < L.pair_begin[p + 1]; q++) {
+            const int e = L.pair_edge[q] >> 1, s = L.pair_edge[q] & 1;
+            if (e < 0 || e >= P.n_edges) return "pair edge range";
+            const int a = L.free_of[P.edge_i[e]], b = L.free_of[P.edge_j[e]];
+            if ((s ? a : b) != hi || (s ? b : a) != lo) return "pair edge";
+            if (q > L.pair_begin[p] && (L.pair_edge[q - 1] >> 1) >= e) return "pair edge order";
+        }
+    }
+    return nullptr;
+}
+
+int main(int argc, char** argv) {
+    for (int a = 1; a < argc; a++) {
+        FILE* f = fopen(argv[a], "rb");
+        int32_t hd[6];
+        double sc[2];
+        if (!f || fread(hd, 4, 6, f) != 6 || fread(sc, 8, 2, f) != 2) { printf("error load\n"); if (f) fclose(f); continue; }
+        std::vector<double> S, M, pt;
+        std::vector<uint8_t> fixed;
+        std::vector<int32_t> ei, ej, ref;
+        const size_t nv = hd[0], ne = hd[1], np = hd[4];
+        const bool ok = take(f, S, 8 * nv) && take(f, fixed, nv) && take(f, ei, ne) && take(f, ej, ne) && take(f, M, 8 * ne) && take(f, pt, 3 * np) && take(f, ref, np);
+        fclose(f);
+        if (!ok) { printf("error load\n"); continue; }
+        vba_posegraph_problem P;
+        std::memset(&P, 0, sizeof P);
+        P.n_vertices = hd[0]; P.n_edges = hd[1]; P.fix_scale = hd[2]; P.its = hd[3]; P.n_pt = hd[4];
+        P.lambda_init = sc[0];
+        P.S = S.data(); P.fixed = fixed.data(); P.edge_i = ei.data(); P.edge_j = ej.data(); P.edge_S = M.data(); P.pt = pt.data(); P.pt_ref = ref.data();
+        switch (hd[5]) {
+            case 1: P.n_vertices = -1; break;
+            case 2: P.n_edges = -1; break;
+            case 3: P.n_pt = -1; break;
+            case 4: P.S = nullptr; break;
+            case 5: P.edge_S = nullptr; break;
+            case 6: P.pt = nullptr; break;
+            case 7: P.fixed = nullptr; break;
+            default: break;
+        }
+        vba_host::PoseGraphLayout L;
+        std::string err;
+        if (vba_host::build_posegraph(&P, L, err, (long long)sc[1])) { printf("error %s\n", err.c_str()); continue; }
+        if (const char* bad = invariants(P, L)) { printf("error invariant: %s\n", bad); continue; }
+        int widest = 0;
+        for (int r = 0; r < L.n_free; r++) widest = std::max(widest, r - L.first[r] + 1);
+        printf("ok n_free %d env %lld widest %d inc %zu pairs %zu pair_edges %zu\n", L.n_free, L.env_blocks, widest, L.inc.size(), L.pair_lo.size(),
+               L.pair_edge.size());
+    }
+    return 0;
+}

@@ -1,0 +1,109 @@
+"""The host half of vba_posegraph_optimize (validation, free-vertex numbering, block envelope, owner lists) under
+AddressSanitizer + UBSan (CPU only): every graph of the GPU tests, every bad input of the entry point, and a 5 000-vertex graph
+with a 40-keyframe band.  The harness (tests/host_posegraph_check.cpp) checks the envelope invariants itself."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import posegraph_cases as pc
+from mc_slam_amd import abi
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+MUTATE = dict(n_vertices_neg=1, n_edges_neg=2, n_pt_neg=3, S_null=4, edge_S_null=5, pt_null=6, fixed_null=7)
+
+
+@pytest.fixture(scope="module")
+def checker(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("pg") / "host_posegraph_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
+                           "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "host_posegraph_check.cpp"), "-o", exe])
+    return exe
+
+
+def _write(path, p, mutate=0, env_before=0):
+    with open(path, "wb") as f:
+        f.write(np.array([p.n_vertices, p.n_edges, p.fix_scale, p.its, p.n_pt, mutate], dtype="<i4").tobytes())
+        f.write(np.array([p.lambda_init, env_before], dtype="<f8").tobytes())
+        for a in (p.S, p.fixed, p.edge_i, p.edge_j, p.edge_S, p.pt, p.pt_ref):
+            f.write(np.ascontiguousarray(a).tobytes())
+
+
+def _run(checker, tmp_path, items):
+    files = []
+    for i, it in enumerate(items):
+        p, mutate, env_before = it if isinstance(it, tuple) else (it, 0, 0)
+        f = str(tmp_path / ("g%d.pg" % i))
+        _write(f, p, mutate, env_before)
+        files.append(f)
+    r = subprocess.run([checker] + files, capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"), timeout=300)
+    assert r.returncode == 0 and "ERROR" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-2000:]
+    lines = r.stdout.strip().splitlines()
+    assert len(lines) == len(items)
+    return lines
+
+
+def _fields(line):
+    assert line.startswith("ok "), line
+    return {k: int(v) for k, v in zip(line.split()[1::2], line.split()[2::2])}
+
+
+def _big(n=5000, band=40, n_loop=8):
+    """5 000 vertices, every one tied to its 40 predecessors, a loop of 8 edges over the whole length; identity poses (the host
+    side reads the values only to validate them)"""
+    i = np.repeat(np.arange(n), band)
+    j = i - np.tile(np.arange(1, band + 1), n)
+    keep = j >= 0
+    ei = np.concatenate([i[keep], n - 1 - np.arange(n_loop)])
+    ej = np.concatenate([j[keep], 1 + np.arange(n_loop)])
+    unit = np.array([0, 0, 0, 0, 0, 0, 1.0, 1.0])
+    fixed = np.zeros(n, dtype=np.uint8)
+    fixed[0] = 1
+    return abi.PoseGraphProblem(S=np.tile(unit, (n, 1)), fixed=fixed, edge_i=ei, edge_j=ej, edge_S=np.tile(unit, (len(ei), 1)))
+
+
+def test_every_gpu_graph_has_a_consistent_envelope(checker, tmp_path):
+    names = pc.CASES + ["REJECT"]
+    ps = [pc.case(n) for n in names]
+    got = dict(zip(names, map(_fields, _run(checker, tmp_path, ps))))
+    for n, p in zip(names, ps):
+        f = got[n]
+        assert f["n_free"] == int((p.fixed == 0).sum())
+        assert f["inc"] == int((p.fixed[p.edge_i] == 0).sum() + (p.fixed[p.edge_j] == 0).sum())
+        assert f["pair_edges"] == int(((p.fixed[p.edge_i] == 0) & (p.fixed[p.edge_j] == 0)).sum())
+    assert got["TWO_I"]["env"] == got["TWO_J"]["env"] == 1 and got["TWO_I"]["pairs"] == 0
+    assert got["ARROW"]["widest"] == 11 and got["ARROW"]["env"] == 1 + 2 * 9 + 11      # vertex 0 fixed: rows of 1, 2 ... 2, then (1, 11)
+    assert got["MID"]["widest"] == 10 and got["MID"]["n_free"] == 11                   # free numbering skips vertex 5
+    assert got["BAND"]["pair_edges"] == got["BAND"]["pairs"] + 1                       # the duplicated edge shares its pair
+    assert got["BAND"]["n_free"] == 70 and got["BAND"]["widest"] == 68              # rows of 66..69 reach back to vertex 2
+    assert got["NEST"]["widest"] == 129 and got["NEST"]["env"] == 1 + 2 + 3 * 127 + 126 + 48    # the loop (90, 40) inside the loop (129, 1)
+
+
+def test_five_thousand_vertices_fit_the_bound_eight_times(checker, tmp_path):
+    p = _big()
+    f = _fields(_run(checker, tmp_path, [p])[0])
+    assert f["n_free"] == 4999 and f["widest"] == 4999
+    assert f["env"] * 8 <= 2 ** 21
+    line = _run(checker, tmp_path, [(p, 0, 2 ** 21 - f["env"] + 1)])[0]                 # the bound holds for the whole call
+    assert line.startswith("error ") and "exceeds the bound of 2097152 blocks" in line
+    assert _run(checker, tmp_path, [(p, 0, 2 ** 21 - f["env"])])[0].startswith("ok ")
+
+
+def test_bad_graphs_are_refused_with_a_message(checker, tmp_path):
+    from test_gpu_posegraph import _bad_graphs
+    bad = _bad_graphs()
+    for (q, msg), line in zip(bad, _run(checker, tmp_path, [b[0] for b in bad])):
+        assert line.startswith("error ") and msg in line, (msg, line)
+    p = pc.case("BIG")
+    muts = [("n_vertices_neg", "negative count"), ("n_edges_neg", "negative count"), ("n_pt_neg", "negative count"),
+            ("S_null", "NULL array"), ("edge_S_null", "NULL array"), ("pt_null", "NULL array"), ("fixed_null", "NULL array")]
+    for (m, msg), line in zip(muts, _run(checker, tmp_path, [(p, MUTATE[m], 0) for m, _ in muts])):
+        assert line.startswith("error ") and msg in line, (m, line)
+    # a truncated file is refused by the harness' reader, not read out of bounds
+    f = str(tmp_path / "t.pg")
+    _write(f, p)
+    raw = open(f, "rb").read()
+    open(f, "wb").write(raw[:len(raw) // 2])
+    r = subprocess.run([checker, f], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and r.stdout.startswith("error load") and "ERROR" not in r.stderr
