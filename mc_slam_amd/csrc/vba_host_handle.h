@@ -1,6 +1,7 @@
 // vba_host_handle.h -- host side of the library, part 1: the handle, its device buffers and pinned staging, the copy helpers of
 // an upload, the host thread pool.  Like the kernel headers, part of the one translation unit vislam_ba.hip.
 #pragma once
+#include "vba_host_arena.h"
 #include "vba_host_layout.h"
 
 #include <sched.h>
@@ -64,6 +65,22 @@ struct PinnedBuf {   // persistent pinned host staging (grown on demand)
         p = nullptr;
         cap = 0;
     }
+};
+
+// The arena of a small-problem entry point (vba_host_arena.h, vba_host_small.h): the device block and its pinned staging, one H2D
+// of `in` and one D2H into `out` per call.  One per entry point: a call finds only its own stale bytes.
+struct SideArena {
+    DevBuf dev;
+    PinnedBuf in, out;
+    // download_bytes: what the call copies back, when that is a prefix of the back section
+    hipError_t ensure(const vba_host::ArenaLayout& L, size_t download_bytes) {
+        hipError_t e = dev.ensure(L.total_bytes());
+        if (e == hipSuccess) e = in.ensure(L.upload_bytes());
+        if (e == hipSuccess) e = out.ensure(download_bytes);
+        return e;
+    }
+    hipError_t ensure(const vba_host::ArenaLayout& L) { return ensure(L, L.back_bytes()); }
+    void release() { dev.release(); in.release(); out.release(); }
 };
 
 // Growable array in pinned host memory with the few std::vector members the upload / download code uses.  The staging
@@ -199,13 +216,7 @@ struct Handle {
     bool owns_streams = true;
     std::string err;
     DevBuf buf[BUF_N];
-    DevBuf preint;  // arena of vba_preintegrate
-    DevBuf pose_arena;  // arena of vba_pose_optimize
-    PinnedBuf pose_host_in, pose_host_out;  // its pinned staging: one H2D and one D2H per call
-    DevBuf sim3_arena;  // arena of vba_sim3_optimize
-    PinnedBuf sim3_host_in, sim3_host_out;  // its pinned staging, same scheme
-    DevBuf pg_arena;    // arena of vba_posegraph_optimize
-    PinnedBuf pg_host_in, pg_host_out;      // its pinned staging, same scheme
+    SideArena preint, pose, sim3, pg;   // vba_preintegrate (dev only), vba_pose_optimize, vba_sim3_optimize, vba_posegraph_optimize
     // small batches (<= 8 windows): every host-built array of an upload goes through ONE pinned arena and ONE H2D copy into one
     // device arena (a single window is ~25 arrays of a few KB to a few 100 KB: 25 copies cost 0.4 ms of queue latency)
     struct Pending { int id; const void* src; size_t bytes; };

@@ -1,4 +1,4 @@
-// vba_host_hooks.h -- host side of the library, part 5: the vba_debug_* hooks of the hooks flavour.
+// vba_host_hooks.h -- host side of the library, part 6: the vba_debug_* hooks of the hooks flavour.
 #pragma once
 
 // ---- test / diagnostic hooks: NOT part of include/vislam_ba.h and not in the shipped library.  `make` builds a second flavour,

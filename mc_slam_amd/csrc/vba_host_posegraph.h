@@ -1,5 +1,5 @@
-// vba_host_posegraph.h -- host half of vba_posegraph_optimize (plain C++17, no HIP): included by vislam_ba.hip and by the
-// sanitizer harness tests/host_posegraph_check.cpp (g++ -fsanitize=address,undefined, tests/test_host_posegraph.py).
+// vba_host_posegraph.h -- host half of vba_posegraph_optimize (plain C++17, no HIP): included by vislam_ba.hip (vba_host_small.h)
+// and by the sanitizer harness tests/host_posegraph_check.cpp (g++ -fsanitize=address,undefined, tests/test_host_posegraph.py).
 //
 // One walk validates a graph of Optimizer::OptimizeEssentialGraph (src/Optimizer.cpp:4243-4552: VertexSim3Expmap per keyframe,
 // EdgeSim3 per pair) and lays out its linear system:
@@ -15,10 +15,13 @@
 // length has about 5 000 x 41 + 8 x 5 000 = 245 000 blocks, an eighth of the bound.
 #pragma once
 #include "../../include/vislam_ba.h"
+#include "vba_host_arena.h"
+#include "vba_layout.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -150,6 +153,106 @@ inline int build_posegraph(const vba_posegraph_problem* P, PoseGraphLayout& L, s
     }
     L.pair_begin.push_back((int)pe.size());
     return 0;
+}
+
+// One call: the layout and descriptor of every graph and the arena [upload | back | work].  The staging block [desc | estimates |
+// measurements | index lists | points] goes up in one copy, [out | estimates | points] come back in one.
+struct PoseGraphCall {
+    std::vector<PoseGraphLayout> lay;
+    std::vector<PgDesc> desc;
+    size_t npt = 0;   // map points of the call
+    ArenaLayout L;
+    size_t o_desc, o_Sin, o_meas, o_ei, o_ej, o_free, o_vert, o_first, o_last, o_roff, o_incb, o_inc, o_plo, o_phi, o_pb, o_pe, o_pt, o_ref;   // upload
+    size_t o_out, o_S, o_pto;                                                                                                                // back
+    size_t o_Sbk, o_err, o_J, o_H, o_F, o_Ld, o_b, o_w, o_y, o_x;                                                                            // work
+};
+
+// 0: every graph is usable and C describes the call; otherwise err says which graph is not and why.  debug: graph 0 stops after
+// the solve of its first trial (hooks flavour)
+inline int describe_posegraph(int n_graphs, const vba_posegraph_problem* const* in, const vba_posegraph_result* const* out, bool debug,
+                              PoseGraphCall& C, std::string& err) {
+    C = PoseGraphCall();
+    C.lay.resize(n_graphs);
+    C.desc.resize(n_graphs);
+    size_t nv = 0, ne = 0, nf = 0, nenv = 0, ninc = 0, npair = 0, npe = 0, npt = 0;
+    for (int g = 0; g < n_graphs; g++) {
+        const std::string who = "graph " + std::to_string(g) + ": ";
+        if (!in[g] || !out[g]) { err = who + "NULL problem or result"; return 1; }
+        if (build_posegraph(in[g], C.lay[g], err, (long long)nenv)) { err = who + err; return 1; }
+        const vba_posegraph_problem* P = in[g];
+        const PoseGraphLayout& L = C.lay[g];
+        PgDesc& d = C.desc[g];
+        std::memset(&d, 0, sizeof d);
+        d.nv = P->n_vertices; d.ne = P->n_edges; d.nf = L.n_free; d.npair = (int)L.pair_lo.size();
+        d.fix_scale = P->fix_scale ? 1 : 0; d.its = P->its; d.n_pt = P->n_pt; d.debug = (debug && g == 0) ? 1 : 0;
+        d.lambda_init = P->lambda_init;
+        d.v0 = (long long)nv; d.e0 = (long long)ne; d.f0 = (long long)nf; d.r0 = (long long)nf + g; d.env0 = (long long)nenv;
+        d.inc0 = (long long)ninc; d.pair0 = (long long)npair; d.pb0 = (long long)npair + g; d.pe0 = (long long)npe; d.pt0 = (long long)npt;
+        nv += (size_t)d.nv; ne += (size_t)d.ne; nf += (size_t)d.nf; nenv += (size_t)L.env_blocks; ninc += L.inc.size();
+        npair += L.pair_lo.size(); npe += L.pair_edge.size(); npt += (size_t)d.n_pt;
+    }
+    C.npt = npt;
+    ArenaLayout& A = C.L;
+    auto take = [&A](size_t bytes) { return A.take(bytes + 8); };
+    const size_t G = (size_t)n_graphs;
+    C.o_desc = take(sizeof(PgDesc) * G); C.o_Sin = take(64 * nv); C.o_meas = take(64 * ne); C.o_ei = take(4 * ne); C.o_ej = take(4 * ne);
+    C.o_free = take(4 * nv); C.o_vert = take(4 * nf); C.o_first = take(4 * nf); C.o_last = take(4 * nf); C.o_roff = take(4 * (nf + G));
+    C.o_incb = take(4 * (nf + G)); C.o_inc = take(4 * ninc); C.o_plo = take(4 * npair); C.o_phi = take(4 * npair);
+    C.o_pb = take(4 * (npair + G)); C.o_pe = take(4 * npe); C.o_pt = take(24 * npt); C.o_ref = take(4 * npt);
+    A.end_upload();
+    C.o_out = take(sizeof(PgOut) * G); C.o_S = take(64 * nv); C.o_pto = take(24 * npt);
+    A.end_back();
+    C.o_Sbk = take(64 * nv); C.o_err = take(56 * ne); C.o_J = take(784 * ne); C.o_H = take(392 * nenv); C.o_F = take(392 * nenv);
+    C.o_Ld = take(392 * nf); C.o_b = take(56 * nf); C.o_w = take(56 * nf); C.o_y = take(56 * nf); C.o_x = take(56 * nf);
+    return 0;
+}
+
+// graph g into the staging block hin: its slices of the concatenated arrays (the descriptors go in as one block)
+inline void pack_posegraph(const PoseGraphCall& C, int g, const vba_posegraph_problem* P, char* hin) {
+    const PoseGraphLayout& L = C.lay[g];
+    const PgDesc& d = C.desc[g];
+    auto put = [hin](size_t o, size_t at, const void* src, size_t bytes) { if (bytes) std::memcpy(hin + o + at, src, bytes); };
+    put(C.o_Sin, 64 * (size_t)d.v0, P->S, 64 * (size_t)d.nv);
+    put(C.o_meas, 64 * (size_t)d.e0, P->edge_S, 64 * (size_t)d.ne);
+    put(C.o_ei, 4 * (size_t)d.e0, P->edge_i, 4 * (size_t)d.ne);
+    put(C.o_ej, 4 * (size_t)d.e0, P->edge_j, 4 * (size_t)d.ne);
+    put(C.o_free, 4 * (size_t)d.v0, L.free_of.data(), 4 * (size_t)d.nv);
+    put(C.o_vert, 4 * (size_t)d.f0, L.vert_of.data(), 4 * (size_t)d.nf);
+    put(C.o_first, 4 * (size_t)d.f0, L.first.data(), 4 * (size_t)d.nf);
+    put(C.o_last, 4 * (size_t)d.f0, L.last_row.data(), 4 * (size_t)d.nf);
+    put(C.o_roff, 4 * (size_t)d.r0, L.row_off.data(), 4 * ((size_t)d.nf + 1));
+    put(C.o_incb, 4 * (size_t)d.r0, L.inc_begin.data(), 4 * ((size_t)d.nf + 1));
+    put(C.o_inc, 4 * (size_t)d.inc0, L.inc.data(), 4 * L.inc.size());
+    put(C.o_plo, 4 * (size_t)d.pair0, L.pair_lo.data(), 4 * L.pair_lo.size());
+    put(C.o_phi, 4 * (size_t)d.pair0, L.pair_hi.data(), 4 * L.pair_hi.size());
+    put(C.o_pb, 4 * (size_t)d.pb0, L.pair_begin.data(), 4 * L.pair_begin.size());
+    put(C.o_pe, 4 * (size_t)d.pe0, L.pair_edge.data(), 4 * L.pair_edge.size());
+    put(C.o_pt, 24 * (size_t)d.pt0, P->pt, 24 * (size_t)d.n_pt);
+    int* ref = at<int>(hin, C.o_ref) + d.pt0;
+    for (int p = 0; p < d.n_pt; p++) ref[p] = (int)d.v0 + P->pt_ref[p];   // index into the concatenated vertices
+}
+
+// Sf, pf: the call's estimate and point regions as they came back
+inline void unpack_posegraph(vba_posegraph_problem* P, vba_posegraph_result* R, const PgDesc& d, const PgOut& r, const double* Sf, const double* pf) {
+    R->status = r.status; R->its_done = r.its_done; R->lm_trials = r.lm_trials; R->stop = r.stop;
+    R->chi2_initial = r.chi2_initial; R->chi2_final = r.chi2_final; R->lambda_final = r.lambda_final;
+    if (d.nv) std::memcpy(P->S, Sf + 8 * (size_t)d.v0, 64 * (size_t)d.nv);   // fixed vertices: the input, bit for bit
+    if (d.n_pt) std::memcpy(P->pt, pf + 3 * (size_t)d.pt0, 24 * (size_t)d.n_pt);
+}
+
+// the envelope blocks of one graph (env, [env_blocks][49]) expanded to the dense symmetric H, [7 n_free]^2 row-major
+inline void expand_envelope(const PoseGraphLayout& L, const double* env, double* H) {
+    const size_t n = 7 * (size_t)L.n_free;
+    std::fill(H, H + n * n, 0.0);
+    for (int r = 0; r < L.n_free; r++)
+        for (int c = L.first[r]; c <= r; c++) {
+            const double* blk = env + 49 * (size_t)(L.row_off[r] + c - L.first[r]);
+            for (int a = 0; a < 7; a++)
+                for (int k = 0; k < 7; k++) {
+                    H[(7 * (size_t)r + a) * n + 7 * (size_t)c + k] = blk[7 * a + k];
+                    if (c < r) H[(7 * (size_t)c + k) * n + 7 * (size_t)r + a] = blk[7 * a + k];
+                }
+        }
 }
 
 }  // namespace vba_host

@@ -1,0 +1,174 @@
+// vba_host_small.h -- host side of the library, part 5: the drivers of the small-problem entry points (vba_preintegrate,
+// vba_pose_optimize, vba_sim3_optimize, vba_posegraph_optimize).  Each lays its arena out once (vba_host_arena.h), packs the
+// pinned staging block with the plain-C++ half of its topic (vba_host_pose.h, vba_host_sim3.h, vba_host_posegraph.h), and does one
+// H2D copy, one or two launches and one D2H copy on the handle's stream.  No entry point shares its arena with another.
+#pragma once
+#include "vba_host_pose.h"
+#include "vba_host_sim3.h"
+#include "vba_host_posegraph.h"
+
+namespace {
+using vba_host::at;
+
+// threads that pack the items of a vba_pose_optimize / vba_sim3_optimize call
+int small_pack_threads(int n_items) { return (n_items >= 256) ? std::max(1, std::min(8, host_threads())) : 1; }
+
+int preintegrate(Handle* h, int32_t n_edges, const int32_t* sample_begin, const double* gyr, const double* acc, const double* dt,
+                 double gyr_meas_cov, double acc_meas_cov, double* imu_meas, double* cov_pvphi, double* imu_info_prv) {
+    if (n_edges <= 0 || !sample_begin || !gyr || !acc || !dt || !imu_meas || !cov_pvphi) return fail(h, "vba_preintegrate: bad arguments");
+    HIPCHK(h, hipSetDevice(h->device));
+    const int ns = sample_begin[n_edges];
+    for (int e = 0; e < n_edges; e++)
+        if (sample_begin[e] > sample_begin[e + 1] || sample_begin[e] < 0) return fail(h, "vba_preintegrate: sample_begin is not a CSR");
+    // a small private arena, inputs | outputs, copied straight from and to the caller's arrays
+    const size_t b_m = (size_t)n_edges * 61 * 8, b_c = (size_t)n_edges * 81 * 8;
+    vba_host::ArenaLayout L;
+    const size_t o_sb = L.take((size_t)(n_edges + 1) * 4), o_g = L.take((size_t)ns * 24), o_a = L.take((size_t)ns * 24), o_dt = L.take((size_t)ns * 8);
+    const size_t o_m = L.take(b_m + 2 * b_c + 1024);   // imu_meas, cov_pvphi, imu_info_prv back to back
+    HIPCHK(h, h->preint.dev.ensure(L.total_bytes()));
+    void* base = h->preint.dev.p;
+    int* d_sb = at<int>(base, o_sb);
+    double *d_g = at<double>(base, o_g), *d_a = at<double>(base, o_a), *d_dt = at<double>(base, o_dt), *d_m = at<double>(base, o_m);
+    double* d_c = d_m + (size_t)n_edges * 61;
+    double* d_i = d_c + (size_t)n_edges * 81;
+    HIPCHK(h, hipMemcpyAsync(d_sb, sample_begin, (size_t)(n_edges + 1) * 4, hipMemcpyHostToDevice, h->stream));
+    if (ns > 0) {
+        HIPCHK(h, hipMemcpyAsync(d_g, gyr, (size_t)ns * 24, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(d_a, acc, (size_t)ns * 24, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(d_dt, dt, (size_t)ns * 8, hipMemcpyHostToDevice, h->stream));
+    }
+    VBA_LAUNCH(k_preint, dim3(n_edges), dim3(128), 0, h->stream, n_edges, d_sb, d_g, d_a, d_dt, gyr_meas_cov, acc_meas_cov,
+                       d_m, d_c, imu_info_prv ? d_i : nullptr);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(imu_meas, d_m, b_m, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(cov_pvphi, d_c, b_c, hipMemcpyDeviceToHost, h->stream));
+    if (imu_info_prv) HIPCHK(h, hipMemcpyAsync(imu_info_prv, d_i, b_c, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int pose_optimize(Handle* h, int32_t n_frames, vba_frame_problem* const* inout, vba_frame_result* const* out) {
+    if (n_frames <= 0 || !inout || !out) return fail(h, "vba_pose_optimize: bad arguments");
+    HIPCHK(h, hipSetDevice(h->device));
+    size_t n_tot = 0;
+    if (const char* m = vba_host::check_pose(n_frames, inout, out, n_tot)) return fail(h, std::string("vba_pose_optimize: ") + m);
+    const vba_host::PoseArena A(n_frames, n_tot);
+    HIPCHK(h, h->pose.ensure(A.L));
+    void *hin = h->pose.in.p, *hout = h->pose.out.p, *base = h->pose.dev.p;
+    FrameDesc* desc = at<FrameDesc>(hin, A.desc);
+    vba_host::describe_pose(n_frames, inout, desc);   // offsets first, then the frames are packed by a few host threads
+    std::atomic<int> bad_cov(0);
+    host_parallel_for(h, n_frames, small_pack_threads(n_frames), [&](int f) {
+        if (!vba_host::pack_frame(inout[f], desc[f], at<double>(hin, A.pw), at<double>(hin, A.uv), at<double>(hin, A.w))) bad_cov.store(1);
+    });
+    if (bad_cov.load()) return fail(h, "vba_pose_optimize: imu_cov_pvphi is singular or not finite");
+    PoseBatch B;
+    B.desc = at<FrameDesc>(base, A.desc); B.pw = at<double>(base, A.pw); B.uv = at<double>(base, A.uv); B.w = at<double>(base, A.w);
+    B.out = at<FrameOut>(base, A.out); B.lvl = at<unsigned char>(base, A.lvl); B.err = at<double>(base, A.err);
+    B.n_frames = n_frames;
+    HIPCHK(h, hipMemcpyAsync(base, hin, A.L.upload_bytes(), hipMemcpyHostToDevice, h->stream));
+    VBA_LAUNCH(k_pose_opt, dim3(n_frames), dim3(64), 0, h->stream, B);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(hout, B.out, A.L.back_bytes(), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const FrameOut* res = at<FrameOut>(hout, A.L.in_back(A.out));
+    const unsigned char* lvl = at<unsigned char>(hout, A.L.in_back(A.lvl));
+    for (int f = 0; f < n_frames; f++) vba_host::unpack_frame(inout[f], out[f], desc[f], res[f], lvl);
+    return 0;
+}
+
+// Optimizer::OptimizeSim3 (src/Optimizer.cpp:4579-4785) between edge set-up and write-back, for a batch of independent loop
+// candidates: k_sim3_opt runs one workgroup per candidate
+int sim3_optimize(Handle* h, int32_t n_problems, vba_sim3_problem* const* inout, vba_sim3_result* const* out) {
+    if (n_problems < 0 || (n_problems > 0 && (!inout || !out))) return fail(h, "vba_sim3_optimize: bad arguments");
+    if (n_problems == 0) return 0;
+    size_t n_tot = 0;
+    bool want_chi2 = false;
+    std::string err;
+    if (vba_host::check_sim3(n_problems, inout, out, n_tot, want_chi2, err)) return fail(h, "vba_sim3_optimize: " + err);
+    HIPCHK(h, hipSetDevice(h->device));
+    const vba_host::Sim3Arena A(n_problems, n_tot);
+    const size_t b_back = A.download_bytes(want_chi2);
+    HIPCHK(h, h->sim3.ensure(A.L, b_back));
+    void *hin = h->sim3.in.p, *hout = h->sim3.out.p, *base = h->sim3.dev.p;
+    Sim3Desc* desc = at<Sim3Desc>(hin, A.desc);
+    vba_host::describe_sim3(n_problems, inout, desc);
+    host_parallel_for(h, n_problems, small_pack_threads(n_problems), [&](int f) {
+        vba_host::pack_sim3(inout[f], desc[f], at<double>(hin, A.p), at<double>(hin, A.uv), at<double>(hin, A.w));
+    });
+    Sim3Batch B;
+    B.desc = at<Sim3Desc>(base, A.desc); B.p = at<double>(base, A.p); B.uv = at<double>(base, A.uv); B.w = at<double>(base, A.w);
+    B.out = at<Sim3Out>(base, A.out); B.flag = at<unsigned char>(base, A.flag); B.c = at<double>(base, A.c);
+    const long long launch0 = h->n_launch;
+    HIPCHK(h, hipMemcpyAsync(base, hin, A.L.upload_bytes(), hipMemcpyHostToDevice, h->stream));
+    VBA_LAUNCH(k_sim3_opt, dim3(n_problems), dim3(64), 0, h->stream, B);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(hout, B.out, b_back, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->prof.kernel_launches = h->n_launch - launch0;
+    const Sim3Out* res = at<Sim3Out>(hout, A.L.in_back(A.out));
+    const unsigned char* flag = at<unsigned char>(hout, A.L.in_back(A.flag));
+    const double* cc = at<double>(hout, A.L.in_back(A.c));
+    for (int f = 0; f < n_problems; f++) vba_host::unpack_sim3(inout[f], out[f], desc[f], res[f], flag, cc);
+    return 0;
+}
+
+// what vba_debug_posegraph_system asks of a run: graph 0 stops after the solve of its first trial, and H, b, x come back
+struct PgDebug { double *H, *b, *x; };
+
+// Optimizer::OptimizeEssentialGraph (src/Optimizer.cpp:4243-4552) between edge set-up and write-back, for a batch of independent
+// graphs: the host validates every graph and lays out its envelope (vba_host_posegraph.h), k_posegraph_opt runs one workgroup per
+// graph, k_posegraph_points moves the map points when there are any
+int posegraph_run(Handle* h, int32_t n_graphs, vba_posegraph_problem* const* inout, vba_posegraph_result* const* out, PgDebug* dbg) {
+    if (n_graphs < 0 || (n_graphs > 0 && (!inout || !out))) return fail(h, "vba_posegraph_optimize: bad arguments");
+    if (n_graphs == 0) return 0;
+    vba_host::PoseGraphCall C;
+    std::string err;
+    if (vba_host::describe_posegraph(n_graphs, inout, out, dbg != nullptr, C, err)) return fail(h, "vba_posegraph_optimize: " + err);
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, h->pg.ensure(C.L));
+    char* hin = at<char>(h->pg.in.p, 0);
+    void *hout = h->pg.out.p, *base = h->pg.dev.p;
+    std::memcpy(hin + C.o_desc, C.desc.data(), sizeof(PgDesc) * (size_t)n_graphs);
+    for (int g = 0; g < n_graphs; g++) vba_host::pack_posegraph(C, g, inout[g], hin);
+    PgBatch B;
+    auto d = [base](size_t o) { return at<double>(base, o); };
+    auto i = [base](size_t o) { return at<int>(base, o); };
+    B.desc = at<PgDesc>(base, C.o_desc);
+    B.out = at<PgOut>(base, C.o_out);
+    B.Sin = d(C.o_Sin); B.meas = d(C.o_meas); B.ei = i(C.o_ei); B.ej = i(C.o_ej); B.free_of = i(C.o_free);
+    B.vert_of = i(C.o_vert); B.first = i(C.o_first); B.last_row = i(C.o_last); B.row_off = i(C.o_roff); B.inc_begin = i(C.o_incb);
+    B.inc = i(C.o_inc); B.pair_lo = i(C.o_plo); B.pair_hi = i(C.o_phi); B.pair_begin = i(C.o_pb); B.pair_edge = i(C.o_pe);
+    B.pt_in = d(C.o_pt); B.pt_ref = i(C.o_ref);
+    B.S = d(C.o_S); B.Sbk = d(C.o_Sbk); B.err = d(C.o_err); B.J = d(C.o_J); B.H = d(C.o_H); B.F = d(C.o_F); B.Ld = d(C.o_Ld);
+    B.b = d(C.o_b); B.w = d(C.o_w); B.y = d(C.o_y); B.x = d(C.o_x); B.pt_out = d(C.o_pto);
+    B.n_pt_total = (long long)C.npt;
+    const long long launch0 = h->n_launch;
+    HIPCHK(h, hipMemcpyAsync(base, hin, C.L.upload_bytes(), hipMemcpyHostToDevice, h->stream));
+    VBA_LAUNCH(k_posegraph_opt, dim3(n_graphs), dim3(PG_NT), 0, h->stream, B);
+    HIPCHK(h, hipGetLastError());
+    if (C.npt > 0 && !dbg) {
+        VBA_LAUNCH(k_posegraph_points, dim3((unsigned)((C.npt + 255) / 256)), dim3(256), 0, h->stream, B);
+        HIPCHK(h, hipGetLastError());
+    }
+    HIPCHK(h, hipMemcpyAsync(hout, B.out, C.L.back_bytes(), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->prof.kernel_launches = h->n_launch - launch0;
+    if (dbg) {   // graph 0 as the kernel formed it: the envelope expanded to a dense symmetric matrix, b, x
+        const vba_host::PoseGraphLayout& L = C.lay[0];
+        const size_t n = 7 * (size_t)L.n_free;
+        std::vector<double> env(49 * (size_t)L.env_blocks);
+        HIPCHK(h, hipMemcpy(env.data(), B.H, env.size() * 8, hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(dbg->b, B.b, n * 8, hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(dbg->x, B.x, n * 8, hipMemcpyDeviceToHost));
+        vba_host::expand_envelope(L, env.data(), dbg->H);
+        return 0;
+    }
+    const PgOut* res = at<PgOut>(hout, C.L.in_back(C.o_out));
+    const double* Sf = at<double>(hout, C.L.in_back(C.o_S));
+    const double* pf = at<double>(hout, C.L.in_back(C.o_pto));
+    for (int g = 0; g < n_graphs; g++) vba_host::unpack_posegraph(inout[g], out[g], C.desc[g], res[g], Sf, pf);
+    return 0;
+}
+
+}  // namespace

@@ -1,5 +1,5 @@
-// vba_layout.h -- the records the host describes a batch with and the device reads: window descriptor, control block and the
-// record-size constants.  Plain C / C++ (no HIP): included by vba_device.h for the kernels, and by the host code that lays a batch
+// vba_layout.h -- the records the host describes a batch with and the device reads: window descriptor, control block, the
+// record-size constants and the item records of the small-problem entry points.  Plain C / C++ (no HIP): included by vba_device.h for the kernels, and by the host code that lays a batch
 // out (vba_host_layout.h), which the tests compile with plain g++ under sanitizers.
 #pragma once
 #include <stdint.h>
@@ -88,4 +88,55 @@ struct WinCtrl {
     double chi_ini;   // LM: iniChi
     double chi2_vis, chi2_prv, chi2_bias;
     double trace[VBA_TRACE];
+};
+
+// ---- the small-problem entry points: per-item descriptor (host -> device) and result record (device -> host); the *Batch
+// structs of device pointers stay with their kernels
+// vba_pose_optimize (vba_pose.h)
+struct FrameDesc {
+    int last_is_frame, compute_marg, n_obs, n_last;
+    int obs0, last0;           // offsets into the concatenated observation arrays
+    int pad0, pad1;
+    double nav[22], nav_last[22], prior_nav[22];
+    double K[4], Rcb[9], tcb[3], g[3];
+    double meas[61];
+    double info_pvr[81];       // inverse of the P,V,phi covariance (host, as the reference's set-up code does)
+    double prior_info[225];
+    double inv_bg, inv_ba;
+    double hub_prior, hub_pvr, hub_bias, hub_mono;  // float-rounded Huber widths (:1741, :2107, :2125, :2137)
+};
+struct FrameOut {
+    int n_inliers, status, its[4];
+    int pad[2];
+    double chi2_round[4];
+    double nav[22];
+    double marg[225];
+};
+// vba_sim3_optimize (vba_sim3.h)
+struct Sim3Desc {
+    int n_pairs, fix_scale;
+    int its1, its2_bad, its2_clean, min_inliers;
+    long long pair0;           // offset of the candidate's pairs in the concatenated arrays
+    double S[8];               // t(3) q(4, xyzw) s
+    double K1[4], K2[4];
+    double th2, huber;
+};
+struct Sim3Out {
+    int n_inliers, status, n_bad1, its[2];
+    int pad[3];
+    double chi2_stage[2];
+    double S[8];
+};
+static_assert(sizeof(Sim3Desc) == 176 && sizeof(Sim3Out) == 112, "scripts/sim3_bench.py derives the copied bytes from these sizes");
+// vba_posegraph_optimize (vba_posegraph.h)
+struct PgDesc {
+    int nv, ne, nf, npair;
+    int fix_scale, its, n_pt, debug;   // debug: stop after the solve of the first trial of the first iteration (hooks flavour)
+    double lambda_init;
+    long long v0, e0, f0, r0, env0, inc0, pair0, pb0, pe0, pt0;   // offsets of the graph in the concatenated arrays (r0, pb0: the
+                                                                  // arrays with one entry more than rows / pairs)
+};
+struct PgOut {
+    int status, its_done, lm_trials, stop;
+    double chi2_initial, chi2_final, lambda_final;
 };

@@ -9,26 +9,8 @@
 // the small dense products.  Hessian order: [frame PVR | frame Bias | last PVR | last Bias].
 #pragma once
 #include "vba_device.h"
+#include "vba_layout.h"
 
-struct FrameDesc {
-    int last_is_frame, compute_marg, n_obs, n_last;
-    int obs0, last0;           // offsets into the concatenated observation arrays
-    int pad0, pad1;
-    double nav[22], nav_last[22], prior_nav[22];
-    double K[4], Rcb[9], tcb[3], g[3];
-    double meas[61];
-    double info_pvr[81];       // inverse of the P,V,phi covariance (host, as the reference's set-up code does)
-    double prior_info[225];
-    double inv_bg, inv_ba;
-    double hub_prior, hub_pvr, hub_bias, hub_mono;  // float-rounded Huber widths (:1741, :2107, :2125, :2137)
-};
-struct FrameOut {
-    int n_inliers, status, its[4];
-    int pad[2];
-    double chi2_round[4];
-    double nav[22];
-    double marg[225];
-};
 struct PoseBatch {
     const FrameDesc* desc;
     FrameOut* out;

@@ -26,21 +26,11 @@
 // columns, backward solve by rows.  A pivot that is not positive and finite fails the trial (tempChi = DBL_MAX).
 #pragma once
 #include "vba_device.h"
+#include "vba_layout.h"
 #include "vba_sim3.h"   // Sim3State, Sim3Step, s3_oplus
 
 #define PG_NT 256
 
-struct PgDesc {
-    int nv, ne, nf, npair;
-    int fix_scale, its, n_pt, debug;   // debug: stop after the solve of the first trial of the first iteration (hooks flavour)
-    double lambda_init;
-    long long v0, e0, f0, r0, env0, inc0, pair0, pb0, pe0, pt0;   // offsets of the graph in the concatenated arrays (r0, pb0: the
-                                                                  // arrays with one entry more than rows / pairs)
-};
-struct PgOut {
-    int status, its_done, lm_trials, stop;
-    double chi2_initial, chi2_final, lambda_final;
-};
 struct PgBatch {
     const PgDesc* desc;
     PgOut* out;

@@ -20,23 +20,9 @@
 // Lane l is the only reader and writer of the entries of pairs l, l + 64, ...: no synchronisation is needed.
 #pragma once
 #include "vba_device.h"
+#include "vba_layout.h"
 #include "vba_pose.h"   // po_wave_sum
 
-struct Sim3Desc {
-    int n_pairs, fix_scale;
-    int its1, its2_bad, its2_clean, min_inliers;
-    long long pair0;           // offset of the candidate's pairs in the concatenated arrays
-    double S[8];               // t(3) q(4, xyzw) s
-    double K1[4], K2[4];
-    double th2, huber;
-};
-struct Sim3Out {
-    int n_inliers, status, n_bad1, its[2];
-    int pad[3];
-    double chi2_stage[2];
-    double S[8];
-};
-static_assert(sizeof(Sim3Desc) == 176 && sizeof(Sim3Out) == 112, "scripts/sim3_bench.py derives the copied bytes from these sizes");
 struct Sim3Batch {
     const Sim3Desc* desc;
     Sim3Out* out;

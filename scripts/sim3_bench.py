@@ -24,7 +24,7 @@ sys.path.insert(0, ROOT)
 
 from mc_slam_amd import backend, synth  # noqa: E402
 
-SIZEOF_DESC, SIZEOF_OUT = 176, 112      # Sim3Desc / Sim3Out of mc_slam_amd/csrc/vba_sim3.h
+SIZEOF_DESC, SIZEOF_OUT = 176, 112      # Sim3Desc / Sim3Out of mc_slam_amd/csrc/vba_layout.h
 
 
 def _up(b):

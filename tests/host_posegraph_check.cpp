@@ -1,6 +1,8 @@
 // Sanitizer harness of the host half of vba_posegraph_optimize (mc_slam_amd/csrc/vba_host_posegraph.h): plain C++, built by
 // tests/test_host_posegraph.py with g++ -fsanitize=address,undefined.
-//   host_posegraph_check <file>...   -> one line per file: "ok <summary>" or "error <message>"
+//   host_posegraph_check <file>...            -> one line per file: "ok <summary>" or "error <message>"
+//   host_posegraph_check --call <file>...     -> the files as the graphs of one call: sizes and the arena offsets in arena order
+//   host_posegraph_check --expand <file>      -> the dense expansion of the graph's envelope (expand_envelope)
 // File (little-endian, written by the test): i32 n_vertices n_edges fix_scale its n_pt mutate, f64 lambda_init, f64 env_before,
 // then S [nv][8] f64, fixed [nv] u8, edge_i [ne] i32, edge_j [ne] i32, edge_S [ne][8] f64, pt [n_pt][3] f64, pt_ref [n_pt] i32.
 // mutate: 0 nothing, 1 n_vertices = -1, 2 n_edges = -1, 3 n_pt = -1, 4 S = NULL, 5 edge_S = NULL, 6 pt = NULL, 7 fixed = NULL.
@@ -76,23 +78,26 @@ static const char* invariants(const vba_posegraph_problem& P, const vba_host::Po
     return nullptr;
 }
 
-int main(int argc, char** argv) {
-    for (int a = 1; a < argc; a++) {
-        FILE* f = fopen(argv[a], "rb");
+// one file: the caller's arrays and the problem that points at them
+struct Graph {
+    std::vector<double> S, M, pt;
+    std::vector<uint8_t> fixed;
+    std::vector<int32_t> ei, ej, ref;
+    vba_posegraph_problem P;
+    double env_before = 0;
+    bool load(const char* path) {
+        FILE* f = fopen(path, "rb");
         int32_t hd[6];
         double sc[2];
-        if (!f || fread(hd, 4, 6, f) != 6 || fread(sc, 8, 2, f) != 2) { printf("error load\n"); if (f) fclose(f); continue; }
-        std::vector<double> S, M, pt;
-        std::vector<uint8_t> fixed;
-        std::vector<int32_t> ei, ej, ref;
+        if (!f || fread(hd, 4, 6, f) != 6 || fread(sc, 8, 2, f) != 2) { if (f) fclose(f); return false; }
         const size_t nv = hd[0], ne = hd[1], np = hd[4];
         const bool ok = take(f, S, 8 * nv) && take(f, fixed, nv) && take(f, ei, ne) && take(f, ej, ne) && take(f, M, 8 * ne) && take(f, pt, 3 * np) && take(f, ref, np);
         fclose(f);
-        if (!ok) { printf("error load\n"); continue; }
-        vba_posegraph_problem P;
+        if (!ok) return false;
         std::memset(&P, 0, sizeof P);
         P.n_vertices = hd[0]; P.n_edges = hd[1]; P.fix_scale = hd[2]; P.its = hd[3]; P.n_pt = hd[4];
         P.lambda_init = sc[0];
+        env_before = sc[1];
         P.S = S.data(); P.fixed = fixed.data(); P.edge_i = ei.data(); P.edge_j = ej.data(); P.edge_S = M.data(); P.pt = pt.data(); P.pt_ref = ref.data();
         switch (hd[5]) {
             case 1: P.n_vertices = -1; break;
@@ -104,9 +109,72 @@ int main(int argc, char** argv) {
             case 7: P.fixed = nullptr; break;
             default: break;
         }
+        return true;
+    }
+};
+
+// --call <file>...: the files as the graphs of ONE call -- its sizes and the offset of every region of the arena, in arena order;
+// the staging block is a heap block of exactly upload_bytes(), so a packing overrun is an ASan report
+static void one_call(int n, char** files) {
+    std::vector<Graph> G(n);
+    std::vector<vba_posegraph_problem*> pp(n);
+    std::vector<vba_posegraph_result> R(n);
+    std::vector<vba_posegraph_result*> rr(n);
+    for (int g = 0; g < n; g++) {
+        if (!G[g].load(files[g])) { printf("error load\n"); return; }
+        pp[g] = &G[g].P; rr[g] = &R[g];
+    }
+    vba_host::PoseGraphCall C;
+    std::string err;
+    if (vba_host::describe_posegraph(n, pp.data(), rr.data(), false, C, err)) { printf("error %s\n", err.c_str()); return; }
+    std::vector<char> heap_in(C.L.upload_bytes());   // exactly the upload section
+    for (int g = 0; g < n; g++) vba_host::pack_posegraph(C, g, pp[g], heap_in.data());
+    size_t nv = 0, ne = 0, nf = 0, nenv = 0, ninc = 0, npair = 0, npe = 0;
+    for (int g = 0; g < n; g++) {
+        const vba_host::PoseGraphLayout& L = C.lay[g];
+        nv += G[g].P.n_vertices; ne += G[g].P.n_edges; nf += L.n_free; nenv += L.env_blocks; ninc += L.inc.size(); npair += L.pair_lo.size(); npe += L.pair_edge.size();
+    }
+    printf("call nv %zu ne %zu nf %zu nenv %zu ninc %zu npair %zu npe %zu npt %zu upload %zu back %zu total %zu offsets", nv, ne, nf, nenv, ninc, npair, npe, C.npt,
+           C.L.upload_bytes(), C.L.back_bytes(), C.L.total_bytes());
+    for (size_t o : {C.o_desc, C.o_Sin, C.o_meas, C.o_ei, C.o_ej, C.o_free, C.o_vert, C.o_first, C.o_last, C.o_roff, C.o_incb, C.o_inc, C.o_plo, C.o_phi, C.o_pb,
+                     C.o_pe, C.o_pt, C.o_ref, C.o_out, C.o_S, C.o_pto, C.o_Sbk, C.o_err, C.o_J, C.o_H, C.o_F, C.o_Ld, C.o_b, C.o_w, C.o_y, C.o_x})
+        printf(" %zu", o);
+    // the last point reference of the last graph, as packed: an index into the concatenated vertices
+    if (C.npt) printf(" last_ref %d", vba_host::at<int>(heap_in.data(), C.o_ref)[C.npt - 1]);
+    printf("\n");
+}
+
+// --expand <file>: envelope block q holds 100 q + 7 a + k + 1 at (a, k) below the diagonal; the dense expansion, row by row
+static void expand(const char* file) {
+    Graph G;
+    vba_host::PoseGraphLayout L;
+    std::string err;
+    if (!G.load(file) || vba_host::build_posegraph(&G.P, L, err)) { printf("error %s\n", err.c_str()); return; }
+    std::vector<double> env(49 * (size_t)L.env_blocks), H(49 * (size_t)L.n_free * L.n_free, -1.0);
+    for (size_t q = 0; q < env.size(); q++) env[q] = 100.0 * (double)(q / 49) + (double)(q % 49) + 1.0;
+    for (int r = 0; r < L.n_free; r++) {   // a diagonal block is symmetric itself: 100 q + 7 min(a, k) + max(a, k) + 1
+        double* blk = env.data() + 49 * (size_t)(L.row_off[r] + r - L.first[r]);
+        for (int a = 0; a < 7; a++)
+            for (int k = 0; k < a; k++) blk[7 * a + k] = blk[7 * k + a];
+    }
+    vba_host::expand_envelope(L, env.data(), H.data());
+    printf("expand n_free %d first", L.n_free);
+    for (int v : L.first) printf(" %d", v);
+    printf(" H");
+    for (double v : H) printf(" %.0f", v);
+    printf("\n");
+}
+
+int main(int argc, char** argv) {
+    if (argc > 2 && !strcmp(argv[1], "--call")) { one_call(argc - 2, argv + 2); return 0; }
+    if (argc > 2 && !strcmp(argv[1], "--expand")) { expand(argv[2]); return 0; }
+    for (int a = 1; a < argc; a++) {
+        Graph G;
+        if (!G.load(argv[a])) { printf("error load\n"); continue; }
+        const vba_posegraph_problem& P = G.P;
         vba_host::PoseGraphLayout L;
         std::string err;
-        if (vba_host::build_posegraph(&P, L, err, (long long)sc[1])) { printf("error %s\n", err.c_str()); continue; }
+        if (vba_host::build_posegraph(&P, L, err, (long long)G.env_before)) { printf("error %s\n", err.c_str()); continue; }
         if (const char* bad = invariants(P, L)) { printf("error invariant: %s\n", bad); continue; }
         int widest = 0;
         for (int r = 0; r < L.n_free; r++) widest = std::max(widest, r - L.first[r] + 1);

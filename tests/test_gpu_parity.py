@@ -456,6 +456,16 @@ def test_on_device_preintegration_matches_oracle_and_numpy(ba, oracle):
     # the information it returns is what vba_problem.imu_info_prv expects
     p = synth.make_window(abi.VARIANT_PRV_IDP, n_kf=6, n_fixed=1, n_pt=60, n_obs=240, seed=31)
     assert info.shape[1:] == (9, 9) and p.imu_info_prv.shape[1] == 81
+    # arena reuse: 32 edges of 20 samples, then 1 edge of 3 samples on the same handle -- the small call's outputs equal, bit for
+    # bit, those of the same call on a fresh handle
+    ba.preintegrate(np.arange(33) * 20, rng.normal(0, 0.3, (640, 3)), rng.normal(0, 1.0, (640, 3)) + [0, 0, 9.8], np.full(640, 0.005))
+    small = ba.preintegrate([0, 3], gyr[:3], acc[:3], dt[:3])
+    fresh = backend.LocalBA(0, hooks=True)
+    try:
+        want = fresh.preintegrate([0, 3], gyr[:3], acc[:3], dt[:3])
+    finally:
+        fresh.close()
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(small, want))
 
 
 # ---- global bundle adjustment: one optimize(n), optional kernels, per-vertex fixed flags ----

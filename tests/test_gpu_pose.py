@@ -54,6 +54,25 @@ def test_batch_of_frames_equals_single_calls(ba, oracle):
     assert rs[-1].n_inliers == 0 and (rs[-1].nav == tiny.nav).all()     # fewer than 3 correspondences: untouched
 
 
+def test_small_call_after_a_large_one_equals_a_fresh_handle(ba):
+    """arena reuse: 64 frames of 200 observations, then 1 frame of 9 observations on the same handle -- bit for bit what a fresh
+    handle returns for the small call (nothing the large call left in the arena or the staging is read)"""
+    big = [synth.make_frame(seed=60 + i, n_obs=200, last_is_frame=bool(i % 2)) for i in range(4)]
+    ba.pose_optimize([big[i % 4] for i in range(64)])
+    s = synth.make_frame(seed=64, n_obs=60)
+    small = abi.FrameProblem(nav=s.nav, nav_last=s.nav_last, obs_pw=s.obs_pw[:9], obs_uv=s.obs_uv[:9], obs_w=s.obs_w[:9], K=s.K, T_cb=s.T_cb,
+                             g_w=s.g_w, imu_meas=s.imu_meas, imu_cov_pvphi=s.imu_cov_pvphi)
+    got = ba.pose_optimize([small])[0]
+    fresh = backend.LocalBA(0)
+    try:
+        want = fresh.pose_optimize([small])[0]
+    finally:
+        fresh.close()
+    assert got.n_inliers == want.n_inliers and got.its_done == want.its_done and got.status == want.status == 0
+    for k in ("nav", "outlier", "outlier_last", "chi2_round", "marg_cov_inv"):
+        assert getattr(got, k).tobytes() == getattr(want, k).tobytes(), k
+
+
 def test_noise_free_frame_recovers_the_truth(ba):
     f = synth.make_frame(seed=41, n_obs=200, noise=False)
     r = ba.pose_optimize([f])[0]

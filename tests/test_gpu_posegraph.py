@@ -116,6 +116,21 @@ def test_batch_equals_single_calls_and_a_repeated_call(ba):
         assert _bits(batch[k]) == _bits(one) == _bits(again[k]) == _bits(rev[k]), k
 
 
+def test_small_call_after_a_large_one_equals_a_fresh_handle(ba):
+    """arena reuse: 4 graphs of 60 vertices, then 1 graph of 5 vertices with 3 map points on the same handle -- bit for bit what a
+    fresh handle returns for the small call (nothing the large call left in the arena or the staging is read)"""
+    ba.posegraph_optimize([synth.make_posegraph(70 + k, 60, loops=[(55, 3)]) for k in range(4)])
+    p = synth.make_posegraph(75, 5, span=2, n_pt=3)
+    assert (p.n_vertices, p.n_pt) == (5, 3)
+    got = ba.posegraph_optimize([p])[0]
+    fresh = backend.LocalBA(0, hooks=True)
+    try:
+        want = fresh.posegraph_optimize([p])[0]
+    finally:
+        fresh.close()
+    assert got.chi2_final < got.chi2_initial and _bits(got) == _bits(want)            # the small call did move its estimates
+
+
 def test_launch_counts(ba):
     ba.posegraph_optimize([pc.case("ARROW"), pc.case("BAND")])
     assert ba.get_profile()["kernel_launches"] == 1

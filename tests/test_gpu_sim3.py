@@ -105,6 +105,20 @@ def test_ragged_batch_equals_single_calls_bit_for_bit(ba):
         _estimate_close(batch[k].S12, r.S12, "ragged %d" % k)
 
 
+def test_small_call_after_a_large_one_equals_a_fresh_handle(ba):
+    """arena reuse: 64 candidates of 200 pairs, then 1 candidate of 7 pairs on the same handle -- bit for bit what a fresh handle
+    returns for the small call (nothing the large call left in the arena or the staging is read)"""
+    ba.sim3_optimize([synth.make_sim3_pair(200 + k, 200) for k in range(64)])
+    p = synth.make_sim3_pair(39, 7, outlier_frac=0.0).copy(min_inliers=3)                # seven pairs are enough: both stages run
+    got = ba.sim3_optimize([p])[0]
+    fresh = backend.LocalBA(0, hooks=True)
+    try:
+        want = fresh.sim3_optimize([p])[0]
+    finally:
+        fresh.close()
+    assert got.n_inliers > 0 and got.its_done[1] > 0 and _bits(got) == _bits(want)
+
+
 def test_batched_call_is_one_kernel_launch(ba):
     ba.sim3_optimize(_ragged())
     assert ba.get_profile()["kernel_launches"] == 1

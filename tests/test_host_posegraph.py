@@ -107,3 +107,76 @@ def test_bad_graphs_are_refused_with_a_message(checker, tmp_path):
     open(f, "wb").write(raw[:len(raw) // 2])
     r = subprocess.run([checker, f], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0 and r.stdout.startswith("error load") and "ERROR" not in r.stderr
+
+
+def _layout_sizes(p):
+    """free count, envelope rows and list totals of one graph, from its edges alone"""
+    free_of = np.cumsum(p.fixed == 0) - 1
+    free_of[p.fixed != 0] = -1
+    nf = int((p.fixed == 0).sum())
+    a, b = free_of[p.edge_i], free_of[p.edge_j]
+    both = (a >= 0) & (b >= 0)
+    first = np.arange(nf)
+    np.minimum.at(first, np.maximum(a, b)[both], np.minimum(a, b)[both])
+    pairs = {(max(x, y), min(x, y)) for x, y in zip(a[both], b[both])}
+    return dict(nv=p.n_vertices, ne=p.n_edges, nf=nf, nenv=int((np.arange(nf) - first + 1).sum()), ninc=int((a >= 0).sum() + (b >= 0).sum()),
+                npair=len(pairs), npe=int(both.sum()), npt=p.n_pt), first
+
+
+def test_arena_of_a_two_graph_call(checker, tmp_path):
+    """every region of the arena [upload | back | work] sits where the entry point has always put it: in this order, each
+    (bytes + 8) rounded up to 256, nothing overlapping; packing runs into a block of exactly the upload section"""
+    ps = [pc.case("ARROW"), pc.case("BIG")]                     # the graph with map points second: its references move by the first one's vertices
+    files = []
+    for i, p in enumerate(ps):
+        files.append(str(tmp_path / ("c%d.pg" % i)))
+        _write(files[-1], p)
+    r = subprocess.run([checker, "--call"] + files, capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"), timeout=300)
+    assert r.returncode == 0 and "ERROR" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-2000:]
+    t = r.stdout.split()
+    assert t[0] == "call" and t[23] == "offsets"
+    got = {k: int(v) for k, v in zip(t[1:23:2], t[2:23:2])}
+    offs = [int(v) for v in t[24:55]]
+    s = {k: sum(_layout_sizes(p)[0][k] for p in ps) for k in ("nv", "ne", "nf", "nenv", "ninc", "npair", "npe", "npt")}
+    assert {k: got[k] for k in s} == s and s["npt"] > 0
+    G, nv, ne, nf, nenv, npt = 2, s["nv"], s["ne"], s["nf"], s["nenv"], s["npt"]
+    upload = [120 * G, 64 * nv, 64 * ne, 4 * ne, 4 * ne, 4 * nv, 4 * nf, 4 * nf, 4 * nf, 4 * (nf + G), 4 * (nf + G), 4 * s["ninc"], 4 * s["npair"],
+              4 * s["npair"], 4 * (s["npair"] + G), 4 * s["npe"], 24 * npt, 4 * npt]
+    back = [40 * G, 64 * nv, 24 * npt]
+    work = [64 * nv, 56 * ne, 784 * ne, 392 * nenv, 392 * nenv, 392 * nf, 56 * nf, 56 * nf, 56 * nf, 56 * nf]
+    sizes = upload + back + work
+    assert len(offs) == len(sizes) == 31
+    assert all(o % 256 == 0 for o in offs) and offs[0] == 0                                       # aligned
+    assert all(offs[k] + sizes[k] + 8 <= offs[k + 1] for k in range(30))                          # in today's order, disjoint (slack of 8 included)
+    assert offs[30] + sizes[30] + 8 <= got["total"]
+    want = np.concatenate([[0], np.cumsum([(b + 8 + 255) // 256 * 256 for b in sizes])])
+    assert offs == want[:31].tolist()                                                              # and exactly where they were
+    assert (got["upload"], got["back"], got["total"]) == (want[18], want[21] - want[18], want[31])
+    assert t[55] == "last_ref" and int(t[56]) == ps[0].n_vertices + int(ps[1].pt_ref[-1])
+
+
+def test_dense_expansion_of_a_three_vertex_envelope(checker, tmp_path):
+    """vertex 0 fixed, a chain 1 - 2 - 3: the envelope holds (0,0), (1,0), (1,1), (2,1), (2,2) and no block (2,0)"""
+    from mc_slam_amd import synth
+    p = synth.make_posegraph(3, 4, span=1, fixed_at=0)
+    sizes, first = _layout_sizes(p)
+    assert sizes["nf"] == 3 and first.tolist() == [0, 0, 1]
+    f = str(tmp_path / "e.pg")
+    _write(f, p)
+    r = subprocess.run([checker, "--expand", f], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"), timeout=60)
+    assert r.returncode == 0 and "ERROR" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-2000:]
+    t = r.stdout.split()
+    assert t[:3] == ["expand", "n_free", "3"] and [int(v) for v in t[4:7]] == first.tolist() and t[7] == "H"
+    H = np.array(t[8:], dtype=float).reshape(21, 21)
+    assert np.array_equal(H, H.T)
+    q = 0
+    for row in range(3):
+        for col in range(3):
+            blk = H[7 * row:7 * row + 7, 7 * col:7 * col + 7]
+            if first[row] <= col <= row:                 # block q of the envelope, row by row: 100 q + 7 a + k + 1 at (a, k)
+                want = 100 * q + np.arange(1, 50).reshape(7, 7)
+                assert np.array_equal(blk, want if col < row else np.triu(want) + np.triu(want, 1).T), (row, col)
+                q += 1
+            elif col <= row:
+                assert not blk.any(), (row, col)
+    assert q == sizes["nenv"] == 5
