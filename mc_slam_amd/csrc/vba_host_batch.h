@@ -91,47 +91,10 @@ int batch_solve(void* handle, int32_t n, vba_problem* const* inout, vba_result* 
     Handle* h = reinterpret_cast<Handle*>(handle);
     if (!h || async_busy(h)) return -1;
     if (n <= 0 || !inout) return fail(h, "vba_batch_solve: bad arguments");
-    // measured on MI355X, 4096 fresh C3 windows (scripts/e2e_sweep.py, resident 12.1-13.0k windows/s): chunk x lanes 512x4 7.8k windows/s,
-    // 768x3 8.1k, 1024x2 9.05k, 1024x3 8.97k, 1365x2 9.3-9.4k, 1536x2 9.4k, 1700x2 9.6k, 2048x2 (no ramp) 7.7k -- one lane solves while
-    // the other packs / transfers / builds its structure / scatters; every chunk pays the fixed cost of its ~1700 launches again
-    static const int env_lanes = getenv("VBA_LANES") ? atoi(getenv("VBA_LANES")) : 2;
-    static const int env_chunk = getenv("VBA_CHUNK") ? atoi(getenv("VBA_CHUNK")) : 1536;
-    const int chunk_max = std::max(1, h->opt_chunk > 0 ? h->opt_chunk : env_chunk);
-    // chunk boundaries: a ramp at the start, then equal chunks (no tiny tail).  Uploads go one at a time in chunk order (below) at
-    // ~57 us per window, a chunk of s windows solves in ~14 + 0.075 s ms: chunk k+1 is on the device before chunk k's solve ends when
-    // the uploads of chunks 2..k+1 fit into the solves of chunks 1..k -- sizes c, 2c, 3.25c, 4.5c with c a quarter of VBA_CHUNK (384,
-    // 768, 1248, 1696 for 4096 windows: measured timeline in DESIGN.md section 6).  No chunk falls below 256 windows when the batch has
-    // that many: the kernel choice of a chunk (section "regime") then equals the batch's.
-    std::vector<int> cbeg(1, 0);
-    {
-        static const int ramp = getenv("VBA_NO_RAMP") ? 0 : 1;
-        int left = n;
-        if (const char* e = getenv("VBA_CHUNKS")) {   // experiment: explicit chunk sizes "384,1024,1664" (the rest goes into one last chunk)
-            for (const char* q = e; *q && left > 0;) {
-                const int c = std::min(left, std::max(1, atoi(q)));
-                cbeg.push_back(cbeg.back() + c);
-                left -= c;
-                while (*q && *q != ',') q++;
-                if (*q == ',') q++;
-            }
-            if (left > 0) cbeg.push_back(cbeg.back() + left);
-            left = 0;
-        }
-        const int c = std::max(256, chunk_max / 4);
-        const int steps[4] = {c, 2 * c, 13 * c / 4, 9 * c / 2};
-        int cap = chunk_max;
-        if (ramp && chunk_max >= 1024) {
-            cap = steps[3];
-            for (int i = 0; i < 4 && left >= steps[i] + 256; i++) {
-                cbeg.push_back(cbeg.back() + steps[i]);
-                left -= steps[i];
-            }
-        }
-        const int rest = (left > 0) ? std::max(1, (left + cap - 1) / cap) : 0;
-        const int base = cbeg.back();
-        for (int q = 1; q <= rest; q++) cbeg.push_back(base + (int)((long long)left * q / rest));
-    }
-    const int n_lanes = std::max(1, std::min(h->opt_lanes > 0 ? h->opt_lanes : env_lanes, (int)cbeg.size() - 1));
+    // chunk boundaries and lanes: vba_host_plan.h (a ramp at the start, then equal chunks; no chunk below 256 windows when the batch has that many)
+    const vba_host::Knobs K = vba_host::current_knobs();
+    const std::vector<int> cbeg = vba_host::chunk_bounds(n, vba_host::chunk_max_of(h->ov, K), !K.no_ramp, K.chunks);
+    const int n_lanes = vba_host::lanes_of(h->ov, K, (int)cbeg.size() - 1);
     if (cbeg.size() == 2) {
         if (do_upload(h, n, inout) || do_run(h, stop_flag)) return -1;
         return do_download(h, n, inout, out);
@@ -139,7 +102,7 @@ int batch_solve(void* handle, int32_t n, vba_problem* const* inout, vba_result* 
     while ((int)h->lanes.size() < n_lanes) {
         Handle* l = nullptr;
         if (make_handle(h->device, h, &l) != 0) return fail(h, "vba_batch_solve: could not create a lane");
-        l->path = h->path;
+        l->ov.path = h->ov.path;   // (the path overrides only: a lane takes VBA_LANE_STREAMS, not the parent's streams)
         h->lanes.push_back(l);
     }
     const int n_chunks2 = (int)cbeg.size() - 1;
@@ -147,8 +110,7 @@ int batch_solve(void* handle, int32_t n, vba_problem* const* inout, vba_result* 
     // Lanes that start together stay in step (all pack, then all solve, then all scatter: the GPU idles while the hosts pack).
     // A run token breaks the symmetry: only `run_slots` lanes may be inside the solve at a time, the others pack / transfer /
     // build the structure of their next chunk or scatter their last one meanwhile.
-    static const int env_slots = getenv("VBA_RUN_SLOTS") ? atoi(getenv("VBA_RUN_SLOTS")) : 1;
-    int run_free = std::max(1, std::min(env_slots, n_lanes));
+    int run_free = std::max(1, std::min(K.run_slots, n_lanes));
     std::mutex run_mu;
     std::condition_variable run_cv;
     auto run_gated = [&](Handle* lane) -> int {
@@ -165,7 +127,7 @@ int batch_solve(void* handle, int32_t n, vba_problem* const* inout, vba_result* 
         run_cv.notify_one();
         return rc;
     };
-    static const bool timing = getenv("VBA_TIMING") != nullptr;
+    const bool timing = K.timing;
     const double t_call = now_ms();
     int up_turn = 0;
     std::mutex up_mu;
@@ -262,7 +224,7 @@ AsyncState& async_state(Handle* h) {
 }
 
 void async_worker(Handle* h, Handle* arena) {
-    static const bool timing = getenv("VBA_TIMING") != nullptr;
+    const bool timing = vba_host::process_knobs().timing;
     AsyncState& A = *h->as;
     (void)hipSetDevice(h->device);
     for (;;) {
@@ -353,7 +315,7 @@ int submit(Handle* h, int32_t n, vba_problem* const* inout, vba_result* const* o
         while ((int)A.arenas.size() < h->async_depth) {
             Handle* a = nullptr;
             if (make_handle(h->device, h, &a) != 0) return fail(h, "vba_batch_submit: could not create an arena");
-            a->path = h->path;   // (the paths of the parent, as the lanes of vba_batch_solve take them)
+            a->ov.path = h->ov.path;   // (the path overrides of the parent, as the lanes of vba_batch_solve take them)
             a->budget = &A.budget;
             A.arenas.push_back(a);
         }

@@ -3,6 +3,7 @@
 #pragma once
 #include "vba_host_arena.h"
 #include "vba_host_layout.h"
+#include "vba_host_plan.h"
 
 #include <sched.h>
 #include <algorithm>
@@ -119,13 +120,6 @@ struct PinVec {
     }
 };
 
-// an A/B switch from the environment: 1 if the variable is set, read once per process (one instance per switch I)
-template <int I>
-int env_once(const char* name) {
-    static const int v = getenv(name) ? 1 : 0;
-    return v;
-}
-
 // pinned staging of vba_batch_upload (the concatenated arrays of a batch) and vba_batch_download
 struct Staging {
     PinVec<double> pose, vel, bias, pt, uv, ow, meas, info;
@@ -192,18 +186,6 @@ struct HostBudget {
         cv.notify_all();
     }
 };
-// The path options a lane of vba_batch_solve and an arena of vba_batch_submit inherit from their parent, copied as a whole.
-// A/B paths: each defaults to its environment variable (read once per process); vba_debug_set_path overrides it
-struct PathOpts {
-    int opt_ll_min = 0;        // test hook: batch size from which the left-looking factorisation kernels are used (0: VBA_LL_MIN / 256)
-    int opt_no_chain = 0;      // test hook: 1 = one launch per block column everywhere (vba_debug_set_chain)
-    int opt_stop_after = -1;   // test hook: >= 0 -- every window reads the stop flag as 1 from that terminate() poll on (poll_stop)
-    int opt_lin_fallback = 0;  // test hook: XYZ windows without the edge-parallel work split
-    int opt_chol_step = 0;     // test hook: 1 = the first form of the fused factorisation step (k_chol_step) instead of k_chol_step4
-    int schur_split = env_once<0>("VBA_SCHUR_SPLIT");  // 1: inverse-depth Schur diagonal and off-diagonal pairs in two launches
-    int trsv_old = env_once<1>("VBA_TRSV_OLD");        // 1: k_trsv also for the row-major factor of the few-window regime
-    int pcg_jacobi = env_once<2>("VBA_PCG_JACOBI");    // 1: block-Jacobi PCG preconditioner instead of the block-tridiagonal one
-};
 struct AsyncState;   // the tickets, arenas and workers of vba_batch_submit (defined with it)
 
 struct Handle {
@@ -217,11 +199,9 @@ struct Handle {
     std::string err;
     DevBuf buf[BUF_N];
     SideArena preint, pose, sim3, pg;   // vba_preintegrate (dev only), vba_pose_optimize, vba_sim3_optimize, vba_posegraph_optimize
-    // small batches (<= 8 windows): every host-built array of an upload goes through ONE pinned arena and ONE H2D copy into one
-    // device arena (a single window is ~25 arrays of a few KB to a few 100 KB: 25 copies cost 0.4 ms of queue latency)
+    // small batches (UploadPlan::arena_on): every host-built array of an upload goes through ONE pinned arena and ONE H2D copy
     struct Pending { int id; const void* src; size_t bytes; };
     std::vector<Pending> pending;
-    bool arena_on = false;
     DevBuf up_arena;
     PinnedBuf up_arena_host;
     Staging stg;   // pinned staging: upload arrays; download: one D2H per array, windows scattered to the callers' arrays by host threads
@@ -241,8 +221,9 @@ struct Handle {
     bool up_pending = false;
     bool dl_prefetched = false;   // few windows: the run left the result arrays in the download staging already
     int n_win = 0;
-    int regime_n = 0;  // windows of the uploaded batch: decides WHICH kernels run (few-window / many-window variants), so that
-                       // cutting the batch into window groups never changes a summation order
+    vba_host::Overrides ov;   // what the vba_debug_set_* hooks set
+    vba_host::UploadPlan up;  // the policy of the uploaded batch (vba_host_plan.h), fixed at upload_begin
+    vba_host::RunPlan rp;     // ... and of the run being enqueued / the last run
     vba_host::LaunchGeom geom;   // launch geometry (maxima over the batch)
     std::vector<int> win_tiles;  // tile products of one factorisation of window w
     std::vector<long long> win_prod_order;  // per window: tile products under the V/Bias-first and the keyframe order (-1: not evaluated)
@@ -250,9 +231,6 @@ struct Handle {
     volatile int* stop_host = nullptr;  // pinned, device-visible
     int* stop_dev = nullptr;
     bool profile = false;
-    PathOpts path;
-    int opt_chunk = 0, opt_lanes = 0;  // > 0: chunk size / lanes of vba_batch_solve (test hook; defaults from VBA_CHUNK, VBA_LANES)
-    int opt_streams = 0;  // > 0: window groups / streams for GN batches (test hook; default from VBA_STREAMS, 1)
     long long n_launch = 0;   // kernel launches enqueued through this handle so far
 #ifdef VBA_TEST_HOOKS
     // vba_debug_capture: at the cap_call-th enqueue_solve_iteration of the next run, device copies of the stage products
@@ -267,7 +245,6 @@ struct Handle {
     vba_profile prof;
     bool uploaded = false;
     bool ran = false;
-    bool ll_mode = false;  // left-looking factorisation kernels (batch size at upload >= VBA_LL_MIN)
 };
 
 #define HIPCHK(h, call)                                                                          \
@@ -331,14 +308,14 @@ using vba_host::LaunchGeom;
 int build_structure(Handle* h, const vba_problem* P, Structure& st, bool two_sided = false) {
     std::string err;
     if (vba_host::build_structure(P, st, err, two_sided)) return fail(h, err);
-    if (h->path.opt_lin_fallback && P->variant != VBA_VARIANT_PRV_IDP) st.linblk.clear();   // test hook: the thread-per-landmark linearisation
+    if (h->ov.path.lin_fallback && P->variant != VBA_VARIANT_PRV_IDP) st.linblk.clear();   // test hook: the thread-per-landmark linearisation
     return 0;
 }
 
 // a pageable std::vector goes through a pinned copy first: a pageable hipMemcpyAsync is a synchronous, staged transfer
 template <typename T>
 int h2d_vec(Handle* h, int id, const std::vector<T>& v, PinVec<T>& pin) {
-    if (h->arena_on) {
+    if (h->up.arena_on) {
         h->pending.push_back({id, v.data(), v.size() * sizeof(T)});
         return 0;
     }
@@ -354,7 +331,7 @@ int h2d_vec(Handle* h, int id, const std::vector<T>& v, PinVec<T>& pin) {
 template <typename V>
 int h2d(Handle* h, int id, const V& v) {
     typedef typename V::value_type T;
-    if (h->arena_on) {
+    if (h->up.arena_on) {
         h->pending.push_back({id, v.data(), v.size() * sizeof(T)});
         return 0;
     }
@@ -364,7 +341,7 @@ int h2d(Handle* h, int id, const V& v) {
 }
 // arena mode: lay the recorded arrays out (256-B aligned), gather them into the pinned arena, one copy, point the views
 int h2d_flush(Handle* h) {
-    if (!h->arena_on) return 0;
+    if (!h->up.arena_on) return 0;
     size_t total = 0;
     for (auto& q : h->pending) total += (std::max<size_t>(q.bytes, 16) + 255) / 256 * 256;
     HIPCHK(h, h->up_arena.ensure(total + 256));
@@ -393,7 +370,8 @@ int dalloc(Handle* h, int id, size_t bytes) {
 // share by the launcher counts only that share).
 int host_threads() {
     static const int n = [] {
-        if (const char* e = getenv("VBA_UPLOAD_THREADS")) return std::max(1, atoi(e));
+        const vba_host::Knobs& K = vba_host::process_knobs();
+        if (K.upload_threads != vba_host::KNOB_UNSET) return std::max(1, K.upload_threads);
         int cores = (int)std::thread::hardware_concurrency();
         cpu_set_t set;
         CPU_ZERO(&set);
@@ -402,10 +380,7 @@ int host_threads() {
         // and is not used).  A rank counts as pinned to its share only when the launcher says so (mc_slam_amd/launch.py exports
         // VBA_RANK_CPUS with the cores it bound the rank to): a cpuset-limited container also shows fewer cores than the machine
         // has, and there the ranks still share what it shows.
-        int local_world = 1;
-        if (const char* e = getenv("LOCAL_WORLD_SIZE")) local_world = std::max(1, atoi(e));
-        const bool pinned = getenv("VBA_RANK_CPUS") != nullptr;
-        const int share = pinned ? cores : std::max(1, cores / local_world);
+        const int share = K.rank_cpus ? cores : std::max(1, cores / std::max(1, K.local_world_size));
         return std::max(std::min(2, std::max(1, cores)), std::min(16, share));
     }();
     return n;
@@ -425,12 +400,4 @@ void host_parallel_for(Handle* h, int count, int want_threads, const F& job) {
     for (auto& t : pool) t.join();
     if (h->budget) h->budget->give(nt);
 }
-// >= this many windows: left-looking factorisation kernels, which never modify S (measured: the right-looking pair is faster
-// up to ~256 windows)
-bool use_left_looking(const Handle* h, int n) {
-    static const int left_looking = getenv("VBA_RIGHT_LOOKING") ? 0 : 1;
-    static const int ll_min = getenv("VBA_LL_MIN") ? atoi(getenv("VBA_LL_MIN")) : 256;
-    return left_looking && n >= (h->path.opt_ll_min > 0 ? h->path.opt_ll_min : ll_min);
-}
-
 }  // namespace

@@ -6,12 +6,13 @@
 // that libvislam_ba.so exports exactly the header).
 #ifdef VBA_TEST_HOOKS
 namespace {
-// a path option of the handle, pushed to the lanes vba_batch_solve has created already (new lanes and arenas copy the parent's)
-int set_path_opt(void* handle, int PathOpts::*f, int value) {
+// a path override of the handle, pushed to the lanes vba_batch_solve has created already (new lanes and arenas copy the parent's)
+using vba_host::PathOverrides;
+int set_path_opt(void* handle, int PathOverrides::*f, int value) {
     Handle* h = reinterpret_cast<Handle*>(handle);
     if (!h) return -1;
-    h->path.*f = value;
-    for (Handle* l : h->lanes) l->path = h->path;
+    h->ov.path.*f = value;
+    for (Handle* l : h->lanes) l->ov.path = h->ov.path;
     return 0;
 }
 }  // namespace
@@ -37,20 +38,20 @@ int vba_debug_tile_products(void* handle, int32_t w, int64_t* out) {
 int vba_debug_set_streams(void* handle, int32_t n) {
     Handle* h = reinterpret_cast<Handle*>(handle);
     if (!h) return -1;
-    h->opt_streams = n;
+    h->ov.streams = n;
     return 0;
 }
 // every window reads the stop flag as 1 from its n-th terminate() poll on (n < 0: off); the oracle's vba_oracle_solve_ex counts alike
-int vba_debug_set_stop_after(void* handle, int32_t n) { return set_path_opt(handle, &PathOpts::opt_stop_after, n); }
+int vba_debug_set_stop_after(void* handle, int32_t n) { return set_path_opt(handle, &PathOverrides::stop_after, n); }
 // 1: the first form of the fused factorisation step (v_readlane broadcasts, panel solves after the diagonal tile); anything else: k_chol_step4
-int vba_debug_set_chol_step(void* handle, int32_t form) { return set_path_opt(handle, &PathOpts::opt_chol_step, form); }
-int vba_debug_set_lin_fallback(void* handle, int32_t on) { return set_path_opt(handle, &PathOpts::opt_lin_fallback, on); }
-int vba_debug_set_ll_min(void* handle, int32_t n) { return set_path_opt(handle, &PathOpts::opt_ll_min, n); }
+int vba_debug_set_chol_step(void* handle, int32_t form) { return set_path_opt(handle, &PathOverrides::chol_step, form); }
+int vba_debug_set_lin_fallback(void* handle, int32_t on) { return set_path_opt(handle, &PathOverrides::lin_fallback, on); }
+int vba_debug_set_ll_min(void* handle, int32_t n) { return set_path_opt(handle, &PathOverrides::ll_min, n); }
 int vba_debug_set_chunking(void* handle, int32_t chunk, int32_t lanes) {
     Handle* h = reinterpret_cast<Handle*>(handle);
     if (!h) return -1;
-    h->opt_chunk = chunk;
-    h->opt_lanes = lanes;
+    h->ov.chunk = chunk;
+    h->ov.lanes = lanes;
     return 0;
 }
 // test hook: while on, the workers of vba_batch_submit start no upload (submitted tickets stay pending: observable without timing)
@@ -75,13 +76,13 @@ int vba_debug_buf_id(const char* name) {
 }
 
 // chain columns of the factorisation (vba_chain.h): 0 = one launch per block column everywhere, 1 = the default policy
-int vba_debug_set_chain(void* handle, int32_t on) { return set_path_opt(handle, &PathOpts::opt_no_chain, on ? 0 : 1); }
+int vba_debug_set_chain(void* handle, int32_t on) { return set_path_opt(handle, &PathOverrides::no_chain, on ? 0 : 1); }
 
 // the A/B paths read from the environment, per handle: "schur_split", "trsv_old", "pcg_jacobi" (value 0 / 1)
 int vba_debug_set_path(void* handle, const char* name, int32_t value) {
     if (!name) return -1;
-    int PathOpts::*f = !strcmp(name, "schur_split") ? &PathOpts::schur_split : !strcmp(name, "trsv_old") ? &PathOpts::trsv_old
-                     : !strcmp(name, "pcg_jacobi") ? &PathOpts::pcg_jacobi : nullptr;
+    int PathOverrides::*f = !strcmp(name, "schur_split") ? &PathOverrides::schur_split : !strcmp(name, "trsv_old") ? &PathOverrides::trsv_old
+                          : !strcmp(name, "pcg_jacobi") ? &PathOverrides::pcg_jacobi : nullptr;
     return f ? set_path_opt(handle, f, value ? 1 : 0) : -1;
 }
 
@@ -130,16 +131,26 @@ int vba_debug_window_layout(void* handle, int32_t w, int64_t* out, int64_t n_out
     const WinDesc& d = h->desc[w];
     if (n_out < 20 + (int64_t)d.pdim * d.n_free + 6) return -1;
     out[0] = d.nS; out[1] = d.nb; out[2] = d.pdim; out[3] = d.n_free; out[4] = d.order; out[5] = d.nc; out[6] = d.nc_split;
-    out[7] = h->B.l_packed; out[8] = h->regime_n; out[9] = h->n_win;
+    out[7] = h->B.l_packed; out[8] = h->up.n_win; out[9] = h->n_win;
     for (int i = 0; i < 3; i++) out[10 + i] = h->cap_path[i];
     out[13] = sizeof(WinCtrl);
-    out[14] = h->solver == VBA_SOLVER_PCG; out[15] = h->B.pcg_tri;
+    out[14] = h->solver == VBA_SOLVER_PCG; out[15] = h->rp.pcg_tri;
     out[16] = offsetof(WinCtrl, stage); out[17] = offsetof(WinCtrl, active); out[18] = offsetof(WinCtrl, robust_vis);
     out[19] = offsetof(WinCtrl, lambda);
     int64_t* vp = out + 20;
     for (int a = 0; a < d.n_free; a++)
         for (int r = 0; r < d.pdim; r++) vp[d.pdim * a + r] = vba_host::vpos(d, a, r);
     for (int q = 0; q < 3; q++) { vp[d.pdim * d.n_free + q] = d.pad0[q]; vp[d.pdim * d.n_free + 3 + q] = d.padn[q]; }
+    return 0;
+}
+// The plan of the uploaded batch and of its last run (vba_host_plan.h: UploadPlan, RunPlan) as PLAN_INTS integers, in the order
+// documented at vba_host::plan_ints; before the first run of an upload the RunPlan entries are -1
+int vba_debug_plan(void* handle, int64_t* out, int64_t n_out) {
+    Handle* h = reinterpret_cast<Handle*>(handle);
+    if (!h || !out || n_out < vba_host::PLAN_INTS || !h->uploaded) return -1;
+    long long v[vba_host::PLAN_INTS];
+    vba_host::plan_ints(h->up, h->rp, v);
+    for (int i = 0; i < vba_host::PLAN_INTS; i++) out[i] = (i < vba_host::PLAN_UPLOAD_INTS || h->ran) ? v[i] : -1;
     return 0;
 }
 // From the captured factor of window w: L (unit lower) with D on its diagonal, dense nS x nS row-major, exactly the tiles the

@@ -44,8 +44,7 @@ struct Group {
     volatile int* alive;  // pinned words of this group: [stage * 32 + it]
     bool dead;
 };
-// grids whose workgroups schur_map() deals to the XCDs by window: the windows of a group, rounded up to the 8 XCDs
-inline int xcd_windows(int n) { return (n >= 8) ? 8 * ((n + 7) / 8) : n; }
+using vba_host::xcd_windows;
 
 #ifdef VBA_TEST_HOOKS
 // vba_debug_capture: the captured items (per window: vba_debug_capture_get) and the kernel paths an iteration took
@@ -81,47 +80,48 @@ void cap_copy(Handle* h, hipStream_t stream, int first, int last) {
 #define CAP_COPY(h, st, a, b) do { } while (0)
 #define CAP_PATH(h, i, v) do { } while (0)
 #endif
-// kernel paths reported by the capture hook (vba_debug_window_layout)
-enum { CAP_SCHUR_ALL_W, CAP_SCHUR_ALL, CAP_SCHUR_SPLIT_W, CAP_SCHUR_SPLIT, CAP_SCHUR3_W, CAP_SCHUR3 };
-enum { CAP_FACTOR_STEP1 = 1, CAP_FACTOR_STEP4 = 4, CAP_FACTOR_STEP4_ONE = 5, CAP_FACTOR_LL = 6, CAP_FACTOR_PCG = 7, CAP_FACTOR_MIXED = 8 };
-enum { CAP_TRSV_P, CAP_TRSV };
 
+// One solve iteration of a group.  WHICH kernels: the run's plan (h->rp, decided for the whole batch: vba_host_plan.h); grid sizes:
+// the group's n_win; what is tested here is geometry only.  CAP_PATH records what was launched (vba_debug_window_layout [10..12]).
 void enqueue_solve_iteration(Handle* h, const Group& g, StopRef stop_flag = StopRef()) {
     const Batch& B = g.B;
     const LaunchGeom& L = h->geom;
     hipStream_t stream = g.stream;
+    const vba_host::RunPlan& P = h->rp;
     const int n = g.n_win;          // windows of this group: grid sizes
-    const int rn = h->regime_n;     // windows of the batch: kernel choice
     const bool idp = h->variant == VBA_VARIANT_PRV_IDP;
     const int ngrp = xcd_windows(n);
     CAP_COPY(h, stream, CAP_POSE_A, CAP_VARACT_A + 1);
     {
         ProfScope ps(h, stream, VBA_PROF_SCHUR);
-        if (idp) {
-            const int fused_schur = h->path.schur_split ? 0 : 1;
-            if (rn >= 8 && fused_schur) {
-                CAP_PATH(h, 0, CAP_SCHUR_ALL);
-                VBA_LAUNCH(k_schur_all, dim3((L.max_free + L.max_quads) * ngrp), dim3(64), 0, stream, B, L.max_free, L.max_quads);
-            } else if (fused_schur) {
-                CAP_PATH(h, 0, CAP_SCHUR_ALL_W);
-                VBA_LAUNCH(k_schur_all_w, dim3((L.max_free + L.max_offp) * ngrp), dim3(64), 0, stream, B, L.max_free, L.max_offp);
-            } else {
-            CAP_PATH(h, 0, rn >= 8 ? CAP_SCHUR_SPLIT : CAP_SCHUR_SPLIT_W);
+        using namespace vba_host;   // (CAP_SCHUR_*: the plan's value selects, the launch site records what it launched)
+        const bool quads = P.schur == CAP_SCHUR_SPLIT || P.schur == CAP_SCHUR3;   // off-diagonal blocks per quad of pairs, XCD-mapped
+        switch (P.schur) {
+        case CAP_SCHUR_ALL:
+            CAP_PATH(h, 0, CAP_SCHUR_ALL);
+            VBA_LAUNCH(k_schur_all, dim3((L.max_free + L.max_quads) * ngrp), dim3(64), 0, stream, B, L.max_free, L.max_quads);
+            break;
+        case CAP_SCHUR_ALL_W:
+            CAP_PATH(h, 0, CAP_SCHUR_ALL_W);
+            VBA_LAUNCH(k_schur_all_w, dim3((L.max_free + L.max_offp) * ngrp), dim3(64), 0, stream, B, L.max_free, L.max_offp);
+            break;
+        case CAP_SCHUR_SPLIT:
+        case CAP_SCHUR_SPLIT_W:
+            CAP_PATH(h, 0, quads ? CAP_SCHUR_SPLIT : CAP_SCHUR_SPLIT_W);
             VBA_LAUNCH(k_schur_diag, dim3(L.max_free * ngrp), dim3(64), 0, stream, B, L.max_free);
-            if (rn >= 8) VBA_LAUNCH(k_schur_off, dim3(L.max_quads * ngrp), dim3(64), 0, stream, B, L.max_quads);
+            if (quads) VBA_LAUNCH(k_schur_off, dim3(L.max_quads * ngrp), dim3(64), 0, stream, B, L.max_quads);
             else VBA_LAUNCH(k_schur_off_w, dim3(L.max_offp * ngrp), dim3(64), 0, stream, B, L.max_offp);
-            }
-        } else {
-            CAP_PATH(h, 0, rn >= 8 ? CAP_SCHUR3 : CAP_SCHUR3_W);
+            break;
+        default:   // CAP_SCHUR3, CAP_SCHUR3_W
+            CAP_PATH(h, 0, quads ? CAP_SCHUR3 : CAP_SCHUR3_W);
             VBA_LAUNCH(k_dinv, dim3(L.max_pt_blk, n), dim3(64), 0, stream, B);
-            // (diagonal and off-diagonal pairs in two launches: fusing them as for the inverse-depth records gained nothing at C2)
             VBA_LAUNCH(k_schur_diag3, dim3(L.max_free * ngrp), dim3(64), 0, stream, B, L.max_free, 0);
-            if (rn >= 8) VBA_LAUNCH(k_schur_off3, dim3(L.max_quads * ngrp), dim3(64), 0, stream, B, L.max_quads);
+            if (quads) VBA_LAUNCH(k_schur_off3, dim3(L.max_quads * ngrp), dim3(64), 0, stream, B, L.max_quads);
             else VBA_LAUNCH(k_schur_off3_w, dim3(L.max_offp * ngrp), dim3(64), 0, stream, B, L.max_offp);
         }
     }
     CAP_COPY(h, stream, CAP_S_B, CAP_VEC_B + 1);
-    if (h->solver == VBA_SOLVER_PCG) {
+    if (P.factor == vba_host::CAP_FACTOR_PCG) {
         // Two launches per CG iteration for all windows of the group; the host enqueues BATCHES of iterations and reads one pinned
         // word per batch (did any window go on?) two batches behind the device.  Converged windows exit at the first instruction.
         ProfScope ps(h, stream, VBA_PROF_FACTOR);
@@ -147,21 +147,15 @@ void enqueue_solve_iteration(Handle* h, const Group& g, StopRef stop_flag = Stop
             (void)hipEventRecord(ev.back(), stream);
         }
         VBA_LAUNCH(k_pcg_finish, dim3(n), dim3(256), 0, stream, B);
-        CAP_PATH(h, 1, CAP_FACTOR_PCG);
+        CAP_PATH(h, 1, vba_host::CAP_FACTOR_PCG);
         CAP_COPY(h, stream, CAP_VEC_C, CAP_VEC_C + 1);
     } else {
     {
         ProfScope ps(h, stream, VBA_PROF_FACTOR);
-        // Two regimes (decided for the whole batch at upload, also for its window groups): from VBA_LL_MIN = 256 windows on the
-        // left-looking tile kernels (S stays pristine, the factor is tile-packed), below that one fused right-looking launch per block
-        // column.  (Until round 3 there was a third one in between, 64..255 windows: the panel solves and the MFMA updates of a
-        // column in two launches, because the fused kernel redid the diagonal tile and two panel solves in every tile-pair workgroup.
-        // With the DPP elimination of k_chol_step4 (then: its first form, k_chol_step3) the fused launch wins up to the left-looking threshold -- 64 windows 9.2 ms per step
-        // against 12.7, 128: 15.1 / 17.7, 200: 21.8 / 23.1, left-looking at 200: 21.7 -- and the split kernels are gone.)
         // the chain columns [0, nc) of every window in one launch (vba_chain.h); the per-column kernels start behind them
         const int k_first = L.max_nc > 0 ? std::min(L.min_nc, L.max_nc) : 0;
         if (L.max_nc > 0) {
-            if (h->ll_mode) {
+            if (P.factor == vba_host::CAP_FACTOR_LL) {
                 VBA_LAUNCH(k_chol_chain_diag, dim3(n), dim3(64), 0, stream, B);
                 if (L.max_chain_rows > 0) VBA_LAUNCH(k_chol_chain_panel, dim3(L.max_chain_rows * ngrp), dim3(64), 0, stream, B, L.max_chain_rows);
             }
@@ -170,25 +164,22 @@ void enqueue_solve_iteration(Handle* h, const Group& g, StopRef stop_flag = Stop
                 if (L.max_cu > 0) VBA_LAUNCH(k_chol_chain_upd, dim3(L.max_cu, n), dim3(512), 0, stream, B);
             }
         }
-        if (h->ll_mode) {
-            CAP_PATH(h, 1, CAP_FACTOR_LL);
+        if (P.factor == vba_host::CAP_FACTOR_LL) {
+            CAP_PATH(h, 1, vba_host::CAP_FACTOR_LL);
             for (int k = k_first; k < L.max_nb; k++) {  // every tile read once, updated in registers, written once
                 VBA_LAUNCH(k_chol_diag_ll2, dim3(n), dim3(64), 0, stream, B, k);
                 if (L.pan_grid[k] > 0) VBA_LAUNCH(k_chol_panel_ll, dim3(L.pan_grid[k] * ngrp), dim3(64), 0, stream, B, k, L.pan_grid[k]);
             }
         } else {
-            // form 1 (test hook vba_debug_set_chol_step / VBA_CHOL_STEP=1): the first version of the step -- diagonal tile, then the
-            // panel solves, v_readlane broadcasts; kept as the cross-check of the hand-written DPP instruction stream
-            static const int env_form = getenv("VBA_CHOL_STEP") ? atoi(getenv("VBA_CHOL_STEP")) : 0;
-            const int step_form = h->path.opt_chol_step > 0 ? h->path.opt_chol_step : (env_form > 0 ? env_form : 4);
             for (int k = k_first; k < L.max_nb; k++) {
+                // one window: descriptor and step table ride in the kernel arguments, for the columns the step table covers
+                const bool one = P.factor == vba_host::CAP_FACTOR_STEP4_ONE && (int)h->one_sb.size() > k + 1;
                 // (the capture reports the step kernel of the columns; columns that took different ones: CAP_FACTOR_MIXED)
-                const int form = step_form == 1 ? CAP_FACTOR_STEP1
-                               : (n == 1 && (int)h->one_sb.size() > k + 1) ? CAP_FACTOR_STEP4_ONE : CAP_FACTOR_STEP4;
-                CAP_PATH(h, 1, (k == k_first || h->cap_path[1] == form) ? form : CAP_FACTOR_MIXED);
+                const int form = (P.factor == vba_host::CAP_FACTOR_STEP4_ONE && !one) ? vba_host::CAP_FACTOR_STEP4 : P.factor;
+                CAP_PATH(h, 1, (k == k_first || h->cap_path[1] == form) ? form : vba_host::CAP_FACTOR_MIXED);
                 (void)form;
-                if (step_form == 1) VBA_LAUNCH(k_chol_step, dim3(L.step_grid[k], n), dim3(64), 0, stream, B, k);
-                else if (n == 1 && (int)h->one_sb.size() > k + 1) {   // one window: descriptor and step table ride in the kernel arguments
+                if (P.factor == vba_host::CAP_FACTOR_STEP1) VBA_LAUNCH(k_chol_step, dim3(L.step_grid[k], n), dim3(64), 0, stream, B, k);
+                else if (one) {
                     const WinDesc& d0 = h->desc[0];
                     StepOne so;
                     so.algo = d0.algo; so.nS = d0.nS; so.nb = d0.nb; so.vec0 = d0.vec0; so.S0 = d0.S0;
@@ -200,12 +191,12 @@ void enqueue_solve_iteration(Handle* h, const Group& g, StopRef stop_flag = Stop
     }
     {
         ProfScope ps(h, stream, VBA_PROF_TRSV);
-        if (h->ll_mode || h->path.trsv_old) {
-            CAP_PATH(h, 2, CAP_TRSV);
+        if (P.trsv == vba_host::CAP_TRSV) {
+            CAP_PATH(h, 2, vba_host::CAP_TRSV);
             const size_t shm = ((size_t)L.max_nS + 256 + 32 * 33) * sizeof(double);
             VBA_LAUNCH(k_trsv, dim3(n), dim3(256), shm, stream, B);
-        } else {   // row-major factor: a solving wave + seven waves that work one column ahead
-            CAP_PATH(h, 2, CAP_TRSV_P);
+        } else {
+            CAP_PATH(h, 2, vba_host::CAP_TRSV_P);
             const size_t shm = ((size_t)L.max_nS + 2 * TRSV_P_DW * 32 + 2 * 32 * 65 + 32) * sizeof(double) + ((size_t)L.max_pan + L.max_nb + 2) * sizeof(int);
             VBA_LAUNCH(k_trsv_p, dim3(n), dim3(512), shm, stream, B);
         }
@@ -225,11 +216,11 @@ void enqueue_solve_iteration(Handle* h, const Group& g, StopRef stop_flag = Stop
 
 void enqueue_lin(Handle* h, const Group& g, int mode) {
     const LaunchGeom& L = h->geom;
+    const int imu_lin = L.max_imu > 0 ? h->rp.imu_lin : -1;
     ProfScope ps(h, g.stream, VBA_PROF_LINEARIZE);
     if (h->variant == VBA_VARIANT_PRV_IDP) {
         const size_t shm = LIN2_LDS;
-        static const int fuse_imu = getenv("VBA_LIN_IMU_SPLIT") ? 0 : 1;
-        if (fuse_imu && L.max_imu > 0 && h->regime_n < 64) {   // few windows: edges and IMU factors in one launch
+        if (imu_lin == vba_host::LIN_IMU_FUSED) {   // edges and IMU factors in one launch
             VBA_LAUNCH(k_lin2_imu, dim3(L.max_lin_blk + L.max_imu, g.n_win), dim3(256), shm, g.stream, g.B, L.max_lin_blk, mode);
             return;
         }
@@ -238,9 +229,9 @@ void enqueue_lin(Handle* h, const Group& g, int mode) {
         VBA_LAUNCH(k_lin_xyz_e, dim3(L.max_lin_blk, g.n_win), dim3(256), 0, g.stream, g.B, mode);
         if (L.any_lin_fallback) VBA_LAUNCH(k_lin_xyz, dim3(L.max_pt_blk, g.n_win), dim3(64), 0, g.stream, g.B, L.max_pt_blk, mode);
     }
-    if (L.max_imu > 0 && h->regime_n < 64) {   // few windows: latency matters, one launch
+    if (imu_lin == vba_host::LIN_IMU_PAIR) {
         VBA_LAUNCH(k_lin_imu_pair, dim3(L.max_imu, g.n_win), dim3(64), 0, g.stream, g.B, mode);
-    } else if (L.max_imu > 0) {   // the IMU factors: a lane per keyframe pair for the Lie-group part, then a wave per pair for J^T Omega J
+    } else if (imu_lin == vba_host::LIN_IMU_RES_HESS) {   // a lane per keyframe pair for the Lie-group part, then a wave per pair for J^T Omega J
         VBA_LAUNCH(k_lin_imu_res, dim3((L.max_imu + 63) / 64, g.n_win), dim3(64), 0, g.stream, g.B, mode);
         if (mode == LIN_FULL) VBA_LAUNCH(k_lin_imu_hess, dim3(L.max_imu, g.n_win), dim3(64), 0, g.stream, g.B);
     }
@@ -256,7 +247,7 @@ void sched_reset(Handle* h, const Group& g) {
 void sched_stage_begin(Handle* h, const Group& g, int stage) {
     const LaunchGeom& L = h->geom;
     ProfScope ps(h, g.stream, VBA_PROF_MISC);
-    if (h->regime_n >= 64) VBA_LAUNCH(k_poll_stop, dim3(1), dim3(1), 0, g.stream, g.B);
+    if (h->rp.poll) VBA_LAUNCH(k_poll_stop, dim3(1), dim3(1), 0, g.stream, g.B);
     VBA_LAUNCH(k_stage_clear, dim3(L.max_ns_blk, g.n_win), dim3(64), 0, g.stream, g.B, stage);
     if (stage == 1) VBA_LAUNCH(k_classify, dim3(L.max_obs_blk, g.n_win), dim3(64), 0, g.stream, g.B);
     VBA_LAUNCH(k_stage_mark, dim3(L.max_free + (L.max_imu + 63) / 64, g.n_win), dim3(64), 0, g.stream, g.B, L.max_free);
@@ -296,7 +287,7 @@ int enqueue_schedule_lm(Handle* h, std::vector<Group>& groups, StopRef stop_flag
             VBA_LAUNCH(k_schur_diag3, dim3(L.max_free * xcd_windows(g.n_win)), dim3(64), 0, g.stream, g.B, L.max_free, 1);
         }
         ProfScope ps(h, g.stream, VBA_PROF_CONTROL);
-        if (h->regime_n >= 64) VBA_LAUNCH(k_poll_stop, dim3(1), dim3(1), 0, g.stream, g.B);
+        if (h->rp.poll) VBA_LAUNCH(k_poll_stop, dim3(1), dim3(1), 0, g.stream, g.B);
         VBA_LAUNCH(k_ctrl_lm_outer, dim3(g.n_win), dim3(64), 0, g.stream, g.B);
     };
     auto trial = [&](Group& g, int* alive_dev, int* alive_mirror) {
@@ -308,7 +299,7 @@ int enqueue_schedule_lm(Handle* h, std::vector<Group>& groups, StopRef stop_flag
         enqueue_lin(h, g, LIN_ERR_TRIAL);
         {
             ProfScope ps(h, g.stream, VBA_PROF_CONTROL);
-            if (h->regime_n >= 64) VBA_LAUNCH(k_poll_stop, dim3(1), dim3(1), 0, g.stream, g.B);
+            if (h->rp.poll) VBA_LAUNCH(k_poll_stop, dim3(1), dim3(1), 0, g.stream, g.B);
             VBA_LAUNCH(k_ctrl_lm_trial, dim3(g.n_win), dim3(64), 0, g.stream, g.B, alive_dev, alive_mirror);
         }
         {
@@ -372,13 +363,9 @@ int enqueue_schedule(Handle* h, std::vector<Group>& groups, StopRef stop_flag) {
             // never starves: one full iteration is always queued behind the one being waited for.
             const int nit = L.max_its[stage];
             std::vector<std::vector<hipEvent_t>> ev(groups.size(), std::vector<hipEvent_t>(nit, nullptr));
-            const bool word_report = h->n_win == 1 && groups.size() == 1 && !h->profile && nit <= 32;   // see k_ctrl_gn
+            const bool word_report = h->rp.word_report && nit <= 32;   // see k_ctrl_gn
             const bool pace = nit <= 32;  // also when profiling: the launch counts (and hence the per-launch averages) then equal those of a normal run
-            // how far ahead: two iterations for batches (the device must never wait for the host); ONE for a handful of windows,
-            // where an iteration is a chain of ~30 short launches that the host enqueues three times faster than the device runs
-            // them, and every launch enqueued for a window that has already converged (1.7 us each, 30 per iteration) is latency
-            static const int env_depth = getenv("VBA_PACE_DEPTH") ? atoi(getenv("VBA_PACE_DEPTH")) : 0;
-            const int depth = env_depth > 0 ? env_depth : (h->regime_n < 8 ? 1 : 2);
+            const int depth = h->rp.pace_depth;   // how far ahead
             for (auto& g : groups) g.dead = false;
             for (int it = 0; it < nit; it++) {
                 bool any = false;
@@ -405,7 +392,7 @@ int enqueue_schedule(Handle* h, std::vector<Group>& groups, StopRef stop_flag) {
                     enqueue_lin(h, g, LIN_FULL);
                     {
                         ProfScope ps(h, g.stream, VBA_PROF_CONTROL);
-                        if (h->regime_n >= 64) VBA_LAUNCH(k_poll_stop, dim3(1), dim3(1), 0, g.stream, g.B);
+                        if (h->rp.poll) VBA_LAUNCH(k_poll_stop, dim3(1), dim3(1), 0, g.stream, g.B);
                         VBA_LAUNCH(k_ctrl_gn, dim3(g.n_win), dim3(64), 0, g.stream, g.B, 0, word_report ? stage * 32 + it : -1);
                     }
                     if (pace && !word_report) {
@@ -429,14 +416,17 @@ int enqueue_schedule(Handle* h, std::vector<Group>& groups, StopRef stop_flag) {
 }
 
 int do_run(Handle* h, StopRef stop_flag) {
-    static const bool timing = getenv("VBA_TIMING") != nullptr;
+    const bool timing = vba_host::process_knobs().timing;
     const double t_run0 = timing ? now_ms() : 0.0;
     if (!h->uploaded) return fail(h, "vba_batch_run before vba_batch_upload");
     HIPCHK(h, hipSetDevice(h->device));
-    h->B.dbg_stop_after = h->path.opt_stop_after;
-    h->B.pcg_tri = h->path.pcg_jacobi ? 0 : 1;
-    const Batch B = h->B;
     const int n = h->n_win;
+    // (the hooks may have changed since the upload, and between runs of one upload)
+    h->rp = vba_host::plan_run(h->up, n, h->variant, h->algo, h->ov, vba_host::process_knobs(), h->profile, h->is_lane,
+                               (int)h->xstreams.size() + (h->owns_streams ? 11 : 1));
+    h->B.dbg_stop_after = h->rp.dbg_stop_after;
+    h->B.pcg_tri = h->rp.pcg_tri;
+    const Batch B = h->B;
     *h->stop_host = stop_flag.set() ? 1 : 0;
     for (int i = 64; i < 1024; i++) h->stop_host[i] = 0;
     const long long launch0 = h->n_launch;
@@ -448,22 +438,7 @@ int do_run(Handle* h, StopRef stop_flag) {
         ev_end = get_evt(h);
         (void)hipEventRecord(ev_begin, h->stream);
     }
-    // Large Gauss-Newton batches can be cut into groups of windows, each with its own stream (enqueue_schedule).
-    // (Profiling runs and LM, which needs a host decision per trial, use one group.)
-    // Measured on MI355X, C3 windows, windows/s with 1 / 2 / 4 / 8 groups: 64 windows 5.1k / 5.6k / 5.8k / 4.1k; 256: 7.5k / 8.0k /
-    // 8.5k / 6.1k; 512: 8.9k / 9.2k / 9.9k / 8.6k; 1024: 9.7k / 10.1k / 10.2k / 10.0k; 2048: 10.2k / 10.4k / 10.3k / 10.1k.
-    // LM (C2 windows, 1 / 2 / 4 groups): 256 windows 5.9k / 6.2k / 6.5k, 2048: 6.4k / 6.6k / 6.8k.
-    static const int env_streams = getenv("VBA_STREAMS") ? atoi(getenv("VBA_STREAMS")) : 0;
-    int want = h->opt_streams > 0 ? h->opt_streams : env_streams;
-    static const int lane_streams = getenv("VBA_LANE_STREAMS") ? atoi(getenv("VBA_LANE_STREAMS")) : 2;
-    if (want <= 0 && h->is_lane) want = lane_streams;   // several lanes share the chip: fewer window groups each
-    // default policy (16..48 windows: 2 groups +5..10 %, 4 groups -40 %; from 64 windows on 4 groups -- round 3, 16 distinct ragged
-    // windows with 3+1 .. 5+3 iterations: 4096 windows 14.0-14.2 k/s with 2 groups, 14.6-14.8 k with 4; 2048 windows 13.7 k either way)
-    if (want <= 0) want = (n >= 64) ? 4 : (n >= 16) ? 2 : 1;
-    const int max_streams = std::min(std::min(14, want), (int)h->xstreams.size() + (h->owns_streams ? 11 : 1));
-    int ngroups = 1;
-    if (!h->profile && max_streams > 1 && n >= 8)
-        ngroups = std::max(1, std::min(max_streams, n / 8));   // a group never falls below the 8 windows of the XCD-aware mapping
+    const int ngroups = h->rp.ngroups;   // window groups, each with its own stream (enqueue_schedule)
     while ((int)h->xstreams.size() < ngroups - 1) {
         hipStream_t st;
         HIPCHK(h, hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
@@ -486,8 +461,9 @@ int do_run(Handle* h, StopRef stop_flag) {
 #endif
     std::vector<Group> groups(ngroups);
     std::vector<hipEvent_t> done(ngroups);
+    const std::vector<int> gb = vba_host::group_bounds(n, ngroups);
     for (int g = 0; g < ngroups; g++) {
-        const int w0 = (int)((long long)n * g / ngroups), w1 = (int)((long long)n * (g + 1) / ngroups);
+        const int w0 = gb[g], w1 = gb[g + 1];
         groups[g].B = B;
         groups[g].B.desc = B.desc + w0;
         groups[g].B.ctrl = B.ctrl + w0;
@@ -583,7 +559,7 @@ int do_run(Handle* h, StopRef stop_flag) {
 }
 
 int do_download(Handle* h, int n, vba_problem* const* inout, vba_result* const* out) {
-    static const bool timing = getenv("VBA_TIMING") != nullptr;
+    const bool timing = vba_host::process_knobs().timing;
     const double t_dl0 = timing ? now_ms() : 0.0;
     if (!h->ran) return fail(h, "vba_batch_download before vba_batch_run");
     if (n != h->n_win) return fail(h, "window count mismatch");
@@ -591,7 +567,7 @@ int do_download(Handle* h, int n, vba_problem* const* inout, vba_result* const* 
     const Batch& B = h->B;
     // Many windows: every result array crosses PCIe ONCE into host staging and host threads scatter it to the callers'
     // arrays (per-window copies cost ~12 synchronous hipMemcpy calls per window, 0.25 ms).  Few windows: the run has left them in the staging already (do_run).
-    const bool staged = n >= 4 || h->dl_prefetched;
+    const bool staged = !h->up.results_block || h->dl_prefetched;
     if (staged && !h->dl_prefetched) {
         bool want_state = false, want_outl = false, want_chi2 = false;
         for (int w = 0; w < n; w++) {

@@ -2,6 +2,7 @@
 // sanitizer harness tests/host_structure_check.cpp (g++ -fsanitize=address,undefined, tests/test_host_structure.py).
 #pragma once
 #include "../../include/vislam_ba.h"
+#include "vba_host_plan.h"
 
 #include <algorithm>
 #include <chrono>
@@ -88,7 +89,7 @@ inline int order_rows(int order, int pdim, int nf) {   // rows of the reduced sy
 inline int build_structure(const vba_problem* P, Structure& st, std::string& err, bool prefer_two_sided = false) {
     auto fail = [&err](int, const char* m) { err = m; return -1; };
     const int h = 0;
-    static const bool timing = getenv("VBA_TIMING") != nullptr;
+    const bool timing = process_knobs().timing;
     const double t_b0 = timing ? now_ms() : 0.0;
     const int nf = P->n_kf_free, npairs = nf * (nf + 1) / 2, nkf = P->n_kf;
     auto pidx = [nf](int a, int b) { return a * nf - a * (a - 1) / 2 + (b - a); };
@@ -306,7 +307,7 @@ inline int build_structure(const vba_problem* P, Structure& st, std::string& err
     }
     st.kl_begin.push_back((int)st.klist.size());
     {   // chain columns (see Structure::nc): T holds L's pattern
-        static const int chain_min = getenv("VBA_CHAIN_MIN") ? atoi(getenv("VBA_CHAIN_MIN")) : 4;
+        const int chain_min = process_knobs().chain_min;
         int nc = 0;
         for (int J = 0; J < nb; J++) {
             bool ok = true;
@@ -370,7 +371,7 @@ inline int build_structure(const vba_problem* P, Structure& st, std::string& err
     }
     return cost;
     };
-    static const int env_order = getenv("VBA_ORDER") ? atoi(getenv("VBA_ORDER")) : -1;
+    const int env_order = process_knobs().order;
     st.order = 0;
     if (pdim == 15) {
         if (env_order >= 0) st.order = (env_order >= 2 && (nf < 4 || P->solver == VBA_SOLVER_PCG)) ? 0 : std::min(env_order, 2);   // (PCG walks keyframe-pair blocks: orders 0 / 1)

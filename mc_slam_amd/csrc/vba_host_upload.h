@@ -13,7 +13,6 @@ struct Upload {
     int n = 0;
     vba_problem* const* probs = nullptr;
     vba_host::DescribeOpts opts;
-    bool two_sided = false, pristine = false, inc_on = false;
     int n_threads = 1;
     vba_host::BatchCursor cur;
     vba_host::BatchTables tab;
@@ -24,9 +23,7 @@ struct Upload {
 };
 
 // the stop word the windows of a batch (or of one of its window groups) poll
-int* stop_word_of(Handle* h, const Batch& B) {
-    return (h->regime_n >= 64) ? B.alive_dev + 1023 : h->stop_dev;   // few windows read the pinned word themselves (no poll launches)
-}
+int* stop_word_of(Handle* h, const Batch& B) { return h->up.dev_stop ? B.alive_dev + 1023 : h->stop_dev; }
 
 // check and size: the handle's per-batch state, the options of the batch, one allocation per concatenated array
 int upload_begin(Handle* h, Upload& U) {
@@ -36,31 +33,18 @@ int upload_begin(Handle* h, Upload& U) {
     HIPCHK(h, hipStreamSynchronize(h->up_stream));   // (an upload that failed half way may still have copies out of the staging in flight)
     h->uploaded = false;
     h->n_win = n;
-    h->regime_n = n;
+    U.opts.pcg = probs[0] && probs[0]->solver == VBA_SOLVER_PCG;
+    U.opts.pcg_rows = PCG_ROWS;
+    h->up = vba_host::plan_upload(n, U.opts.pcg, h->ov, vba_host::current_knobs());
+    U.opts.chain_on = h->up.chain_on;
     for (auto& b : h->buf) { b.view = nullptr; b.view_bytes = 0; }
     h->pending.clear();
-    static const int arena_max = getenv("VBA_ARENA_MAX") ? atoi(getenv("VBA_ARENA_MAX")) : 8;
-    h->arena_on = n <= arena_max;
     h->desc.assign(n, WinDesc());
     h->win_tiles.assign(n, 0);
     h->win_prod_order.assign(3 * (size_t)n, -1);
     h->geom = LaunchGeom();
     Staging& G = h->stg;
     G.each([](auto& v) { v.clear(); });
-    U.opts.pcg = probs[0] && probs[0]->solver == VBA_SOLVER_PCG;
-    U.opts.pcg_rows = PCG_ROWS;
-    // Chain columns in one launch (vba_chain.h): in the left-looking regime (two lean launches for all chain columns of all windows),
-    // and for up to 64 windows in the right-looking one (one workgroup per tile row walks the chain, the two chains of the two-sided
-    // order side by side).  Every row workgroup redoes the chain's diagonal work, which is only free while compute units idle --
-    // measured on MI355X, ms per run with / without: 1 window 2.11 / 2.37, 8: 2.71 / 3.06, 16: 3.16 / 3.72, 32: 4.70 / 5.10,
-    // 64: 7.44 / 7.52, 96: 10.6 / 10.0, 128: 13.4 / 12.0.  In between: one launch per block column.
-    // VBA_NO_CHAIN: A/B switch, one launch per block column everywhere.
-    static const int chain_rl_max = getenv("VBA_CHAIN_RL_MAX") ? atoi(getenv("VBA_CHAIN_RL_MAX")) : 64;
-    U.opts.chain_on = getenv("VBA_NO_CHAIN") == nullptr && !h->path.opt_no_chain && (use_left_looking(h, n) || n <= chain_rl_max);
-    // the two-sided V/Bias-first order (vba_host_structure.h, order 2) is a candidate for every window: its two half-length chains leave
-    // half the fill in the PR rows (C3: 408 tile products against 581), and the few-window chain kernel walks them side by side.
-    // VBA_ONE_CHAIN: A/B switch, orders 0 and 1 only as before.
-    U.two_sided = getenv("VBA_ONE_CHAIN") == nullptr;
     static const int n_threads = host_threads();
     U.n_threads = n_threads;
     {   // one allocation per concatenated array instead of the doubling growth of std::vector
@@ -80,15 +64,11 @@ int upload_begin(Handle* h, Upload& U) {
         G.pair_a.reserve(spair); G.pair_b.reserve(spair); G.offpair.reserve(spair); G.pairmask.reserve(spair);
         G.pimu_begin.reserve(spair + n);
     }
-    U.pristine = use_left_looking(h, n);
-    h->ll_mode = U.pristine;
     // The bulk of a window (observations, landmarks, masks: 1 MB of the 1.06 MB of a C3 window) crosses PCIe WHILE the host works on the
     // next windows: after every packing pass the freshly packed tail of these arrays is copied (their final sizes are known from
     // the pre-pass above, the pinned staging is never re-allocated under a copy).  Before: validate + symbolic (5.4 ms per 384
     // windows), pack (5.0), then ONE copy per array (7.5) one after the other -- the link idle for the first half, the host for the second.
-    static const int inc_off = getenv("VBA_UPLOAD_NO_OVERLAP") ? 1 : 0;
-    U.inc_on = !h->arena_on && !inc_off;
-    if (U.inc_on) {
+    if (h->up.inc_copy) {
         auto reg = [&](int id, const void* base, size_t esz, size_t total) -> int {
             if (dalloc(h, id, total * esz)) return -1;
             U.inc.push_back({id, reinterpret_cast<const char*>(base), esz, total, 0});
@@ -111,7 +91,7 @@ int upload_structures(Handle* h, Upload& U, int chunk0, int cn) {
     host_parallel_for(h, cn, std::min(U.n_threads, cn), [&](int q) {
         const vba_problem* Q = U.probs[chunk0 + q];
         if (!vba_host::window_sizes_ok(Q)) return;  // reported by upload_describe
-        if (build_structure(h, Q, U.sts[q], U.two_sided)) bad.store(1);
+        if (build_structure(h, Q, U.sts[q], h->up.two_sided)) bad.store(1);
     });
     U.t_struct += now_ms() - ts0;
     if (bad.load()) return -1;
@@ -215,7 +195,7 @@ int upload_alloc_copy(Handle* h, Upload& U) {
     const vba_host::BatchCursor& c = U.cur;
     const LaunchGeom& g = h->geom;
     const size_t kf0 = c.kf0, pt0 = c.pt0, obs0 = c.obs0, imu0 = c.imu0, pair0 = c.pair0, vec0 = c.vec0, item0 = (size_t)c.item0;
-    const bool inc_on = U.inc_on, idp = U.probs[0]->variant == VBA_VARIANT_PRV_IDP;
+    const bool inc_on = h->up.inc_copy, idp = U.probs[0]->variant == VBA_VARIANT_PRV_IDP;
     if (h2d_vec(h, BUF_DESC, h->desc, G.s_desc)) return -1;
     if (dalloc(h, BUF_CTRL, sizeof(WinCtrl) * n)) return -1;
     if (!inc_on && (h2d(h, BUF_POSE0, G.pose) || h2d(h, BUF_VEL0, G.vel) || h2d(h, BUF_BIAS0, G.bias) || h2d(h, BUF_PT0, G.pt))) return -1;
@@ -247,7 +227,7 @@ int upload_alloc_copy(Handle* h, Upload& U) {
     if (h2d_vec(h, BUF_TLSTEP, T.tlstep, G.s_int[0]) || h2d_vec(h, BUF_TLPAIR, T.tlpair, G.s_int[1]) || h2d_vec(h, BUF_TLPANB, T.tlpanb, G.s_int[2]) ||
         h2d_vec(h, BUF_TLPAN, T.tlpan, G.s_int[3]) || h2d_vec(h, BUF_TLKB, T.tlkb, G.s_int[4]) || h2d_vec(h, BUF_TLK, T.tlk, G.s_int[5]) ||
         h2d_vec(h, BUF_CU, T.culist, G.s_int[12]) || h2d_vec(h, BUF_CHAINTAB, T.chaintab, G.s_int[13])) return -1;
-    if (dalloc(h, BUF_DVEC, vec0 * 8) || dalloc(h, BUF_WINV, (size_t)n * 1024 * 8 * (1 + (size_t)(h->ll_mode ? g.max_nc : 0)))) return -1;
+    if (dalloc(h, BUF_DVEC, vec0 * 8) || dalloc(h, BUF_WINV, (size_t)n * 1024 * 8 * (1 + (size_t)(h->up.left_looking ? g.max_nc : 0)))) return -1;
     if (dalloc(h, BUF_VARACT, vec0 * 4)) return -1;
     if (h2d(h, BUF_PAIRA, G.pair_a) || h2d(h, BUF_PAIRB, G.pair_b)) return -1;
     h->solver = U.probs[0]->solver;
@@ -267,7 +247,7 @@ int upload_alloc_copy(Handle* h, Upload& U) {
 // few windows: everything the download reads lives in ONE block -- one D2H copy behind the run (do_run)
 int upload_results_block(Handle* h, const Upload& U) {
     h->res_bytes = 0;
-    if (U.n >= 4) return 0;
+    if (!h->up.results_block) return 0;
     Staging& G = h->stg;
     const size_t obs0 = U.cur.obs0;
     const size_t sz[7] = {sizeof(WinCtrl) * (size_t)U.n, G.pose.size() * 8, G.vel.size() * 8, G.bias.size() * 8, G.pt.size() * 8, obs0, obs0 * 8};
@@ -289,8 +269,8 @@ int upload_zero_pad(Handle* h, const Upload& U) {
     const int n = U.n;
     const size_t vec0 = U.cur.vec0;
     // (PCG reads whole keyframe-pair blocks, also the sub-blocks no factor tile covers and no Schur kernel writes: zero them once)
-    if (use_left_looking(h, n) || U.opts.pcg) HIPCHK(h, hipMemsetAsync(h->buf[BUF_S].p, 0, U.cur.S_tot * 8, h->up_stream));
-    for (int w = 0; w < n && !(use_left_looking(h, n) || U.opts.pcg); w++) {  // only the pad rows of S must be zero (identity on their diagonal, below)
+    if (h->up.zero_s) HIPCHK(h, hipMemsetAsync(h->buf[BUF_S].p, 0, U.cur.S_tot * 8, h->up_stream));
+    for (int w = 0; w < n && !h->up.zero_s; w++) {  // only the pad rows of S must be zero (identity on their diagonal, below)
         const WinDesc& d = h->desc[w];
         if (d.order == 2) {   // pads between the parts: their COLUMNS run through tiles of the factor too -- zero the whole block once
             HIPCHK(h, hipMemsetAsync(dp<double>(h, BUF_S) + d.S0, 0, (size_t)d.nS * d.nS * 8, h->up_stream));
@@ -325,7 +305,7 @@ int bind_batch(Handle* h, int n, bool idp) {
     B.imuH = dp<double>(h, BUF_IMUH); B.imu_chi = dp<double>(h, BUF_IMUCHI); B.imu_jrec = dp<double>(h, BUF_IMUJREC);
     B.S = dp<double>(h, BUF_S); B.vec = dp<double>(h, BUF_VEC); B.bpose = dp<double>(h, BUF_BPOSE);
     B.Lf = dp<double>(h, BUF_LF); B.yv = dp<double>(h, BUF_YV);
-    B.l_packed = h->ll_mode ? 1 : 0;
+    B.l_packed = h->up.left_looking;
     B.tl_step_begin = dp<int>(h, BUF_TLSTEP); B.tl_pairs = dp<int>(h, BUF_TLPAIR);
     B.tl_pan_begin = dp<int>(h, BUF_TLPANB); B.tl_pan = dp<int>(h, BUF_TLPAN);
     B.tl_kl_begin = dp<int>(h, BUF_TLKB); B.tl_kl = dp<int>(h, BUF_TLK); B.tl_cu = dp<int>(h, BUF_CU); B.tl_ct = dp<int>(h, BUF_CHAINTAB);
@@ -336,7 +316,6 @@ int bind_batch(Handle* h, int n, bool idp) {
     B.item_begin = dp<int>(h, BUF_ITEMBEG); B.items = dp<int>(h, BUF_ITEMS); B.item_mid = dp<int>(h, BUF_ITEMMID);
     B.kf_dir = dp<double>(h, BUF_KFDIR); B.slot_lm = dp<int>(h, BUF_SLOTOBS); B.slot_o = dp<int>(h, BUF_SLOTO); B.rec_lm = dp<int>(h, BUF_PTINV);
     B.adj_begin = dp<int>(h, BUF_ADJBEG); B.adj = dp<int>(h, BUF_ADJ); B.pcg_v = dp<double>(h, BUF_PCGV); B.pcg_m = dp<double>(h, BUF_PCGM); B.pcg_s = dp<double>(h, BUF_PCGS);
-    B.pcg_tri = h->path.pcg_jacobi ? 0 : 1;
     B.lmask = dp<unsigned long long>(h, BUF_LMASK); B.kf_seg = dp<int>(h, BUF_KFSEG); B.ref_seg = dp<int>(h, BUF_REFSEG);
     B.pimu_begin = dp<int>(h, BUF_PIMUBEG); B.pimu = dp<int>(h, BUF_PIMU);
     B.lin_blk = dp<int>(h, BUF_LINBLK);
@@ -369,10 +348,10 @@ int enqueue_structure_build(Handle* h, const Upload& U) {
     T.key_seg = dp<int>(h, BUF_KEYSEG); T.tslot = dp<int>(h, BUF_TSLOT);
     T.mask_q = dp<unsigned long long>(h, BUF_MASKQ); T.slot_mask = dp<unsigned long long>(h, BUF_SLOTMASK); T.ref_q = dp<int>(h, BUF_REFQ);
     T.smw = g.max_mwords;
-    T.row_lds = getenv("VBA_ST_ROW_LDS") ? 1 : 0;   // (read per upload: the test flips it inside one process)
+    T.row_lds = h->up.row_lds;
     T.slot_o = dp<int>(h, BUF_SLOTO);
     T.slot_ref = dp<int>(h, BUF_SLOTREF); T.slot_q = dp<int>(h, BUF_SLOTQ); T.rec_q = dp<int>(h, BUF_RECQ); T.tsq = dp<int>(h, BUF_TSQ);
-    VBA_LAUNCH(k_st_hist, dim3(n), dim3(n <= 64 ? 1024 : 256), sh_order, h->up_stream, B, T);
+    VBA_LAUNCH(k_st_hist, dim3(n), dim3(h->up.hist_block), sh_order, h->up_stream, B, T);
     {
         const int max_chunks = std::max(1, g.max_pt_blk);   // 64-landmark blocks of the largest window
         if (dalloc(h, BUF_RECCNT, (size_t)U.cur.kf0 * max_chunks * 2 * 4)) return -1;
@@ -392,7 +371,7 @@ int enqueue_structure_build(Handle* h, const Upload& U) {
 }
 
 int do_upload(Handle* h, int n, vba_problem* const* probs, bool defer_sync = false) {
-    static const bool timing = getenv("VBA_TIMING") != nullptr;
+    const bool timing = vba_host::process_knobs().timing;
     const double t_begin = now_ms();
     if (n <= 0) return fail(h, "empty batch");
     Upload U;
@@ -407,10 +386,10 @@ int do_upload(Handle* h, int n, vba_problem* const* probs, bool defer_sync = fal
     for (int chunk0 = 0; chunk0 < n; chunk0 += chunk) {
         const int cn = std::min(chunk, n - chunk0);
         if (upload_structures(h, U, chunk0, cn) || upload_describe(h, U, chunk0, cn) || upload_grow_staging(h, U, chunk0 + cn)) return -1;
-        host_parallel_for(h, cn, std::min(U.n_threads, cn), [&](int q) { pack_window(G, probs[chunk0 + q], h->desc[chunk0 + q], U.sts[q], U.pristine); });
-        if (U.inc_on && upload_inc_push(h, U)) return -1;
+        host_parallel_for(h, cn, std::min(U.n_threads, cn), [&](int q) { pack_window(G, probs[chunk0 + q], h->desc[chunk0 + q], U.sts[q], h->up.left_looking); });
+        if (h->up.inc_copy && upload_inc_push(h, U)) return -1;
     }
-    if (U.inc_on && (G.uv.data() != reinterpret_cast<const double*>(U.inc[0].base) || G.pt.data() != reinterpret_cast<const double*>(U.inc[3].base)))
+    if (h->up.inc_copy && (G.uv.data() != reinterpret_cast<const double*>(U.inc[0].base) || G.pt.data() != reinterpret_cast<const double*>(U.inc[3].base)))
         return fail(h, "internal: the upload staging moved under an incremental copy");
     h->algo = probs[0]->algo;
     h->variant = probs[0]->variant;
@@ -437,7 +416,7 @@ int do_upload(Handle* h, int n, vba_problem* const* probs, bool defer_sync = fal
         h->up_pending = true;
     } else
         HIPCHK(h, hipStreamSynchronize(h->up_stream));
-    if (timing) fprintf(stderr, "[vba] chain columns: min %d max %d, update tiles %d, rows %d, ll %d\n", g.min_nc, g.max_nc, g.max_cu, g.max_chain_rows, (int)h->ll_mode);
+    if (timing) fprintf(stderr, "[vba] chain columns: min %d max %d, update tiles %d, rows %d, ll %d\n", g.min_nc, g.max_nc, g.max_cu, g.max_chain_rows, h->up.left_looking);
     if (timing) fprintf(stderr, "[vba] %p t=%.1f upload %d windows: total %.3f ms (structure %.3f, pack %.3f, alloc+H2D enqueue %.3f, sync %.3f)\n", (void*)h, now_ms(), n,
                         now_ms() - t_begin, U.t_struct, t_pack - t_begin - U.t_struct, t_enq - t_pack, now_ms() - t_enq);
     h->uploaded = true;

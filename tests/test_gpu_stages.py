@@ -336,3 +336,79 @@ def test_pcg_preconditioners(jacobi):
     p = _idp(seed=90)
     p.solver = abi.SOLVER_PCG
     _run([p], 0, 0, dict(pcg=1, pcg_tri=1 - jacobi, factor=7), path=[("pcg_jacobi", jacobi)])
+
+
+# ---- the plan of a batch (csrc/vba_host_plan.h): what vba_debug_plan reports, what the launch sites recorded, what came out --------
+import plan_cases as pc
+
+
+def _tiny(i):
+    return _idp(n_kf=6, n_fixed=1, n_pt=60, n_obs=300, seed=200 + i)
+
+
+@pytest.fixture(scope="module")
+def tiny_alone():
+    """64 tiny windows, each solved in a call of its own on one fresh handle: the reference of every batch below (left unchanged)"""
+    ba = backend.LocalBA(0)
+    try:
+        return [ba.solve(_tiny(i)) for i in range(64)]
+    finally:
+        ba.close()
+
+
+def _plan(cap):
+    out = np.zeros(len(pc.FIELDS), np.int64)
+    cap.lib.vba_debug_plan.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_int64]
+    assert cap.lib.vba_debug_plan(cap.ba.h, out.ctypes.data_as(C.POINTER(C.c_int64)), len(out) - 1) == -1   # bounds
+    assert cap.lib.vba_debug_plan(cap.ba.h, out.ctypes.data_as(C.POINTER(C.c_int64)), len(out)) == 0
+    return out.tolist()
+
+
+@pytest.mark.parametrize("n,ll_min", [(1, 0), (7, 0), (8, 0), (64, 0), (8, 8)])
+def test_plan_of_a_batch_and_what_it_launched(tiny_alone, n, ll_min):
+    probs = [_tiny(i) for i in range(n)]
+    cap = Capture(probs, 0, setup=[("set_ll_min", ll_min)] if ll_min else [])
+    try:
+        want = dict(zip(pc.FIELDS, pc.expected(n, ll_min=ll_min or 256)))
+        want["ngroups"] = 1                                     # vba_debug_set_streams(h, 1)
+        got = dict(zip(pc.FIELDS, _plan(cap)))
+        print("plan of %d windows: %s" % (n, got))
+        assert got == want
+        lay = cap.layout(n - 1)
+        assert (lay["schur"], lay["factor"], lay["trsv"]) == (got["schur"], got["factor"], got["trsv"])   # planned == launched
+        assert (lay["regime_n"], lay["l_packed"], lay["pcg_tri"]) == (n, got["left_looking"], got["pcg_tri"])
+        qs, rs = cap.ba.download()
+    finally:
+        cap.close()
+    exact = n < 8 and not ll_min                                # the regime of a window solved alone
+    for (q0, r0), q, r in zip(tiny_alone, qs, rs):
+        dp, dc = np.abs(q.kf_pose - q0.kf_pose).max(), abs(r.chi2_vis - r0.chi2_vis) / r0.chi2_vis
+        print("  max |dpose| %.3g  rel dchi2 %.3g" % (dp, dc))
+        assert r.status == r0.status == 0 and r.its_done == r0.its_done and (r.obs_outlier == r0.obs_outlier).all()
+        if exact:
+            assert r.chi2_vis == r0.chi2_vis and (r.obs_chi2 == r0.obs_chi2).all()
+            assert (q.kf_pose == q0.kf_pose).all() and (q.pt == q0.pt).all() and (q.kf_vel == q0.kf_vel).all()
+        else:                                                   # across a threshold: the bound of tests/test_gpu_parity.py
+            assert dc <= 1e-10 and dp < 1e-9
+
+
+def test_one_chain_flips_two_sided_at_the_next_upload(monkeypatch):
+    probs = [_tiny(i) for i in range(8)]
+    monkeypatch.delenv("VBA_ONE_CHAIN", raising=False)
+    cap = Capture(probs, 0)
+    try:
+        two_sided, n_up = pc.FIELDS.index("two_sided"), pc.N_UPLOAD
+        first = _plan(cap)
+        assert first[two_sided] == 1
+        monkeypatch.setenv("VBA_ONE_CHAIN", "1")                # read at every upload: the same handle, no new process
+        cap.ba.upload(probs)
+        second = _plan(cap)
+        assert second[two_sided] == 0 and second[n_up:] == [-1] * (len(pc.FIELDS) - n_up)      # no run of this upload yet
+        assert [v for i, v in enumerate(second[:n_up]) if i != two_sided] == [v for i, v in enumerate(first[:n_up]) if i != two_sided]
+        cap.ba.run()
+        assert _plan(cap)[n_up:] == first[n_up:]
+        monkeypatch.delenv("VBA_ONE_CHAIN")
+        cap.ba.upload(probs)
+        assert _plan(cap)[two_sided] == 1
+    finally:
+        cap.close()
