@@ -123,7 +123,7 @@ typedef struct vba_profile {
     double total_ms;             /* first launch -> last launch of the run */
     double factor_flops;         /* FP64 flop the factorisation class executed on MFMA: 2*32^3 per tile product of the
                                     symbolic tile lists, per solve (structurally zero tiles are never touched) */
-    int64_t kernel_launches;     /* kernel launches the last vba_batch_run / vba_solve / vba_sim3_optimize / vba_posegraph_optimize enqueued (filled with or without profiling) */
+    int64_t kernel_launches;     /* kernel launches the last vba_batch_run / vba_solve / vba_sim3_optimize / vba_sim3_ransac / vba_posegraph_optimize enqueued (filled with or without profiling) */
 } vba_profile;
 
 /* One handle per host thread / GPU; owns device buffers and a stream.  Errors: nonzero return, message
@@ -178,7 +178,7 @@ int vba_batch_solve_b(void *handle, int32_t n_windows, vba_problem *const *inout
  *           every later one, those submitted afterwards included, with the same message: no GPU work starts for them (earlier
  *           tickets finish).  Waiting on an unknown or retired ticket returns -1.
  *   handle  while any ticket is submitted and not yet waited for, every synchronous entry point of the handle (vba_solve*,
- *           vba_batch_upload / run / download / solve*, vba_pose_optimize, vba_sim3_optimize, vba_posegraph_optimize, vba_preintegrate, vba_set_profile,
+ *           vba_batch_upload / run / download / solve*, vba_pose_optimize, vba_sim3_optimize, vba_sim3_ransac, vba_posegraph_optimize, vba_preintegrate, vba_set_profile,
  *           vba_batch_set_depth) returns -1 with "asynchronous batches pending: wait for them first"; afterwards the handle
  *           works synchronously as before.  vba_destroy finishes pending tickets (their results land) before it frees.
  *           Profiling (vba_set_profile) covers synchronous calls only.  One caller thread at a time, as everywhere. */
@@ -284,6 +284,50 @@ typedef struct vba_sim3_result {
  * (negative n_pairs, NULL array with n_pairs > 0, non-finite S12, scale <= 0, zero quaternion, a budget below 1) fails the whole
  * call before any GPU work, message through vba_last_error.  No upper bound on n_pairs. */
 int vba_sim3_optimize(void *handle, int32_t n_problems, vba_sim3_problem *const *inout, vba_sim3_result *const *out);
+
+/* ---- loop-candidate Sim3 RANSAC ----
+ * Sim3Solver::iterate (src/Sim3Solver.cpp:138-220), ComputeSim3 (:253-359: Horn's closed form on three pairs) and CheckInliers
+ * (:363-388: the two-sided reprojection test of every pair), the first of the three solver stages of LoopClosing::ComputeSim3
+ * (src/LoopClosing.cpp:329-426); its hit is the S12 that vba_sim3_optimize takes.  One call runs n_hyp hypotheses of every
+ * candidate of a batch (one workgroup per candidate, one kernel launch per call) and applies iterate's accept rule in hypothesis
+ * order.  With c[h] the inlier count of hypothesis h and b = best_inliers: for h = 0 .. n_hyp-1, c[h] >= b makes b = c[h],
+ * best_hyp = h, best_S12 = S12[h] (a later tie replaces the best, :193); if in addition c[h] > min_inliers (strict, :203), hit = h
+ * and the scan stops.  best_inliers is written back as b.  The library has no random numbers: the caller draws the triples (the
+ * reference draws with rand(), and its removal step (:182) lets a triple hold a pair twice, so duplicates are legal here).  A
+ * degenerate triple gives whatever Horn's formulas give; a NaN estimate counts 0 inliers, as in the reference.  FP64 throughout;
+ * the reference computes in CV_32F (gives the measured difference). */
+typedef struct vba_sim3_ransac_problem {
+    int32_t n_pairs;          /* N: pairs that passed the constructor's filters (:49-95) */
+    int32_t fix_scale;        /* mbFixScale */
+    const double *p1c, *p2c;  /* [n_pairs][3] mvX3Dc1, mvX3Dc2 (camera frames of KF1 / KF2) */
+    const double *max_err1, *max_err2; /* [n_pairs] 9.210 * sigma2 of the keypoints' octaves (:78-79) */
+    double K1[4], K2[4];      /* fx fy cx cy; the kernel forms mvP1im1 / mvP2im2 itself (:441-460) */
+    int32_t min_inliers;      /* mRansacMinInliers (20 at the call site) */
+    int32_t n_hyp;            /* hypotheses of THIS call (iterate's nIterations, or the whole budget) */
+    const int32_t *sample;    /* [n_hyp][3] pair indices of every hypothesis, drawn by the caller */
+    int32_t best_inliers;     /* in/out: mnBestInliers, 0 for a fresh solver */
+    double  best_S12[8];      /* in/out: mBestRotation / Translation / Scale as t(3) q(4, xyzw) s */
+} vba_sim3_ransac_problem;
+
+typedef struct vba_sim3_ransac_result {
+    int32_t status;           /* VBA_OK */
+    int32_t hit;              /* hypothesis at which iterate() returns (:203-211), -1: none */
+    int32_t its_done;         /* hypotheses consumed: hit + 1, or n_hyp */
+    int32_t best_hyp;         /* last hypothesis of this call that became the best, -1: none */
+    int32_t n_inliers;        /* mnInliersi of the hit, 0 without one */
+    double  S12[8];           /* the hit's T12, vba_sim3_problem.S12 layout; untouched without a hit */
+    uint8_t *inlier;          /* [n_pairs] caller-allocated: mvbInliersi of the hit; untouched without one */
+    int32_t *hyp_inliers;     /* [n_hyp] caller-allocated or NULL: inlier count of EVERY hypothesis of the call */
+} vba_sim3_ransac_result;
+
+/* Synchronous, like vba_sim3_optimize; -1 while asynchronous tickets are pending.  n_problems == 0 returns 0; n_hyp == 0 is legal
+ * (hit = -1, its_done = 0, state untouched); n_pairs < min_inliers is legal and not short-circuited (the iteration budget and
+ * bNoMore belong to the caller).  A bad problem fails the whole call before any GPU work, message through vba_last_error naming
+ * the problem: NULL problem or result, a negative n_pairs / n_hyp / min_inliers / best_inliers, a NULL array with a non-zero count
+ * (inlier is required when n_pairs > 0), n_pairs < 3 with n_hyp > 0, a sample index outside [0, n_pairs), a non-finite K, point
+ * or gate.  The quaternion of S12 / best_S12 is the unit eigenvector of Horn's N with w >= 0. */
+int vba_sim3_ransac(void *handle, int32_t n_problems, vba_sim3_ransac_problem *const *inout,
+                    vba_sim3_ransac_result *const *out);
 
 /* ---- essential-graph optimisation (Sim3 pose graph) ----
  * Optimizer::OptimizeEssentialGraph(Map*, KeyFrame* pLoopKF, KeyFrame* pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections,

@@ -484,6 +484,104 @@ class Sim3ResultBuf:
                           np.array(st.S12[:]))
 
 
+# ---- loop-candidate Sim3 RANSAC (include/vislam_ba.h: vba_sim3_ransac_problem / vba_sim3_ransac_result) ----
+class vba_sim3_ransac_problem(C.Structure):
+    _fields_ = [
+        ("n_pairs", C.c_int32), ("fix_scale", C.c_int32), ("p1c", _pd), ("p2c", _pd), ("max_err1", _pd), ("max_err2", _pd),
+        ("K1", C.c_double * 4), ("K2", C.c_double * 4), ("min_inliers", C.c_int32), ("n_hyp", C.c_int32), ("sample", _pi),
+        ("best_inliers", C.c_int32), ("best_S12", C.c_double * 8),
+    ]
+
+
+class vba_sim3_ransac_result(C.Structure):
+    _fields_ = [
+        ("status", C.c_int32), ("hit", C.c_int32), ("its_done", C.c_int32), ("best_hyp", C.c_int32), ("n_inliers", C.c_int32),
+        ("S12", C.c_double * 8), ("inlier", _pu8), ("hyp_inliers", _pi),
+    ]
+
+
+@dataclass
+class Sim3RansacProblem:
+    """One Sim3Solver (src/Sim3Solver.cpp) as flat arrays: the pairs that passed the constructor's filters, the triples of one
+    iterate() call and the solver's running best."""
+    p1c: np.ndarray                # [n,3]
+    p2c: np.ndarray                # [n,3]
+    max_err1: np.ndarray           # [n]
+    max_err2: np.ndarray           # [n]
+    K1: np.ndarray                 # [4]
+    K2: np.ndarray                 # [4]
+    sample: np.ndarray             # [n_hyp,3] int32
+    fix_scale: int = 0
+    min_inliers: int = 20
+    best_inliers: int = 0
+    best_S12: np.ndarray = None    # [8] t(3) q(4, xyzw) s
+    truth: dict = field(default_factory=dict)
+
+    def __post_init__(self):
+        self.p1c = _f64(self.p1c, (-1, 3)); self.p2c = _f64(self.p2c, (-1, 3))
+        self.max_err1 = _f64(self.max_err1, (-1,)); self.max_err2 = _f64(self.max_err2, (-1,))
+        self.K1 = _f64(self.K1, (4,)); self.K2 = _f64(self.K2, (4,))
+        self.sample = np.ascontiguousarray(self.sample, dtype=np.int32).reshape(-1, 3)
+        self.best_S12 = _f64(np.zeros(8) if self.best_S12 is None else self.best_S12, (8,))
+
+    n_pairs = property(lambda self: self.p1c.shape[0])
+    n_hyp = property(lambda self: self.sample.shape[0])
+
+    def copy(self, **changes):
+        import copy as _c
+        q = _c.copy(self)
+        q.best_S12 = self.best_S12.copy()
+        for k, v in changes.items():
+            setattr(q, k, v)
+        q.__post_init__()
+        return q
+
+    def as_struct(self) -> vba_sim3_ransac_problem:
+        s = vba_sim3_ransac_problem()
+        s.n_pairs, s.fix_scale = self.n_pairs, int(self.fix_scale)
+        p = lambda a: a.ctypes.data_as(_pd)
+        s.p1c, s.p2c, s.max_err1, s.max_err2 = p(self.p1c), p(self.p2c), p(self.max_err1), p(self.max_err2)
+        s.K1[:] = self.K1.tolist(); s.K2[:] = self.K2.tolist()
+        s.min_inliers, s.n_hyp = int(self.min_inliers), self.n_hyp
+        s.sample = self.sample.ctypes.data_as(_pi)
+        s.best_inliers = int(self.best_inliers)
+        s.best_S12[:] = self.best_S12.tolist()
+        return s
+
+
+@dataclass
+class Sim3RansacResult:
+    status: int
+    hit: int
+    its_done: int
+    best_hyp: int
+    n_inliers: int
+    S12: np.ndarray                 # of the hit; zeros without one (the ABI leaves the caller's array untouched)
+    inlier: np.ndarray              # [n] of the hit; zeros without one
+    hyp_inliers: Optional[np.ndarray]
+    best_inliers: int               # the problem's in/out state after the call
+    best_S12: np.ndarray
+
+
+class Sim3RansacResultBuf:
+    """Caller-allocated result storage of one candidate."""
+
+    def __init__(self, p: Sim3RansacProblem, want_counts: bool = True):
+        self.n, self.nh = p.n_pairs, p.n_hyp
+        self.o = np.zeros(max(self.n, 1), dtype=np.uint8)
+        self.want_counts = want_counts
+        self.s = vba_sim3_ransac_result()
+        self.s.inlier = self.o.ctypes.data_as(_pu8)
+        if want_counts:
+            self.c = np.full(max(self.nh, 1), -1, dtype=np.int32)
+            self.s.hyp_inliers = self.c.ctypes.data_as(_pi)
+
+    def get(self, st: vba_sim3_ransac_problem) -> Sim3RansacResult:
+        s = self.s
+        return Sim3RansacResult(s.status, s.hit, s.its_done, s.best_hyp, s.n_inliers, np.array(s.S12[:]), self.o[:self.n].copy(),
+                                self.c[:self.nh].copy() if self.want_counts else None, int(st.best_inliers), np.array(st.best_S12[:]))
+
+
 # ---- essential-graph optimisation (include/vislam_ba.h: vba_posegraph_problem / vba_posegraph_result) ----
 class vba_posegraph_problem(C.Structure):
     _fields_ = [

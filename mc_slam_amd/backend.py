@@ -19,7 +19,7 @@ _libs = {}
 EXPORTS = ["vba_create", "vba_destroy", "vba_last_error", "vba_solve", "vba_batch_upload", "vba_batch_run",
            "vba_batch_download", "vba_batch_solve", "vba_solve_b", "vba_batch_run_b", "vba_batch_solve_b", "vba_preintegrate", "vba_pose_optimize", "vba_problem_save", "vba_problem_load", "vba_problem_free", "vba_set_profile", "vba_get_profile", "vba_host_threads",
            "vba_batch_set_depth", "vba_batch_submit", "vba_batch_submit_b", "vba_batch_poll", "vba_batch_wait", "vba_sim3_optimize",
-           "vba_posegraph_optimize"]
+           "vba_posegraph_optimize", "vba_sim3_ransac"]
 
 
 def load_library(hooks=False):
@@ -50,6 +50,8 @@ def load_library(hooks=False):
     lib.vba_preintegrate.argtypes = [C.c_void_p, C.c_int32, _pi, _pd, _pd, _pd, C.c_double, C.c_double, _pd, _pd, _pd]
     lib.vba_pose_optimize.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.POINTER(abi.vba_frame_problem)), C.POINTER(C.POINTER(abi.vba_frame_result))]
     lib.vba_sim3_optimize.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.POINTER(abi.vba_sim3_problem)), C.POINTER(C.POINTER(abi.vba_sim3_result))]
+    lib.vba_sim3_ransac.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.POINTER(abi.vba_sim3_ransac_problem)),
+                                    C.POINTER(C.POINTER(abi.vba_sim3_ransac_result))]
     lib.vba_posegraph_optimize.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.POINTER(abi.vba_posegraph_problem)),
                                            C.POINTER(C.POINTER(abi.vba_posegraph_result))]
     lib.vba_set_profile.argtypes = [C.c_void_p, C.c_int32]
@@ -277,6 +279,33 @@ class LocalBA:
         """vba_sim3_optimize on a list of abi.Sim3Problem (left untouched): list of abi.Sim3Result with the refined S12"""
         packed = self.sim3_pack(problems, want_chi2)
         self.sim3_call(packed)
+        return [b.get(s) for b, s in zip(packed[2], packed[1])]
+
+    # ---- loop-candidate Sim3 RANSAC (vba_sim3_ransac): the hypotheses of a batch of independent candidates per call ----
+    def sim3_ransac_pack(self, problems, want_counts=True):
+        """ctypes views of a list of abi.Sim3RansacProblem for vba_sim3_ransac (kept alive by the returned tuple)"""
+        n = len(problems)
+        structs = [p.as_struct() for p in problems]
+        bufs = [abi.Sim3RansacResultBuf(p, want_counts) for p in problems]
+        pp = (C.POINTER(abi.vba_sim3_ransac_problem) * n)(*[C.pointer(s) for s in structs])
+        rr = (C.POINTER(abi.vba_sim3_ransac_result) * n)(*[C.pointer(b.s) for b in bufs])
+        return n, structs, bufs, pp, rr, problems
+
+    def sim3_ransac_reset(self, packed):
+        """vba_sim3_ransac updates best_inliers / best_S12 in place: put the solvers' states back before the next run"""
+        for s, p in zip(packed[1], packed[5]):
+            s.best_inliers = int(p.best_inliers)
+            s.best_S12[:] = p.best_S12.tolist()
+
+    def sim3_ransac_call(self, packed):
+        if self.lib.vba_sim3_ransac(self.h, packed[0], packed[3], packed[4]) != 0:
+            raise self._err("vba_sim3_ransac")
+
+    def sim3_ransac(self, problems, want_counts=True):
+        """vba_sim3_ransac on a list of abi.Sim3RansacProblem (left untouched): list of abi.Sim3RansacResult, each with the
+        solver's state (best_inliers, best_S12) after the call"""
+        packed = self.sim3_ransac_pack(problems, want_counts)
+        self.sim3_ransac_call(packed)
         return [b.get(s) for b, s in zip(packed[2], packed[1])]
 
     # ---- essential-graph optimisation (vba_posegraph_optimize): a batch of independent Sim3 pose graphs per call ----

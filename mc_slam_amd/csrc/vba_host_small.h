@@ -1,16 +1,18 @@
 // vba_host_small.h -- host side of the library, part 5: the drivers of the small-problem entry points (vba_preintegrate,
-// vba_pose_optimize, vba_sim3_optimize, vba_posegraph_optimize).  Each lays its arena out once (vba_host_arena.h), packs the
-// pinned staging block with the plain-C++ half of its topic (vba_host_pose.h, vba_host_sim3.h, vba_host_posegraph.h), and does one
+// vba_pose_optimize, vba_sim3_optimize, vba_sim3_ransac, vba_posegraph_optimize).  Each lays its arena out once (vba_host_arena.h), packs the
+// pinned staging block with the plain-C++ half of its topic (vba_host_pose.h, vba_host_sim3.h, vba_host_sim3_ransac.h,
+// vba_host_posegraph.h), and does one
 // H2D copy, one or two launches and one D2H copy on the handle's stream.  No entry point shares its arena with another.
 #pragma once
 #include "vba_host_pose.h"
 #include "vba_host_sim3.h"
+#include "vba_host_sim3_ransac.h"
 #include "vba_host_posegraph.h"
 
 namespace {
 using vba_host::at;
 
-// threads that pack the items of a vba_pose_optimize / vba_sim3_optimize call
+// threads that pack the items of a vba_pose_optimize / vba_sim3_optimize / vba_sim3_ransac call
 int small_pack_threads(int n_items) { return (n_items >= 256) ? std::max(1, std::min(8, host_threads())) : 1; }
 
 int preintegrate(Handle* h, int32_t n_edges, const int32_t* sample_begin, const double* gyr, const double* acc, const double* dt,
@@ -110,6 +112,42 @@ int sim3_optimize(Handle* h, int32_t n_problems, vba_sim3_problem* const* inout,
     const unsigned char* flag = at<unsigned char>(hout, A.L.in_back(A.flag));
     const double* cc = at<double>(hout, A.L.in_back(A.c));
     for (int f = 0; f < n_problems; f++) vba_host::unpack_sim3(inout[f], out[f], desc[f], res[f], flag, cc);
+    return 0;
+}
+
+// Sim3Solver::iterate (src/Sim3Solver.cpp:138-220) for the triples the caller drew, for a batch of independent loop candidates:
+// k_sim3_ransac runs one workgroup per candidate
+int sim3_ransac(Handle* h, int32_t n_problems, vba_sim3_ransac_problem* const* inout, vba_sim3_ransac_result* const* out) {
+    if (n_problems < 0 || (n_problems > 0 && (!inout || !out))) return fail(h, "vba_sim3_ransac: bad arguments");
+    if (n_problems == 0) return 0;
+    size_t n_tot = 0, h_tot = 0;
+    bool want_counts = false;
+    std::string err;
+    if (vba_host::check_sim3_ransac(n_problems, inout, out, n_tot, h_tot, want_counts, err)) return fail(h, "vba_sim3_ransac: " + err);
+    HIPCHK(h, hipSetDevice(h->device));
+    const vba_host::RansacArena A(n_problems, n_tot, h_tot);
+    const size_t b_back = A.download_bytes(want_counts);
+    HIPCHK(h, h->ransac.ensure(A.L, b_back));
+    void *hin = h->ransac.in.p, *hout = h->ransac.out.p, *base = h->ransac.dev.p;
+    RansacDesc* desc = at<RansacDesc>(hin, A.desc);
+    vba_host::describe_sim3_ransac(n_problems, inout, desc);
+    host_parallel_for(h, n_problems, small_pack_threads(n_problems), [&](int f) {
+        vba_host::pack_sim3_ransac(inout[f], desc[f], at<double>(hin, A.p), at<double>(hin, A.gate), at<int32_t>(hin, A.sample));
+    });
+    RansacBatch B;
+    B.desc = at<RansacDesc>(base, A.desc); B.p = at<double>(base, A.p); B.gate = at<double>(base, A.gate); B.sample = at<int>(base, A.sample);
+    B.out = at<RansacOut>(base, A.out); B.flag = at<unsigned char>(base, A.flag); B.cnt = at<int>(base, A.cnt); B.hyp = at<double>(base, A.hyp);
+    const long long launch0 = h->n_launch;
+    HIPCHK(h, hipMemcpyAsync(base, hin, A.L.upload_bytes(), hipMemcpyHostToDevice, h->stream));
+    VBA_LAUNCH(k_sim3_ransac, dim3(n_problems), dim3(RS_NT), 0, h->stream, B);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(hout, B.out, b_back, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->prof.kernel_launches = h->n_launch - launch0;
+    const RansacOut* res = at<RansacOut>(hout, A.L.in_back(A.out));
+    const unsigned char* flag = at<unsigned char>(hout, A.L.in_back(A.flag));
+    const int32_t* cnt = at<int32_t>(hout, A.L.in_back(A.cnt));
+    for (int f = 0; f < n_problems; f++) vba_host::unpack_sim3_ransac(inout[f], out[f], desc[f], res[f], flag, cnt);
     return 0;
 }
 

@@ -128,6 +128,21 @@ struct Sim3Out {
     double S[8];
 };
 static_assert(sizeof(Sim3Desc) == 176 && sizeof(Sim3Out) == 112, "scripts/sim3_bench.py derives the copied bytes from these sizes");
+// vba_sim3_ransac (vba_sim3_ransac.h)
+struct RansacDesc {
+    int n_pairs, fix_scale, min_inliers, n_hyp, best_inliers;
+    int pad;
+    long long pair0, hyp0;     // offsets of the candidate's pairs / hypotheses in the concatenated arrays
+    double K1[4], K2[4];
+};
+struct RansacOut {
+    int status, hit, its_done, best_hyp, n_inliers, best_inliers;
+    int pad[2];
+    double S[8];               // (t, q, s) of the hit
+    double best_S[8];          // (t, q, s) of best_hyp
+};
+#define VBA_RANSAC_HYP 32      // doubles per hypothesis record (device only): sR12 (9) t12 (3) sR21 (9) t21 (3) t (3) q (4) s (1)
+static_assert(sizeof(RansacDesc) == 104 && sizeof(RansacOut) == 160, "scripts/sim3_ransac_bench.py derives the copied bytes from these sizes");
 // vba_posegraph_optimize (vba_posegraph.h)
 struct PgDesc {
     int nv, ne, nf, npair;

@@ -25,6 +25,10 @@ void* handle() {
     return t_handle;
 }
 
+}  // namespace
+void* Optimizer::BackendHandle() { return handle(); }
+namespace {
+
 Quaterniond MatrixToQuat(const double* m) {  // Eigen::Quaterniond(Matrix3d), then normalised
     Quaterniond q;
     double t = m[0] + m[4] + m[8];

@@ -106,6 +106,7 @@ public:
     static const FacadeTiming& LastTiming();   // of this thread's last LocalBAPRVIDP call
     static PackedWindow& LastWindowMutable();   // test harness: extraction-only calls pack into it
     static int Device;  // HIP device of the backend handle (one handle per calling thread)
+    static void* BackendHandle();   // this thread's vba_create handle (NULL without a HIP device): shared with Sim3Solver
 };
 
 }  // namespace ORB_SLAM2

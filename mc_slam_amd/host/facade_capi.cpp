@@ -7,6 +7,7 @@
 #include <memory>
 
 #include "Optimizer.h"
+#include "Sim3Solver.h"
 
 using namespace ORB_SLAM2;
 
@@ -44,6 +45,8 @@ int fc_add_keyframe(void* m, long id, const double* nav, const double* K, long p
     k->mNavState.Set_DeltaBiasGyr({{nav[16], nav[17], nav[18]}});
     k->mNavState.Set_DeltaBiasAcc({{nav[19], nav[20], nav[21]}});
     k->mvInvLevelSigma2.resize(8);
+    k->mvLevelSigma2.resize(8);
+    for (int l = 0; l < 8; l++) k->mvLevelSigma2[l] = (float)std::pow(1.2, 2 * l);
     for (int l = 0; l < 8; l++) k->mvInvLevelSigma2[l] = 1.0f / (float)std::pow(1.2, 2 * l);  // ORBextractor.cpp:427-441
     k->mbBad = bad != 0;
     if (prev_id >= 0 && M->kfs.count(prev_id)) k->mpPrevKeyFrame = M->kfs[prev_id].get();
@@ -339,6 +342,71 @@ void fc_sim3_ops(const double* a8, const double* b8, const double* x3, double* o
     for (int k = 0; k < 3; k++) out19[k] = y[k];
     put(A.inverse(), out19 + 3);
     put(A * B, out19 + 11);
+}
+// ---- loop-candidate Sim3 RANSAC (Sim3Solver.h) ----
+// Sim3Solver(kf1, kf2, vpMatched12, bFixScale): matches[i] = id of the map point matched to keypoint i of kf1 (-1: NULL)
+void* fc_sim3solver_create(void* m, long kf1, long kf2, const long* matches, int n, int fix_scale) {
+    FcMap* M = reinterpret_cast<FcMap*>(m);
+    std::vector<MapPoint*> v((size_t)n, nullptr);
+    for (int i = 0; i < n; i++)
+        if (matches[i] >= 0) v[i] = M->mps.at(matches[i]).get();
+    return new Sim3Solver(M->kfs.at(kf1).get(), M->kfs.at(kf2).get(), v, fix_scale != 0);
+}
+void fc_sim3solver_destroy(void* s) { delete reinterpret_cast<Sim3Solver*>(s); }
+void fc_sim3solver_set_ransac(void* s, double probability, int min_inliers, int max_iterations) {
+    reinterpret_cast<Sim3Solver*>(s)->SetRansacParameters(probability, min_inliers, max_iterations);
+}
+// out: N, mN1, mRansacMaxIts, mnIterations, mnBestInliers, mRansacMinInliers
+void fc_sim3solver_info(void* s, int* out6) {
+    const Sim3Solver* S = reinterpret_cast<Sim3Solver*>(s);
+    out6[0] = S->N; out6[1] = S->mN1; out6[2] = S->mRansacMaxIts; out6[3] = S->mnIterations; out6[4] = S->mnBestInliers; out6[5] = S->mRansacMinInliers;
+}
+// the constructor's products: mvnIndices1 [N], the gates [N] each, mvX3Dc1 / mvX3Dc2 [N][3], K1 / K2 [4]
+void fc_sim3solver_arrays(void* s, long* indices1, double* gate1, double* gate2, double* p1c, double* p2c, double* K1, double* K2) {
+    const Sim3Solver* S = reinterpret_cast<Sim3Solver*>(s);
+    for (size_t i = 0; i < S->mvnIndices1.size(); i++) {
+        indices1[i] = (long)S->mvnIndices1[i];
+        gate1[i] = (double)S->mvnMaxError1[i];
+        gate2[i] = (double)S->mvnMaxError2[i];
+    }
+    if (!S->mvX3Dc1.empty()) {
+        std::memcpy(p1c, S->mvX3Dc1.data(), 8 * S->mvX3Dc1.size());
+        std::memcpy(p2c, S->mvX3Dc2.data(), 8 * S->mvX3Dc2.size());
+    }
+    std::memcpy(K1, S->mK1, 32);
+    std::memcpy(K2, S->mK2, 32);
+}
+void fc_srand(unsigned seed) { srand(seed); }
+// the draw alone (no backend call): n hypotheses, triples [n][3]
+void fc_sim3solver_draw(void* s, int n, int32_t* triples) {
+    std::vector<int32_t> t;
+    reinterpret_cast<Sim3Solver*>(s)->DrawTriples(n, t);
+    if (!t.empty()) std::memcpy(triples, t.data(), 4 * t.size());
+}
+// iterate(nIterations, ...) (find when nIterations < 0): returns 1 with T12 on a hit; inliers [mN1]; triples: the draws of the
+// call [up to max_hyp][3], *n_hyp how many hypotheses were drawn
+int fc_sim3solver_iterate(void* s, int nIterations, int* no_more, uint8_t* inliers, int* n_inliers, float* T16, int32_t* triples, int max_hyp,
+                          int* n_hyp) {
+    Sim3Solver* S = reinterpret_cast<Sim3Solver*>(s);
+    std::vector<bool> vb;
+    bool bNoMore = false;
+    Mat4f T{};
+    const bool found = nIterations < 0 ? S->find(vb, *n_inliers, T) : S->iterate(nIterations, bNoMore, vb, *n_inliers, T);
+    *no_more = bNoMore ? 1 : 0;
+    for (size_t i = 0; i < vb.size(); i++) inliers[i] = vb[i] ? 1 : 0;
+    std::memcpy(T16, T.data(), 64);
+    *n_hyp = (int)S->mvLastTriples.size() / 3;
+    if (*n_hyp > 0) std::memcpy(triples, S->mvLastTriples.data(), 12 * (size_t)std::min(*n_hyp, max_hyp));
+    return found ? 1 : 0;
+}
+// GetEstimatedRotation [9] / Translation [3] / Scale
+void fc_sim3solver_estimate(void* s, float* R9, float* t3, float* scale) {
+    Sim3Solver* S = reinterpret_cast<Sim3Solver*>(s);
+    const std::array<float, 9> R = S->GetEstimatedRotation();
+    const std::array<float, 3> t = S->GetEstimatedTranslation();
+    std::memcpy(R9, R.data(), 36);
+    std::memcpy(t3, t.data(), 12);
+    *scale = S->GetEstimatedScale();
 }
 // ---- essential graph ----
 // spanning tree, loop edges and the ordered covisibility list (descending weights) of one keyframe

@@ -134,6 +134,7 @@ public:
     std::vector<KeyPoint> mvKeysUn;
     std::vector<float> mvuRight;          // negative for monocular points
     std::vector<float> mvInvLevelSigma2;
+    std::vector<float> mvLevelSigma2;     // include/KeyFrame.h: what Sim3Solver reads (src/Sim3Solver.cpp:75-76)
 
     std::vector<MapPoint*> GetMapPointMatches() { return mvpMapPoints; }
     KeyFrame* GetPrevKeyFrame() { return mpPrevKeyFrame; }

@@ -544,6 +544,40 @@ def make_sim3_pair(seed, n_pairs, fix_scale=False, outlier_frac=0.1, noise=True,
                            truth=dict(S12=np.concatenate([t, rot_to_quat(R), [s]]), is_outlier=m))
 
 
+def make_sim3_ransac(seed, n_pairs, fix_scale, outlier_frac, noise3d=0.01, same_K=False):
+    """One loop candidate as Sim3Solver sees it after its constructor (src/Sim3Solver.cpp:29-95): the geometry of make_sim3_pair
+    (a true S12, points 3-10 m in front of KF2 mapped into KF1), but with the noise ON THE 3D POINTS of both sides, proportional
+    to the depth: noise3d (1 %) of z along z and a tenth of that across, as triangulated map points err.  Exact 3D correspondences
+    would make every clean hypothesis perfect and the first one a hit.  The p1c of outlier_frac of the pairs are replaced by
+    unrelated points; the gates are 9.210 sigma2 of octaves 0-3 (:78-79).  No triples: draw_triples; truth: S12, is_outlier."""
+    r = np.random.default_rng(seed)
+    n = int(n_pairs)
+    K1 = EUROC_K.copy()
+    K2 = K1.copy() if same_K else K1 * np.array([1.02, 0.99, 1.01, 0.97])
+    R, _, _ = _sim3_exp(np.concatenate([r.normal(size=3) * 0.2, np.zeros(4)]))
+    t = r.normal(size=3) * 0.3
+    s = 1.0 if fix_scale else float(np.exp(r.normal() * 0.15))
+    p2 = np.stack([r.uniform(-2, 2, n), r.uniform(-1.5, 1.5, n), r.uniform(3, 10, n)], axis=1)
+    p1 = s * p2 @ R.T + t
+    sig = np.array([0.1 * noise3d, 0.1 * noise3d, noise3d])
+    p1 = p1 + r.normal(size=(n, 3)) * sig * p1[:, 2:3]
+    p2 = p2 + r.normal(size=(n, 3)) * sig * p2[:, 2:3]
+    m = r.random(n) < outlier_frac
+    k = int(m.sum())
+    p1[m] = np.stack([r.uniform(-2, 2, k), r.uniform(-1.5, 1.5, k), r.uniform(3, 10, k)], axis=1)
+    lv1, lv2 = r.integers(0, 4, n), r.integers(0, 4, n)
+    return abi.Sim3RansacProblem(p1c=p1, p2c=p2, max_err1=9.210 * 1.2 ** (2.0 * lv1), max_err2=9.210 * 1.2 ** (2.0 * lv2), K1=K1, K2=K2,
+                                 sample=np.zeros((0, 3), dtype=np.int32), fix_scale=int(bool(fix_scale)),
+                                 truth=dict(S12=np.concatenate([t, rot_to_quat(R), [s]]), is_outlier=m))
+
+
+def draw_triples(seed, n_pairs, n_hyp):
+    """[n_hyp, 3] int32: three distinct pair indices per hypothesis (the library takes any indices; the facade draws as the
+    reference does)"""
+    r = np.random.default_rng(seed)
+    return np.stack([r.choice(int(n_pairs), 3, replace=False) for _ in range(int(n_hyp))]).astype(np.int32).reshape(-1, 3)
+
+
 # ---------------------------------------------------------------- essential graphs (vba_posegraph_optimize)
 def _s3_mul(a, b):
     return a[0] @ b[0], a[2] * (a[0] @ b[1]) + a[1], a[2] * b[2]
