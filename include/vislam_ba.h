@@ -123,7 +123,7 @@ typedef struct vba_profile {
     double total_ms;             /* first launch -> last launch of the run */
     double factor_flops;         /* FP64 flop the factorisation class executed on MFMA: 2*32^3 per tile product of the
                                     symbolic tile lists, per solve (structurally zero tiles are never touched) */
-    int64_t kernel_launches;     /* kernel launches the last vba_batch_run / vba_solve / vba_sim3_optimize / vba_sim3_ransac / vba_posegraph_optimize enqueued (filled with or without profiling) */
+    int64_t kernel_launches;     /* kernel launches the last vba_batch_run / vba_solve / vba_sim3_optimize / vba_sim3_ransac / vba_triangulate / vba_posegraph_optimize enqueued (filled with or without profiling) */
 } vba_profile;
 
 /* One handle per host thread / GPU; owns device buffers and a stream.  Errors: nonzero return, message
@@ -178,7 +178,7 @@ int vba_batch_solve_b(void *handle, int32_t n_windows, vba_problem *const *inout
  *           every later one, those submitted afterwards included, with the same message: no GPU work starts for them (earlier
  *           tickets finish).  Waiting on an unknown or retired ticket returns -1.
  *   handle  while any ticket is submitted and not yet waited for, every synchronous entry point of the handle (vba_solve*,
- *           vba_batch_upload / run / download / solve*, vba_pose_optimize, vba_sim3_optimize, vba_sim3_ransac, vba_posegraph_optimize, vba_preintegrate, vba_set_profile,
+ *           vba_batch_upload / run / download / solve*, vba_pose_optimize, vba_sim3_optimize, vba_sim3_ransac, vba_triangulate, vba_posegraph_optimize, vba_preintegrate, vba_set_profile,
  *           vba_batch_set_depth) returns -1 with "asynchronous batches pending: wait for them first"; afterwards the handle
  *           works synchronously as before.  vba_destroy finishes pending tickets (their results land) before it frees.
  *           Profiling (vba_set_profile) covers synchronous calls only.  One caller thread at a time, as everywhere. */
@@ -328,6 +328,60 @@ typedef struct vba_sim3_ransac_result {
  * or gate.  The quaternion of S12 / best_S12 is the unit eigenvector of Horn's N with w >= 0. */
 int vba_sim3_ransac(void *handle, int32_t n_problems, vba_sim3_ransac_problem *const *inout,
                     vba_sim3_ransac_result *const *out);
+
+/* ---- two-view triangulation of new map points ----
+ * The geometric part of LocalMapping::CreateNewMapPoints (src/LocalMapping.cpp:1334-1517), monocular: for every match of a
+ * keyframe pair (keyframe 1 = mpCurrentKeyFrame, keyframe 2 = one neighbour) the two rays and the parallax gate (:1360-1389), the
+ * linear triangulation (:1393-1408: the right singular vector of the smallest singular value of the 4x4 A, divided by its last
+ * entry), the two depth tests (:1428-1433), the two chi-square reprojection tests (:1437-1480) and the scale-consistency test
+ * (:1499-1517).  One problem is one keyframe pair with all its matches; one call takes any number of pairs, ragged, in one kernel
+ * launch (one lane per match).  The tests are applied in the reference's order with its comparison operators, and `reason` says
+ * which `continue` dropped a match:
+ *   0  accepted (:1520)
+ *   1  parallax gate: not (cos > 0 && cos < cos_max); a NaN cosine lands here (:1389, :1423)
+ *   2  homogeneous coordinate == 0 (:1404)
+ *   3  z1 <= 0 (:1429)
+ *   4  z2 <= 0 (:1433)
+ *   5  squared reprojection error in keyframe 1 > chi2_th * sigma2 of the keypoint's octave (:1450)
+ *   6  the same in keyframe 2 (:1479)
+ *   7  dist1 == 0 || dist2 == 0 (:1505)
+ *   8  ratioDist * ratio_factor < ratioOctave || ratioDist > ratioOctave * ratio_factor (:1516)
+ * x3d holds the triangulated point for reason 0 and for 3 .. 8 (the point that failed), zeros for 1 and 2.  Past the input
+ * validation NaN compares as IEEE says, as in the reference.  MONOCULAR ONLY, as everywhere in this backend: the stereo branches
+ * (:1374-1377, :1411-1419, :1455-1465, :1484-1494) do not exist here.  FP64 throughout; the reference computes in CV_32F
+ * (gives the measured difference).  The singular vector comes from A itself (one-sided Jacobi), not
+ * from A^T A. */
+typedef struct vba_triangulate_problem {
+    double Rcw1[9], tcw1[3];  /* GetRotation() (row-major) / GetTranslation() of mpCurrentKeyFrame (:1254-1256), float32 widened */
+    double Ow1[3];            /* GetCameraCenter() as the keyframe holds it (:1262), not recomputed */
+    double K1[4];             /* fx fy cx cy (:1265-1268); invfx = 1 / fx is formed in FP64 */
+    double Rcw2[9], tcw2[3];  /* the neighbour pKF2 (:1320-1322) */
+    double Ow2[3];            /* :1287 */
+    double K2[4];             /* :1327-1330 */
+    int32_t n_levels1, n_levels2;             /* 1 .. 64: entries of the level tables */
+    const double *level_sigma2_1, *scale_1;   /* [n_levels1] mvLevelSigma2 (:1437), mvScaleFactors (:1513) of keyframe 1 */
+    const double *level_sigma2_2, *scale_2;   /* [n_levels2] of keyframe 2 (:1468, :1513) */
+    double ratio_factor;      /* 1.5f * mfScaleFactor (:1272) */
+    double cos_max;           /* 0.9998 (:1389) */
+    double chi2_th;           /* 5.991 (:1450, :1479) */
+    int32_t n_matches;        /* vMatchedIndices.size() (:1335) */
+    const double *uv1, *uv2;  /* [n_matches][2] mvKeysUn[idx].pt of the match in keyframe 1 / 2 (:1347, :1353) */
+    const uint8_t *oct1, *oct2; /* [n_matches] kp.octave (:1437, :1468, :1513) */
+} vba_triangulate_problem;
+
+typedef struct vba_triangulate_result {
+    int32_t status;           /* VBA_OK */
+    int32_t n_accepted;       /* matches with reason 0 (nnew of the pair, :1542), counted on the host from the reasons */
+    double *x3d;              /* [n_matches][3] caller-allocated: x3D (:1408) */
+    uint8_t *reason;          /* [n_matches] caller-allocated: the codes above */
+} vba_triangulate_result;
+
+/* Synchronous, like vba_sim3_ransac; -1 while asynchronous tickets are pending.  n_pairs == 0 returns 0; n_matches == 0 is legal
+ * (n_accepted = 0, nothing else written).  A bad pair fails the whole call before any GPU work with "vba_triangulate: pair K:
+ * <why>" through vba_last_error: a NULL problem or result, a negative count, a NULL array with a non-zero count (x3d and reason
+ * are required when n_matches > 0), n_levels outside 1 .. 64, an octave >= n_levels, a non-finite pose, K, level table, threshold
+ * or pixel, a zero fx / fy, a level scale <= 0.  A match's outputs do not depend on where its pair stands in the batch. */
+int vba_triangulate(void *handle, int32_t n_pairs, vba_triangulate_problem *const *in, vba_triangulate_result *const *out);
 
 /* ---- essential-graph optimisation (Sim3 pose graph) ----
  * Optimizer::OptimizeEssentialGraph(Map*, KeyFrame* pLoopKF, KeyFrame* pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections,

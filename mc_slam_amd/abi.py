@@ -582,6 +582,109 @@ class Sim3RansacResultBuf:
                                 self.c[:self.nh].copy() if self.want_counts else None, int(st.best_inliers), np.array(st.best_S12[:]))
 
 
+# ---- two-view triangulation of new map points (include/vislam_ba.h: vba_triangulate_problem / vba_triangulate_result) ----
+class vba_triangulate_problem(C.Structure):
+    _fields_ = [
+        ("Rcw1", C.c_double * 9), ("tcw1", C.c_double * 3), ("Ow1", C.c_double * 3), ("K1", C.c_double * 4),
+        ("Rcw2", C.c_double * 9), ("tcw2", C.c_double * 3), ("Ow2", C.c_double * 3), ("K2", C.c_double * 4),
+        ("n_levels1", C.c_int32), ("n_levels2", C.c_int32), ("level_sigma2_1", _pd), ("scale_1", _pd), ("level_sigma2_2", _pd), ("scale_2", _pd),
+        ("ratio_factor", C.c_double), ("cos_max", C.c_double), ("chi2_th", C.c_double),
+        ("n_matches", C.c_int32), ("uv1", _pd), ("uv2", _pd), ("oct1", _pu8), ("oct2", _pu8),
+    ]
+
+
+class vba_triangulate_result(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_accepted", C.c_int32), ("x3d", _pd), ("reason", _pu8)]
+
+
+TRI_ACCEPTED, TRI_PARALLAX, TRI_W_ZERO, TRI_Z1, TRI_Z2, TRI_CHI2_1, TRI_CHI2_2, TRI_DIST_ZERO, TRI_SCALE = range(9)
+
+
+@dataclass
+class TriangulateProblem:
+    """One keyframe pair of LocalMapping::CreateNewMapPoints (src/LocalMapping.cpp:1334-1517) as flat arrays: keyframe 1 =
+    mpCurrentKeyFrame, keyframe 2 = one neighbour, and all their matches."""
+    Rcw1: np.ndarray               # [3,3]
+    tcw1: np.ndarray               # [3]
+    Ow1: np.ndarray                # [3]
+    K1: np.ndarray                 # [4] fx fy cx cy
+    Rcw2: np.ndarray
+    tcw2: np.ndarray
+    Ow2: np.ndarray
+    K2: np.ndarray
+    level_sigma2_1: np.ndarray     # [n_levels1]
+    scale_1: np.ndarray            # [n_levels1]
+    level_sigma2_2: np.ndarray     # [n_levels2]
+    scale_2: np.ndarray            # [n_levels2]
+    uv1: np.ndarray                # [n,2]
+    uv2: np.ndarray                # [n,2]
+    oct1: np.ndarray               # [n] uint8
+    oct2: np.ndarray               # [n] uint8
+    ratio_factor: float = 1.5 * 1.2
+    cos_max: float = 0.9998
+    chi2_th: float = 5.991
+    truth: dict = field(default_factory=dict)
+
+    def __post_init__(self):
+        self.Rcw1 = _f64(self.Rcw1, (3, 3)); self.Rcw2 = _f64(self.Rcw2, (3, 3))
+        for k in ("tcw1", "Ow1", "tcw2", "Ow2"):
+            setattr(self, k, _f64(getattr(self, k), (3,)))
+        self.K1 = _f64(self.K1, (4,)); self.K2 = _f64(self.K2, (4,))
+        for k in ("level_sigma2_1", "scale_1", "level_sigma2_2", "scale_2"):
+            setattr(self, k, _f64(getattr(self, k), (-1,)))
+        self.uv1 = _f64(self.uv1, (-1, 2)); self.uv2 = _f64(self.uv2, (-1, 2))
+        self.oct1 = np.ascontiguousarray(self.oct1, dtype=np.uint8).reshape(-1)
+        self.oct2 = np.ascontiguousarray(self.oct2, dtype=np.uint8).reshape(-1)
+
+    n_matches = property(lambda self: self.uv1.shape[0])
+    n_levels1 = property(lambda self: self.level_sigma2_1.shape[0])
+    n_levels2 = property(lambda self: self.level_sigma2_2.shape[0])
+
+    def copy(self, **changes):
+        import copy as _c
+        q = _c.copy(self)
+        for k, v in changes.items():
+            setattr(q, k, v)
+        q.__post_init__()
+        return q
+
+    def as_struct(self) -> vba_triangulate_problem:
+        s = vba_triangulate_problem()
+        for k in ("Rcw1", "tcw1", "Ow1", "K1", "Rcw2", "tcw2", "Ow2", "K2"):
+            getattr(s, k)[:] = getattr(self, k).ravel().tolist()
+        p = lambda a: a.ctypes.data_as(_pd)
+        s.n_levels1, s.n_levels2 = self.n_levels1, self.n_levels2
+        s.level_sigma2_1, s.scale_1, s.level_sigma2_2, s.scale_2 = p(self.level_sigma2_1), p(self.scale_1), p(self.level_sigma2_2), p(self.scale_2)
+        s.ratio_factor, s.cos_max, s.chi2_th = float(self.ratio_factor), float(self.cos_max), float(self.chi2_th)
+        s.n_matches = self.n_matches
+        s.uv1, s.uv2 = p(self.uv1), p(self.uv2)
+        s.oct1, s.oct2 = self.oct1.ctypes.data_as(_pu8), self.oct2.ctypes.data_as(_pu8)
+        return s
+
+
+@dataclass
+class TriangulateResult:
+    status: int
+    n_accepted: int
+    x3d: np.ndarray                 # [n,3]
+    reason: np.ndarray              # [n] uint8
+
+
+class TriangulateResultBuf:
+    """Caller-allocated result storage of one keyframe pair."""
+
+    def __init__(self, p: TriangulateProblem):
+        self.n = p.n_matches
+        self.x = np.zeros((max(self.n, 1), 3))
+        self.r = np.full(max(self.n, 1), 255, dtype=np.uint8)
+        self.s = vba_triangulate_result()
+        self.s.x3d = self.x.ctypes.data_as(_pd)
+        self.s.reason = self.r.ctypes.data_as(_pu8)
+
+    def get(self) -> TriangulateResult:
+        return TriangulateResult(self.s.status, self.s.n_accepted, self.x[:self.n].copy(), self.r[:self.n].copy())
+
+
 # ---- essential-graph optimisation (include/vislam_ba.h: vba_posegraph_problem / vba_posegraph_result) ----
 class vba_posegraph_problem(C.Structure):
     _fields_ = [

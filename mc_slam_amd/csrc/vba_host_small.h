@@ -1,18 +1,19 @@
 // vba_host_small.h -- host side of the library, part 5: the drivers of the small-problem entry points (vba_preintegrate,
-// vba_pose_optimize, vba_sim3_optimize, vba_sim3_ransac, vba_posegraph_optimize).  Each lays its arena out once (vba_host_arena.h), packs the
+// vba_pose_optimize, vba_sim3_optimize, vba_sim3_ransac, vba_triangulate, vba_posegraph_optimize).  Each lays its arena out once (vba_host_arena.h), packs the
 // pinned staging block with the plain-C++ half of its topic (vba_host_pose.h, vba_host_sim3.h, vba_host_sim3_ransac.h,
-// vba_host_posegraph.h), and does one
+// vba_host_triangulate.h, vba_host_posegraph.h), and does one
 // H2D copy, one or two launches and one D2H copy on the handle's stream.  No entry point shares its arena with another.
 #pragma once
 #include "vba_host_pose.h"
 #include "vba_host_sim3.h"
 #include "vba_host_sim3_ransac.h"
+#include "vba_host_triangulate.h"
 #include "vba_host_posegraph.h"
 
 namespace {
 using vba_host::at;
 
-// threads that pack the items of a vba_pose_optimize / vba_sim3_optimize / vba_sim3_ransac call
+// threads that pack the items of a vba_pose_optimize / vba_sim3_optimize / vba_sim3_ransac / vba_triangulate call
 int small_pack_threads(int n_items) { return (n_items >= 256) ? std::max(1, std::min(8, host_threads())) : 1; }
 
 int preintegrate(Handle* h, int32_t n_edges, const int32_t* sample_begin, const double* gyr, const double* acc, const double* dt,
@@ -148,6 +149,41 @@ int sim3_ransac(Handle* h, int32_t n_problems, vba_sim3_ransac_problem* const* i
     const unsigned char* flag = at<unsigned char>(hout, A.L.in_back(A.flag));
     const int32_t* cnt = at<int32_t>(hout, A.L.in_back(A.cnt));
     for (int f = 0; f < n_problems; f++) vba_host::unpack_sim3_ransac(inout[f], out[f], desc[f], res[f], flag, cnt);
+    return 0;
+}
+
+// The per-match loop body of LocalMapping::CreateNewMapPoints (src/LocalMapping.cpp:1358-1517) for a batch of keyframe pairs:
+// k_triangulate runs one lane per match, every workgroup inside one pair.  A call without a single match launches nothing
+int triangulate(Handle* h, int32_t n_pairs, vba_triangulate_problem* const* in, vba_triangulate_result* const* out) {
+    if (n_pairs < 0 || (n_pairs > 0 && (!in || !out))) return fail(h, "vba_triangulate: bad arguments");
+    if (n_pairs == 0) return 0;
+    size_t n_tot = 0, l_tot = 0, n_blocks = 0;
+    std::string err;
+    if (vba_host::check_triangulate(n_pairs, in, out, n_tot, l_tot, n_blocks, err)) return fail(h, "vba_triangulate: " + err);
+    HIPCHK(h, hipSetDevice(h->device));
+    const vba_host::TriArena A(n_pairs, n_tot, l_tot, n_blocks);
+    HIPCHK(h, h->tri.ensure(A.L, A.L.back_bytes()));
+    void *hin = h->tri.in.p, *hout = h->tri.out.p, *base = h->tri.dev.p;
+    TriDesc* desc = at<TriDesc>(hin, A.desc);
+    vba_host::describe_triangulate(n_pairs, in, desc, at<TriBlock>(hin, A.blk));
+    host_parallel_for(h, n_pairs, small_pack_threads(n_pairs), [&](int f) {
+        vba_host::pack_triangulate(in[f], desc[f], at<double>(hin, A.lev), at<double>(hin, A.uv), at<unsigned char>(hin, A.oct));
+    });
+    const long long launch0 = h->n_launch;
+    if (n_blocks) {
+        TriBatch B;
+        B.desc = at<TriDesc>(base, A.desc); B.blk = at<TriBlock>(base, A.blk); B.lev = at<double>(base, A.lev); B.uv = at<double>(base, A.uv);
+        B.oct = at<unsigned char>(base, A.oct); B.x3d = at<double>(base, A.x3d); B.reason = at<unsigned char>(base, A.reason);
+        HIPCHK(h, hipMemcpyAsync(base, hin, A.L.upload_bytes(), hipMemcpyHostToDevice, h->stream));
+        VBA_LAUNCH(k_triangulate, dim3((unsigned)n_blocks), dim3(TR_NT), 0, h->stream, B);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipMemcpyAsync(hout, B.x3d, A.L.back_bytes(), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    h->prof.kernel_launches = h->n_launch - launch0;
+    const double* x3d = at<double>(hout, A.L.in_back(A.x3d));
+    const unsigned char* reason = at<unsigned char>(hout, A.L.in_back(A.reason));
+    for (int f = 0; f < n_pairs; f++) vba_host::unpack_triangulate(out[f], desc[f], x3d, reason);
     return 0;
 }
 

@@ -143,6 +143,20 @@ struct RansacOut {
 };
 #define VBA_RANSAC_HYP 32      // doubles per hypothesis record (device only): sR12 (9) t12 (3) sR21 (9) t21 (3) t (3) q (4) s (1)
 static_assert(sizeof(RansacDesc) == 104 && sizeof(RansacOut) == 160, "scripts/sim3_ransac_bench.py derives the copied bytes from these sizes");
+// vba_triangulate (vba_triangulate.h)
+#define VBA_TRI_CONST 41       // doubles of a pair's constants: Rcw1 (9) tcw1 (3) Ow1 (3) K1 (4), the same of keyframe 2, ratio_factor cos_max chi2_th
+#define VBA_TRI_LEVELS 64      // most pyramid levels of a keyframe
+#define VBA_TRI_NT 256         // matches per workgroup: the unit of the block-to-pair map
+struct TriDesc {
+    long long match0, lev0;    // offsets of the pair's matches in the concatenated arrays / of its level tables in the level region
+    int n_matches, n_levels1, n_levels2;
+    int pad;
+    double c[VBA_TRI_CONST];
+};
+struct TriBlock {
+    int pair, first;           // the pair of a workgroup and its first match inside the pair
+};
+static_assert(sizeof(TriDesc) == 360 && sizeof(TriBlock) == 8, "scripts/triangulate_bench.py derives the copied bytes from these sizes");
 // vba_posegraph_optimize (vba_posegraph.h)
 struct PgDesc {
     int nv, ne, nf, npair;

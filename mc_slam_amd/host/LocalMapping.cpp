@@ -1,0 +1,94 @@
+// LocalMapping.cpp -- LocalMapping::CreateNewMapPoints (src/LocalMapping.cpp:1237-1546, monocular) over vba_triangulate: the
+// reference's loop over the neighbours with its gate, the matcher through the caller's function object, ONE vba_triangulate call
+// per neighbour (the matcher of neighbour i + 1 must see the points created from neighbour i, so the pairs of a keyframe cannot
+// share a call here), and the map-point construction for every accepted match in match order.
+#include <cmath>
+#include <iostream>
+
+#include "../../include/vislam_ba.h"
+#include "Optimizer.h"
+
+namespace ORB_SLAM2 {
+
+namespace {
+// the keyframe's side of a vba_triangulate_problem: pose, centre, intrinsics (float32 widened) and the level tables
+struct TriSide {
+    double R[9], t[3], O[3], K[4];
+    std::vector<double> sigma2, scale;
+    explicit TriSide(KeyFrame* kf) : sigma2(kf->mvLevelSigma2.begin(), kf->mvLevelSigma2.end()), scale(kf->mvScaleFactors.begin(), kf->mvScaleFactors.end()) {
+        kf->GetRotation(R);
+        kf->GetTranslation(t);
+        kf->GetCameraCenter(O);
+        K[0] = kf->fx; K[1] = kf->fy; K[2] = kf->cx; K[3] = kf->cy;
+    }
+};
+}  // namespace
+
+int LocalMapping::CreateNewMapPoints(KeyFrame* pKF, const std::vector<KeyFrame*>& vpNeighKFs, const TriangulationMatcher& matcher, Map* pMap,
+                                     std::list<MapPoint*>& lpRecentAddedMapPoints) {
+    const TriSide s1(pKF);
+    const float ratioFactor = 1.5f * pKF->mfScaleFactor;   // :1272
+    int nnew = 0;
+    for (size_t i = 0; i < vpNeighKFs.size(); i++) {
+        KeyFrame* pKF2 = vpNeighKFs[i];
+        // :1287-1311 the baseline against the median scene depth of the neighbour, in float32
+        double Ow2[3];
+        pKF2->GetCameraCenter(Ow2);
+        const float b[3] = {(float)Ow2[0] - (float)s1.O[0], (float)Ow2[1] - (float)s1.O[1], (float)Ow2[2] - (float)s1.O[2]};
+        const float baseline = (float)std::sqrt((double)b[0] * b[0] + (double)b[1] * b[1] + (double)b[2] * b[2]);   // cv::norm accumulates in double
+        const float medianDepthKF2 = pKF2->ComputeSceneMedianDepth(2);
+        const float ratioBaselineDepth = baseline / medianDepthKF2;
+        if (ratioBaselineDepth < 0.01) continue;
+        // :1318 the matcher (ComputeF12 of :1314 belongs to it)
+        std::vector<std::pair<size_t, size_t>> vMatchedIndices;
+        matcher(pKF, pKF2, vMatchedIndices);
+        const int nmatches = (int)vMatchedIndices.size();
+        if (nmatches == 0) continue;
+        const TriSide s2(pKF2);
+        std::vector<double> uv1(2 * (size_t)nmatches), uv2(2 * (size_t)nmatches), x3d(3 * (size_t)nmatches);
+        std::vector<uint8_t> oct1(nmatches), oct2(nmatches), reason(nmatches);
+        for (int ikp = 0; ikp < nmatches; ikp++) {
+            const KeyPoint& kp1 = pKF->mvKeysUn[vMatchedIndices[ikp].first];
+            const KeyPoint& kp2 = pKF2->mvKeysUn[vMatchedIndices[ikp].second];
+            uv1[2 * ikp] = kp1.pt.x; uv1[2 * ikp + 1] = kp1.pt.y;
+            uv2[2 * ikp] = kp2.pt.x; uv2[2 * ikp + 1] = kp2.pt.y;
+            oct1[ikp] = (uint8_t)kp1.octave; oct2[ikp] = (uint8_t)kp2.octave;
+        }
+        vba_triangulate_problem P{};
+        std::copy(s1.R, s1.R + 9, P.Rcw1); std::copy(s1.t, s1.t + 3, P.tcw1); std::copy(s1.O, s1.O + 3, P.Ow1); std::copy(s1.K, s1.K + 4, P.K1);
+        std::copy(s2.R, s2.R + 9, P.Rcw2); std::copy(s2.t, s2.t + 3, P.tcw2); std::copy(s2.O, s2.O + 3, P.Ow2); std::copy(s2.K, s2.K + 4, P.K2);
+        P.n_levels1 = (int32_t)s1.sigma2.size(); P.n_levels2 = (int32_t)s2.sigma2.size();
+        P.level_sigma2_1 = s1.sigma2.data(); P.scale_1 = s1.scale.data();
+        P.level_sigma2_2 = s2.sigma2.data(); P.scale_2 = s2.scale.data();
+        P.ratio_factor = ratioFactor; P.cos_max = 0.9998; P.chi2_th = 5.991;
+        P.n_matches = nmatches;
+        P.uv1 = uv1.data(); P.uv2 = uv2.data(); P.oct1 = oct1.data(); P.oct2 = oct2.data();
+        vba_triangulate_result R{};
+        R.x3d = x3d.data(); R.reason = reason.data();
+        vba_triangulate_problem* pp = &P;
+        vba_triangulate_result* pr = &R;
+        void* h = Optimizer::BackendHandle();
+        if (!h || vba_triangulate(h, 1, &pp, &pr) != 0) {
+            std::cerr << "CreateNewMapPoints: " << (h ? vba_last_error(h) : "no HIP device (the backend has no CPU path)") << std::endl;
+            return -1;
+        }
+        // :1520-1542 for every accepted match, in match order
+        for (int ikp = 0; ikp < nmatches; ikp++) {
+            if (reason[ikp] != 0) continue;
+            const size_t idx1 = vMatchedIndices[ikp].first, idx2 = vMatchedIndices[ikp].second;
+            const float x3D[3] = {(float)x3d[3 * ikp], (float)x3d[3 * ikp + 1], (float)x3d[3 * ikp + 2]};
+            MapPoint* pMP = new MapPoint(x3D, pKF);
+            pMP->AddObservation(pKF, idx1);
+            pMP->AddObservation(pKF2, idx2);
+            pKF->AddMapPoint(pMP, idx1);
+            pKF2->AddMapPoint(pMP, idx2);
+            pMP->UpdateNormalAndDepth();   // ComputeDistinctiveDescriptors / UpdateNormalAndDepth: bookkeeping of the map, out of scope
+            pMap->AddMapPoint(pMP);
+            lpRecentAddedMapPoints.push_back(pMP);
+            nnew++;
+        }
+    }
+    return nnew;
+}
+
+}  // namespace ORB_SLAM2

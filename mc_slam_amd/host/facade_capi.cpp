@@ -47,6 +47,8 @@ int fc_add_keyframe(void* m, long id, const double* nav, const double* K, long p
     k->mvInvLevelSigma2.resize(8);
     k->mvLevelSigma2.resize(8);
     for (int l = 0; l < 8; l++) k->mvLevelSigma2[l] = (float)std::pow(1.2, 2 * l);
+    k->mvScaleFactors.resize(8);
+    for (int l = 0; l < 8; l++) k->mvScaleFactors[l] = (float)std::pow(1.2, l);
     for (int l = 0; l < 8; l++) k->mvInvLevelSigma2[l] = 1.0f / (float)std::pow(1.2, 2 * l);  // ORBextractor.cpp:427-441
     k->mbBad = bad != 0;
     if (prev_id >= 0 && M->kfs.count(prev_id)) k->mpPrevKeyFrame = M->kfs[prev_id].get();
@@ -408,6 +410,51 @@ void fc_sim3solver_estimate(void* s, float* R9, float* t3, float* scale) {
     std::memcpy(t3, t.data(), 12);
     *scale = S->GetEstimatedScale();
 }
+// ---- new map points (LocalMapping::CreateNewMapPoints, LocalMapping.cpp) ----
+// The matcher is a table: neighbour i of `neigh` gets matches [begin[i], begin[i + 1]) of `matches` ([..][2] keypoint indices in kf /
+// in the neighbour).  seen[i]: how many keypoints of kf had a map point when the matcher was called for neighbour i, -1 where it was
+// not called (the neighbour failed the baseline gate).  The created points move into the map under their mnId; new_ids lists them
+// in the order of the recent list.  Returns nnew (-1: the backend failed)
+int fc_create_new_map_points(void* m, long kf, const long* neigh, int n_neigh, const int* begin, const long* matches, int* seen, long* new_ids, int cap) {
+    FcMap* M = reinterpret_cast<FcMap*>(m);
+    KeyFrame* pKF = M->kfs.at(kf).get();
+    std::vector<KeyFrame*> vpNeighKFs;
+    for (int i = 0; i < n_neigh; i++) { vpNeighKFs.push_back(M->kfs.at(neigh[i]).get()); seen[i] = -1; }
+    const TriangulationMatcher matcher = [&](KeyFrame* k1, KeyFrame* k2, std::vector<std::pair<size_t, size_t>>& out) {
+        const int i = (int)(std::find(vpNeighKFs.begin(), vpNeighKFs.end(), k2) - vpNeighKFs.begin());
+        seen[i] = (int)std::count_if(k1->mvpMapPoints.begin(), k1->mvpMapPoints.end(), [](MapPoint* p) { return p != nullptr; });
+        for (int j = begin[i]; j < begin[i + 1]; j++) out.emplace_back((size_t)matches[2 * j], (size_t)matches[2 * j + 1]);
+    };
+    std::list<MapPoint*> recent;
+    const int nnew = M->lm.CreateNewMapPoints(pKF, vpNeighKFs, matcher, &M->map, recent);
+    int k = 0;
+    for (MapPoint* p : recent) {
+        if (k < cap) new_ids[k] = (long)p->mnId;
+        k++;
+        M->mps[(long)p->mnId].reset(p);
+    }
+    return nnew;
+}
+// one map point in full: position, reference keyframe, nObs, and its observations as (keyframe id, keypoint index) in keyframe order
+int fc_get_mappoint_obs(void* m, long id, float* Pw, long* ref_kf, int* n_obs_counter, long* obs, int cap) {
+    MapPoint* p = reinterpret_cast<FcMap*>(m)->mps.at(id).get();
+    std::memcpy(Pw, p->mWorldPos, 12);
+    *ref_kf = p->mpRefKF ? (long)p->mpRefKF->mnId : -1;
+    *n_obs_counter = p->nObs;
+    int k = 0;
+    for (const auto& o : p->mObservations) {
+        if (k < cap) { obs[2 * k] = (long)o.first->mnId; obs[2 * k + 1] = (long)o.second; }
+        k++;
+    }
+    return k;
+}
+// the map point id behind keypoint idx of a keyframe (-1: NULL), and how many points the map lists
+long fc_kf_mappoint_at(void* m, long kf, int idx) {
+    MapPoint* p = reinterpret_cast<FcMap*>(m)->kfs.at(kf)->mvpMapPoints.at(idx);
+    return p ? (long)p->mnId : -1;
+}
+int fc_map_n_points(void* m) { return (int)reinterpret_cast<FcMap*>(m)->map.mspMapPoints.size(); }
+float fc_kf_median_depth(void* m, long kf, int q) { return reinterpret_cast<FcMap*>(m)->kfs.at(kf)->ComputeSceneMedianDepth(q); }
 // ---- essential graph ----
 // spanning tree, loop edges and the ordered covisibility list (descending weights) of one keyframe
 int fc_kf_set_graph(void* m, long kf, long parent, const long* children, int n_children, const long* loop_edges, int n_loop,

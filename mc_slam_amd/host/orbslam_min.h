@@ -8,11 +8,14 @@
 #pragma once
 #include <array>
 #include <cmath>
+#include <algorithm>
 #include <cstddef>
+#include <functional>
 #include <list>
 #include <map>
 #include <mutex>
 #include <set>
+#include <utility>
 #include <vector>
 
 namespace ORB_SLAM2 {
@@ -114,15 +117,25 @@ public:
     std::vector<KeyFrame*> GetAllKeyFrames() { return mspKeyFrames; }    // include/Map.h:44 (a std::set there: id order)
     std::vector<MapPoint*> GetAllMapPoints() { return mspMapPoints; }    // include/Map.h:45
     long unsigned int GetMaxKFid() { return mnMaxKFid; }                 // include/Map.h:50
+    void AddMapPoint(MapPoint* pMP) { mspMapPoints.push_back(pMP); }     // src/Map.cpp (a std::set there)
     long unsigned int mnMaxKFid = 0;
     std::vector<KeyFrame*> mspKeyFrames;
     std::vector<MapPoint*> mspMapPoints;
 };
 
+// ORBmatcher::SearchForTriangulation stays matcher code: CreateNewMapPoints calls it per neighbour, in order, through this function
+// object (keyframe 1, keyframe 2, the matched keypoint indices to fill)
+typedef std::function<void(KeyFrame*, KeyFrame*, std::vector<std::pair<size_t, size_t>>&)> TriangulationMatcher;
+
 class LocalMapping {
 public:
     void SetMapUpdateFlagInTracking(bool b) { mbMapUpdateFlagForTracking = b; }
     bool mbMapUpdateFlagForTracking = false;
+    // src/LocalMapping.cpp:1237-1546 for a monocular pKF (= mpCurrentKeyFrame) and the neighbours the caller chose (:1243-1251): the
+    // baseline / median-depth gate, the matcher and one vba_triangulate call per neighbour, then the map-point construction of
+    // :1520-1542 for every accepted match (LocalMapping.cpp).  Returns nnew, -1 when the backend failed
+    int CreateNewMapPoints(KeyFrame* pKF, const std::vector<KeyFrame*>& vpNeighKFs, const TriangulationMatcher& matcher, Map* pMap,
+                           std::list<MapPoint*>& lpRecentAddedMapPoints);
 };
 
 class KeyFrame {
@@ -135,6 +148,8 @@ public:
     std::vector<float> mvuRight;          // negative for monocular points
     std::vector<float> mvInvLevelSigma2;
     std::vector<float> mvLevelSigma2;     // include/KeyFrame.h: what Sim3Solver reads (src/Sim3Solver.cpp:75-76)
+    std::vector<float> mvScaleFactors;    // include/KeyFrame.h: what CreateNewMapPoints reads (src/LocalMapping.cpp:1513)
+    float mfScaleFactor = 1.2f;           // src/LocalMapping.cpp:1272
 
     std::vector<MapPoint*> GetMapPointMatches() { return mvpMapPoints; }
     KeyFrame* GetPrevKeyFrame() { return mpPrevKeyFrame; }
@@ -185,6 +200,10 @@ public:
         T[15] = 1.0f;
         SetPose(T);
     }
+    void AddMapPoint(MapPoint* pMP, const size_t& idx) { mvpMapPoints[idx] = pMP; }   // src/KeyFrame.cpp
+    // src/KeyFrame.cpp:1163-1195 in float32 like cv::Mat (below MapPoint).  Without a single map point the reference indexes an empty
+    // vector; here that case returns -1 (every baseline ratio is then below the gate of CreateNewMapPoints)
+    float ComputeSceneMedianDepth(const int q);
     void EraseMapPointMatch(MapPoint* pMP);   // src/KeyFrame.cpp:573-579: through pMP->GetIndexInKeyFrame(this) (below MapPoint)
     std::vector<KeyFrame*> GetVectorCovisibleKeyFrames() { return mvpOrderedConnectedKeyFrames; }
     // spanning tree, loop edges and covisibility weights: what OptimizeEssentialGraph reads (include/KeyFrame.h:104-128)
@@ -227,6 +246,9 @@ public:
 
 class MapPoint {
 public:
+    MapPoint() {}
+    // MapPoint(const cv::Mat& Pos, KeyFrame* pRefKF, Map* pMap) (src/MapPoint.cpp): the position, the reference keyframe, the next id
+    MapPoint(const float Pos[3], KeyFrame* pRefKF) : mnId(nNextId++), mpRefKF(pRefKF) { SetWorldPos(Pos); }
     long unsigned int mnId = 0;
     static long unsigned int nNextId;
     long unsigned int mnBALocalForKF = (long unsigned int)-1;
@@ -237,6 +259,11 @@ public:
     mapMapPointObs GetObservations() { return mObservations; }
     KeyFrame* GetReferenceKeyFrame() { return mpRefKF; }
     void EraseObservation(KeyFrame* pKF) { mObservations.erase(pKF); }
+    void AddObservation(KeyFrame* pKF, size_t idx) {   // src/MapPoint.cpp (monocular: nObs grows by one)
+        if (mObservations.count(pKF)) return;
+        mObservations[pKF] = idx;
+        nObs++;
+    }
     int GetIndexInKeyFrame(KeyFrame* pKF) {   // src/MapPoint.cpp: the keypoint index of this point in pKF, -1 if pKF does not observe it
         const auto it = mObservations.find(pKF);
         return it == mObservations.end() ? -1 : (int)it->second;
@@ -248,6 +275,7 @@ public:
     float mWorldPos[3] = {0, 0, 0};
     bool mbBad = false;
     int nNormalUpdates = 0;
+    int nObs = 0;
     float mPosGBA[3] = {0, 0, 0};          // include/MapPoint.h:90-91
     long unsigned int mnBAGlobalForKF = 0;
 };
@@ -330,6 +358,18 @@ inline void KeyFrame::UpdateNavStatePVRFromTcw(const Mat4f& Tcw_, const Matrix3d
     mNavState.Set_Pos(Pwb);
     mNavState.Set_Rot(MatrixToQuat(Rwb));
     mNavState.Set_Vel(Vw2);
+}
+inline float KeyFrame::ComputeSceneMedianDepth(const int q) {
+    std::vector<float> vDepths;
+    vDepths.reserve(mvpMapPoints.size());
+    for (MapPoint* pMP : mvpMapPoints)
+        if (pMP) {
+            const float* P = pMP->mWorldPos;
+            vDepths.push_back((Tcw[8] * P[0] + Tcw[9] * P[1] + Tcw[10] * P[2]) + Tcw[11]);
+        }
+    if (vDepths.empty()) return -1.0f;
+    std::sort(vDepths.begin(), vDepths.end());
+    return vDepths[(vDepths.size() - 1) / q];
 }
 inline void KeyFrame::EraseMapPointMatch(MapPoint* pMP) {
     const int idx = pMP->GetIndexInKeyFrame(this);

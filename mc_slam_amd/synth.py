@@ -578,6 +578,94 @@ def draw_triples(seed, n_pairs, n_hyp):
     return np.stack([r.choice(int(n_pairs), 3, replace=False) for _ in range(int(n_hyp))]).astype(np.int32).reshape(-1, 3)
 
 
+# ---------------------------------------------------------------- new map points (vba_triangulate)
+TRI_KINDS = ("good", "far", "gross", "octave", "behind2", "chi2_2")
+
+
+def level_tables(n_levels=8, scale_factor=1.2):
+    """mvScaleFactors and mvLevelSigma2 as ORBextractor builds them in float32, widened"""
+    s = np.ones(n_levels, dtype=np.float32)
+    for i in range(1, n_levels):
+        s[i] = s[i - 1] * np.float32(scale_factor)
+    return s.astype(np.float64), (s * s).astype(np.float64)
+
+
+def make_triangulate(seed, n_matches, kind="std", n_levels=8, scale_factor=1.2, same_K=True):
+    """One keyframe pair of LocalMapping::CreateNewMapPoints with its matches, every input rounded through float32 as the reference
+    holds it.  EuRoC intrinsics, a baseline of 0.1-0.5 m, a relative rotation of a few degrees.  kind:
+      std      a sideways baseline near the origin; matches: 68 % true points 1.5-12 m deep, 15 % 60-400 m deep (these fail the
+               parallax gate), 10 % gross mismatches (a random pixel in keyframe 2), 7 % with octaves that disagree by five levels
+      far      the pair about 50 m from the origin, every depth chosen so that the parallax lies just inside the gate (1.03-1.6
+               times the gate's angle)
+      forward  a baseline along the optical axis; beside the std mix, a tenth of the matches is a point between the two cameras
+               (in front of keyframe 1, behind keyframe 2) and a tenth a close point seen at octave 7 in keyframe 1 and octave 0 in
+               keyframe 2 with a few pixels of error in keyframe 2 (passes keyframe 1's chi-square test, fails keyframe 2's)
+    Pixel noise: 0.7 pixels times the scale of the octave.  truth: kind [n] (index into TRI_KINDS), Xw [n,3]."""
+    r = np.random.default_rng(seed)
+    n = int(n_matches)
+    f32 = lambda a: np.asarray(a, dtype=np.float32)
+    K1 = f32(EUROC_K).astype(np.float64)
+    K2 = K1.copy() if same_K else f32(K1 * np.array([1.02, 0.99, 1.01, 0.97])).astype(np.float64)
+    scale, sigma2 = level_tables(n_levels, scale_factor)
+    R1 = so3_exp(r.normal(size=3) * 0.5)
+    C1 = r.uniform(-2, 2, 3)
+    if kind == "far":
+        u = r.normal(size=3)
+        C1 = 50.0 * u / np.linalg.norm(u)
+    b = r.uniform(0.1, 0.5)
+    a = r.uniform(0, 2 * np.pi)
+    d = np.array([0.2 * np.cos(a), 0.1 * np.sin(a), 1.0]) if kind == "forward" else np.array([np.cos(a), 0.3 * np.sin(a), r.uniform(-0.1, 0.1)])
+    d /= np.linalg.norm(d)
+    C2 = C1 + R1.T @ (b * d)
+    R2 = so3_exp(r.normal(size=3) * 0.03) @ R1
+
+    def pose(R, Cw):   # the float32 pose of a keyframe and the centre it derives from it (KeyFrame::SetPose)
+        R32 = f32(R)
+        t32 = f32(-(R32.astype(np.float64) @ Cw))
+        return R32.astype(np.float64), t32.astype(np.float64), (-(R32.T @ t32)).astype(np.float64)
+
+    Rcw1, tcw1, Ow1 = pose(R1, C1)
+    Rcw2, tcw2, Ow2 = pose(R2, C2)
+    probs = dict(std=[0.68, 0.15, 0.10, 0.07, 0, 0], far=[1, 0, 0, 0, 0, 0], forward=[0.50, 0.13, 0.10, 0.07, 0.10, 0.10])[kind]
+    kinds = r.choice(len(TRI_KINDS), size=n, p=probs)
+    oct1 = r.choice(n_levels, size=n, p=np.array([35, 25, 15, 10, 6, 4, 3, 2])[:n_levels] / np.array([35, 25, 15, 10, 6, 4, 3, 2])[:n_levels].sum())
+    oct2 = np.clip(oct1 + r.choice([-1, 0, 0, 0, 1], size=n), 0, n_levels - 1)
+    uv1 = np.stack([r.uniform(20, 732, n), r.uniform(20, 460, n)], axis=1)
+    depth = r.uniform(1.5, 12, n)
+    depth = np.where(kinds == 1, r.uniform(60, 400, n), depth)
+    if kind == "far":
+        depth = b * np.sqrt(1 - d[2] ** 2) / (np.arccos(0.9998) * r.uniform(1.03, 1.6, n))
+    m = kinds == 5
+    depth = np.where(m, r.uniform(1.2, 2.5, n), depth)
+    oct1 = np.where(m, n_levels - 1, oct1)
+    oct2 = np.where(m, 0, oct2)
+    m = kinds == 3
+    flip = r.random(n) < 0.5
+    oct1 = np.where(m, np.where(flip, r.integers(0, 2, n), n_levels - 1 - r.integers(0, 2, n)), oct1)
+    oct2 = np.where(m, np.where(flip, n_levels - 1 - r.integers(0, 2, n), r.integers(0, 2, n)), oct2)
+    oct1, oct2 = np.clip(oct1, 0, n_levels - 1), np.clip(oct2, 0, n_levels - 1)
+    Xc1 = depth[:, None] * np.stack([(uv1[:, 0] - K1[2]) / K1[0], (uv1[:, 1] - K1[3]) / K1[1], np.ones(n)], axis=1)
+    m = kinds == 4     # between the cameras, a third of the baseline off the axis
+    ph = r.uniform(0, 2 * np.pi, n)
+    Xc1 = np.where(m[:, None], b * np.stack([0.3 * np.cos(ph), 0.3 * np.sin(ph), r.uniform(0.35, 0.65, n)], axis=1), Xc1)
+    Xw = Xc1 @ R1 + C1
+    proj = lambda K, R, C, X: (lambda Y: np.stack([K[0] * Y[:, 0] / Y[:, 2] + K[2], K[1] * Y[:, 1] / Y[:, 2] + K[3]], axis=1))((X - C) @ R.T)
+    uv1 = proj(K1, R1, C1, Xw)
+    uv2 = proj(K2, R2, C2, Xw)
+    noise = np.where((kinds == 4)[:, None], 0.05, 0.7)
+    uv1 = uv1 + r.normal(size=(n, 2)) * noise * scale[oct1][:, None]
+    uv2 = uv2 + r.normal(size=(n, 2)) * noise * scale[oct2][:, None]
+    m = kinds == 5
+    ph = r.uniform(0, 2 * np.pi, n)
+    uv2 = np.where(m[:, None], uv2 + r.uniform(4, 7, n)[:, None] * np.stack([np.cos(ph), np.sin(ph)], axis=1), uv2)
+    m = kinds == 2
+    uv2 = np.where(m[:, None], np.stack([r.uniform(20, 732, n), r.uniform(20, 460, n)], axis=1), uv2)
+    return abi.TriangulateProblem(Rcw1=Rcw1, tcw1=tcw1, Ow1=Ow1, K1=K1, Rcw2=Rcw2, tcw2=tcw2, Ow2=Ow2, K2=K2, level_sigma2_1=sigma2, scale_1=scale,
+                                  level_sigma2_2=sigma2, scale_2=scale, uv1=f32(uv1).astype(np.float64), uv2=f32(uv2).astype(np.float64),
+                                  oct1=oct1, oct2=oct2, ratio_factor=float(np.float32(1.5) * np.float32(scale_factor)), cos_max=0.9998, chi2_th=5.991,
+                                  truth=dict(kind=kinds, Xw=Xw))
+
+
 # ---------------------------------------------------------------- essential graphs (vba_posegraph_optimize)
 def _s3_mul(a, b):
     return a[0] @ b[0], a[2] * (a[0] @ b[1]) + a[1], a[2] * b[2]

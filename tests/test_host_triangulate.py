@@ -1,0 +1,194 @@
+"""The host half of vba_triangulate (mc_slam_amd/csrc/vba_host_triangulate.h, vba_host_arena.h: refusals, arena offsets, the
+block-to-pair map, packing, write-back) under AddressSanitizer + UBSan (CPU only).  The harness (tests/host_triangulate_check.cpp)
+packs into heap blocks of exactly the arena's sizes; every expected offset below is restated from the sizes alone, and the packed
+regions are compared with the interleaving done in NumPy through an order-sensitive checksum."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from mc_slam_amd import synth
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DESC = np.dtype([("match0", "<i8"), ("lev0", "<i8"), ("i", "<i4", 4), ("c", "<f8", 41)])
+NT = 256
+
+
+@pytest.fixture(scope="module")
+def checker(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("ht") / "host_triangulate_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-pthread", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-fno-omit-frame-pointer", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "host_triangulate_check.cpp"),
+                           "-o", exe])
+    return exe
+
+
+def _run(checker, files):
+    r = subprocess.run([checker] + files, capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"), timeout=300)
+    assert r.returncode == 0 and "ERROR" not in r.stderr and "runtime error" not in r.stderr, (r.stdout[-500:], r.stderr[-2000:])
+    lines = r.stdout.strip().splitlines()
+    assert len(lines) == len(files), lines
+    return lines
+
+
+def _fields(line):
+    assert line.startswith("ok "), line
+    t = line.split()
+    return {k: int(v) for k, v in zip(t[1::2], t[2::2])}
+
+
+def up(b):
+    return (b + 255) // 256 * 256
+
+
+def checksum(*arrays):
+    """sum of (2 i + 1) * word i over the 64-bit words of the arrays' bytes (padded with zeros to whole words), mod 2^64"""
+    b = b"".join(np.ascontiguousarray(a).tobytes() for a in arrays)
+    w = np.frombuffer(b + b"\0" * (-len(b) % 8), dtype="<u8")
+    with np.errstate(over="ignore"):
+        return int((w * (2 * np.arange(len(w), dtype=np.uint64) + 1)).sum(dtype=np.uint64))
+
+
+def consts(p):
+    return np.concatenate([p.Rcw1.ravel(), p.tcw1, p.Ow1, p.K1, p.Rcw2.ravel(), p.tcw2, p.Ow2, p.K2, [p.ratio_factor, p.cos_max, p.chi2_th]])
+
+
+def _write(path, items):
+    """items: (problem, dict of n_matches / n_levels1 / n_levels2 / nulls overrides)"""
+    with open(path, "wb") as f:
+        f.write(np.array([len(items)], dtype="<i4").tobytes())
+        for p, o in items:
+            f.write(np.array([o.get("n_matches", p.n_matches), p.n_matches, o.get("n_levels1", p.n_levels1), p.n_levels1,
+                              o.get("n_levels2", p.n_levels2), p.n_levels2, o.get("nulls", 0)], dtype="<i4").tobytes())
+            f.write(consts(p).astype("<f8").tobytes())
+            for a in (p.level_sigma2_1, p.scale_1, p.level_sigma2_2, p.scale_2, p.uv1, p.uv2):
+                f.write(np.ascontiguousarray(a, dtype="<f8").tobytes())
+            f.write(p.oct1.tobytes())
+            f.write(p.oct2.tobytes())
+
+
+def _batch(shapes, seed0):
+    """shapes: (n_matches, n_levels) per pair; keyframe 2 gets one level more than keyframe 1 where that stays legal"""
+    out = []
+    for k, (n, nl) in enumerate(shapes):
+        p = synth.make_triangulate(seed0 + k, n, ("std", "forward", "far")[k % 3], n_levels=min(nl, 8))
+        if nl > 8:
+            s = 1.02 ** np.arange(nl)
+            p = p.copy(level_sigma2_1=s * s, scale_1=s)
+        s2 = 1.1 ** np.arange(min(p.n_levels1 + 1, 64))
+        out.append(p.copy(level_sigma2_2=s2 * s2, scale_2=s2, ratio_factor=1.8 + k, cos_max=0.9 + 0.001 * k))
+    return out
+
+
+SHAPES = [[(0, 8)], [(1, 1)], [(7, 8), (0, 3), (257, 64), (0, 8)], [(256, 8), (255, 2), (513, 8)],
+          [((k * 37) % 5 * (k % 3), 1 + k % 8) for k in range(300)]]   # 300: the threaded path, most pairs tiny, a third empty
+
+
+def test_offsets_packing_block_map_and_write_back(checker, tmp_path):
+    batches = [_batch(s, 100 * k) for k, s in enumerate(SHAPES)]
+    files = []
+    for k, ps in enumerate(batches):
+        files.append(str(tmp_path / ("b%d.tr" % k)))
+        _write(files[-1], [(p, {}) for p in ps])
+    for ps, line in zip(batches, _run(checker, files)):
+        f = _fields(line)
+        n, n_tot = len(ps), sum(p.n_matches for p in ps)
+        l_tot = sum(2 * (p.n_levels1 + p.n_levels2) for p in ps)
+        n_blocks = sum((p.n_matches + NT - 1) // NT for p in ps)
+        assert (f["n_tot"], f["l_tot"], f["n_blocks"]) == (n_tot, l_tot, n_blocks)
+        # the arena, restated from the sizes: five upload regions, two back regions, nothing device-only
+        o, offs = 0, []
+        for b in (DESC.itemsize * n, 8 * (n_blocks + 1), (l_tot + 1) * 8, (4 * n_tot + 4) * 8, 2 * n_tot + 2, (3 * n_tot + 3) * 8, n_tot + 1):
+            offs.append(o)
+            o += up(b)
+        assert [f[k] for k in ("desc", "blk", "lev", "uv", "oct", "x3d", "reason")] == offs
+        assert f["upload"] == offs[5] and f["back"] == o - offs[5] and f["total"] == o
+        # the packed regions
+        d = np.zeros(n, dtype=DESC)
+        blk = []
+        mo = lo = 0
+        for k, p in enumerate(ps):
+            d[k]["i"] = [p.n_matches, p.n_levels1, p.n_levels2, 0]
+            d[k]["match0"], d[k]["lev0"], d[k]["c"] = mo, lo, consts(p)
+            blk += [(k, first) for first in range(0, p.n_matches, NT)]
+            mo += p.n_matches; lo += 2 * (p.n_levels1 + p.n_levels2)
+        assert DESC.itemsize == 360
+        assert f["sum_desc"] == checksum(d)
+        assert len(blk) == n_blocks and f["sum_blk"] == checksum(np.array(blk, dtype="<i4").reshape(-1, 2))
+        assert f["sum_lev"] == checksum(*[np.concatenate([p.level_sigma2_1, p.scale_1, p.level_sigma2_2, p.scale_2]) for p in ps])
+        assert f["sum_uv"] == checksum(*[np.hstack([p.uv1, p.uv2]) for p in ps])
+        assert f["sum_oct"] == checksum(*[np.stack([p.oct1, p.oct2], axis=1) for p in ps])
+        # the write-back of the synthetic result: double j of x3d is j, match i of the call has reason i mod 9
+        reason = np.arange(n_tot) % 9
+        mo, acc = 0, 0
+        for k, p in enumerate(ps):
+            acc += int((reason[mo:mo + p.n_matches] == 0).sum()) * (k + 1)
+            mo += p.n_matches
+        assert f["got_acc"] == acc and f["got_status"] == 0
+        assert f["got_reason"] == int(reason.sum()) and f["got_x"] == sum(range(3 * n_tot))
+
+
+def _with(p, **kw):
+    """a copy of p with single entries of its arrays replaced: name=(index, value)"""
+    ch = {}
+    for k, (i, v) in kw.items():
+        a = getattr(p, k).copy()
+        a.reshape(-1)[i] = v
+        ch[k] = a
+    return p.copy(**ch)
+
+
+REFUSALS = [
+    (dict(n_matches=-1), "pair 1: negative n_matches"),
+    (dict(nulls=1), "pair 1: NULL array with n_matches > 0"),
+    (dict(nulls=2), "pair 1: NULL array with n_matches > 0"),
+    (dict(nulls=32), "pair 1: NULL array with n_matches > 0"),
+    (dict(nulls=4), "pair 1: NULL problem or result"),
+    (dict(nulls=16), "pair 1: NULL problem or result"),
+    (dict(nulls=8), "pair 1: NULL level table"),
+    (dict(n_levels1=0), "pair 1: n_levels outside 1 .. 64"),
+    (dict(n_levels2=65), "pair 1: n_levels outside 1 .. 64"),
+    (dict(n_levels2=-3), "pair 1: n_levels outside 1 .. 64"),
+    (dict(edit=dict(oct1=(3, 8))), "pair 1: match 3: octave >= n_levels"),
+    (dict(edit=dict(oct2=(6, 255))), "pair 1: match 6: octave >= n_levels"),
+    (dict(edit=dict(Rcw2=(4, np.nan))), "pair 1: a pose is not finite"),
+    (dict(edit=dict(tcw1=(2, np.inf))), "pair 1: a pose is not finite"),
+    (dict(edit=dict(Ow2=(0, -np.inf))), "pair 1: a pose is not finite"),
+    (dict(edit=dict(K1=(3, np.nan))), "pair 1: K1 / K2 is not finite"),
+    (dict(edit=dict(K2=(1, 0.0))), "pair 1: zero fx / fy"),
+    (dict(edit=dict(K1=(0, 0.0))), "pair 1: zero fx / fy"),
+    (dict(copy=dict(chi2_th=np.inf)), "pair 1: a threshold is not finite"),
+    (dict(copy=dict(cos_max=np.nan)), "pair 1: a threshold is not finite"),
+    (dict(copy=dict(ratio_factor=np.nan)), "pair 1: a threshold is not finite"),
+    (dict(edit=dict(level_sigma2_1=(7, np.nan))), "pair 1: a level table is not finite"),
+    (dict(edit=dict(scale_2=(0, np.inf))), "pair 1: a level table is not finite"),
+    (dict(edit=dict(scale_1=(2, 0.0))), "pair 1: level 2: scale <= 0"),
+    (dict(edit=dict(scale_2=(5, -1.2))), "pair 1: level 5: scale <= 0"),
+    (dict(edit=dict(uv1=(11, np.nan))), "pair 1: match 5: a pixel is not finite"),
+    (dict(edit=dict(uv2=(0, np.inf))), "pair 1: match 0: a pixel is not finite"),
+]
+
+
+@pytest.mark.parametrize("change,message", REFUSALS, ids=[m.split(": ", 1)[1].replace(" ", "_").replace("/", "") + str(k) for k, (_, m) in enumerate(REFUSALS)])
+def test_refusals(checker, tmp_path, change, message):
+    good, bad = synth.make_triangulate(40, 9), synth.make_triangulate(41, 9)
+    o = {k: v for k, v in change.items() if k in ("n_matches", "n_levels1", "n_levels2", "nulls")}
+    if "edit" in change:
+        bad = _with(bad, **change["edit"])
+    if "copy" in change:
+        bad = bad.copy(**change["copy"])
+    path = str(tmp_path / "r.tr")
+    _write(path, [(good, {}), (bad, o)])
+    assert _run(checker, [path]) == ["error " + message]
+
+
+def test_legal_edges(checker, tmp_path):
+    """a pair without matches needs no match arrays and no result arrays; 64 levels and octave 63 are legal"""
+    a = synth.make_triangulate(7, 0)
+    s = 1.01 ** np.arange(64)
+    b = synth.make_triangulate(8, 5).copy(level_sigma2_1=s * s, scale_1=s, oct1=np.array([63, 0, 1, 63, 7], dtype=np.uint8))
+    path = str(tmp_path / "e.tr")
+    _write(path, [(a, dict(nulls=1 | 2 | 32)), (b, {})])
+    f = _fields(_run(checker, [path])[0])
+    assert (f["n_tot"], f["n_blocks"], f["l_tot"]) == (5, 1, 2 * 16 + 2 * 72)
