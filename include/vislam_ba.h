@@ -123,7 +123,7 @@ typedef struct vba_profile {
     double total_ms;             /* first launch -> last launch of the run */
     double factor_flops;         /* FP64 flop the factorisation class executed on MFMA: 2*32^3 per tile product of the
                                     symbolic tile lists, per solve (structurally zero tiles are never touched) */
-    int64_t kernel_launches;     /* kernel launches the last vba_batch_run / vba_solve / vba_sim3_optimize / vba_sim3_ransac / vba_triangulate / vba_posegraph_optimize enqueued (filled with or without profiling) */
+    int64_t kernel_launches;     /* kernel launches the last vba_batch_run / vba_solve / vba_sim3_optimize / vba_sim3_ransac / vba_triangulate / vba_two_view_init (at most 2) / vba_posegraph_optimize enqueued (filled with or without profiling) */
 } vba_profile;
 
 /* One handle per host thread / GPU; owns device buffers and a stream.  Errors: nonzero return, message
@@ -178,7 +178,7 @@ int vba_batch_solve_b(void *handle, int32_t n_windows, vba_problem *const *inout
  *           every later one, those submitted afterwards included, with the same message: no GPU work starts for them (earlier
  *           tickets finish).  Waiting on an unknown or retired ticket returns -1.
  *   handle  while any ticket is submitted and not yet waited for, every synchronous entry point of the handle (vba_solve*,
- *           vba_batch_upload / run / download / solve*, vba_pose_optimize, vba_sim3_optimize, vba_sim3_ransac, vba_triangulate, vba_posegraph_optimize, vba_preintegrate, vba_set_profile,
+ *           vba_batch_upload / run / download / solve*, vba_pose_optimize, vba_sim3_optimize, vba_sim3_ransac, vba_triangulate, vba_two_view_init, vba_posegraph_optimize, vba_preintegrate, vba_set_profile,
  *           vba_batch_set_depth) returns -1 with "asynchronous batches pending: wait for them first"; afterwards the handle
  *           works synchronously as before.  vba_destroy finishes pending tickets (their results land) before it frees.
  *           Profiling (vba_set_profile) covers synchronous calls only.  One caller thread at a time, as everywhere. */
@@ -382,6 +382,74 @@ typedef struct vba_triangulate_result {
  * are required when n_matches > 0), n_levels outside 1 .. 64, an octave >= n_levels, a non-finite pose, K, level table, threshold
  * or pixel, a zero fx / fy, a level scale <= 0.  A match's outputs do not depend on where its pair stands in the batch. */
 int vba_triangulate(void *handle, int32_t n_pairs, vba_triangulate_problem *const *in, vba_triangulate_result *const *out);
+
+/* ---- monocular two-view initialisation ----
+ * Initializer::Initialize (src/Initializer.cpp:36-130) for a batch of frame pairs (frame 1 = reference, frame 2 = current): the
+ * normalisation of both frames' keypoints (:893-946, once per frame), for every 8-set the caller drew ComputeH21 (:263-305) and
+ * ComputeF21 (:320-356), CheckHomography (:362-461) and CheckFundamental (:465-545) over all matches, the scans (:179, :233), the
+ * model choice (:120-126), ReconstructH (:673-835) or ReconstructF (:555-667) with CheckRT (:950-1082) and Triangulate (:859-880).
+ * One problem is one frame pair; one call takes any number of pairs, ragged, in one kernel launch (one 256-lane workgroup per
+ * pair).  The library has no RNG: the caller draws the sets (mvSets, :78-101), as in vba_sim3_ransac.  FP64 on float32 inputs
+ * widened; the reference computes in CV_32F.  The chi-square gates are the reference's float
+ * variables widened: (double)5.991f in H, (double)3.841f (gate) and (double)5.991f (score) in F.
+ *   reason  0  success
+ *           1  the chosen model has no hypothesis with a score above 0 (the reference would read an empty cv::Mat)
+ *           2  d1 / d2 < 1.00001 || d2 / d3 < 1.00001 (:699)
+ *           3  the rule of :822 failed (ReconstructH)
+ *           4  maxGood < nMinGood || nsimilar > 1 (:613)
+ *           5  the parallax of the hypothesis with maxGood is not > min_parallax (:619-663)
+ * The scans run in hypothesis order with a strict > against a score that starts at 0.0: a tie keeps the earlier hypothesis, and a
+ * hypothesis whose score is NaN (a singular H21, whose inverse is not finite here) never becomes the best.  RH = SH / (SH + SF);
+ * the H path is taken when RH > 0.40, a NaN goes to F.
+ * Sign convention of the 3x3 SVDs: singular values descending; (u_i, v_i) are flipped together so that the
+ * largest-magnitude component of u_i (the first among equals) is positive; in DecomposeE, where the third singular value is zero,
+ * u_3 = u_1 x u_2 and v_3 = v_1 x v_2.  rt_good[] / rt_parallax[] are listed in the reference's order under this convention: F:
+ * (R1,t) (R2,t) (R1,-t) (R2,-t); H: the eight Faugeras hypotheses of :718-790.  ok, reason, R21, t21, x3d and triangulated do not
+ * depend on the convention. */
+typedef struct vba_two_view_problem {
+    int32_t n_keys1, n_keys2; /* mvKeys1.size(), mvKeys2.size() (:33, :42) */
+    const double *uv1;        /* [n_keys1][2] mvKeysUn[i].pt of ALL keypoints of frame 1: Normalize averages over all (:893-946) */
+    const double *uv2;        /* [n_keys2][2] the same of frame 2 */
+    int32_t n_matches;        /* mvMatches12.size() (:65) */
+    int32_t n_hyp;            /* mMaxIterations (200, :78) */
+    const int32_t *match;     /* [n_matches][2] mvMatches12 (:51-62): index in frame 1, index in frame 2; the first indices are distinct */
+    const int32_t *sets;      /* [n_hyp][8] mvSets (:78-101): match indices of every hypothesis */
+    double K[4];              /* fx fy cx cy (mK, :30) */
+    double sigma;             /* mSigma (1.0, :32) */
+    double min_parallax;      /* minParallax in degrees (1.0, :124) */
+    int32_t min_triangulated; /* minTriangulated (50, :124) */
+    int32_t pad;
+} vba_two_view_problem;
+
+typedef struct vba_two_view_result {
+    int32_t status;           /* VBA_OK */
+    int32_t ok;               /* the return value of Initialize */
+    int32_t model;            /* 1 = H (RH > 0.40), 2 = F */
+    int32_t reason;           /* the codes above */
+    int32_t best_hyp_h, best_hyp_f;    /* the hypotheses the scans kept (-1: none) */
+    int32_t n_inliers_h, n_inliers_f;  /* set flags of vbMatchesInliersH / F (0 without a best hypothesis) */
+    int32_t n_rt;             /* (R, t) hypotheses CheckRT ran on: 0 (reasons 1, 2), 4 (F) or 8 (H) */
+    int32_t best_rt;          /* the winner among them when ok, otherwise -1 */
+    int32_t rt_good[8];       /* nGood of every hypothesis (:1075) */
+    double score_h, score_f;  /* SH, SF (:105) */
+    double rh;                /* RH (:120) */
+    double H21[9], F21[9];    /* of the two best hypotheses, row-major, denormalised as in :172 and :228 (zeros without one) */
+    double rt_parallax[8];    /* parallax of every hypothesis in degrees (:1067-1079) */
+    double R21[9], t21[3];    /* written when ok */
+    uint8_t *inlier_h, *inlier_f; /* [n_matches] caller-allocated, required: vbMatchesInliersH / F (zeros without a best hypothesis) */
+    double *x3d;              /* [n_keys1][3] caller-allocated, required: vP3D, written when ok (zeros where no point was accepted) */
+    uint8_t *triangulated;    /* [n_keys1] caller-allocated, required: vbTriangulated, written when ok (1 only where cosParallax < 0.99998) */
+    double *hyp_score_h, *hyp_score_f; /* [n_hyp] caller-allocated or NULL: currentScore of every hypothesis */
+} vba_two_view_result;
+
+/* Synchronous, like vba_triangulate; -1 while asynchronous tickets are pending.  n_problems == 0 returns 0; n_hyp == 0 is legal
+ * (best_hyp_* = -1, ok = 0, reason = 1).  On failure (ok = 0) R21, t21, x3d and triangulated are left untouched.  A bad problem
+ * fails the whole call before any GPU work with "vba_two_view_init: pair K: <why>" through vba_last_error: a NULL problem or
+ * result, a negative count, a NULL array with a non-zero count (inlier_h / inlier_f are required when n_matches > 0, x3d and
+ * triangulated when n_keys1 > 0), n_matches < 8 with n_hyp > 0, a set index outside [0, n_matches), a match index outside its
+ * frame, a repeated first index, a non-finite pixel, K, sigma or min_parallax, a zero fx / fy / sigma.  A pair's outputs do not
+ * depend on where it stands in the batch. */
+int vba_two_view_init(void *handle, int32_t n_problems, vba_two_view_problem *const *in, vba_two_view_result *const *out);
 
 /* ---- essential-graph optimisation (Sim3 pose graph) ----
  * Optimizer::OptimizeEssentialGraph(Map*, KeyFrame* pLoopKF, KeyFrame* pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections,

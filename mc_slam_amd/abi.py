@@ -685,6 +685,127 @@ class TriangulateResultBuf:
         return TriangulateResult(self.s.status, self.s.n_accepted, self.x[:self.n].copy(), self.r[:self.n].copy())
 
 
+# ---- monocular two-view initialisation (include/vislam_ba.h: vba_two_view_problem / vba_two_view_result) ----
+class vba_two_view_problem(C.Structure):
+    _fields_ = [
+        ("n_keys1", C.c_int32), ("n_keys2", C.c_int32), ("uv1", _pd), ("uv2", _pd), ("n_matches", C.c_int32), ("n_hyp", C.c_int32),
+        ("match", _pi), ("sets", _pi), ("K", C.c_double * 4), ("sigma", C.c_double), ("min_parallax", C.c_double),
+        ("min_triangulated", C.c_int32), ("pad", C.c_int32),
+    ]
+
+
+class vba_two_view_result(C.Structure):
+    _fields_ = [
+        ("status", C.c_int32), ("ok", C.c_int32), ("model", C.c_int32), ("reason", C.c_int32), ("best_hyp_h", C.c_int32),
+        ("best_hyp_f", C.c_int32), ("n_inliers_h", C.c_int32), ("n_inliers_f", C.c_int32), ("n_rt", C.c_int32), ("best_rt", C.c_int32),
+        ("rt_good", C.c_int32 * 8), ("score_h", C.c_double), ("score_f", C.c_double), ("rh", C.c_double), ("H21", C.c_double * 9),
+        ("F21", C.c_double * 9), ("rt_parallax", C.c_double * 8), ("R21", C.c_double * 9), ("t21", C.c_double * 3),
+        ("inlier_h", _pu8), ("inlier_f", _pu8), ("x3d", _pd), ("triangulated", _pu8), ("hyp_score_h", _pd), ("hyp_score_f", _pd),
+    ]
+
+
+TV_MODEL_H, TV_MODEL_F = 1, 2
+
+
+@dataclass
+class TwoViewProblem:
+    """One frame pair of Initializer::Initialize (src/Initializer.cpp:36-130) as flat arrays: frame 1 = reference, frame 2 =
+    current, ALL their keypoints, the matches and the 8-sets the caller drew."""
+    uv1: np.ndarray                # [n_keys1,2]
+    uv2: np.ndarray                # [n_keys2,2]
+    match: np.ndarray              # [n_matches,2] int32
+    sets: np.ndarray               # [n_hyp,8] int32
+    K: np.ndarray                  # [4] fx fy cx cy
+    sigma: float = 1.0
+    min_parallax: float = 1.0
+    min_triangulated: int = 50
+    truth: dict = field(default_factory=dict)
+
+    def __post_init__(self):
+        self.uv1 = _f64(self.uv1, (-1, 2)); self.uv2 = _f64(self.uv2, (-1, 2))
+        self.match = np.ascontiguousarray(self.match, dtype=np.int32).reshape(-1, 2)
+        self.sets = np.ascontiguousarray(self.sets, dtype=np.int32).reshape(-1, 8)
+        self.K = _f64(self.K, (4,))
+
+    n_keys1 = property(lambda self: self.uv1.shape[0])
+    n_keys2 = property(lambda self: self.uv2.shape[0])
+    n_matches = property(lambda self: self.match.shape[0])
+    n_hyp = property(lambda self: self.sets.shape[0])
+
+    def copy(self, **changes):
+        import copy as _c
+        q = _c.copy(self)
+        for k, v in changes.items():
+            setattr(q, k, v)
+        q.__post_init__()
+        return q
+
+    def as_struct(self) -> vba_two_view_problem:
+        s = vba_two_view_problem()
+        s.n_keys1, s.n_keys2, s.n_matches, s.n_hyp = self.n_keys1, self.n_keys2, self.n_matches, self.n_hyp
+        s.uv1, s.uv2 = self.uv1.ctypes.data_as(_pd), self.uv2.ctypes.data_as(_pd)
+        s.match, s.sets = self.match.ctypes.data_as(_pi), self.sets.ctypes.data_as(_pi)
+        s.K[:] = self.K.tolist()
+        s.sigma, s.min_parallax, s.min_triangulated = float(self.sigma), float(self.min_parallax), int(self.min_triangulated)
+        return s
+
+
+@dataclass
+class TwoViewResult:
+    status: int
+    ok: int
+    model: int
+    reason: int
+    best_hyp_h: int
+    best_hyp_f: int
+    n_inliers_h: int
+    n_inliers_f: int
+    n_rt: int
+    best_rt: int
+    rt_good: np.ndarray             # [8]
+    score_h: float
+    score_f: float
+    rh: float
+    H21: np.ndarray                 # [3,3]
+    F21: np.ndarray                 # [3,3]
+    rt_parallax: np.ndarray         # [8]
+    R21: np.ndarray                 # [3,3]
+    t21: np.ndarray                 # [3]
+    inlier_h: np.ndarray            # [n_matches] uint8
+    inlier_f: np.ndarray
+    x3d: np.ndarray                 # [n_keys1,3]
+    triangulated: np.ndarray        # [n_keys1] uint8
+    hyp_score_h: Optional[np.ndarray]
+    hyp_score_f: Optional[np.ndarray]
+
+
+class TwoViewResultBuf:
+    """Caller-allocated result storage of one frame pair.  The buffers start from `fill` patterns so that a test can tell what
+    the library wrote."""
+
+    def __init__(self, p: TwoViewProblem, want_scores=True, fill=0):
+        self.n, self.nk, self.nh, self.want = p.n_matches, p.n_keys1, p.n_hyp, want_scores
+        self.ih = np.full(max(self.n, 1), fill, dtype=np.uint8)
+        self.jf = np.full(max(self.n, 1), fill, dtype=np.uint8)
+        self.x = np.full((max(self.nk, 1), 3), float(fill))
+        self.tr = np.full(max(self.nk, 1), fill, dtype=np.uint8)
+        self.sh = np.full(max(self.nh, 1), float(fill))
+        self.sf = np.full(max(self.nh, 1), float(fill))
+        self.s = vba_two_view_result()
+        self.s.inlier_h, self.s.inlier_f = self.ih.ctypes.data_as(_pu8), self.jf.ctypes.data_as(_pu8)
+        self.s.x3d, self.s.triangulated = self.x.ctypes.data_as(_pd), self.tr.ctypes.data_as(_pu8)
+        if want_scores:
+            self.s.hyp_score_h, self.s.hyp_score_f = self.sh.ctypes.data_as(_pd), self.sf.ctypes.data_as(_pd)
+
+    def get(self) -> TwoViewResult:
+        s = self.s
+        a = lambda v, shape=None: np.array(v[:]).reshape(shape) if shape else np.array(v[:])
+        return TwoViewResult(s.status, s.ok, s.model, s.reason, s.best_hyp_h, s.best_hyp_f, s.n_inliers_h, s.n_inliers_f, s.n_rt, s.best_rt,
+                             a(s.rt_good), s.score_h, s.score_f, s.rh, a(s.H21, (3, 3)), a(s.F21, (3, 3)), a(s.rt_parallax), a(s.R21, (3, 3)),
+                             a(s.t21), self.ih[:self.n].copy(), self.jf[:self.n].copy(), self.x[:self.nk].copy(), self.tr[:self.nk].copy(),
+                             self.sh[:self.nh].copy() if self.want else None, self.sf[:self.nh].copy() if self.want else None)
+
+
 # ---- essential-graph optimisation (include/vislam_ba.h: vba_posegraph_problem / vba_posegraph_result) ----
 class vba_posegraph_problem(C.Structure):
     _fields_ = [

@@ -1,13 +1,14 @@
 // vba_host_small.h -- host side of the library, part 5: the drivers of the small-problem entry points (vba_preintegrate,
-// vba_pose_optimize, vba_sim3_optimize, vba_sim3_ransac, vba_triangulate, vba_posegraph_optimize).  Each lays its arena out once (vba_host_arena.h), packs the
+// vba_pose_optimize, vba_sim3_optimize, vba_sim3_ransac, vba_triangulate, vba_two_view_init, vba_posegraph_optimize).  Each lays its arena out once (vba_host_arena.h), packs the
 // pinned staging block with the plain-C++ half of its topic (vba_host_pose.h, vba_host_sim3.h, vba_host_sim3_ransac.h,
-// vba_host_triangulate.h, vba_host_posegraph.h), and does one
+// vba_host_triangulate.h, vba_host_two_view.h, vba_host_posegraph.h), and does one
 // H2D copy, one or two launches and one D2H copy on the handle's stream.  No entry point shares its arena with another.
 #pragma once
 #include "vba_host_pose.h"
 #include "vba_host_sim3.h"
 #include "vba_host_sim3_ransac.h"
 #include "vba_host_triangulate.h"
+#include "vba_host_two_view.h"
 #include "vba_host_posegraph.h"
 
 namespace {
@@ -184,6 +185,46 @@ int triangulate(Handle* h, int32_t n_pairs, vba_triangulate_problem* const* in, 
     const double* x3d = at<double>(hout, A.L.in_back(A.x3d));
     const unsigned char* reason = at<unsigned char>(hout, A.L.in_back(A.reason));
     for (int f = 0; f < n_pairs; f++) vba_host::unpack_triangulate(out[f], desc[f], x3d, reason);
+    return 0;
+}
+
+// Initializer::Initialize (src/Initializer.cpp:36-130) behind the drawing of the 8-sets, for a batch of frame pairs: k_two_view
+// runs one workgroup per pair, one launch
+int two_view_init(Handle* h, int32_t n_problems, vba_two_view_problem* const* in, vba_two_view_result* const* out) {
+    if (n_problems < 0 || (n_problems > 0 && (!in || !out))) return fail(h, "vba_two_view_init: bad arguments");
+    if (n_problems == 0) return 0;
+    vba_host::TwoViewTotals T;
+    std::string err;
+    if (vba_host::check_two_view(n_problems, in, out, T, err)) return fail(h, "vba_two_view_init: " + err);
+    HIPCHK(h, hipSetDevice(h->device));
+    const vba_host::TwoViewArena A(n_problems, T);
+    const size_t b_back = A.download_bytes(T.want_scores);
+    HIPCHK(h, h->tv.ensure(A.L, b_back));
+    void *hin = h->tv.in.p, *hout = h->tv.out.p, *base = h->tv.dev.p;
+    TvDesc* desc = at<TvDesc>(hin, A.desc);
+    vba_host::describe_two_view(n_problems, in, desc);
+    host_parallel_for(h, n_problems, small_pack_threads(n_problems), [&](int f) {
+        vba_host::pack_two_view(in[f], desc[f], at<double>(hin, A.uv1), at<double>(hin, A.uv2), at<int32_t>(hin, A.match), at<int32_t>(hin, A.sets));
+    });
+    TvBatch B;
+    B.desc = at<TvDesc>(base, A.desc); B.uv1 = at<double>(base, A.uv1); B.uv2 = at<double>(base, A.uv2); B.match = at<int>(base, A.match);
+    B.sets = at<int>(base, A.sets); B.out = at<TvOut>(base, A.out); B.flag_h = at<unsigned char>(base, A.flag_h);
+    B.flag_f = at<unsigned char>(base, A.flag_f); B.tri = at<unsigned char>(base, A.tri); B.x3d = at<double>(base, A.x3d);
+    B.score_h = at<double>(base, A.score_h); B.score_f = at<double>(base, A.score_f); B.hyp_h = at<double>(base, A.hyp_h);
+    B.hyp_f = at<double>(base, A.hyp_f); B.rt_state = at<unsigned char>(base, A.rt_state); B.rt_cos = at<double>(base, A.rt_cos);
+    B.rt_x = at<double>(base, A.rt_x);
+    const long long launch0 = h->n_launch;
+    HIPCHK(h, hipMemcpyAsync(base, hin, A.L.upload_bytes(), hipMemcpyHostToDevice, h->stream));
+    VBA_LAUNCH(k_two_view, dim3(n_problems), dim3(TV_NT), 0, h->stream, B);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(hout, B.out, b_back, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->prof.kernel_launches = h->n_launch - launch0;
+    const TvOut* res = at<TvOut>(hout, A.L.in_back(A.out));
+    auto u8 = [&](size_t o) { return at<unsigned char>(hout, A.L.in_back(o)); };
+    auto f64 = [&](size_t o) { return at<double>(hout, A.L.in_back(o)); };
+    for (int f = 0; f < n_problems; f++)
+        vba_host::unpack_two_view(out[f], desc[f], res[f], u8(A.flag_h), u8(A.flag_f), u8(A.tri), f64(A.x3d), f64(A.score_h), f64(A.score_f));
     return 0;
 }
 

@@ -157,6 +157,22 @@ struct TriBlock {
     int pair, first;           // the pair of a workgroup and its first match inside the pair
 };
 static_assert(sizeof(TriDesc) == 360 && sizeof(TriBlock) == 8, "scripts/triangulate_bench.py derives the copied bytes from these sizes");
+// vba_two_view_init (vba_two_view.h)
+struct TvDesc {
+    long long key1_0, key2_0, match0, hyp0;   // offsets of the pair's keypoints, matches and hypotheses in the concatenated arrays
+    int n_keys1, n_keys2, n_matches, n_hyp;
+    int min_triangulated, pad;
+    double K[4], sigma, min_parallax;
+};
+struct TvOut {
+    int status, ok, model, reason, best_hyp_h, best_hyp_f, n_inliers_h, n_inliers_f, n_rt, best_rt;
+    int rt_good[8];
+    double score_h, score_f, rh, H21[9], F21[9], rt_parallax[8], R21[9], t21[3];
+};
+#define VBA_TV_HYP_H 18        // doubles per H hypothesis record (device only): H21 (9) H12 (9)
+#define VBA_TV_HYP_F 9         // doubles per F hypothesis record (device only): F21
+#define VBA_TV_RT 8            // most (R, t) hypotheses of a pair: the per-(hypothesis, match) regions hold this many per match
+static_assert(sizeof(TvDesc) == 104 && sizeof(TvOut) == 400, "scripts/two_view_bench.py derives the copied bytes from these sizes");
 // vba_posegraph_optimize (vba_posegraph.h)
 struct PgDesc {
     int nv, ne, nf, npair;

@@ -8,6 +8,7 @@
 
 #include "Optimizer.h"
 #include "Sim3Solver.h"
+#include "Initializer.h"
 
 using namespace ORB_SLAM2;
 
@@ -409,6 +410,44 @@ void fc_sim3solver_estimate(void* s, float* R9, float* t3, float* scale) {
     std::memcpy(R9, R.data(), 36);
     std::memcpy(t3, t.data(), 12);
     *scale = S->GetEstimatedScale();
+}
+// ---- monocular map initialisation (Initializer.h) ----
+// Initializer(ReferenceFrame, sigma, iterations) over a Frame made of K (fx fy cx cy) and n keypoints uv [n][2]
+void* fc_initializer_create(const float* K, const float* uv, int n, float sigma, int iterations) {
+    Frame F;
+    F.fx = K[0]; F.fy = K[1]; F.cx = K[2]; F.cy = K[3];
+    F.N = n;
+    F.mvKeysUn.resize((size_t)n);
+    for (int i = 0; i < n; i++) { F.mvKeysUn[i].pt.x = uv[2 * i]; F.mvKeysUn[i].pt.y = uv[2 * i + 1]; }
+    return new Initializer(F, sigma, iterations);
+}
+void fc_initializer_destroy(void* s) { delete reinterpret_cast<Initializer*>(s); }
+// Initialize(CurrentFrame, vMatches12 [n keypoints of the reference frame], ...): returns its return value; R21 [9], t21 [3],
+// vP3D [n1][3] and vbTriangulated [n1] are written on success only; sets [iterations][8]: mvSets of the call; info [10]: ok model
+// reason best_hyp_h best_hyp_f n_inliers_h n_inliers_f n_rt best_rt n_matches of the backend call
+int fc_initializer_initialize(void* s, const float* uv2, int n2, const int* vMatches12, int n1, float* R21, float* t21, float* vP3D,
+                              uint8_t* vbTriangulated, int32_t* sets, int32_t* info) {
+    Initializer* I = reinterpret_cast<Initializer*>(s);
+    Frame F;
+    F.N = n2;
+    F.mvKeysUn.resize((size_t)n2);
+    for (int i = 0; i < n2; i++) { F.mvKeysUn[i].pt.x = uv2[2 * i]; F.mvKeysUn[i].pt.y = uv2[2 * i + 1]; }
+    std::array<float, 9> R{};
+    std::array<float, 3> t{};
+    std::vector<Point3f> P3D;
+    std::vector<bool> tri;
+    const bool ok = I->Initialize(F, std::vector<int>(vMatches12, vMatches12 + n1), R, t, P3D, tri);
+    if (ok) {
+        std::memcpy(R21, R.data(), 36);
+        std::memcpy(t21, t.data(), 12);
+        for (size_t i = 0; i < P3D.size(); i++) { vP3D[3 * i] = P3D[i].x; vP3D[3 * i + 1] = P3D[i].y; vP3D[3 * i + 2] = P3D[i].z; vbTriangulated[i] = tri[i] ? 1 : 0; }
+    }
+    for (size_t it = 0; it < I->mvSets.size(); it++)
+        for (int j = 0; j < 8; j++) sets[8 * it + j] = (int32_t)I->mvSets[it][j];
+    const vba_two_view_result& L = I->mLast;
+    const int32_t v[10] = {L.ok, L.model, L.reason, L.best_hyp_h, L.best_hyp_f, L.n_inliers_h, L.n_inliers_f, L.n_rt, L.best_rt, (int32_t)I->mvMatches12.size()};
+    std::memcpy(info, v, sizeof v);
+    return ok ? 1 : 0;
 }
 // ---- new map points (LocalMapping::CreateNewMapPoints, LocalMapping.cpp) ----
 // The matcher is a table: neighbour i of `neigh` gets matches [begin[i], begin[i + 1]) of `matches` ([..][2] keypoint indices in kf /

@@ -667,6 +667,63 @@ def make_triangulate(seed, n_matches, kind="std", n_levels=8, scale_factor=1.2, 
 
 
 # ---------------------------------------------------------------- essential graphs (vba_posegraph_optimize)
+TWO_VIEW_KINDS = ("general", "plane", "rotation")
+
+
+def draw_sets(seed, n_matches, n_hyp):
+    """n_hyp sets of eight distinct match indices (mvSets, src/Initializer.cpp:78-101, drawn with NumPy's generator); where
+    n_matches allows it no two sets hold the same eight matches, so that no two hypotheses fit the same data"""
+    rng = np.random.default_rng(seed)
+    sets, seen = [], set()
+    for _ in range(n_hyp):
+        for attempt in range(50):
+            s = rng.choice(n_matches, 8, replace=False)
+            key = tuple(sorted(s.tolist()))
+            if key not in seen:
+                break
+        seen.add(key)
+        sets.append(s)
+    return np.array(sets, dtype=np.int32).reshape(-1, 8)
+
+
+def make_two_view(seed, n_matches, n_hyp, kind="general", baseline=0.5, noise=0.3, outlier_frac=0.0, far_frac=0.0, extra_keys=(37, 53),
+                  min_triangulated=50, min_parallax=1.0, rot_deg=3.0, float32=True):
+    """One frame pair of Initializer::Initialize: n_matches points of a scene seen from frame 1 (the origin) and frame 2 (R21, t21),
+    pixel noise of `noise` pixels, a share of wrong matches, a share of points some hundred metres away (parallax below the
+    0.99998 cosine), unmatched keypoints in both frames, everything through float32 (float32=False: exact doubles, for known-answer checks).  kind: 'general' (a box 4-10 m deep),
+    'plane' (a tilted plane 6 m away), 'rotation' (the general scene, t = 0).  truth: R21, t21 (unit), the wrong matches."""
+    rng = np.random.default_rng(seed)
+    K = np.array([500.0, 480.0, 320.0, 240.0])
+    n = n_matches
+    z = rng.uniform(4.0, 10.0, n)
+    if kind == "plane":
+        a, b = rng.uniform(-0.3, 0.3, 2)
+    xy = rng.uniform(-0.45, 0.45, (n, 2))
+    if kind == "plane":
+        z = 6.0 / (1.0 - a * xy[:, 0] - b * xy[:, 1])                  # z = 6 + a x + b y with x = xy z
+    far = rng.random(n) < far_frac
+    z = np.where(far, rng.uniform(300.0, 600.0, n), z)
+    X = np.column_stack([xy[:, 0] * z, xy[:, 1] * z, z])
+    R = so3_exp(np.deg2rad(rot_deg) * rng.normal(size=3) / np.sqrt(3.0))
+    d = rng.normal(size=3) * np.array([1.0, 0.6, 0.25])
+    d /= np.linalg.norm(d)
+    t = np.zeros(3) if kind == "rotation" else baseline * d
+    Y = X @ R.T + t
+    proj = lambda P: np.column_stack([K[0] * P[:, 0] / P[:, 2] + K[2], K[1] * P[:, 1] / P[:, 2] + K[3]])
+    p1 = proj(X) + noise * rng.normal(size=(n, 2))
+    p2 = proj(Y) + noise * rng.normal(size=(n, 2))
+    wrong = rng.random(n) < outlier_frac
+    p2[wrong] = np.column_stack([rng.uniform(0, 640, wrong.sum()), rng.uniform(0, 480, wrong.sum())])
+    nk1, nk2 = n + extra_keys[0], n + extra_keys[1]
+    i1, i2 = np.sort(rng.permutation(nk1)[:n]), rng.permutation(nk2)[:n]   # mvMatches12 ascends in the first index (:51-62)
+    uv1 = np.column_stack([rng.uniform(0, 640, nk1), rng.uniform(0, 480, nk1)])
+    uv2 = np.column_stack([rng.uniform(0, 640, nk2), rng.uniform(0, 480, nk2)])
+    uv1[i1], uv2[i2] = p1, p2
+    f32 = (lambda a: np.asarray(a, dtype=np.float32).astype(np.float64)) if float32 else (lambda a: np.asarray(a, dtype=np.float64))
+    return abi.TwoViewProblem(f32(uv1), f32(uv2), np.column_stack([i1, i2]), draw_sets(seed + 7919, n, n_hyp), f32(K), 1.0, min_parallax,
+                              min_triangulated, truth=dict(R21=R, t21=d if kind != "rotation" else t, wrong=wrong, far=far))
+
+
 def _s3_mul(a, b):
     return a[0] @ b[0], a[2] * (a[0] @ b[1]) + a[1], a[2] * b[2]
 

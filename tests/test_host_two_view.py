@@ -1,0 +1,208 @@
+"""The host half of vba_two_view_init (mc_slam_amd/csrc/vba_host_two_view.h, vba_host_arena.h: refusals, arena offsets, packing,
+write-back) under AddressSanitizer + UBSan (CPU only).  The harness (tests/host_two_view_check.cpp) is a stand-alone program: it
+packs into heap blocks of exactly the arena's sizes; every expected offset below is restated from the sizes alone, and the packed
+regions are compared with NumPy's concatenation through an order-sensitive checksum."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from mc_slam_amd import synth
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DESC = np.dtype([("off", "<i8", 4), ("i", "<i4", 6), ("c", "<f8", 6)])
+OUT_BYTES = 400
+
+
+@pytest.fixture(scope="module")
+def checker(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("htv") / "host_two_view_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-pthread", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-fno-omit-frame-pointer", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "host_two_view_check.cpp"),
+                           "-o", exe])
+    return exe
+
+
+def _run(checker, files):
+    r = subprocess.run([checker] + files, capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"), timeout=300)
+    assert r.returncode == 0 and "ERROR" not in r.stderr and "runtime error" not in r.stderr, (r.stdout[-500:], r.stderr[-2000:])
+    lines = r.stdout.strip().splitlines()
+    assert len(lines) == len(files), lines
+    return lines
+
+
+def _fields(line):
+    assert line.startswith("ok "), line
+    t = line.split()
+    return {k: float(v) if "." in v else int(v) for k, v in zip(t[1::2], t[2::2])}
+
+
+def up(b):
+    return (b + 255) // 256 * 256
+
+
+def checksum(*arrays):
+    """sum of (2 i + 1) * word i over the 64-bit words of the arrays' bytes (padded with zeros to whole words), mod 2^64"""
+    b = b"".join(np.ascontiguousarray(a).tobytes() for a in arrays)
+    w = np.frombuffer(b + b"\0" * (-len(b) % 8), dtype="<u8")
+    with np.errstate(over="ignore"):
+        return int((w * (2 * np.arange(len(w), dtype=np.uint64) + 1)).sum(dtype=np.uint64))
+
+
+def _write(path, items):
+    """items: (problem, dict of n_keys1 / n_keys2 / n_matches / n_hyp / nulls overrides)"""
+    with open(path, "wb") as f:
+        f.write(np.array([len(items)], dtype="<i4").tobytes())
+        for p, o in items:
+            f.write(np.array([o.get("n_keys1", p.n_keys1), p.n_keys1, o.get("n_keys2", p.n_keys2), p.n_keys2, o.get("n_matches", p.n_matches), p.n_matches,
+                              o.get("n_hyp", p.n_hyp), p.n_hyp, o.get("nulls", 0), p.min_triangulated], dtype="<i4").tobytes())
+            f.write(np.concatenate([p.K, [p.sigma, p.min_parallax]]).astype("<f8").tobytes())
+            for a in (p.uv1, p.uv2):
+                f.write(np.ascontiguousarray(a, dtype="<f8").tobytes())
+            for a in (p.match, p.sets):
+                f.write(np.ascontiguousarray(a, dtype="<i4").tobytes())
+
+
+def _batch(shapes, seed0):
+    """shapes: (n_matches, n_hyp) per pair; sigma, min_parallax and min_triangulated differ from pair to pair"""
+    out = []
+    for k, (n, nh) in enumerate(shapes):
+        p = synth.make_two_view(seed0 + k, max(n, 8), nh, ("general", "plane", "rotation")[k % 3], extra_keys=(k % 5, 1 + k % 7))
+        if n < 8:   # legal only without hypotheses
+            p = p.copy(match=p.match[:n])
+        out.append(p.copy(sigma=1.0 + 0.25 * k, min_parallax=0.5 + k, min_triangulated=20 + k))
+    return out
+
+
+SHAPES = [[(0, 0)], [(8, 1)], [(9, 3), (0, 0), (257, 17), (3, 0)], [(256, 16), (64, 0), (300, 200)],
+          [(8 + (k * 37) % 5, (k % 3) * (k % 4)) for k in range(300)]]   # 300: the threaded path, most pairs tiny, many without hypotheses
+
+
+@pytest.mark.parametrize("nulls", [0, 128], ids=["scores", "no-scores"])
+def test_offsets_packing_and_write_back(checker, tmp_path, nulls):
+    batches = [_batch(s, 100 * k) for k, s in enumerate(SHAPES)]
+    files = []
+    for k, ps in enumerate(batches):
+        files.append(str(tmp_path / ("b%d.tv" % k)))
+        _write(files[-1], [(p, dict(nulls=nulls)) for p in ps])
+    for ps, line in zip(batches, _run(checker, files)):
+        f = _fields(line)
+        n = len(ps)
+        k1, k2, m, h = (sum(getattr(p, a) for p in ps) for a in ("n_keys1", "n_keys2", "n_matches", "n_hyp"))
+        assert (f["k1"], f["k2"], f["m"], f["h"], f["want"]) == (k1, k2, m, h, int(nulls == 0))
+        # the arena, restated from the sizes: five upload regions, seven back regions, five device-only regions
+        o, offs = 0, []
+        for b in (DESC.itemsize * n, (2 * k1 + 2) * 8, (2 * k2 + 2) * 8, (2 * m + 2) * 4, (8 * h + 8) * 4,
+                  OUT_BYTES * n, m + 1, m + 1, k1 + 1, (3 * k1 + 3) * 8, (h + 1) * 8, (h + 1) * 8,
+                  (h + 1) * 18 * 8, (h + 1) * 9 * 8, 8 * m + 1, (8 * m + 1) * 8, (8 * m + 1) * 24):
+            offs.append(o)
+            o += up(b)
+        names = ("desc", "uv1", "uv2", "match", "sets", "out", "flag_h", "flag_f", "tri", "x3d", "score_h", "score_f", "hyp_h", "hyp_f", "rt_state", "rt_cos", "rt_x")
+        assert [f[k] for k in names] == offs
+        assert f["upload"] == offs[5] and f["back"] == offs[12] - offs[5] and f["total"] == o
+        assert f["down"] == (f["back"] if nulls == 0 else offs[10] - offs[5])       # the score regions stay on the device unless asked for
+        # the packed regions
+        d = np.zeros(n, dtype=DESC)
+        o1 = o2 = om = oh = 0
+        for k, p in enumerate(ps):
+            d[k]["off"] = [o1, o2, om, oh]
+            d[k]["i"] = [p.n_keys1, p.n_keys2, p.n_matches, p.n_hyp, p.min_triangulated, 0]
+            d[k]["c"] = np.concatenate([p.K, [p.sigma, p.min_parallax]])
+            o1 += p.n_keys1; o2 += p.n_keys2; om += p.n_matches; oh += p.n_hyp
+        assert DESC.itemsize == 104
+        assert f["sum_desc"] == checksum(d)
+        assert f["sum_uv1"] == checksum(*[p.uv1 for p in ps]) and f["sum_uv2"] == checksum(*[p.uv2 for p in ps])
+        assert f["sum_match"] == checksum(*[p.match for p in ps]) and f["sum_sets"] == checksum(*[p.sets for p in ps])
+        # the write-back of the synthetic result (see the harness): pair k is ok when k is odd, and only then gets R21, t21, x3d, triangulated
+        ks = np.arange(n)
+        assert f["got_ok"] == int((ks % 2).sum())
+        assert f["got_head"] == int((0 + 1 + ks % 2 + ks % 6 + ks - 1 + 2 * ks + 3 * ks + 4 + 3 + ks + 7).sum())
+        assert f["got_mat"] == pytest.approx(n * (8 - 8 + 3.5 + 1.5 + 2.5 + 0.375))
+        fh, ff, tri, x = np.arange(m) % 2, (np.arange(m) % 3 == 0).astype(int), np.arange(k1) % 2, np.arange(3 * k1, dtype=float)
+        e_fh = e_ff = e_tri = 0
+        e_x = e_R = e_sc = 0.0
+        o1 = om = oh = 0
+        for k, p in enumerate(ps):
+            e_fh += int(fh[om:om + p.n_matches].sum()); e_ff += int(ff[om:om + p.n_matches].sum())
+            if k % 2:
+                e_tri += int(tri[o1:o1 + p.n_keys1].sum()); e_x += x[3 * o1:3 * (o1 + p.n_keys1)].sum(); e_R += 10 + 18 + 22
+            else:   # left untouched: the harness filled them with 7
+                e_tri += 7 * p.n_keys1; e_x += 21.0 * p.n_keys1; e_R += 7 + 7 + 0
+            if nulls == 0:
+                e_sc += 3.0 * np.arange(oh, oh + p.n_hyp).sum()
+            o1 += p.n_keys1; om += p.n_matches; oh += p.n_hyp
+        assert (f["got_fh"], f["got_ff"], f["got_tri"]) == (e_fh, e_ff, e_tri)
+        assert (f["got_x"], f["got_R"], f["got_sc"]) == (e_x, e_R, e_sc)
+
+
+def _with(p, **kw):
+    """a copy of p with single entries of its arrays replaced: name=(index, value)"""
+    ch = {}
+    for k, (i, v) in kw.items():
+        a = getattr(p, k).copy()
+        a.reshape(-1)[i] = v
+        ch[k] = a
+    return p.copy(**ch)
+
+
+REFUSALS = [
+    (dict(n_keys1=-1), "pair 1: negative n_keys"),
+    (dict(n_keys2=-5), "pair 1: negative n_keys"),
+    (dict(n_matches=-1), "pair 1: negative n_matches"),
+    (dict(n_hyp=-2), "pair 1: negative n_hyp"),
+    (dict(nulls=4), "pair 1: NULL problem or result"),
+    (dict(nulls=16), "pair 1: NULL problem or result"),
+    (dict(nulls=512), "pair 1: NULL array with n_keys > 0"),
+    (dict(nulls=1), "pair 1: NULL array with n_keys > 0"),
+    (dict(nulls=32), "pair 1: NULL array with n_keys > 0"),
+    (dict(nulls=256), "pair 1: NULL array with n_keys > 0"),
+    (dict(nulls=64), "pair 1: NULL array with n_matches > 0"),
+    (dict(nulls=2), "pair 1: NULL array with n_matches > 0"),
+    (dict(nulls=1024), "pair 1: NULL array with n_matches > 0"),
+    (dict(nulls=8), "pair 1: NULL sets with n_hyp > 0"),
+    (dict(n_matches=7), "pair 1: n_matches < 8 with n_hyp > 0"),
+    (dict(edit=dict(sets=(8 * 3 + 2, 40))), "pair 1: hypothesis 3: set index out of range"),
+    (dict(edit=dict(sets=(0, -1))), "pair 1: hypothesis 0: set index out of range"),
+    (dict(edit=dict(match=(2 * 6, 60))), "pair 1: match 6: index outside its frame"),
+    (dict(edit=dict(match=(2 * 6 + 1, -1))), "pair 1: match 6: index outside its frame"),
+    (dict(edit=dict(match=(2 * 39 + 1, 71))), "pair 1: match 39: index outside its frame"),
+    (dict(repeat=(9, 4)), "pair 1: match 9: repeated first index"),
+    (dict(edit=dict(uv1=(11, np.nan))), "pair 1: keypoint 5 of frame 1: a pixel is not finite"),
+    (dict(edit=dict(uv2=(0, np.inf))), "pair 1: keypoint 0 of frame 2: a pixel is not finite"),
+    (dict(edit=dict(K=(3, np.nan))), "pair 1: K is not finite"),
+    (dict(edit=dict(K=(1, 0.0))), "pair 1: zero fx / fy"),
+    (dict(edit=dict(K=(0, 0.0))), "pair 1: zero fx / fy"),
+    (dict(copy=dict(sigma=np.inf)), "pair 1: sigma / min_parallax is not finite"),
+    (dict(copy=dict(min_parallax=np.nan)), "pair 1: sigma / min_parallax is not finite"),
+    (dict(copy=dict(sigma=0.0)), "pair 1: zero sigma"),
+]
+
+
+@pytest.mark.parametrize("change,message", REFUSALS, ids=[m.split(": ", 1)[1].replace(" ", "_").replace("/", "").replace(">", "gt").replace("<", "lt") + str(k) for k, (_, m) in enumerate(REFUSALS)])
+def test_refusals(checker, tmp_path, change, message):
+    good = synth.make_two_view(40, 40, 5, extra_keys=(20, 31))
+    bad = synth.make_two_view(41, 40, 5, extra_keys=(20, 31))       # 60 / 71 keypoints
+    o = {k: v for k, v in change.items() if k in ("n_keys1", "n_keys2", "n_matches", "n_hyp", "nulls")}
+    if "edit" in change:
+        bad = _with(bad, **change["edit"])
+    if "repeat" in change:
+        i, j = change["repeat"]
+        bad = _with(bad, match=(2 * i, bad.match[j, 0]))
+    if "copy" in change:
+        bad = bad.copy(**change["copy"])
+    path = str(tmp_path / "r.tv")
+    _write(path, [(good, {}), (bad, o)])
+    assert _run(checker, [path]) == ["error " + message]
+
+
+def test_legal_edges(checker, tmp_path):
+    """a pair without hypotheses may have fewer than eight matches, none at all, and no keypoints; then it needs no arrays"""
+    a = synth.make_two_view(7, 8, 0).copy(match=np.zeros((0, 2), dtype=np.int32))
+    b = synth.make_two_view(8, 8, 0)
+    c = b.copy(match=b.match[:5])
+    e = a.copy(uv1=np.zeros((0, 2)), uv2=np.zeros((0, 2)))
+    path = str(tmp_path / "e.tv")
+    _write(path, [(a, dict(nulls=2 | 64 | 1024 | 8 | 128)), (b, dict(nulls=8)), (c, {}), (e, dict(nulls=1 | 2 | 8 | 32 | 64 | 128 | 256 | 512 | 1024))])
+    f = _fields(_run(checker, [path])[0])
+    assert (f["k1"], f["m"], f["h"]) == (a.n_keys1 + b.n_keys1 + c.n_keys1, 13, 0)
