@@ -123,7 +123,7 @@ typedef struct vba_profile {
     double total_ms;             /* first launch -> last launch of the run */
     double factor_flops;         /* FP64 flop the factorisation class executed on MFMA: 2*32^3 per tile product of the
                                     symbolic tile lists, per solve (structurally zero tiles are never touched) */
-    int64_t kernel_launches;     /* kernel launches the last vba_batch_run / vba_solve / vba_sim3_optimize / vba_sim3_ransac / vba_triangulate / vba_two_view_init (at most 2) / vba_posegraph_optimize enqueued (filled with or without profiling) */
+    int64_t kernel_launches;     /* kernel launches the last vba_batch_run / vba_solve / vba_sim3_optimize / vba_sim3_ransac / vba_triangulate / vba_two_view_init (at most 2) / vba_search_triangulation / vba_posegraph_optimize enqueued (filled with or without profiling) */
 } vba_profile;
 
 /* One handle per host thread / GPU; owns device buffers and a stream.  Errors: nonzero return, message
@@ -178,7 +178,7 @@ int vba_batch_solve_b(void *handle, int32_t n_windows, vba_problem *const *inout
  *           every later one, those submitted afterwards included, with the same message: no GPU work starts for them (earlier
  *           tickets finish).  Waiting on an unknown or retired ticket returns -1.
  *   handle  while any ticket is submitted and not yet waited for, every synchronous entry point of the handle (vba_solve*,
- *           vba_batch_upload / run / download / solve*, vba_pose_optimize, vba_sim3_optimize, vba_sim3_ransac, vba_triangulate, vba_two_view_init, vba_posegraph_optimize, vba_preintegrate, vba_set_profile,
+ *           vba_batch_upload / run / download / solve*, vba_pose_optimize, vba_sim3_optimize, vba_sim3_ransac, vba_triangulate, vba_two_view_init, vba_search_triangulation, vba_posegraph_optimize, vba_preintegrate, vba_set_profile,
  *           vba_batch_set_depth) returns -1 with "asynchronous batches pending: wait for them first"; afterwards the handle
  *           works synchronously as before.  vba_destroy finishes pending tickets (their results land) before it frees.
  *           Profiling (vba_set_profile) covers synchronous calls only.  One caller thread at a time, as everywhere. */
@@ -450,6 +450,74 @@ typedef struct vba_two_view_result {
  * frame, a repeated first index, a non-finite pixel, K, sigma or min_parallax, a zero fx / fy / sigma.  A pair's outputs do not
  * depend on where it stands in the batch. */
 int vba_two_view_init(void *handle, int32_t n_problems, vba_two_view_problem *const *in, vba_two_view_result *const *out);
+
+/* ---- matching for triangulation ----
+ * ORBmatcher::SearchForTriangulation (src/ORBmatcher.cpp:760-955) with CheckDistEpipolarLine (:167-192) and ComputeThreeMaxima
+ * (:1800-1841), monocular (bOnlyStereo == false, no mvuRight): the matcher call in front of every vba_triangulate call of
+ * LocalMapping::CreateNewMapPoints.  One problem is one keyframe pair; one call takes any number of pairs, ragged, in one kernel
+ * launch (one 256-lane workgroup per pair).  The reference is restated as it stands:
+ *   node join   the two feature vectors are walked as the `while` of :801-921 does; a keypoint of keyframe 1 is compared with the
+ *               keypoints of keyframe 2 that its vocabulary node lists, in the order the node lists them
+ *   query       bestDist = th_low, bestIdx2 = -1 (:833-834); a candidate is skipped when it has a map point (:848), when
+ *               dist > th_low || dist > bestDist (:863: an EQUAL distance replaces the best, so the last one in list order wins among
+ *               equals), when (ex - u2)^2 + (ey - v2)^2 < epipole_r2 * scale_2[octave] (:871-875), when den == 0 or not
+ *               num^2 / den < chi2_epi * level_sigma2_2[octave] (:184-191); otherwise it becomes the best (:881-882)
+ *   vbMatched2  is declared at :782 and read at :848 but never set: nothing marks a keypoint of keyframe 2 as taken, the queries are
+ *               independent of each other and two of them may return the same idx2.  That is kept
+ *   orientation rot = angle1 - angle2; if (rot < 0) rot += 360.0f; bin = round(rot * (1.0f / 30)) in float32 with C round (:898-905,
+ *               bit for bit the reference's bin; only bins 0 .. 12 can occur and that is kept), ComputeThreeMaxima with its strict >
+ *               and its 0.1f * (float)max1 rules, every match of another bin back to -1 (:931-940)
+ * `state` says where a keypoint of keyframe 1 left the function, numbered in the order of the reference's exits:
+ *   0  matched (:893) and kept by the orientation filter
+ *   1  it has a map point (:817); this wins over 2
+ *   2  no node that both keyframes list holds it (the walk of :801-921 never reaches it)
+ *   3  no candidate passed (:890 fails)
+ *   4  matched, then dropped by the orientation filter (:937)
+ * Everything but the bin is FP64 on the float32 inputs widened; the reference computes in float32 (DESIGN.md section 8, row f-10,
+ * gives the measured difference). */
+typedef struct vba_search_tri_problem {
+    int32_t n_keys1, n_keys2;        /* pKF->N */
+    const uint8_t *desc1, *desc2;    /* [n_keys][32] the rows of mDescriptors (:831, :858) */
+    const uint8_t *has_mp1, *has_mp2; /* [n_keys] GetMapPoint(idx) != NULL (:813, :843) */
+    int32_t n_nodes1, n_nodes2;      /* entries of mFeatVec (:763-764) */
+    const uint32_t *node_id1, *node_id2;      /* [n_nodes] strictly ascending: the order of the std::map */
+    const int32_t *node_begin1, *node_begin2; /* [n_nodes + 1] node k lists node_feat[node_begin[k] .. node_begin[k + 1]) */
+    const int32_t *node_feat1, *node_feat2;   /* keypoint indices in the order the node's vector holds them; each keypoint at most once */
+    const double *uv1, *uv2;         /* [n_keys][2] mvKeysUn[idx].pt (:828, :867) */
+    const float *angle1, *angle2;    /* [n_keys] mvKeysUn[idx].angle in [0, 360) (:898); read only with check_orientation */
+    const uint8_t *oct2;             /* [n_keys2] mvKeysUn[idx].octave (:874, :191) */
+    int32_t n_levels2;               /* 1 .. 64 */
+    const double *level_sigma2_2, *scale_2;   /* [n_levels2] mvLevelSigma2 (:191), mvScaleFactors (:874) of keyframe 2 */
+    double F12[9];                   /* row-major: the caller's ComputeF12 (src/LocalMapping.cpp:1659-1680), float32 widened */
+    double epipole[2];               /* ex, ey of :768-775 */
+    int32_t th_low;                  /* TH_LOW = 50 (:833, :863); 0 .. 255 */
+    int32_t check_orientation;       /* mbCheckOrientation (:896, :923) */
+    double chi2_epi;                 /* 3.84 (:191) */
+    double epipole_r2;               /* 100 (:874) */
+} vba_search_tri_problem;
+
+typedef struct vba_search_tri_result {
+    int32_t status;           /* VBA_OK */
+    int32_t n_matches;        /* the return value (:954) */
+    int32_t n_before_filter;  /* nmatches in front of :923 */
+    int32_t hist[30];         /* rotHist[i].size() in front of the filter (zeros without check_orientation) */
+    int32_t ind[3];           /* ind1 .. ind3 of ComputeThreeMaxima, -1 as the reference leaves them (and without check_orientation) */
+    int32_t *match12;         /* [n_keys1] caller-allocated: vMatches12 behind the filter (:783, :937) */
+    uint8_t *best_dist;       /* [n_keys1] caller-allocated: bestDist of a keypoint in state 0 or 4, 255 otherwise */
+    uint8_t *state;           /* [n_keys1] caller-allocated: the codes above */
+    int32_t *pairs;           /* [n_keys1][2] caller-allocated: vMatchedPairs (:947-952), ascending idx1; the first n_matches rows are
+                                 written (on the host, from match12) */
+} vba_search_tri_result;
+
+/* Synchronous, like vba_triangulate; -1 while asynchronous tickets are pending.  n_pairs == 0 returns 0; a pair without keypoints
+ * or without a shared node is legal (n_matches = 0, every state 1 or 2).  A bad pair fails the whole call before any GPU work with
+ * "vba_search_triangulation: pair K: <why>" through vba_last_error: a NULL problem or result, a negative count, a NULL array with a
+ * non-zero count (match12, best_dist, state and pairs are required when n_keys1 > 0), n_levels2 outside 1 .. 64, th_low outside
+ * 0 .. 255, an octave >= n_levels2, a non-finite pixel, F12, epipole, threshold or level table, node ids that are not strictly
+ * ascending, a node_begin that does not start at 0 or decreases, a keypoint index outside its keyframe or listed twice in one
+ * feature vector, and with check_orientation an angle outside [0, 360).  A pair's outputs do not depend on where it stands in the
+ * batch. */
+int vba_search_triangulation(void *handle, int32_t n_pairs, vba_search_tri_problem *const *in, vba_search_tri_result *const *out);
 
 /* ---- essential-graph optimisation (Sim3 pose graph) ----
  * Optimizer::OptimizeEssentialGraph(Map*, KeyFrame* pLoopKF, KeyFrame* pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections,

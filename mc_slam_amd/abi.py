@@ -806,6 +806,146 @@ class TwoViewResultBuf:
                              self.sh[:self.nh].copy() if self.want else None, self.sf[:self.nh].copy() if self.want else None)
 
 
+# ---- matching for triangulation (include/vislam_ba.h: vba_search_tri_problem / vba_search_tri_result) ----
+_pu32 = C.POINTER(C.c_uint32)
+_pf = C.POINTER(C.c_float)
+
+
+class vba_search_tri_problem(C.Structure):
+    _fields_ = [
+        ("n_keys1", C.c_int32), ("n_keys2", C.c_int32), ("desc1", _pu8), ("desc2", _pu8), ("has_mp1", _pu8), ("has_mp2", _pu8),
+        ("n_nodes1", C.c_int32), ("n_nodes2", C.c_int32), ("node_id1", _pu32), ("node_id2", _pu32), ("node_begin1", _pi), ("node_begin2", _pi),
+        ("node_feat1", _pi), ("node_feat2", _pi), ("uv1", _pd), ("uv2", _pd), ("angle1", _pf), ("angle2", _pf), ("oct2", _pu8),
+        ("n_levels2", C.c_int32), ("level_sigma2_2", _pd), ("scale_2", _pd), ("F12", C.c_double * 9), ("epipole", C.c_double * 2),
+        ("th_low", C.c_int32), ("check_orientation", C.c_int32), ("chi2_epi", C.c_double), ("epipole_r2", C.c_double),
+    ]
+
+
+class vba_search_tri_result(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_matches", C.c_int32), ("n_before_filter", C.c_int32), ("hist", C.c_int32 * 30), ("ind", C.c_int32 * 3),
+                ("match12", _pi), ("best_dist", _pu8), ("state", _pu8), ("pairs", _pi)]
+
+
+ST_MATCHED, ST_HAS_MP, ST_NO_NODE, ST_NO_CANDIDATE, ST_ORIENTATION = range(5)
+
+
+def feat_vec_csr(fv):
+    """a feature vector {node id: [keypoint indices]} as (node_id, node_begin, node_feat), nodes in ascending order like the std::map"""
+    ids = sorted(fv)
+    begin = np.zeros(len(ids) + 1, dtype=np.int32)
+    for k, i in enumerate(ids):
+        begin[k + 1] = begin[k] + len(fv[i])
+    feat = np.array([a for i in ids for a in fv[i]], dtype=np.int32)
+    return np.array(ids, dtype=np.uint32), begin, feat
+
+
+@dataclass
+class SearchTriProblem:
+    """One keyframe pair of ORBmatcher::SearchForTriangulation (src/ORBmatcher.cpp:760-955) as flat arrays: keyframe 1 =
+    mpCurrentKeyFrame, keyframe 2 = one neighbour, feature vectors in CSR form."""
+    desc1: np.ndarray              # [n1,32] uint8
+    desc2: np.ndarray              # [n2,32] uint8
+    has_mp1: np.ndarray            # [n1] uint8
+    has_mp2: np.ndarray            # [n2] uint8
+    node_id1: np.ndarray           # [nodes1] uint32, strictly ascending
+    node_begin1: np.ndarray        # [nodes1 + 1] int32
+    node_feat1: np.ndarray         # int32
+    node_id2: np.ndarray
+    node_begin2: np.ndarray
+    node_feat2: np.ndarray
+    uv1: np.ndarray                # [n1,2]
+    uv2: np.ndarray                # [n2,2]
+    angle1: np.ndarray             # [n1] float32
+    angle2: np.ndarray             # [n2] float32
+    oct2: np.ndarray               # [n2] uint8
+    level_sigma2_2: np.ndarray     # [n_levels2]
+    scale_2: np.ndarray            # [n_levels2]
+    F12: np.ndarray                # [3,3]
+    epipole: np.ndarray            # [2]
+    th_low: int = 50
+    check_orientation: bool = True
+    chi2_epi: float = 3.84
+    epipole_r2: float = 100.0
+    truth: dict = field(default_factory=dict)
+
+    def __post_init__(self):
+        u8 = lambda a, shape: np.ascontiguousarray(a, dtype=np.uint8).reshape(shape)
+        self.desc1 = u8(self.desc1, (-1, 32)); self.desc2 = u8(self.desc2, (-1, 32))
+        self.has_mp1 = u8(self.has_mp1, (-1,)); self.has_mp2 = u8(self.has_mp2, (-1,)); self.oct2 = u8(self.oct2, (-1,))
+        for k in ("node_id1", "node_id2"):
+            setattr(self, k, np.ascontiguousarray(getattr(self, k), dtype=np.uint32).reshape(-1))
+        for k in ("node_begin1", "node_begin2", "node_feat1", "node_feat2"):
+            setattr(self, k, _i32(getattr(self, k)).reshape(-1))
+        self.uv1 = _f64(self.uv1, (-1, 2)); self.uv2 = _f64(self.uv2, (-1, 2))
+        self.angle1 = np.ascontiguousarray(self.angle1, dtype=np.float32).reshape(-1)
+        self.angle2 = np.ascontiguousarray(self.angle2, dtype=np.float32).reshape(-1)
+        self.level_sigma2_2 = _f64(self.level_sigma2_2, (-1,)); self.scale_2 = _f64(self.scale_2, (-1,))
+        self.F12 = _f64(self.F12, (3, 3)); self.epipole = _f64(self.epipole, (2,))
+
+    n_keys1 = property(lambda self: self.desc1.shape[0])
+    n_keys2 = property(lambda self: self.desc2.shape[0])
+    n_levels2 = property(lambda self: self.level_sigma2_2.shape[0])
+
+    def copy(self, **changes):
+        import copy as _c
+        q = _c.copy(self)
+        for k, v in changes.items():
+            setattr(q, k, v)
+        q.__post_init__()
+        return q
+
+    def as_struct(self) -> vba_search_tri_problem:
+        s = vba_search_tri_problem()
+        p = lambda a, t: a.ctypes.data_as(t)
+        s.n_keys1, s.n_keys2 = self.n_keys1, self.n_keys2
+        s.desc1, s.desc2, s.has_mp1, s.has_mp2 = p(self.desc1, _pu8), p(self.desc2, _pu8), p(self.has_mp1, _pu8), p(self.has_mp2, _pu8)
+        s.n_nodes1, s.n_nodes2 = self.node_id1.shape[0], self.node_id2.shape[0]
+        s.node_id1, s.node_id2 = p(self.node_id1, _pu32), p(self.node_id2, _pu32)
+        s.node_begin1, s.node_begin2 = p(self.node_begin1, _pi), p(self.node_begin2, _pi)
+        s.node_feat1, s.node_feat2 = p(self.node_feat1, _pi), p(self.node_feat2, _pi)
+        s.uv1, s.uv2, s.angle1, s.angle2, s.oct2 = p(self.uv1, _pd), p(self.uv2, _pd), p(self.angle1, _pf), p(self.angle2, _pf), p(self.oct2, _pu8)
+        s.n_levels2 = self.n_levels2
+        s.level_sigma2_2, s.scale_2 = p(self.level_sigma2_2, _pd), p(self.scale_2, _pd)
+        s.F12[:] = self.F12.ravel().tolist()
+        s.epipole[:] = self.epipole.tolist()
+        s.th_low, s.check_orientation = int(self.th_low), int(bool(self.check_orientation))
+        s.chi2_epi, s.epipole_r2 = float(self.chi2_epi), float(self.epipole_r2)
+        return s
+
+
+@dataclass
+class SearchTriResult:
+    status: int
+    n_matches: int
+    n_before_filter: int
+    hist: np.ndarray                # [30]
+    ind: np.ndarray                 # [3]
+    match12: np.ndarray             # [n1] int32
+    best_dist: np.ndarray           # [n1] uint8
+    state: np.ndarray               # [n1] uint8
+    pairs: np.ndarray               # [n_matches,2] int32
+
+
+class SearchTriResultBuf:
+    """Caller-allocated result storage of one keyframe pair."""
+
+    def __init__(self, p: SearchTriProblem):
+        self.n = p.n_keys1
+        m = max(self.n, 1)
+        self.m12 = np.full(m, -7, dtype=np.int32)
+        self.bd = np.full(m, 7, dtype=np.uint8)
+        self.st = np.full(m, 255, dtype=np.uint8)
+        self.pr = np.full((m, 2), -7, dtype=np.int32)
+        self.s = vba_search_tri_result()
+        self.s.match12, self.s.best_dist, self.s.state, self.s.pairs = (self.m12.ctypes.data_as(_pi), self.bd.ctypes.data_as(_pu8),
+                                                                        self.st.ctypes.data_as(_pu8), self.pr.ctypes.data_as(_pi))
+
+    def get(self) -> SearchTriResult:
+        s = self.s
+        return SearchTriResult(s.status, s.n_matches, s.n_before_filter, np.array(s.hist[:]), np.array(s.ind[:]), self.m12[:self.n].copy(),
+                               self.bd[:self.n].copy(), self.st[:self.n].copy(), self.pr[:max(min(s.n_matches, self.n), 0)].copy())
+
+
 # ---- essential-graph optimisation (include/vislam_ba.h: vba_posegraph_problem / vba_posegraph_result) ----
 class vba_posegraph_problem(C.Structure):
     _fields_ = [

@@ -19,7 +19,7 @@ _libs = {}
 EXPORTS = ["vba_create", "vba_destroy", "vba_last_error", "vba_solve", "vba_batch_upload", "vba_batch_run",
            "vba_batch_download", "vba_batch_solve", "vba_solve_b", "vba_batch_run_b", "vba_batch_solve_b", "vba_preintegrate", "vba_pose_optimize", "vba_problem_save", "vba_problem_load", "vba_problem_free", "vba_set_profile", "vba_get_profile", "vba_host_threads",
            "vba_batch_set_depth", "vba_batch_submit", "vba_batch_submit_b", "vba_batch_poll", "vba_batch_wait", "vba_sim3_optimize",
-           "vba_posegraph_optimize", "vba_sim3_ransac", "vba_triangulate", "vba_two_view_init"]
+           "vba_posegraph_optimize", "vba_sim3_ransac", "vba_triangulate", "vba_two_view_init", "vba_search_triangulation"]
 
 
 def load_library(hooks=False):
@@ -56,6 +56,8 @@ def load_library(hooks=False):
                                     C.POINTER(C.POINTER(abi.vba_triangulate_result))]
     lib.vba_two_view_init.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.POINTER(abi.vba_two_view_problem)),
                                       C.POINTER(C.POINTER(abi.vba_two_view_result))]
+    lib.vba_search_triangulation.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.POINTER(abi.vba_search_tri_problem)),
+                                             C.POINTER(C.POINTER(abi.vba_search_tri_result))]
     lib.vba_posegraph_optimize.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.POINTER(abi.vba_posegraph_problem)),
                                            C.POINTER(C.POINTER(abi.vba_posegraph_result))]
     lib.vba_set_profile.argtypes = [C.c_void_p, C.c_int32]
@@ -350,6 +352,26 @@ class LocalBA:
         """vba_two_view_init on a list of abi.TwoViewProblem (one frame pair each): list of abi.TwoViewResult"""
         packed = self.two_view_pack(problems, want_scores, fill)
         self.two_view_call(packed)
+        return [b.get() for b in packed[2]]
+
+    # ---- matching for triangulation (vba_search_triangulation): a batch of keyframe pairs per call ----
+    def search_triangulation_pack(self, problems):
+        """ctypes views of a list of abi.SearchTriProblem for vba_search_triangulation (kept alive by the returned tuple)"""
+        n = len(problems)
+        structs = [p.as_struct() for p in problems]
+        bufs = [abi.SearchTriResultBuf(p) for p in problems]
+        pp = (C.POINTER(abi.vba_search_tri_problem) * n)(*[C.pointer(s) for s in structs])
+        rr = (C.POINTER(abi.vba_search_tri_result) * n)(*[C.pointer(b.s) for b in bufs])
+        return n, structs, bufs, pp, rr, problems
+
+    def search_triangulation_call(self, packed):
+        if self.lib.vba_search_triangulation(self.h, packed[0], packed[3], packed[4]) != 0:
+            raise self._err("vba_search_triangulation")
+
+    def search_triangulation(self, problems):
+        """vba_search_triangulation on a list of abi.SearchTriProblem (one keyframe pair each): list of abi.SearchTriResult"""
+        packed = self.search_triangulation_pack(problems)
+        self.search_triangulation_call(packed)
         return [b.get() for b in packed[2]]
 
     # ---- essential-graph optimisation (vba_posegraph_optimize): a batch of independent Sim3 pose graphs per call ----

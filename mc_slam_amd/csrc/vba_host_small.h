@@ -1,7 +1,7 @@
 // vba_host_small.h -- host side of the library, part 5: the drivers of the small-problem entry points (vba_preintegrate,
-// vba_pose_optimize, vba_sim3_optimize, vba_sim3_ransac, vba_triangulate, vba_two_view_init, vba_posegraph_optimize).  Each lays its arena out once (vba_host_arena.h), packs the
+// vba_pose_optimize, vba_sim3_optimize, vba_sim3_ransac, vba_triangulate, vba_two_view_init, vba_search_triangulation, vba_posegraph_optimize).  Each lays its arena out once (vba_host_arena.h), packs the
 // pinned staging block with the plain-C++ half of its topic (vba_host_pose.h, vba_host_sim3.h, vba_host_sim3_ransac.h,
-// vba_host_triangulate.h, vba_host_two_view.h, vba_host_posegraph.h), and does one
+// vba_host_triangulate.h, vba_host_two_view.h, vba_host_search_tri.h, vba_host_posegraph.h), and does one
 // H2D copy, one or two launches and one D2H copy on the handle's stream.  No entry point shares its arena with another.
 #pragma once
 #include "vba_host_pose.h"
@@ -9,6 +9,7 @@
 #include "vba_host_sim3_ransac.h"
 #include "vba_host_triangulate.h"
 #include "vba_host_two_view.h"
+#include "vba_host_search_tri.h"
 #include "vba_host_posegraph.h"
 
 namespace {
@@ -225,6 +226,42 @@ int two_view_init(Handle* h, int32_t n_problems, vba_two_view_problem* const* in
     auto f64 = [&](size_t o) { return at<double>(hout, A.L.in_back(o)); };
     for (int f = 0; f < n_problems; f++)
         vba_host::unpack_two_view(out[f], desc[f], res[f], u8(A.flag_h), u8(A.flag_f), u8(A.tri), f64(A.x3d), f64(A.score_h), f64(A.score_f));
+    return 0;
+}
+
+// ORBmatcher::SearchForTriangulation (src/ORBmatcher.cpp:760-955, monocular) for a batch of keyframe pairs: the host does the node
+// join while it packs, k_search_tri runs one workgroup per pair, one launch
+int search_triangulation(Handle* h, int32_t n_pairs, vba_search_tri_problem* const* in, vba_search_tri_result* const* out) {
+    if (n_pairs < 0 || (n_pairs > 0 && (!in || !out))) return fail(h, "vba_search_triangulation: bad arguments");
+    if (n_pairs == 0) return 0;
+    vba_host::SearchTriTotals T;
+    std::string err;
+    if (vba_host::check_search_tri(n_pairs, in, out, T, err)) return fail(h, "vba_search_triangulation: " + err);
+    HIPCHK(h, hipSetDevice(h->device));
+    const vba_host::SearchTriArena A(n_pairs, T);
+    HIPCHK(h, h->st.ensure(A.L, A.L.back_bytes()));
+    void *hin = h->st.in.p, *hout = h->st.out.p, *base = h->st.dev.p;
+    StDesc* desc = at<StDesc>(hin, A.desc);
+    vba_host::describe_search_tri(n_pairs, in, desc);
+    host_parallel_for(h, n_pairs, small_pack_threads(n_pairs), [&](int f) {
+        vba_host::pack_search_tri(in[f], desc[f], at<StKey>(hin, A.key1), at<StKey>(hin, A.key2), at<StQuery>(hin, A.query), at<int32_t>(hin, A.feat),
+                                  at<double>(hin, A.lev));
+    });
+    StBatch B;
+    B.desc = at<StDesc>(base, A.desc); B.key1 = at<StKey>(base, A.key1); B.key2 = at<StKey>(base, A.key2); B.query = at<StQuery>(base, A.query);
+    B.feat = at<int>(base, A.feat); B.lev = at<double>(base, A.lev); B.out = at<StOut>(base, A.out); B.match12 = at<int>(base, A.match12);
+    B.best_dist = at<unsigned char>(base, A.best_dist); B.state = at<unsigned char>(base, A.state);
+    const long long launch0 = h->n_launch;
+    HIPCHK(h, hipMemcpyAsync(base, hin, A.L.upload_bytes(), hipMemcpyHostToDevice, h->stream));
+    VBA_LAUNCH(k_search_tri, dim3(n_pairs), dim3(ST_NT), 0, h->stream, B);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(hout, B.out, A.L.back_bytes(), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->prof.kernel_launches = h->n_launch - launch0;
+    const StOut* res = at<StOut>(hout, A.L.in_back(A.out));
+    for (int f = 0; f < n_pairs; f++)
+        vba_host::unpack_search_tri(out[f], desc[f], res[f], at<int32_t>(hout, A.L.in_back(A.match12)), at<unsigned char>(hout, A.L.in_back(A.best_dist)),
+                                    at<unsigned char>(hout, A.L.in_back(A.state)));
     return 0;
 }
 

@@ -173,6 +173,36 @@ struct TvOut {
 #define VBA_TV_HYP_F 9         // doubles per F hypothesis record (device only): F21
 #define VBA_TV_RT 8            // most (R, t) hypotheses of a pair: the per-(hypothesis, match) regions hold this many per match
 static_assert(sizeof(TvDesc) == 104 && sizeof(TvOut) == 400, "scripts/two_view_bench.py derives the copied bytes from these sizes");
+// vba_search_triangulation (vba_search_tri.h)
+#define VBA_ST_NT 256          // lanes of the one workgroup of a pair
+#define VBA_ST_HISTO 30        // HISTO_LENGTH (src/ORBmatcher.cpp:42)
+#define VBA_ST_CONST 13        // doubles of a pair's constants: F12 (9) ex ey chi2_epi epipole_r2
+struct alignas(16) StKey {     // one keypoint of either keyframe, 64 bytes: four 16-byte loads, the descriptor in the first two
+    unsigned int d[8];         // the row of mDescriptors
+    double u, v;               // mvKeysUn[idx].pt
+    float angle;               // mvKeysUn[idx].angle
+    unsigned char oct;         // mvKeysUn[idx].octave (keyframe 2; 0 in keyframe 1)
+    unsigned char role;        // keyframe 1: the state the host already knows (1 map point, 2 in no shared node), 0 = a query;
+                               // keyframe 2: has_mp
+    unsigned char pad[10];
+};
+struct alignas(16) StQuery {   // one keypoint of keyframe 1 that a shared node lists and that has no map point
+    int idx1, c_begin, c_end, pad;   // its candidates: feat[feat0 + c_begin .. feat0 + c_end)
+};
+struct StDesc {
+    long long key1_0, key2_0, feat0, lev0;   // offsets of the pair's keypoint records (the queries share key1_0), of its copy of
+                                             // node_feat_2 and of its level tables in the concatenated arrays
+    int n_keys1, n_keys2, n_q, n_levels2;
+    int th_low, check_orientation;
+    double c[VBA_ST_CONST];
+};
+struct StOut {
+    int status, n_matches, n_before_filter;
+    int hist[VBA_ST_HISTO];
+    int ind[3];
+};
+static_assert(sizeof(StKey) == 64 && sizeof(StQuery) == 16 && sizeof(StDesc) == 160 && sizeof(StOut) == 144,
+              "scripts/search_tri_bench.py derives the copied bytes from these sizes");
 // vba_posegraph_optimize (vba_posegraph.h)
 struct PgDesc {
     int nv, ne, nf, npair;

@@ -1,11 +1,13 @@
 // LocalMapping.cpp -- LocalMapping::CreateNewMapPoints (src/LocalMapping.cpp:1237-1546, monocular) over vba_triangulate: the
-// reference's loop over the neighbours with its gate, the matcher through the caller's function object, ONE vba_triangulate call
+// reference's loop over the neighbours with its gate, the matcher -- the caller's function object, or ComputeF12 and
+// ORBmatcher::SearchForTriangulation over vba_search_triangulation in the overload without one --, ONE vba_triangulate call
 // per neighbour (the matcher of neighbour i + 1 must see the points created from neighbour i, so the pairs of a keyframe cannot
 // share a call here), and the map-point construction for every accepted match in match order.
 #include <cmath>
 #include <iostream>
 
 #include "../../include/vislam_ba.h"
+#include "ORBmatcher.h"
 #include "Optimizer.h"
 
 namespace ORB_SLAM2 {
@@ -22,10 +24,13 @@ struct TriSide {
         K[0] = kf->fx; K[1] = kf->fy; K[2] = kf->cx; K[3] = kf->cy;
     }
 };
-}  // namespace
+// a matcher that can fail: false ends the walk over the neighbours at once
+typedef std::function<bool(KeyFrame*, KeyFrame*, std::vector<std::pair<size_t, size_t>>&)> FallibleMatcher;
 
-int LocalMapping::CreateNewMapPoints(KeyFrame* pKF, const std::vector<KeyFrame*>& vpNeighKFs, const TriangulationMatcher& matcher, Map* pMap,
-                                     std::list<MapPoint*>& lpRecentAddedMapPoints) {
+// the loop of both overloads.  -1 when the matcher or the backend failed: nothing is done for the neighbour that failed or for
+// the ones behind it; the points made from the neighbours in front of it stay in the map
+int create_new_map_points(KeyFrame* pKF, const std::vector<KeyFrame*>& vpNeighKFs, const FallibleMatcher& matcher, Map* pMap,
+                          std::list<MapPoint*>& lpRecentAddedMapPoints) {
     const TriSide s1(pKF);
     const float ratioFactor = 1.5f * pKF->mfScaleFactor;   // :1272
     int nnew = 0;
@@ -41,7 +46,7 @@ int LocalMapping::CreateNewMapPoints(KeyFrame* pKF, const std::vector<KeyFrame*>
         if (ratioBaselineDepth < 0.01) continue;
         // :1318 the matcher (ComputeF12 of :1314 belongs to it)
         std::vector<std::pair<size_t, size_t>> vMatchedIndices;
-        matcher(pKF, pKF2, vMatchedIndices);
+        if (!matcher(pKF, pKF2, vMatchedIndices)) return -1;
         const int nmatches = (int)vMatchedIndices.size();
         if (nmatches == 0) continue;
         const TriSide s2(pKF2);
@@ -89,6 +94,47 @@ int LocalMapping::CreateNewMapPoints(KeyFrame* pKF, const std::vector<KeyFrame*>
         }
     }
     return nnew;
+}
+
+}  // namespace
+
+int LocalMapping::CreateNewMapPoints(KeyFrame* pKF, const std::vector<KeyFrame*>& vpNeighKFs, const TriangulationMatcher& matcher, Map* pMap,
+                                     std::list<MapPoint*>& lpRecentAddedMapPoints) {
+    const FallibleMatcher m = [&matcher](KeyFrame* pKF1, KeyFrame* pKF2, std::vector<std::pair<size_t, size_t>>& v) { matcher(pKF1, pKF2, v); return true; };
+    return create_new_map_points(pKF, vpNeighKFs, m, pMap, lpRecentAddedMapPoints);
+}
+
+Mat3f LocalMapping::ComputeF12(KeyFrame* pKF1, KeyFrame* pKF2) {
+    double R1w[9], t1w[3], R2w[9], t2w[3];
+    pKF1->GetRotation(R1w); pKF1->GetTranslation(t1w);
+    pKF2->GetRotation(R2w); pKF2->GetTranslation(t2w);
+    double R12[9], t12[3];   // R12 = R1w R2w^T, t12 = -R12 t2w + t1w (:1670-1671)
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) R12[3 * i + j] = (R1w[3 * i] * R2w[3 * j] + R1w[3 * i + 1] * R2w[3 * j + 1]) + R1w[3 * i + 2] * R2w[3 * j + 2];
+    for (int i = 0; i < 3; i++) t12[i] = -((R12[3 * i] * t2w[0] + R12[3 * i + 1] * t2w[1]) + R12[3 * i + 2] * t2w[2]) + t1w[i];
+    const double tx[9] = {0, -t12[2], t12[1], t12[2], 0, -t12[0], -t12[1], t12[0], 0};   // SkewSymmetricMatrix (:1673)
+    // K^-1 = [1/fx 0 -cx/fx; 0 1/fy -cy/fy; 0 0 1]
+    const double K1i[9] = {1.0 / pKF1->fx, 0, -(double)pKF1->cx / pKF1->fx, 0, 1.0 / pKF1->fy, -(double)pKF1->cy / pKF1->fy, 0, 0, 1};
+    const double K2i[9] = {1.0 / pKF2->fx, 0, -(double)pKF2->cx / pKF2->fx, 0, 1.0 / pKF2->fy, -(double)pKF2->cy / pKF2->fy, 0, 0, 1};
+    auto mul = [](const double* A, const double* B, double* C) {
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) C[3 * i + j] = (A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j]) + A[3 * i + 2] * B[6 + j];
+    };
+    const double K1it[9] = {K1i[0], K1i[3], K1i[6], K1i[1], K1i[4], K1i[7], K1i[2], K1i[5], K1i[8]};
+    double A[9], B[9], F[9];   // K1.t().inv() * t12x * R12 * K2.inv(), left to right (:1678)
+    mul(K1it, tx, A); mul(A, R12, B); mul(B, K2i, F);
+    Mat3f out;
+    for (int i = 0; i < 9; i++) out[i] = (float)F[i];
+    return out;
+}
+
+int LocalMapping::CreateNewMapPoints(KeyFrame* pKF, const std::vector<KeyFrame*>& vpNeighKFs, Map* pMap, std::list<MapPoint*>& lpRecentAddedMapPoints) {
+    const FallibleMatcher matcher = [](KeyFrame* pKF1, KeyFrame* pKF2, std::vector<std::pair<size_t, size_t>>& vMatchedIndices) {
+        const Mat3f F12 = ComputeF12(pKF1, pKF2);                                          // :1314
+        ORBmatcher m(0.6, false);                                                          // :1270
+        return m.SearchForTriangulation(pKF1, pKF2, F12, vMatchedIndices, false) >= 0;     // :1318
+    };
+    return create_new_map_points(pKF, vpNeighKFs, matcher, pMap, lpRecentAddedMapPoints);
 }
 
 }  // namespace ORB_SLAM2

@@ -9,6 +9,7 @@
 #include "Optimizer.h"
 #include "Sim3Solver.h"
 #include "Initializer.h"
+#include "ORBmatcher.h"
 
 using namespace ORB_SLAM2;
 
@@ -494,6 +495,53 @@ long fc_kf_mappoint_at(void* m, long kf, int idx) {
 }
 int fc_map_n_points(void* m) { return (int)reinterpret_cast<FcMap*>(m)->map.mspMapPoints.size(); }
 float fc_kf_median_depth(void* m, long kf, int q) { return reinterpret_cast<FcMap*>(m)->kfs.at(kf)->ComputeSceneMedianDepth(q); }
+// ---- the matcher (ORBmatcher::SearchForTriangulation, ORBmatcher.cpp) ----
+// what the matcher reads beside the keypoints: N x 32 descriptor bytes, one angle per keypoint, the feature vector in CSR form
+// (node ids ascending); N becomes the number of keypoints the keyframe holds
+int fc_kf_set_matcher_data(void* m, long kf, const unsigned char* desc, const float* angle, int n_nodes, const unsigned int* node_id, const int* node_begin,
+                           const int* node_feat) {
+    KeyFrame* k = reinterpret_cast<FcMap*>(m)->kfs.at(kf).get();
+    k->N = (int)k->mvKeysUn.size();
+    k->mDescriptors.assign(desc, desc + 32 * (size_t)k->N);
+    for (int i = 0; i < k->N; i++) k->mvKeysUn[i].angle = angle[i];
+    k->mFeatVec.clear();
+    for (int j = 0; j < n_nodes; j++) {
+        std::vector<unsigned int>& v = k->mFeatVec[node_id[j]];
+        for (int i = node_begin[j]; i < node_begin[j + 1]; i++) v.push_back((unsigned int)node_feat[i]);
+    }
+    return k->N;
+}
+void fc_compute_f12(void* m, long kf1, long kf2, float* F9, float* epipole2) {
+    FcMap* M = reinterpret_cast<FcMap*>(m);
+    const Mat3f F = LocalMapping::ComputeF12(M->kfs.at(kf1).get(), M->kfs.at(kf2).get());
+    std::memcpy(F9, F.data(), 36);
+    ORBmatcher::Epipole(M->kfs.at(kf1).get(), M->kfs.at(kf2).get(), epipole2[0], epipole2[1]);
+}
+// ORBmatcher(0.6, check_ori)::SearchForTriangulation with ComputeF12's matrix: the return value, pairs [cap][2] filled up to cap
+int fc_search_for_triangulation(void* m, long kf1, long kf2, int check_ori, int only_stereo, long* pairs, int cap) {
+    FcMap* M = reinterpret_cast<FcMap*>(m);
+    KeyFrame *k1 = M->kfs.at(kf1).get(), *k2 = M->kfs.at(kf2).get();
+    ORBmatcher matcher(0.6, check_ori != 0);
+    std::vector<std::pair<size_t, size_t>> v;
+    const int n = matcher.SearchForTriangulation(k1, k2, LocalMapping::ComputeF12(k1, k2), v, only_stereo != 0);
+    for (size_t i = 0; i < v.size() && (int)i < cap; i++) { pairs[2 * i] = (long)v[i].first; pairs[2 * i + 1] = (long)v[i].second; }
+    return n;
+}
+// CreateNewMapPoints without a matcher table (the overload that calls the matcher itself); new_ids as fc_create_new_map_points
+int fc_create_new_map_points_matched(void* m, long kf, const long* neigh, int n_neigh, long* new_ids, int cap) {
+    FcMap* M = reinterpret_cast<FcMap*>(m);
+    std::vector<KeyFrame*> vpNeighKFs;
+    for (int i = 0; i < n_neigh; i++) vpNeighKFs.push_back(M->kfs.at(neigh[i]).get());
+    std::list<MapPoint*> recent;
+    const int nnew = M->lm.CreateNewMapPoints(M->kfs.at(kf).get(), vpNeighKFs, &M->map, recent);
+    int k = 0;
+    for (MapPoint* p : recent) {
+        if (k < cap) new_ids[k] = (long)p->mnId;
+        k++;
+        M->mps[(long)p->mnId].reset(p);
+    }
+    return nnew;
+}
 // ---- essential graph ----
 // spanning tree, loop edges and the ordered covisibility list (descending weights) of one keyframe
 int fc_kf_set_graph(void* m, long kf, long parent, const long* children, int n_children, const long* loop_edges, int n_loop,

@@ -24,6 +24,7 @@ typedef std::array<double, 3> Vector3d;
 typedef std::array<double, 4> Quaterniond;  // x y z w (Eigen coefficient order)
 typedef std::array<double, 9> Matrix3d;     // row-major
 typedef std::array<float, 16> Mat4f;        // cv::Mat CV_32F 4x4, row-major
+typedef std::array<float, 9> Mat3f;         // cv::Mat CV_32F 3x3, row-major
 
 inline Matrix3d QuatToMatrix(const Quaterniond& q) {  // Eigen::Quaterniond::toRotationMatrix
     const double x = q[0], y = q[1], z = q[2], w = q[3];
@@ -97,9 +98,10 @@ struct ConfigParam {
     }
 };
 
-struct KeyPoint {  // cv::KeyPoint: pt.x, pt.y are float, octave int
+struct KeyPoint {  // cv::KeyPoint: pt.x, pt.y are float, octave int, angle float (degrees in [0, 360))
     struct { float x, y; } pt;
     int octave;
+    float angle = 0.0f;   // what ORBmatcher::SearchForTriangulation reads (src/ORBmatcher.cpp:898)
 };
 
 class KeyFrame;
@@ -136,6 +138,12 @@ public:
     // :1520-1542 for every accepted match (LocalMapping.cpp).  Returns nnew, -1 when the backend failed
     int CreateNewMapPoints(KeyFrame* pKF, const std::vector<KeyFrame*>& vpNeighKFs, const TriangulationMatcher& matcher, Map* pMap,
                            std::list<MapPoint*>& lpRecentAddedMapPoints);
+    // the same with the reference's own matcher call (:1314-1318): ComputeF12, then ORBmatcher(0.6, false)::SearchForTriangulation
+    // over vba_search_triangulation (ORBmatcher.cpp), so the function runs on its own.  A matcher or backend failure ends the walk at
+    // that neighbour with -1; the points made from the neighbours in front of it stay in the map
+    int CreateNewMapPoints(KeyFrame* pKF, const std::vector<KeyFrame*>& vpNeighKFs, Map* pMap, std::list<MapPoint*>& lpRecentAddedMapPoints);
+    // src/LocalMapping.cpp:1659-1680: K1^-T [t12]x R12 K2^-1 with analytic K inverses, FP64 products, the result held as float32
+    static Mat3f ComputeF12(KeyFrame* pKF1, KeyFrame* pKF2);
 };
 
 class KeyFrame {
@@ -149,6 +157,11 @@ public:
     std::vector<float> mvInvLevelSigma2;
     std::vector<float> mvLevelSigma2;     // include/KeyFrame.h: what Sim3Solver reads (src/Sim3Solver.cpp:75-76)
     std::vector<float> mvScaleFactors;    // include/KeyFrame.h: what CreateNewMapPoints reads (src/LocalMapping.cpp:1513)
+    // what ORBmatcher::SearchForTriangulation reads (src/ORBmatcher.cpp:763-764, :831): N keypoints, N x 32 descriptor bytes (the
+    // rows of the cv::Mat), the DBoW2::FeatureVector as node id -> keypoint indices
+    int N = 0;
+    std::vector<unsigned char> mDescriptors;
+    std::map<unsigned int, std::vector<unsigned int>> mFeatVec;
     float mfScaleFactor = 1.2f;           // src/LocalMapping.cpp:1272
 
     std::vector<MapPoint*> GetMapPointMatches() { return mvpMapPoints; }

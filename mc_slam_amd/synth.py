@@ -802,3 +802,115 @@ def make_posegraph(seed, n_kf, span=3, loops=None, fix_scale=False, fixed_at=0, 
         pt_ref = r.integers(0, n, n_pt)
     return abi.PoseGraphProblem(S=S, fixed=fixed, edge_i=ei, edge_j=ej, edge_S=np.stack([_s3_pack(m) for m in meas]),
                                 fix_scale=int(bool(fix_scale)), pt=pt, pt_ref=pt_ref, truth=dict(S=St))
+
+
+# ---------------------------------------------------------------- matching for triangulation (vba_search_triangulation)
+def compute_f12(Rcw1, tcw1, K1, Rcw2, tcw2, K2):
+    """LocalMapping::ComputeF12 (src/LocalMapping.cpp:1659-1680) in float64 on the inputs as given: K1^-T [t12]x R12 K2^-1"""
+    R12 = Rcw1 @ Rcw2.T
+    t12 = -R12 @ tcw2 + tcw1
+    tx = np.array([[0, -t12[2], t12[1]], [t12[2], 0, -t12[0]], [-t12[1], t12[0], 0]])
+    Kinv = lambda K: np.array([[1 / K[0], 0, -K[2] / K[0]], [0, 1 / K[1], -K[3] / K[1]], [0, 0, 1]])
+    return Kinv(K1).T @ tx @ R12 @ Kinv(K2)
+
+
+def synth_match_pair(seed, n_true=60, n_distract1=20, n_distract2=20, n_nodes=12, flip_bits=12, unshared=0.1, mp1=0.1, mp2=0.1,
+                     n_levels=8, scale_factor=1.2, angle_noise=3.0, rot_outliers=0.1, noise=0.3, check_orientation=True, th_low=50, big_node=0):
+    """One keyframe pair of ORBmatcher::SearchForTriangulation, every input rounded through float32 as the reference holds it.  A
+    two-view scene with known poses (EuRoC intrinsics, a sideways baseline of 0.2-0.5 m, a relative rotation of a few degrees, an
+    in-plane roll of about 40 degrees so that rot = angle1 - angle2 is of either sign); n_true world features 2-10 m deep with
+    random 256-bit descriptors, seen by both keyframes as copies with flip_bits flipped bits each; n_distract1 / n_distract2
+    keypoints per keyframe that exist only there (random descriptor, random pixel).  Every true feature sits in one of n_nodes
+    vocabulary nodes in both keyframes, except the share `unshared`, whose copy in keyframe 2 sits in another node; distractors
+    sit in random nodes, and node ids exist that only one keyframe uses.  Shares mp1 / mp2 of the keypoints already have a map
+    point.  big_node: the first big_node true features sit in node 0 in both keyframes.  Angles: that of keyframe 2 is that of keyframe 1 minus the roll plus angle_noise degrees of noise; the share
+    rot_outliers of the true features gets a random angle in keyframe 2.  Keypoints are shuffled, so node_feat is not ascending.
+    truth: pair [n_true,2] (idx1, idx2), shared [n_true] bool."""
+    r = np.random.default_rng(seed)
+    f32 = lambda a: np.asarray(a, dtype=np.float32)
+    K = f32(EUROC_K).astype(np.float64)
+    scale, sigma2 = level_tables(n_levels, scale_factor)
+    roll = np.deg2rad(r.uniform(30, 50))
+    R1 = so3_exp(r.normal(size=3) * 0.3)
+    C1 = r.uniform(-1, 1, 3)
+    a = r.uniform(0, 2 * np.pi)
+    d = np.array([np.cos(a), 0.4 * np.sin(a), r.uniform(-0.1, 0.1)])
+    C2 = C1 + R1.T @ (r.uniform(0.2, 0.5) * d / np.linalg.norm(d))
+    R2 = so3_exp(np.array([0.0, 0.0, roll])) @ so3_exp(r.normal(size=3) * 0.03) @ R1
+
+    def pose(R, Cw):
+        R32 = f32(R)
+        return R32.astype(np.float64), f32(-(R32.astype(np.float64) @ Cw)).astype(np.float64)
+
+    Rcw1, tcw1 = pose(R1, C1)
+    Rcw2, tcw2 = pose(R2, C2)
+    n1, n2 = n_true + n_distract1, n_true + n_distract2
+    oct_p = np.array([35, 25, 15, 10, 6, 4, 3, 2] + [1] * 56)[:n_levels].astype(float)
+    oct_t = r.choice(n_levels, size=n_true, p=oct_p / oct_p.sum())
+    # true features: a pixel in keyframe 1, a depth, the world point, its pixel in keyframe 2
+    uv1t = np.stack([r.uniform(60, 690, n_true), r.uniform(60, 420, n_true)], axis=1)
+    depth = r.uniform(2, 10, n_true)
+    Xc1 = depth[:, None] * np.stack([(uv1t[:, 0] - K[2]) / K[0], (uv1t[:, 1] - K[3]) / K[1], np.ones(n_true)], axis=1)
+    Xw = Xc1 @ R1 + C1
+    Y = (Xw - C2) @ R2.T
+    uv2t = np.stack([K[0] * Y[:, 0] / Y[:, 2] + K[2], K[1] * Y[:, 1] / Y[:, 2] + K[3]], axis=1)
+    uv1t = uv1t + r.normal(size=(n_true, 2)) * noise * scale[oct_t][:, None]
+    uv2t = uv2t + r.normal(size=(n_true, 2)) * noise * scale[oct_t][:, None]
+    base = r.integers(0, 256, (n_true, 32), dtype=np.uint8)
+
+    def flipped(dsc):
+        out = np.unpackbits(dsc, axis=1)
+        which = np.argsort(r.random(out.shape), axis=1)[:, :flip_bits]     # flip_bits distinct positions per row
+        np.put_along_axis(out, which, 1 - np.take_along_axis(out, which, axis=1), axis=1)
+        return np.packbits(out, axis=1)
+
+    d1 = np.vstack([flipped(base), r.integers(0, 256, (n_distract1, 32), dtype=np.uint8)])
+    d2 = np.vstack([flipped(base), r.integers(0, 256, (n_distract2, 32), dtype=np.uint8)])
+    rnd_uv = lambda n: np.stack([r.uniform(20, 732, n), r.uniform(20, 460, n)], axis=1)
+    uv1 = np.vstack([uv1t, rnd_uv(n_distract1)])
+    uv2 = np.vstack([uv2t, rnd_uv(n_distract2)])
+    ang1 = r.uniform(0, 360, n1)
+    ang2t = ang1[:n_true] - np.rad2deg(roll) + r.normal(size=n_true) * angle_noise
+    out = r.random(n_true) < rot_outliers
+    ang2t = np.where(out, r.uniform(0, 360, n_true), ang2t)
+    ang2 = np.mod(np.concatenate([ang2t, r.uniform(0, 360, n_distract2)]), 360.0)
+    ang1 = f32(ang1); ang2 = f32(ang2)
+    ang1[ang1 >= 360] = 0; ang2[ang2 >= 360] = 0
+    oct2 = np.concatenate([np.clip(oct_t + r.choice([-1, 0, 0, 0, 1], size=n_true), 0, n_levels - 1), r.choice(n_levels, size=n_distract2, p=oct_p / oct_p.sum())])
+    # nodes: ids 10 * k + 5 are shared candidates, 10 * k + 1 exist in keyframe 1 only, 10 * k + 8 in keyframe 2 only
+    node_t = r.integers(0, n_nodes, n_true)
+    shared = r.random(n_true) >= unshared
+    node_t[:big_node] = 0                                  # the first big_node true features share node 0 in both keyframes
+    shared[:big_node] = True
+    node1 = np.concatenate([10 * node_t + 5, np.where(r.random(n_distract1) < 0.3, 10 * r.integers(0, n_nodes, n_distract1) + 1, 10 * r.integers(0, n_nodes, n_distract1) + 5)])
+    node2t = np.where(shared, 10 * node_t + 5, 10 * ((node_t + 1 + r.integers(0, max(n_nodes - 1, 1), n_true)) % n_nodes) + 5)
+    if n_nodes == 1:
+        shared[:] = True
+        node2t = 10 * node_t + 5
+    node2 = np.concatenate([node2t, np.where(r.random(n_distract2) < 0.3, 10 * r.integers(0, n_nodes, n_distract2) + 8, 10 * r.integers(0, n_nodes, n_distract2) + 5)])
+    has1 = (r.random(n1) < mp1).astype(np.uint8)
+    has2 = (r.random(n2) < mp2).astype(np.uint8)
+    # shuffle the keypoints of both keyframes
+    p1, p2 = r.permutation(n1), r.permutation(n2)          # new index -> old index
+    inv1, inv2 = np.argsort(p1), np.argsort(p2)
+
+    def fv(node, perm):
+        m = {}
+        for new in r.permutation(len(perm)):               # the order inside a node is not ascending
+            m.setdefault(int(node[perm[new]]), []).append(int(new))
+        return abi.feat_vec_csr(m)
+
+    id1, b1, ft1 = fv(node1, p1)
+    id2, b2, ft2 = fv(node2, p2)
+    F12 = f32(compute_f12(Rcw1, tcw1, K, Rcw2, tcw2, K)).astype(np.float64)
+    Cw1 = -(f32(Rcw1).T @ f32(tcw1))                       # GetCameraCenter in float32
+    C2c = f32(Rcw2) @ Cw1 + f32(tcw2)
+    invz = np.float32(1.0) / C2c[2]
+    K32 = f32(K)
+    ex, ey = K32[0] * C2c[0] * invz + K32[2], K32[1] * C2c[1] * invz + K32[3]
+    return abi.SearchTriProblem(desc1=d1[p1], desc2=d2[p2], has_mp1=has1[p1], has_mp2=has2[p2], node_id1=id1, node_begin1=b1, node_feat1=ft1,
+                                node_id2=id2, node_begin2=b2, node_feat2=ft2, uv1=f32(uv1[p1]).astype(np.float64), uv2=f32(uv2[p2]).astype(np.float64),
+                                angle1=ang1[p1], angle2=ang2[p2], oct2=oct2[p2], level_sigma2_2=sigma2, scale_2=scale, F12=F12,
+                                epipole=np.array([float(ex), float(ey)]), th_low=th_low, check_orientation=check_orientation,
+                                truth=dict(pair=np.stack([inv1[:n_true], inv2[:n_true]], axis=1), shared=shared,
+                                           pose=(Rcw1, tcw1, Rcw2, tcw2, K)))
