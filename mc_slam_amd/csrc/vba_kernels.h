@@ -926,23 +926,125 @@ DEVI bool schur_map(const Batch& B, int per_win, int& w, int& idx) {
     return w < B.n_win;
 }
 
+// The IMU factors and the sub-block mask of one keyframe pair, fetched ONCE per wave: in the many-window kernel right behind the
+// walk, so that the reductions hide the two dependent round trips (not held across the walk: the Schur kernels have no register
+// to spare there); in the few-window kernels where the block is written.  The structure build (vba_host_structure.h) lists every
+// IMU edge of the problem under its pairs, so a list has no bound in general; a keyframe chain gives one factor per neighbour
+// pair and one or two per diagonal pair.  The first two are resolved here; a longer list goes through the loops that read pimu
+// per factor.
+struct PairImu {
+    int qb, n;               // first entry of the pair's (edge, role) list, number of entries
+    int mask;                // pair_mask: the sub-blocks some tile of the factor reads (schur_write_block)
+    const double *H0, *H1;   // information blocks of the first two factors (valid pointers whatever n is)
+    int ro0, co0, ro1, co1;  // their row / column offsets: role bit0: a is keyframe j of the edge, bit1: b is keyframe j
+};
+DEVI PairImu pair_imu(const Batch& B, const WinDesc& d, int pr) {
+    PairImu f;
+    const int* pb = B.pimu_begin + d.pair0 + d.win + pr;
+    f.qb = pb[0];
+    f.n = pb[1] - f.qb;
+    f.mask = B.pair_mask[d.pair0 + pr];
+    f.H0 = f.H1 = B.imuH;
+    f.ro0 = f.co0 = f.ro1 = f.co1 = 0;
+    if (f.n > 0) {
+        const int* e0 = B.pimu + 2 * (size_t)(d.pimu0 + f.qb);
+        const int* e1 = e0 + ((f.n > 1) ? 2 : 0);   // (both entries requested together)
+        const int k0 = e0[0], role0 = e0[1], k1 = e1[0], role1 = e1[1];
+        f.H0 = B.imuH + VBA_IMUH * (size_t)(d.imu0 + k0);
+        f.H1 = B.imuH + VBA_IMUH * (size_t)(d.imu0 + k1);
+        f.ro0 = (role0 & 1) ? 15 : 0; f.co0 = (role0 & 2) ? 15 : 0;
+        f.ro1 = (role1 & 1) ? 15 : 0; f.co1 = (role1 & 2) ? 15 : 0;
+    }
+    return f;
+}
+
+// A block with IMU terms or a diagonal block, at most two factors: PP = pdim and NT = lanes per pair are compile-time, so the
+// entries of a lane are enumerated without a division, and every load an entry needs (the block value from LDS, H of both
+// factors, var_act of its row and column) is requested before the first entry is formed -- one round trip for up to CH entries
+// instead of one per load.  Each entry is formed exactly as the loop below forms it: blk or 0.0, + H in list order, the
+// diagonal rule, the same store side.
+template <int PP, int NT, bool DIAG>
+DEVI void schur_write_block_imu(const Batch& B, const WinDesc& d, double lambda, int mask, const PairImu& f, int a, int b,
+                                const double* blk, int t, int bstride) {
+    constexpr int NE = PP * PP, TR = (NE + NT - 1) / NT, CH = (TR < 8) ? TR : 8;
+    constexpr bool diag = DIAG;
+    const int n = d.nS;
+    const int* va = B.var_act + d.vec0;
+    double* S = B.S + d.S0;
+    // vpos(d, x, r) = (r < 6 ? pr_x : vb_x) + r
+    const int pr_a = d.vp_pr0 + d.vp_prs * a, pr_b = d.vp_pr0 + d.vp_prs * b;
+    const int vb_a = ((a < d.vp_h) ? d.vp_vb0 + d.vp_vbs * a : d.vp_vb1 - 9 * a) - 6;
+    const int vb_b = ((b < d.vp_h) ? d.vp_vb0 + d.vp_vbs * b : d.vp_vb1 - 9 * b) - 6;
+#pragma unroll
+    for (int c0 = 0; c0 < TR; c0 += CH) {
+        double bl[CH], h0[CH], h1[CH];
+        int gr[CH], gc[CH], ar[CH], ac[CH], hi[CH];
+#pragma unroll
+        for (int i = 0; i < CH; i++) {
+            bl[i] = h0[i] = h1[i] = 0.0;
+            gr[i] = gc[i] = hi[i] = 0;
+            ar[i] = ac[i] = 1;
+            if (c0 + i >= TR) break;
+            const int q0 = t + (c0 + i) * NT;
+            const int q = (q0 < NE) ? q0 : 0;   // (a lane past the block's end requests entry 0 and stores nothing)
+            const int r = q / PP, col = q % PP;
+            gr[i] = ((r < 6) ? pr_a : vb_a) + r;
+            gc[i] = ((col < 6) ? pr_b : vb_b) + col;
+            hi[i] = r * 30 + col;
+            bl[i] = blk[(r < 6 && col < 6) ? r * bstride + col : 0];
+        }
+        if (f.n > 0) {
+            const double* H = f.H0 + f.ro0 * 30 + f.co0;
+#pragma unroll
+            for (int i = 0; i < CH; i++) if (c0 + i < TR) h0[i] = H[hi[i]];
+        }
+        if (f.n > 1) {
+            const double* H = f.H1 + f.ro1 * 30 + f.co1;
+#pragma unroll
+            for (int i = 0; i < CH; i++) if (c0 + i < TR) h1[i] = H[hi[i]];
+        }
+        if (diag) {
+#pragma unroll
+            for (int i = 0; i < CH; i++) if (c0 + i < TR) { ar[i] = va[gr[i]]; ac[i] = va[gc[i]]; }
+        }
+#pragma unroll
+        for (int i = 0; i < CH; i++) {
+            if (c0 + i >= TR) break;
+            const int q = t + (c0 + i) * NT;
+            if (q >= NE) continue;
+            const int r = q / PP, col = q % PP;
+            if (!((mask >> ((r >= 6 ? 2 : 0) + (col >= 6 ? 1 : 0))) & 1)) continue;
+            double s = (r < 6 && col < 6) ? bl[i] : 0.0;
+            if (f.n > 0) s += h0[i];
+            if (f.n > 1) s += h1[i];
+            if (diag) {
+                if (!ar[i] || !ac[i]) s = (r == col) ? 1.0 : 0.0;  // vertex outside the index mapping
+                else if (r == col) s += lambda;                     // setLambda, block_solver.hpp:564-589
+            }
+            if (gr[i] >= gc[i]) S[(size_t)gr[i] * n + gc[i]] = s;
+            else if (!diag) S[(size_t)gc[i] * n + gr[i]] = s;
+        }
+    }
+}
+
 // adds the IMU blocks, applies the active-set / damping rules and writes one pdim x pdim block of S (lower
 // triangle only: the factorisation never reads above the diagonal)
-DEVI void schur_write_block(const Batch& B, const WinDesc& d, const WinCtrl& c, int w, int pr, int a, int b,
-                            const double* blk, int t = threadIdx.x, int nt = 64, int bstride = -1) {
+// LD = landmark dimension of the caller (inverse-depth windows have pdim 15), NT = lanes per pair (64 or 16), DIAG: a == b
+template <int LD, int NT, bool DIAG>
+DEVI void schur_write_block(const Batch& B, const WinDesc& d, const WinCtrl& c, const PairImu& f, int pr, int a, int b,
+                            const double* blk, int t, int bstride) {
     const int P = d.pdim, n = d.nS;
-    if (bstride < 0) bstride = P;
-    const bool diag = (a == b);
+    constexpr bool diag = DIAG;
     const double lambda = (d.algo == 1) ? c.lambda : 0.0;
-    const int qb = B.pimu_begin[d.pair0 + d.win + pr], qe = B.pimu_begin[d.pair0 + d.win + pr + 1];
+    const int qb = f.qb, qe = f.qb + f.n;
     const int* va = B.var_act + d.vec0;
     double* S = B.S + d.S0;
     // sub-blocks that no tile of the factor ever reads (structurally zero in L under the V/Bias-first order) are
     // not written at all: bit0 PRxPR, bit1 PRxVB, bit2 VBxPR, bit3 VBxVB (mask built with the tile lists at upload)
-    const int mask = B.pair_mask[d.pair0 + pr];
+    const int mask = f.mask;
     if (mask == 0) return;   // nothing of this block is ever read (or it keeps the zero of the upload)
     if (mask == 1 && !diag && qb == qe) {  // only the 6x6 PR x PR sub-block lands in a tile the factor reads, no IMU term
-        for (int q = t; q < 36; q += nt) {
+        for (int q = t; q < 36; q += NT) {
             const int r = q / 6, col = q % 6;
             const int gr = vpos(d, a, r), gc = vpos(d, b, col);
             const double s = blk[r * bstride + col];
@@ -951,7 +1053,11 @@ DEVI void schur_write_block(const Batch& B, const WinDesc& d, const WinCtrl& c, 
         }
         return;
     }
-    for (int q = t; q < P * P; q += nt) {
+    if (f.n <= 2) {
+        if (P == 15) { schur_write_block_imu<15, NT, DIAG>(B, d, lambda, mask, f, a, b, blk, t, bstride); return; }
+        if (LD == 3 && P == 6) { schur_write_block_imu<6, NT, DIAG>(B, d, lambda, mask, f, a, b, blk, t, bstride); return; }
+    }
+    for (int q = t; q < P * P; q += NT) {   // more than two factors on the pair
         const int r = q / P, col = q % P;
         if (!((mask >> ((r >= 6 ? 2 : 0) + (col >= 6 ? 1 : 0))) & 1)) continue;
         double s = (r < 6 && col < 6) ? blk[r * bstride + col] : 0.0;
@@ -1164,6 +1270,8 @@ DEVI void schur_off_body(const Batch& B, int max_quads, double* blk4, int w_in =
             }
         }
     }
+    PairImu f = {};
+    if (LP == 16 && have) f = pair_imu(B, d, pr);   // (one pair per wave, the few-window kernels: at the write -- the registers would cost a wave per SIMD)
     // fixed-order sums inside each LP-lane group (skipped when no pair of the wave has an item: most keyframe pairs of a window
     // share no landmark, and in distance order they fill whole waves)
     if (__ballot(ib < ie) != 0ull) {
@@ -1176,7 +1284,8 @@ DEVI void schur_off_body(const Batch& B, int max_quads, double* blk4, int w_in =
         for (int i = 0; i < 36; i++) blk[i] = acc[i];
     }
     __syncthreads();
-    if (have) schur_write_block(B, d, c, w, pr, a, b, blk, l16, LP, 6);
+    if (LP != 16 && have) f = pair_imu(B, d, pr);
+    if (have) schur_write_block<LD, LP, false>(B, d, c, f, pr, a, b, blk, l16, 6);
 }
 __global__ void __launch_bounds__(64, 2) k_schur_off(Batch B, int max_quads) {   // (the split form, VBA_SCHUR_SPLIT: not the default path)
     __shared__ double blk4[4 * 36];
@@ -1197,7 +1306,9 @@ __global__ void __launch_bounds__(64) k_schur_off3_w(Batch B, int max_quads) {
 
 // diagonal pairs (a,a): every slot of keyframe a; also the reduced rhs (block_solver.hpp:436-439), the
 // unreduced b_p and the H_pp diagonal (LM's lambda init)
-template <int LD>
+// EARLY: the pair's IMU list is fetched ahead of the reductions (the many-window kernel; in the few-window kernels the registers
+// this holds cost a wave per SIMD)
+template <int LD, bool EARLY = false>
 DEVI void schur_diag_body(const Batch& B, int max_free, int hd_pass, double* blk, double* sh_r, double* sh_b, double* sh_h,
                           int w_in = -1, int a_in = 0) {
     constexpr int SS = (LD == 1) ? VBA_SLOT : VBA_SLOT3;
@@ -1317,6 +1428,8 @@ DEVI void schur_diag_body(const Batch& B, int max_free, int hd_pass, double* blk
             }
         }
     }
+    PairImu f = {};
+    if (EARLY) f = pair_imu(B, d, pr);
 #pragma unroll
     for (int i = 0; i < 21; i++) acc[i] = wave_sum(acc[i]);
 #pragma unroll
@@ -1351,20 +1464,30 @@ DEVI void schur_diag_body(const Batch& B, int max_free, int hd_pass, double* blk
         }
     }
     __syncthreads();
-    if (!hd_pass) schur_write_block(B, d, c, w, pr, a, a, blk);   // (the hd pass only feeds lambda init and b_p)
+    if (!EARLY) f = pair_imu(B, d, pr);
+    // the rows of the right-hand side: their IMU terms and var_act are requested here, ahead of the block's loads and stores
+    double hb0 = 0.0, hh0 = 0.0, hb1 = 0.0, hh1 = 0.0;
+    int gr = 0, act_i = 0;
+    if (t < P) {
+        gr = vpos(d, a, t);
+        act_i = B.var_act[d.vec0 + gr];
+        if (f.n > 0) { hb0 = f.H0[900 + f.ro0 + t]; hh0 = f.H0[(f.ro0 + t) * 30 + f.ro0 + t]; }
+        if (f.n > 1) { hb1 = f.H1[900 + f.ro1 + t]; hh1 = f.H1[(f.ro1 + t) * 30 + f.ro1 + t]; }
+    }
+    if (!hd_pass) schur_write_block<LD, 64, true>(B, d, c, f, pr, a, a, blk, t, P);   // (the hd pass only feeds lambda init and b_p)
     if (t < P) {
         double s = 0.0, sb = 0.0, h = 0.0;
         if (t < 6) { s = sh_r[t]; sb = sh_b[t]; h = sh_h[t]; }
-        const int qb = B.pimu_begin[d.pair0 + d.win + pr], qe = B.pimu_begin[d.pair0 + d.win + pr + 1];
-        for (int m = qb; m < qe; m++) {
+        if (f.n > 0) { sb += hb0; h += hh0; }
+        if (f.n > 1) { sb += hb1; h += hh1; }
+        for (int m = f.qb + 2; m < f.qb + f.n; m++) {   // more than two factors on the keyframe
             const int k = B.pimu[2 * (size_t)(d.pimu0 + m)], role = B.pimu[2 * (size_t)(d.pimu0 + m) + 1];
             const double* H = B.imuH + VBA_IMUH * (size_t)(d.imu0 + k);
             const int ro = (role & 1) ? 15 : 0;
             sb += H[900 + ro + t];
             h += H[(ro + t) * 30 + ro + t];
         }
-        const int gr = vpos(d, a, t);
-        const bool act = B.var_act[d.vec0 + gr] != 0;
+        const bool act = act_i != 0;
         (B.vec + d.vec0)[gr] = act ? (sb + s) : 0.0;            // reduced rhs = b_p - sum W Dinv b_l
         (B.bpose + 2 * (size_t)d.vec0)[gr] = act ? sb : 0.0;        // unreduced b_p (LM computeScale)
         if (LD == 1 || hd_pass) (B.bpose + 2 * (size_t)d.vec0)[d.nS + gr] = act ? h : 0.0;  // H_pp diagonal (LM computeLambdaInit)
@@ -1382,7 +1505,8 @@ __global__ void __launch_bounds__(64, 3) k_schur_all(Batch B, int max_free, int 
     __shared__ double sh_r[6], sh_b[6], sh_h[6];
     int w, idx;
     if (!schur_map(B, max_free + max_quads, w, idx)) return;
-    if (idx < max_free) schur_diag_body<1>(B, max_free, 0, blk, sh_r, sh_b, sh_h, w, idx);
+    w = __builtin_amdgcn_readfirstlane(w); idx = __builtin_amdgcn_readfirstlane(idx);
+    if (idx < max_free) schur_diag_body<1, true>(B, max_free, 0, blk, sh_r, sh_b, sh_h, w, idx);
     else schur_off_body<1, 16>(B, max_quads, blk, w, idx - max_free);
 }
 // the same for fewer than 8 windows: one off-diagonal pair per wave (latency), still one launch
