@@ -123,7 +123,7 @@ typedef struct vba_profile {
     double total_ms;             /* first launch -> last launch of the run */
     double factor_flops;         /* FP64 flop the factorisation class executed on MFMA: 2*32^3 per tile product of the
                                     symbolic tile lists, per solve (structurally zero tiles are never touched) */
-    int64_t kernel_launches;     /* kernel launches the last vba_batch_run / vba_solve / vba_sim3_optimize / vba_sim3_ransac / vba_triangulate / vba_two_view_init (at most 2) / vba_search_triangulation / vba_posegraph_optimize enqueued (filled with or without profiling) */
+    int64_t kernel_launches;     /* kernel launches the last vba_batch_run / vba_solve / vba_sim3_optimize / vba_sim3_ransac / vba_triangulate / vba_two_view_init (at most 2) / vba_search_triangulation / vba_fuse / vba_posegraph_optimize enqueued (filled with or without profiling) */
 } vba_profile;
 
 /* One handle per host thread / GPU; owns device buffers and a stream.  Errors: nonzero return, message
@@ -178,7 +178,7 @@ int vba_batch_solve_b(void *handle, int32_t n_windows, vba_problem *const *inout
  *           every later one, those submitted afterwards included, with the same message: no GPU work starts for them (earlier
  *           tickets finish).  Waiting on an unknown or retired ticket returns -1.
  *   handle  while any ticket is submitted and not yet waited for, every synchronous entry point of the handle (vba_solve*,
- *           vba_batch_upload / run / download / solve*, vba_pose_optimize, vba_sim3_optimize, vba_sim3_ransac, vba_triangulate, vba_two_view_init, vba_search_triangulation, vba_posegraph_optimize, vba_preintegrate, vba_set_profile,
+ *           vba_batch_upload / run / download / solve*, vba_pose_optimize, vba_sim3_optimize, vba_sim3_ransac, vba_triangulate, vba_two_view_init, vba_search_triangulation, vba_fuse, vba_posegraph_optimize, vba_preintegrate, vba_set_profile,
  *           vba_batch_set_depth) returns -1 with "asynchronous batches pending: wait for them first"; afterwards the handle
  *           works synchronously as before.  vba_destroy finishes pending tickets (their results land) before it frees.
  *           Profiling (vba_set_profile) covers synchronous calls only.  One caller thread at a time, as everywhere. */
@@ -518,6 +518,89 @@ typedef struct vba_search_tri_result {
  * feature vector, and with check_orientation an angle outside [0, 360).  A pair's outputs do not depend on where it stands in the
  * batch. */
 int vba_search_triangulation(void *handle, int32_t n_pairs, vba_search_tri_problem *const *in, vba_search_tri_result *const *out);
+
+/* ---- projection search for map-point fusion ----
+ * The search half of both ORBmatcher::Fuse overloads (src/ORBmatcher.cpp:958-1119 and :1123-1254) with KeyFrame::GetFeaturesInArea
+ * (src/KeyFrame.cpp:1071-1115), IsInImage (:1119-1122) and MapPoint::PredictScale (src/MapPoint.cpp:529-540), monocular (mvuRight < 0,
+ * the `else` branch at :1070): the calls LocalMapping::SearchInNeighbors and LoopClosing::SearchAndFuse are made of.  One problem is
+ * one keyframe and one list of map points; one call takes any number of problems, ragged, in one kernel launch (256 points per
+ * workgroup).  A point's search reads the point and the keyframe's static data only, never the associations the function mutates, so
+ * the points are independent; the mutation (:1095-1115, :1234-1250) stays with the caller.  The reference is restated as it stands:
+ *   gates       p3Dc = Rcw p + tcw; z < 0 leaves (:991).  z == 0 passes: invz is infinite, u and v are infinite or NaN and the point
+ *               leaves at IsInImage, written as the positive conjunction u >= minX && u < maxX && v >= minY && v < maxY (:1004).
+ *               dist3D = |p - Ow| outside [dist_min, dist_max] (:1016), PO . Pn < cos_view * dist3D (:1023),
+ *               nPredictedLevel = ceil(log(pred_max / dist3D) / log_scale_factor) outside 0 .. n_levels - 1 (:1027)
+ *   area        GetFeaturesInArea(u, v, th * scale[level]) literally: floor for the first cell and CEIL for the last one, the four
+ *               early returns, the clamps to the grid, fabs(dx) < r && fabs(dy) < r.  Candidates come in cell order (ix outer, iy
+ *               inner) and inside a cell in list order
+ *   candidate   skipped when kpLevel < nPredictedLevel - 1 || kpLevel > nPredictedLevel (:1052) and, with check_reproj, when
+ *               (ex^2 + ey^2) * inv_level_sigma2[kpLevel] > chi2_reproj (:1072-1080); dist < bestDist is strict (:1087), so among equal
+ *               distances the first in walk order wins
+ * One deviation: the Sim3 overload has no range check in front of mvScaleFactors[nPredictedLevel] (:1196-1200) and PredictScale
+ * does not clamp, so with dist3D in [0.8 min, 1.2 max] the reference can read outside the vector.  vba_fuse applies the check of
+ * :1027 in both modes (state 6).
+ * `state` says where a point left the function, numbered in the order of the reference's exits:
+ *   0  bestDist <= th_low (:1095): the caller applies :1097-1114 or :1236-1249
+ *   1  skipped by the caller's `skip`
+ *   2  z < 0 (:991)
+ *   3  not in the image (:1004)
+ *   4  dist3D outside [dist_min, dist_max] (:1016)
+ *   5  viewing angle (:1023)
+ *   6  predicted level outside 0 .. n_levels - 1 (:1027)
+ *   7  no keypoint in the area (:1034)
+ *   8  keypoints in the area but bestDist > th_low; best_idx and best_dist are what the loop left (-1 and 256 when every candidate
+ *      failed the level or reprojection test)
+ * All floating point is FP64 on the float32 inputs widened; the reference computes in float32 (gives
+ * the measured difference). */
+typedef struct vba_fuse_problem {
+    double Rcw[9], tcw[3], Ow[3];    /* row-major GetRotation(), GetTranslation(), GetCameraCenter(); for the Sim3 overload the caller
+                                        decomposes Scw as :1134-1138 does */
+    double K[4];                     /* fx fy cx cy */
+    double bounds[4];                /* mnMinX mnMaxX mnMinY mnMaxY */
+    int32_t n_keys;                  /* pKF->N */
+    int32_t n_levels;                /* mnScaleLevels, 1 .. 64 */
+    const uint8_t *desc;             /* [n_keys][32] mDescriptors */
+    const double *uv;                /* [n_keys][2] mvKeysUn[idx].pt */
+    const uint8_t *oct;              /* [n_keys] mvKeysUn[idx].octave */
+    const double *scale;             /* [n_levels] mvScaleFactors (:1031) */
+    const double *inv_level_sigma2;  /* [n_levels] mvInvLevelSigma2 (:1079) */
+    double log_scale_factor;         /* mfLogScaleFactor */
+    int32_t grid_cols, grid_rows;    /* mnGridCols, mnGridRows (64 x 48); >= 1, cols * rows <= 65536 */
+    double grid_inv_w, grid_inv_h;   /* mfGridElementWidthInv, mfGridElementHeightInv */
+    const int32_t *cell_begin;       /* [cols * rows + 1] cell (ix, iy) at ix * rows + iy lists cell_feat[cell_begin[c] .. cell_begin[c + 1]) */
+    const int32_t *cell_feat;        /* keypoint indices in the order mGrid[ix][iy] holds them; each keypoint at most once */
+    int32_t n_pt;                    /* vpMapPoints.size() */
+    int32_t th_low;                  /* TH_LOW = 50 (:1095); 0 .. 256 */
+    const double *pos, *normal;      /* [n_pt][3] GetWorldPos(), GetNormal() */
+    const double *dist_min, *dist_max; /* [n_pt] GetMinDistanceInvariance(), GetMaxDistanceInvariance() as the reference returns them */
+    const double *pred_max;          /* [n_pt] mfMaxDistance, which PredictScale reads */
+    const uint8_t *pt_desc;          /* [n_pt][32] GetDescriptor() */
+    const uint8_t *skip;             /* [n_pt] non-zero: the caller's test of :980-984 or :1154 (NULL, bad, already in the keyframe) */
+    double th;                       /* the radius factor: 3.0 for :958, the caller's value for :1123 */
+    double cos_view;                 /* 0.5 (:1023) */
+    int32_t check_reproj;            /* the gate of :1072-1080 exists in the first overload only: the Sim3 caller passes 0 */
+    double chi2_reproj;              /* 5.99 (:1079) */
+} vba_fuse_problem;
+
+typedef struct vba_fuse_result {
+    int32_t status;           /* VBA_OK */
+    int32_t n_found;          /* points in state 0 (summed on the host) */
+    int32_t *best_idx;        /* [n_pt] caller-allocated: bestIdx; -1 unless state 0 or 8 */
+    uint16_t *best_dist;      /* [n_pt] caller-allocated: bestDist; 256 when no candidate passed */
+    int8_t *level;            /* [n_pt] caller-allocated: nPredictedLevel for the states 0, 7 and 8, the out-of-range value itself clamped
+                                 to int8 for state 6, -128 otherwise */
+    double *uv;               /* [n_pt][2] caller-allocated: the projection for the states 0 and 3 .. 8, NaN otherwise */
+    uint8_t *state;           /* [n_pt] caller-allocated: the codes above */
+} vba_fuse_result;
+
+/* Synchronous, like vba_search_triangulation; -1 while asynchronous tickets are pending.  n_problems == 0 returns 0; a problem with
+ * n_pt == 0 or n_keys == 0 is legal.  A bad problem fails the whole call before any GPU work with "vba_fuse: problem K: <why>"
+ * through vba_last_error: a NULL problem or result, a negative count, a NULL array with a non-zero count (the result arrays are
+ * required when n_pt > 0), n_levels outside 1 .. 64, an octave >= n_levels, th_low outside 0 .. 256, grid sizes outside their range,
+ * a cell_begin that does not start at 0, decreases or ends above n_keys, a cell_feat entry out of range or listed twice, any
+ * non-finite pose, intrinsic, bound, pixel, level table, position, normal, distance or threshold.  A problem's outputs do not depend
+ * on where it stands in the batch. */
+int vba_fuse(void *handle, int32_t n_problems, vba_fuse_problem *const *in, vba_fuse_result *const *out);
 
 /* ---- essential-graph optimisation (Sim3 pose graph) ----
  * Optimizer::OptimizeEssentialGraph(Map*, KeyFrame* pLoopKF, KeyFrame* pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections,

@@ -946,6 +946,157 @@ class SearchTriResultBuf:
                                self.bd[:self.n].copy(), self.st[:self.n].copy(), self.pr[:max(min(s.n_matches, self.n), 0)].copy())
 
 
+# ---- projection search for map-point fusion (include/vislam_ba.h: vba_fuse_problem / vba_fuse_result) ----
+_pu16 = C.POINTER(C.c_uint16)
+_pi8 = C.POINTER(C.c_int8)
+
+
+class vba_fuse_problem(C.Structure):
+    _fields_ = [
+        ("Rcw", C.c_double * 9), ("tcw", C.c_double * 3), ("Ow", C.c_double * 3), ("K", C.c_double * 4), ("bounds", C.c_double * 4),
+        ("n_keys", C.c_int32), ("n_levels", C.c_int32), ("desc", _pu8), ("uv", _pd), ("oct", _pu8), ("scale", _pd), ("inv_level_sigma2", _pd),
+        ("log_scale_factor", C.c_double), ("grid_cols", C.c_int32), ("grid_rows", C.c_int32), ("grid_inv_w", C.c_double), ("grid_inv_h", C.c_double),
+        ("cell_begin", _pi), ("cell_feat", _pi), ("n_pt", C.c_int32), ("th_low", C.c_int32), ("pos", _pd), ("normal", _pd), ("dist_min", _pd),
+        ("dist_max", _pd), ("pred_max", _pd), ("pt_desc", _pu8), ("skip", _pu8), ("th", C.c_double), ("cos_view", C.c_double),
+        ("check_reproj", C.c_int32), ("chi2_reproj", C.c_double),
+    ]
+
+
+class vba_fuse_result(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_found", C.c_int32), ("best_idx", _pi), ("best_dist", _pu16), ("level", _pi8), ("uv", _pd), ("state", _pu8)]
+
+
+(FU_FOUND, FU_SKIPPED, FU_BEHIND, FU_NOT_IN_IMAGE, FU_DISTANCE, FU_VIEW_ANGLE, FU_LEVEL, FU_EMPTY_AREA, FU_NO_MATCH) = range(9)
+
+
+def grid_csr(uv, bounds, cols, rows, inv_w, inv_h):
+    """Frame::AssignFeaturesToGrid with PosInGrid as (cell_begin, cell_feat): posX = round((x - mnMinX) * mfGridElementWidthInv) in
+    float32 with C round, a keypoint outside 0 .. cols - 1 x 0 .. rows - 1 is in no cell; cell (ix, iy) stands at ix * rows + iy and
+    lists its keypoints in ascending index order, as the push_back loop leaves them"""
+    uv = np.asarray(uv, dtype=np.float32).reshape(-1, 2)
+
+    def c_round(t):
+        return (np.sign(t) * np.floor(np.abs(t) + np.float32(0.5))).astype(np.int64)
+
+    px = c_round((uv[:, 0] - np.float32(bounds[0])) * np.float32(inv_w))
+    py = c_round((uv[:, 1] - np.float32(bounds[2])) * np.float32(inv_h))
+    ok = (px >= 0) & (px < cols) & (py >= 0) & (py < rows)
+    cell = (px * rows + py)[ok]
+    idx = np.nonzero(ok)[0]
+    begin = np.zeros(cols * rows + 1, dtype=np.int32)
+    begin[1:] = np.cumsum(np.bincount(cell, minlength=cols * rows))
+    return begin, idx[np.argsort(cell, kind="stable")].astype(np.int32)
+
+
+@dataclass
+class FuseProblem:
+    """One ORBmatcher::Fuse call (src/ORBmatcher.cpp:958-1254, the search half) as flat arrays: one keyframe with its grid in CSR form
+    and one list of map points."""
+    Rcw: np.ndarray                # [3,3]
+    tcw: np.ndarray                # [3]
+    Ow: np.ndarray                 # [3]
+    K: np.ndarray                  # [4] fx fy cx cy
+    bounds: np.ndarray             # [4] mnMinX mnMaxX mnMinY mnMaxY
+    desc: np.ndarray               # [n_keys,32] uint8
+    uv: np.ndarray                 # [n_keys,2]
+    oct: np.ndarray                # [n_keys] uint8
+    scale: np.ndarray              # [n_levels]
+    inv_level_sigma2: np.ndarray   # [n_levels]
+    log_scale_factor: float
+    grid_cols: int
+    grid_rows: int
+    grid_inv_w: float
+    grid_inv_h: float
+    cell_begin: np.ndarray         # [cols * rows + 1] int32
+    cell_feat: np.ndarray          # int32
+    pos: np.ndarray                # [n_pt,3]
+    normal: np.ndarray             # [n_pt,3]
+    dist_min: np.ndarray           # [n_pt]
+    dist_max: np.ndarray           # [n_pt]
+    pred_max: np.ndarray           # [n_pt]
+    pt_desc: np.ndarray            # [n_pt,32] uint8
+    skip: np.ndarray               # [n_pt] uint8
+    th: float = 3.0
+    th_low: int = 50
+    cos_view: float = 0.5
+    check_reproj: bool = True
+    chi2_reproj: float = 5.99
+    truth: dict = field(default_factory=dict)
+
+    def __post_init__(self):
+        u8 = lambda a, shape: np.ascontiguousarray(a, dtype=np.uint8).reshape(shape)
+        self.Rcw = _f64(self.Rcw, (3, 3)); self.tcw = _f64(self.tcw, (3,)); self.Ow = _f64(self.Ow, (3,))
+        self.K = _f64(self.K, (4,)); self.bounds = _f64(self.bounds, (4,))
+        self.desc = u8(self.desc, (-1, 32)); self.oct = u8(self.oct, (-1,)); self.uv = _f64(self.uv, (-1, 2))
+        self.scale = _f64(self.scale, (-1,)); self.inv_level_sigma2 = _f64(self.inv_level_sigma2, (-1,))
+        self.cell_begin = _i32(self.cell_begin).reshape(-1); self.cell_feat = _i32(self.cell_feat).reshape(-1)
+        self.pos = _f64(self.pos, (-1, 3)); self.normal = _f64(self.normal, (-1, 3))
+        self.dist_min = _f64(self.dist_min, (-1,)); self.dist_max = _f64(self.dist_max, (-1,)); self.pred_max = _f64(self.pred_max, (-1,))
+        self.pt_desc = u8(self.pt_desc, (-1, 32)); self.skip = u8(self.skip, (-1,))
+
+    n_keys = property(lambda self: self.desc.shape[0])
+    n_pt = property(lambda self: self.pos.shape[0])
+    n_levels = property(lambda self: self.scale.shape[0])
+
+    def copy(self, **changes):
+        import copy as _c
+        q = _c.copy(self)
+        for k, v in changes.items():
+            setattr(q, k, v)
+        q.__post_init__()
+        return q
+
+    def as_struct(self) -> vba_fuse_problem:
+        s = vba_fuse_problem()
+        p = lambda a, t: a.ctypes.data_as(t)
+        s.Rcw[:] = self.Rcw.ravel().tolist(); s.tcw[:] = self.tcw.tolist(); s.Ow[:] = self.Ow.tolist()
+        s.K[:] = self.K.tolist(); s.bounds[:] = self.bounds.tolist()
+        s.n_keys, s.n_levels, s.n_pt = self.n_keys, self.n_levels, self.n_pt
+        s.desc, s.uv, s.oct = p(self.desc, _pu8), p(self.uv, _pd), p(self.oct, _pu8)
+        s.scale, s.inv_level_sigma2 = p(self.scale, _pd), p(self.inv_level_sigma2, _pd)
+        s.log_scale_factor = float(self.log_scale_factor)
+        s.grid_cols, s.grid_rows, s.grid_inv_w, s.grid_inv_h = int(self.grid_cols), int(self.grid_rows), float(self.grid_inv_w), float(self.grid_inv_h)
+        s.cell_begin, s.cell_feat = p(self.cell_begin, _pi), p(self.cell_feat, _pi)
+        s.pos, s.normal, s.dist_min, s.dist_max, s.pred_max = p(self.pos, _pd), p(self.normal, _pd), p(self.dist_min, _pd), p(self.dist_max, _pd), p(self.pred_max, _pd)
+        s.pt_desc, s.skip = p(self.pt_desc, _pu8), p(self.skip, _pu8)
+        s.th, s.th_low, s.cos_view = float(self.th), int(self.th_low), float(self.cos_view)
+        s.check_reproj, s.chi2_reproj = int(bool(self.check_reproj)), float(self.chi2_reproj)
+        return s
+
+
+@dataclass
+class FuseResult:
+    status: int
+    n_found: int
+    best_idx: np.ndarray            # [n_pt] int32
+    best_dist: np.ndarray           # [n_pt] uint16
+    level: np.ndarray               # [n_pt] int8
+    uv: np.ndarray                  # [n_pt,2]
+    state: np.ndarray               # [n_pt] uint8
+
+
+class FuseResultBuf:
+    """Caller-allocated result storage of one problem."""
+
+    def __init__(self, p: FuseProblem):
+        self.n = p.n_pt
+        m = max(self.n, 1)
+        self.bi = np.full(m, -7, dtype=np.int32)
+        self.bd = np.full(m, 7, dtype=np.uint16)
+        self.lv = np.full(m, 77, dtype=np.int8)
+        self.uv = np.full((m, 2), -7.0)
+        self.st = np.full(m, 255, dtype=np.uint8)
+        self.s = vba_fuse_result()
+        self.s.status, self.s.n_found = -7, -7
+        self.s.best_idx, self.s.best_dist, self.s.level, self.s.uv, self.s.state = (self.bi.ctypes.data_as(_pi), self.bd.ctypes.data_as(_pu16),
+                                                                                  self.lv.ctypes.data_as(_pi8), self.uv.ctypes.data_as(_pd),
+                                                                                  self.st.ctypes.data_as(_pu8))
+
+    def get(self) -> FuseResult:
+        n = self.n
+        return FuseResult(self.s.status, self.s.n_found, self.bi[:n].copy(), self.bd[:n].copy(), self.lv[:n].copy(), self.uv[:n].copy(), self.st[:n].copy())
+
+
 # ---- essential-graph optimisation (include/vislam_ba.h: vba_posegraph_problem / vba_posegraph_result) ----
 class vba_posegraph_problem(C.Structure):
     _fields_ = [

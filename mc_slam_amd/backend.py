@@ -19,7 +19,7 @@ _libs = {}
 EXPORTS = ["vba_create", "vba_destroy", "vba_last_error", "vba_solve", "vba_batch_upload", "vba_batch_run",
            "vba_batch_download", "vba_batch_solve", "vba_solve_b", "vba_batch_run_b", "vba_batch_solve_b", "vba_preintegrate", "vba_pose_optimize", "vba_problem_save", "vba_problem_load", "vba_problem_free", "vba_set_profile", "vba_get_profile", "vba_host_threads",
            "vba_batch_set_depth", "vba_batch_submit", "vba_batch_submit_b", "vba_batch_poll", "vba_batch_wait", "vba_sim3_optimize",
-           "vba_posegraph_optimize", "vba_sim3_ransac", "vba_triangulate", "vba_two_view_init", "vba_search_triangulation"]
+           "vba_posegraph_optimize", "vba_sim3_ransac", "vba_triangulate", "vba_two_view_init", "vba_search_triangulation", "vba_fuse"]
 
 
 def load_library(hooks=False):
@@ -58,6 +58,7 @@ def load_library(hooks=False):
                                       C.POINTER(C.POINTER(abi.vba_two_view_result))]
     lib.vba_search_triangulation.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.POINTER(abi.vba_search_tri_problem)),
                                              C.POINTER(C.POINTER(abi.vba_search_tri_result))]
+    lib.vba_fuse.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.POINTER(abi.vba_fuse_problem)), C.POINTER(C.POINTER(abi.vba_fuse_result))]
     lib.vba_posegraph_optimize.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.POINTER(abi.vba_posegraph_problem)),
                                            C.POINTER(C.POINTER(abi.vba_posegraph_result))]
     lib.vba_set_profile.argtypes = [C.c_void_p, C.c_int32]
@@ -372,6 +373,26 @@ class LocalBA:
         """vba_search_triangulation on a list of abi.SearchTriProblem (one keyframe pair each): list of abi.SearchTriResult"""
         packed = self.search_triangulation_pack(problems)
         self.search_triangulation_call(packed)
+        return [b.get() for b in packed[2]]
+
+    # ---- projection search for map-point fusion (vba_fuse): a batch of (keyframe, point list) problems per call ----
+    def fuse_pack(self, problems):
+        """ctypes views of a list of abi.FuseProblem for vba_fuse (kept alive by the returned tuple)"""
+        n = len(problems)
+        structs = [p.as_struct() for p in problems]
+        bufs = [abi.FuseResultBuf(p) for p in problems]
+        pp = (C.POINTER(abi.vba_fuse_problem) * n)(*[C.pointer(s) for s in structs])
+        rr = (C.POINTER(abi.vba_fuse_result) * n)(*[C.pointer(b.s) for b in bufs])
+        return n, structs, bufs, pp, rr, problems
+
+    def fuse_call(self, packed):
+        if self.lib.vba_fuse(self.h, packed[0], packed[3], packed[4]) != 0:
+            raise self._err("vba_fuse")
+
+    def fuse(self, problems):
+        """vba_fuse on a list of abi.FuseProblem (one keyframe and one point list each): list of abi.FuseResult"""
+        packed = self.fuse_pack(problems)
+        self.fuse_call(packed)
         return [b.get() for b in packed[2]]
 
     # ---- essential-graph optimisation (vba_posegraph_optimize): a batch of independent Sim3 pose graphs per call ----

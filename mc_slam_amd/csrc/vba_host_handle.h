@@ -198,7 +198,7 @@ struct Handle {
     bool owns_streams = true;
     std::string err;
     DevBuf buf[BUF_N];
-    SideArena preint, pose, sim3, pg, ransac, tri, tv, st;   // vba_preintegrate (dev only), vba_pose_optimize, vba_sim3_optimize, vba_posegraph_optimize, vba_sim3_ransac, vba_triangulate, vba_two_view_init, vba_search_triangulation
+    SideArena preint, pose, sim3, pg, ransac, tri, tv, st, fu;   // vba_preintegrate (dev only), vba_pose_optimize, vba_sim3_optimize, vba_posegraph_optimize, vba_sim3_ransac, vba_triangulate, vba_two_view_init, vba_search_triangulation, vba_fuse
     // small batches (UploadPlan::arena_on): every host-built array of an upload goes through ONE pinned arena and ONE H2D copy
     struct Pending { int id; const void* src; size_t bytes; };
     std::vector<Pending> pending;

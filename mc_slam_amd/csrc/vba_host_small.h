@@ -1,7 +1,7 @@
 // vba_host_small.h -- host side of the library, part 5: the drivers of the small-problem entry points (vba_preintegrate,
-// vba_pose_optimize, vba_sim3_optimize, vba_sim3_ransac, vba_triangulate, vba_two_view_init, vba_search_triangulation, vba_posegraph_optimize).  Each lays its arena out once (vba_host_arena.h), packs the
+// vba_pose_optimize, vba_sim3_optimize, vba_sim3_ransac, vba_triangulate, vba_two_view_init, vba_search_triangulation, vba_fuse, vba_posegraph_optimize).  Each lays its arena out once (vba_host_arena.h), packs the
 // pinned staging block with the plain-C++ half of its topic (vba_host_pose.h, vba_host_sim3.h, vba_host_sim3_ransac.h,
-// vba_host_triangulate.h, vba_host_two_view.h, vba_host_search_tri.h, vba_host_posegraph.h), and does one
+// vba_host_triangulate.h, vba_host_two_view.h, vba_host_search_tri.h, vba_host_fuse.h, vba_host_posegraph.h), and does one
 // H2D copy, one or two launches and one D2H copy on the handle's stream.  No entry point shares its arena with another.
 #pragma once
 #include "vba_host_pose.h"
@@ -10,6 +10,7 @@
 #include "vba_host_triangulate.h"
 #include "vba_host_two_view.h"
 #include "vba_host_search_tri.h"
+#include "vba_host_fuse.h"
 #include "vba_host_posegraph.h"
 
 namespace {
@@ -262,6 +263,44 @@ int search_triangulation(Handle* h, int32_t n_pairs, vba_search_tri_problem* con
     for (int f = 0; f < n_pairs; f++)
         vba_host::unpack_search_tri(out[f], desc[f], res[f], at<int32_t>(hout, A.L.in_back(A.match12)), at<unsigned char>(hout, A.L.in_back(A.best_dist)),
                                     at<unsigned char>(hout, A.L.in_back(A.state)));
+    return 0;
+}
+
+// The search half of both ORBmatcher::Fuse overloads (src/ORBmatcher.cpp:958-1254, monocular) for a batch of (keyframe, point list)
+// problems: the host lays out the tile table while it packs, k_fuse runs one workgroup per tile of 256 points, one launch
+int fuse(Handle* h, int32_t n_problems, vba_fuse_problem* const* in, vba_fuse_result* const* out) {
+    if (n_problems < 0 || (n_problems > 0 && (!in || !out))) return fail(h, "vba_fuse: bad arguments");
+    if (n_problems == 0) return 0;
+    vba_host::FuseTotals T;
+    std::string err;
+    if (vba_host::check_fuse(n_problems, in, out, T, err)) return fail(h, "vba_fuse: " + err);
+    HIPCHK(h, hipSetDevice(h->device));
+    const vba_host::FuseArena A(n_problems, T);
+    HIPCHK(h, h->fu.ensure(A.L, A.L.back_bytes()));
+    void *hin = h->fu.in.p, *hout = h->fu.out.p, *base = h->fu.dev.p;
+    FuDesc* desc = at<FuDesc>(hin, A.desc);
+    const size_t n_tiles = vba_host::describe_fuse(n_problems, in, desc, at<FuTile>(hin, A.tile));
+    host_parallel_for(h, n_problems, small_pack_threads(n_problems), [&](int f) {
+        vba_host::pack_fuse(in[f], desc[f], at<FuKey>(hin, A.key), at<FuPoint>(hin, A.pt), at<int32_t>(hin, A.cell), at<int32_t>(hin, A.feat),
+                            at<double>(hin, A.lev));
+    });
+    FuBatch B;
+    B.desc = at<FuDesc>(base, A.desc); B.tile = at<FuTile>(base, A.tile); B.key = at<FuKey>(base, A.key); B.pt = at<FuPoint>(base, A.pt);
+    B.cell_begin = at<int>(base, A.cell); B.cell_feat = at<int>(base, A.feat); B.lev = at<double>(base, A.lev);
+    B.best_idx = at<int>(base, A.best_idx); B.best_dist = at<unsigned short>(base, A.best_dist); B.level = at<signed char>(base, A.level);
+    B.uv = at<double>(base, A.uv); B.state = at<unsigned char>(base, A.state);
+    const long long launch0 = h->n_launch;
+    if (n_tiles > 0) {   // a call whose problems all have no points has nothing to search
+        HIPCHK(h, hipMemcpyAsync(base, hin, A.L.upload_bytes(), hipMemcpyHostToDevice, h->stream));
+        VBA_LAUNCH(k_fuse, dim3((unsigned)n_tiles), dim3(FU_NT), 0, h->stream, B);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipMemcpyAsync(hout, B.best_idx, A.L.back_bytes(), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    h->prof.kernel_launches = h->n_launch - launch0;
+    for (int f = 0; f < n_problems; f++)
+        vba_host::unpack_fuse(out[f], desc[f], at<int32_t>(hout, A.L.in_back(A.best_idx)), at<uint16_t>(hout, A.L.in_back(A.best_dist)),
+                              at<int8_t>(hout, A.L.in_back(A.level)), at<double>(hout, A.L.in_back(A.uv)), at<unsigned char>(hout, A.L.in_back(A.state)));
     return 0;
 }
 

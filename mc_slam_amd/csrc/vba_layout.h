@@ -203,6 +203,35 @@ struct StOut {
 };
 static_assert(sizeof(StKey) == 64 && sizeof(StQuery) == 16 && sizeof(StDesc) == 160 && sizeof(StOut) == 144,
               "scripts/search_tri_bench.py derives the copied bytes from these sizes");
+// vba_fuse (vba_fuse.h)
+#define VBA_FU_NT 256          // lanes of a workgroup = most points of a tile
+#define VBA_FU_CONST 29        // doubles of a problem's constants: Rcw (9) tcw (3) Ow (3) K (4) bounds (4) grid_inv_w grid_inv_h
+                               // log_scale_factor th cos_view chi2_reproj
+struct alignas(16) FuKey {     // one keypoint, 64 bytes: the descriptor in the first half, pixel and octave in the second
+    unsigned int d[8];         // the row of mDescriptors
+    double u, v;               // mvKeysUn[idx].pt
+    unsigned char oct;         // mvKeysUn[idx].octave
+    unsigned char pad[15];
+};
+struct alignas(16) FuPoint {   // one map point, 128 bytes
+    unsigned int d[8];         // GetDescriptor()
+    double pos[3], normal[3];
+    double dist_min, dist_max, pred_max;
+    int skip;
+    int pad[5];
+};
+struct FuTile {                // one workgroup: the points first .. first + 255 of problem prob
+    int prob, first;
+};
+struct FuDesc {
+    long long key0, pt0, cell0, feat0, lev0;   // offsets of the problem's keypoint records, point records (and outputs), cell_begin copy,
+                                               // cell_feat copy and level tables in the concatenated arrays
+    int n_keys, n_pt, n_levels, th_low;
+    int cols, rows, check_reproj, pad;
+    double c[VBA_FU_CONST];
+};
+static_assert(sizeof(FuKey) == 64 && sizeof(FuPoint) == 128 && sizeof(FuTile) == 8 && sizeof(FuDesc) == 304,
+              "scripts/fuse_bench.py derives the copied bytes from these sizes");
 // vba_posegraph_optimize (vba_posegraph.h)
 struct PgDesc {
     int nv, ne, nf, npair;

@@ -2,9 +2,9 @@
 // side by topic (vba_host_structure.h / vba_host_posegraph.h: the plain-C++ structure builds, vba_host_handle.h: handle and buffers,
 // vba_host_upload.h: H2D + structure build, vba_host_run.h: the lock-step launch schedule of the two-stage solve and the download,
 // vba_host_batch.h: lanes and tickets, vba_host_small.h: the small-problem entry points over their plain-C++ halves
-// vba_host_pose.h / vba_host_sim3.h / vba_host_sim3_ransac.h / vba_host_triangulate.h / vba_host_two_view.h / vba_host_search_tri.h / vba_host_posegraph.h, vba_host_hooks.h), and below the extern "C"
+// vba_host_pose.h / vba_host_sim3.h / vba_host_sim3_ransac.h / vba_host_triangulate.h / vba_host_two_view.h / vba_host_search_tri.h / vba_host_fuse.h / vba_host_posegraph.h, vba_host_hooks.h), and below the extern "C"
 // entry points: vba_create / destroy / last_error, vba_solve*, vba_batch_upload / run / download / solve*, vba_batch_set_depth /
-// submit* / poll / wait, vba_preintegrate, vba_pose_optimize, vba_triangulate (new map points), vba_two_view_init (monocular initialisation), vba_search_triangulation (the matcher in front of vba_triangulate), vba_sim3_ransac, vba_sim3_optimize, vba_posegraph_optimize (the last
+// submit* / poll / wait, vba_preintegrate, vba_pose_optimize, vba_triangulate (new map points), vba_two_view_init (monocular initialisation), vba_search_triangulation (the matcher in front of vba_triangulate), vba_fuse (the projection search of map-point fusion), vba_sim3_ransac, vba_sim3_optimize, vba_posegraph_optimize (the last
 // three are the solver stages of loop closing), vba_host_threads, vba_set_profile / get_profile.
 //
 // Host-side control flow restated from src/Optimizer.cpp:453-517 (two-stage protocol) and
@@ -23,6 +23,7 @@
 #include "vba_triangulate.h"
 #include "vba_two_view.h"
 #include "vba_search_tri.h"
+#include "vba_fuse.h"
 #include "vba_posegraph.h"
 #include "vba_structure.h"
 #include "vba_pcg.h"
@@ -65,7 +66,7 @@ int vba_destroy(void* handle) {
 #ifdef VBA_TEST_HOOKS
     for (auto& b : h->cap) b.release();
 #endif
-    for (SideArena* a : {&h->preint, &h->pose, &h->sim3, &h->pg, &h->ransac, &h->tri, &h->tv, &h->st}) a->release();
+    for (SideArena* a : {&h->preint, &h->pose, &h->sim3, &h->pg, &h->ransac, &h->tri, &h->tv, &h->st, &h->fu}) a->release();
     for (auto e : h->evt_pool) (void)hipEventDestroy(e);
     if (h->up_done) (void)hipEventDestroy(h->up_done);
     if (h->owns_streams)
@@ -197,6 +198,11 @@ int vba_search_triangulation(void* handle, int32_t n_pairs, vba_search_tri_probl
     Handle* h = reinterpret_cast<Handle*>(handle);
     if (!h || async_busy(h)) return -1;
     return search_triangulation(h, n_pairs, in, out);
+}
+int vba_fuse(void* handle, int32_t n_problems, vba_fuse_problem* const* in, vba_fuse_result* const* out) {
+    Handle* h = reinterpret_cast<Handle*>(handle);
+    if (!h || async_busy(h)) return -1;
+    return fuse(h, n_problems, in, out);
 }
 int vba_posegraph_optimize(void* handle, int32_t n_graphs, vba_posegraph_problem* const* inout, vba_posegraph_result* const* out) {
     Handle* h = reinterpret_cast<Handle*>(handle);

@@ -3,6 +3,10 @@
 // ORBmatcher::SearchForTriangulation over vba_search_triangulation in the overload without one --, ONE vba_triangulate call
 // per neighbour (the matcher of neighbour i + 1 must see the points created from neighbour i, so the pairs of a keyframe cannot
 // share a call here), and the map-point construction for every accepted match in match order.
+// LocalMapping::SearchInNeighbors (:1550-1655), steps 2 and 3, over ORBmatcher::Fuse: ONE vba_fuse call per Fuse call, in the
+// reference's order.  MapPoint::Replace ends in ComputeDistinctiveDescriptors, so the Fuse call of target i + 1 may see a
+// descriptor that the call of target i changed (and points it made bad or put into keyframes): the targets cannot share a call
+// without changing an answer.
 #include <cmath>
 #include <iostream>
 
@@ -126,6 +130,33 @@ Mat3f LocalMapping::ComputeF12(KeyFrame* pKF1, KeyFrame* pKF2) {
     Mat3f out;
     for (int i = 0; i < 9; i++) out[i] = (float)F[i];
     return out;
+}
+
+int LocalMapping::SearchInNeighbors(KeyFrame* pKF, const std::vector<KeyFrame*>& vpTargetKFs) {
+    ORBmatcher matcher;                                                                    // :1584
+    int nFusedAll = 0;
+    // step 2 (:1588-1597): the current keyframe's map points into every target
+    const std::vector<MapPoint*> vpMapPointMatches = pKF->GetMapPointMatches();
+    for (KeyFrame* pKFi : vpTargetKFs) {
+        const int n = matcher.Fuse(pKFi, vpMapPointMatches);
+        if (n < 0) return -1;
+        nFusedAll += n;
+    }
+    // step 3 (:1600-1632): every good map point of the targets, once, into the current keyframe
+    std::vector<MapPoint*> vpFuseCandidates;
+    vpFuseCandidates.reserve(vpTargetKFs.size() * vpMapPointMatches.size());
+    for (KeyFrame* pKFi : vpTargetKFs) {
+        const std::vector<MapPoint*> vpMapPointsKFi = pKFi->GetMapPointMatches();
+        for (MapPoint* pMP : vpMapPointsKFi) {
+            if (!pMP) continue;
+            if (pMP->isBad() || pMP->mnFuseCandidateForKF == pKF->mnId) continue;
+            pMP->mnFuseCandidateForKF = pKF->mnId;
+            vpFuseCandidates.push_back(pMP);
+        }
+    }
+    const int n = matcher.Fuse(pKF, vpFuseCandidates);
+    if (n < 0) return -1;
+    return nFusedAll + n;
 }
 
 int LocalMapping::CreateNewMapPoints(KeyFrame* pKF, const std::vector<KeyFrame*>& vpNeighKFs, Map* pMap, std::list<MapPoint*>& lpRecentAddedMapPoints) {

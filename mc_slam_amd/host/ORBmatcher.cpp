@@ -1,9 +1,13 @@
 // ORBmatcher.cpp -- ORBmatcher::SearchForTriangulation (src/ORBmatcher.cpp:760-955, monocular) over vba_search_triangulation: the
 // keyframe pair as flat arrays (descriptors, map-point flags, the feature vectors in CSR form, keypoints, the level tables of
-// keyframe 2), the epipole in float32 as :768-775, ONE call, vMatchedPairs from the result.
+// keyframe 2), the epipole in float32 as :768-775, ONE call, vMatchedPairs from the result.  And both ORBmatcher::Fuse overloads
+// (:958-1254, monocular) over vba_fuse: the keyframe with its grid in CSR form and the point list as flat arrays, ONE call for the
+// search, then the reference's apply loop in list order on the live map.
 #include "ORBmatcher.h"
 
+#include <cstring>
 #include <iostream>
+#include <set>
 
 #include "../../include/vislam_ba.h"
 #include "Optimizer.h"
@@ -113,6 +117,172 @@ int ORBmatcher::SearchForTriangulation(KeyFrame* pKF1, KeyFrame* pKF2, const Mat
     vMatchedPairs.reserve((size_t)R.n_matches);
     for (int k = 0; k < R.n_matches; k++) vMatchedPairs.emplace_back((size_t)pairs[2 * k], (size_t)pairs[2 * k + 1]);
     return R.n_matches;
+}
+
+namespace {
+// the search half of both Fuse overloads: one vba_fuse problem.  skip[i] is the caller's test of :980-984 / :1154
+struct FuseSearch {
+    std::vector<int32_t> best_idx;
+    std::vector<uint8_t> state;
+    bool run(const char* who, KeyFrame* pKF, const double Rcw[9], const double tcw[3], const double Ow[3], const std::vector<MapPoint*>& pts,
+             const std::vector<uint8_t>& skip, double th, bool check_reproj) {
+        const size_t nk = (size_t)pKF->N, np = pts.size();
+        if (nk != pKF->mvKeysUn.size() || pKF->mDescriptors.size() != 32 * nk || pKF->mvpMapPoints.size() != nk || pKF->mvuRight.size() != nk) {
+            std::cerr << who << ": N, mvKeysUn, mvuRight, mvpMapPoints and mDescriptors of the keyframe disagree" << std::endl;
+            return false;
+        }
+        if (pKF->mnScaleLevels < 1 || pKF->mvScaleFactors.size() != (size_t)pKF->mnScaleLevels || pKF->mvInvLevelSigma2.size() != (size_t)pKF->mnScaleLevels) {
+            std::cerr << who << ": mnScaleLevels, mvScaleFactors and mvInvLevelSigma2 of the keyframe disagree" << std::endl;
+            return false;
+        }
+        if (pKF->mnGridCols < 1 || pKF->mnGridRows < 1 || pKF->mGrid.size() != (size_t)pKF->mnGridCols) {
+            std::cerr << who << ": the keyframe has no grid" << std::endl;
+            return false;
+        }
+        std::vector<double> uv(2 * nk);
+        std::vector<uint8_t> oct(nk);
+        for (size_t i = 0; i < nk; i++) {
+            const KeyPoint& kp = pKF->mvKeysUn[i];
+            if (pKF->mvuRight[i] >= 0) {
+                std::cerr << who << ": the keyframe has a stereo keypoint (the backend is monocular)" << std::endl;
+                return false;
+            }
+            if (kp.octave < 0 || kp.octave > 255) {   // the ABI carries octaves as uint8; the library checks them against n_levels
+                std::cerr << who << ": a keypoint's octave is outside 0 .. 255" << std::endl;
+                return false;
+            }
+            uv[2 * i] = kp.pt.x; uv[2 * i + 1] = kp.pt.y; oct[i] = (uint8_t)kp.octave;
+        }
+        std::vector<int32_t> cell_begin(1, 0), cell_feat;
+        for (int ix = 0; ix < pKF->mnGridCols; ix++)
+            for (int iy = 0; iy < pKF->mnGridRows; iy++) {
+                if (pKF->mGrid[(size_t)ix].size() != (size_t)pKF->mnGridRows) {
+                    std::cerr << who << ": the keyframe has no grid" << std::endl;
+                    return false;
+                }
+                for (size_t idx : pKF->mGrid[(size_t)ix][(size_t)iy]) cell_feat.push_back((int32_t)idx);
+                cell_begin.push_back((int32_t)cell_feat.size());
+            }
+        const std::vector<double> scale(pKF->mvScaleFactors.begin(), pKF->mvScaleFactors.end()), inv_sigma2(pKF->mvInvLevelSigma2.begin(), pKF->mvInvLevelSigma2.end());
+        std::vector<double> pos(3 * np), normal(3 * np), dmin(np), dmax(np), pmax(np);
+        std::vector<uint8_t> desc(32 * np);
+        for (size_t i = 0; i < np; i++) {
+            MapPoint* pMP = pts[i];
+            if (!pMP) continue;   // skipped: zeros
+            pMP->GetWorldPos(&pos[3 * i]);
+            pMP->GetNormal(&normal[3 * i]);
+            dmin[i] = pMP->GetMinDistanceInvariance(); dmax[i] = pMP->GetMaxDistanceInvariance(); pmax[i] = pMP->mfMaxDistance;
+            std::memcpy(&desc[32 * i], pMP->GetDescriptor(), 32);
+        }
+        vba_fuse_problem P{};
+        std::memcpy(P.Rcw, Rcw, 72); std::memcpy(P.tcw, tcw, 24); std::memcpy(P.Ow, Ow, 24);
+        P.K[0] = pKF->fx; P.K[1] = pKF->fy; P.K[2] = pKF->cx; P.K[3] = pKF->cy;
+        P.bounds[0] = pKF->mnMinX; P.bounds[1] = pKF->mnMaxX; P.bounds[2] = pKF->mnMinY; P.bounds[3] = pKF->mnMaxY;
+        P.n_keys = pKF->N; P.n_levels = pKF->mnScaleLevels;
+        P.desc = pKF->mDescriptors.data(); P.uv = uv.data(); P.oct = oct.data();
+        P.scale = scale.data(); P.inv_level_sigma2 = inv_sigma2.data(); P.log_scale_factor = pKF->mfLogScaleFactor;
+        P.grid_cols = pKF->mnGridCols; P.grid_rows = pKF->mnGridRows;
+        P.grid_inv_w = pKF->mfGridElementWidthInv; P.grid_inv_h = pKF->mfGridElementHeightInv;
+        P.cell_begin = cell_begin.data(); P.cell_feat = cell_feat.data();
+        P.n_pt = (int32_t)np; P.th_low = ORBmatcher::TH_LOW;
+        P.pos = pos.data(); P.normal = normal.data(); P.dist_min = dmin.data(); P.dist_max = dmax.data(); P.pred_max = pmax.data();
+        P.pt_desc = desc.data(); P.skip = skip.data();
+        P.th = th; P.cos_view = 0.5; P.check_reproj = check_reproj ? 1 : 0; P.chi2_reproj = 5.99;
+        best_idx.assign(np, -1); state.assign(np, 1);
+        std::vector<uint16_t> best_dist(np);
+        std::vector<int8_t> level(np);
+        std::vector<double> puv(2 * np);
+        vba_fuse_result R{};
+        R.best_idx = best_idx.data(); R.best_dist = best_dist.data(); R.level = level.data(); R.uv = puv.data(); R.state = state.data();
+        vba_fuse_problem* pp = &P;
+        vba_fuse_result* pr = &R;
+        void* h = Optimizer::BackendHandle();
+        if (!h || vba_fuse(h, 1, &pp, &pr) != 0) {
+            std::cerr << who << ": " << (h ? vba_last_error(h) : "no HIP device (the backend has no CPU path)") << std::endl;
+            return false;
+        }
+        return true;
+    }
+};
+}  // namespace
+
+int ORBmatcher::Fuse(KeyFrame* pKF, const std::vector<MapPoint*>& vpMapPoints, const float th) {
+    double Rcw[9], tcw[3], Ow[3];
+    pKF->GetRotation(Rcw); pKF->GetTranslation(tcw); pKF->GetCameraCenter(Ow);
+    const size_t nMPs = vpMapPoints.size();
+    std::vector<uint8_t> skip(nMPs);
+    for (size_t i = 0; i < nMPs; i++) {
+        MapPoint* pMP = vpMapPoints[i];
+        skip[i] = !pMP || pMP->isBad() || pMP->IsInKeyFrame(pKF);   // :980-984
+    }
+    FuseSearch s;
+    if (!s.run("ORBmatcher::Fuse", pKF, Rcw, tcw, Ow, vpMapPoints, skip, th, true)) return -1;
+    int nFused = 0;
+    for (size_t i = 0; i < nMPs; i++) {
+        MapPoint* pMP = vpMapPoints[i];
+        if (!pMP) continue;
+        if (pMP->isBad() || pMP->IsInKeyFrame(pKF)) continue;   // :983 on the live map: a point only moves from searched to skipped
+        if (s.state[i] != 0) continue;
+        const size_t bestIdx = (size_t)s.best_idx[i];
+        MapPoint* pMPinKF = pKF->GetMapPoint(bestIdx);          // :1097-1114
+        if (pMPinKF) {
+            if (!pMPinKF->isBad()) {
+                if (pMPinKF->Observations() > pMP->Observations())
+                    pMP->Replace(pMPinKF);
+                else
+                    pMPinKF->Replace(pMP);
+            }
+        } else {
+            pMP->AddObservation(pKF, bestIdx);
+            pKF->AddMapPoint(pMP, bestIdx);
+        }
+        nFused++;
+    }
+    return nFused;
+}
+
+int ORBmatcher::Fuse(KeyFrame* pKF, const Mat4f& Scw, const std::vector<MapPoint*>& vpPoints, float th, std::vector<MapPoint*>& vpReplacePoint) {
+    // :1134-1138 in float32 like cv::Mat: scw = |row 0 of sRcw|, Rcw = sRcw / scw, tcw = Scw[0:3, 3] / scw, Ow = -Rcw^T tcw
+    const float scw = std::sqrt(Scw[0] * Scw[0] + Scw[1] * Scw[1] + Scw[2] * Scw[2]);
+    float Rf[9], tf[3];
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) Rf[3 * i + j] = Scw[4 * i + j] / scw;
+        tf[i] = Scw[4 * i + 3] / scw;
+    }
+    double Rcw[9], tcw[3], Ow[3];
+    for (int i = 0; i < 9; i++) Rcw[i] = Rf[i];
+    for (int i = 0; i < 3; i++) {
+        tcw[i] = tf[i];
+        float a = 0;
+        for (int k = 0; k < 3; k++) a += -Rf[3 * k + i] * tf[k];
+        Ow[i] = a;
+    }
+    const std::set<MapPoint*> spAlreadyFound = pKF->GetMapPoints();   // :1141
+    const size_t nPoints = vpPoints.size();
+    std::vector<uint8_t> skip(nPoints);
+    for (size_t i = 0; i < nPoints; i++) {
+        MapPoint* pMP = vpPoints[i];
+        skip[i] = !pMP || pMP->isBad() || spAlreadyFound.count(pMP);   // :1154
+    }
+    FuseSearch s;
+    if (!s.run("ORBmatcher::Fuse (Sim3)", pKF, Rcw, tcw, Ow, vpPoints, skip, th, false)) return -1;
+    int nFused = 0;
+    for (size_t iMP = 0; iMP < nPoints && iMP < vpReplacePoint.size(); iMP++) {
+        MapPoint* pMP = vpPoints[iMP];
+        if (!pMP || skip[iMP]) continue;
+        if (pMP->isBad()) continue;                               // :1154 on the live map
+        if (s.state[iMP] != 0) continue;
+        const size_t bestIdx = (size_t)s.best_idx[iMP];
+        MapPoint* pMPinKF = pKF->GetMapPoint(bestIdx);           // :1236-1249
+        if (pMPinKF) {
+            if (!pMPinKF->isBad()) vpReplacePoint[iMP] = pMPinKF;
+        } else {
+            pMP->AddObservation(pKF, bestIdx);
+            pKF->AddMapPoint(pMP, bestIdx);
+        }
+        nFused++;
+    }
+    return nFused;
 }
 
 }  // namespace ORB_SLAM2

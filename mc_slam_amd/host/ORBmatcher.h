@@ -1,5 +1,6 @@
 // ORBmatcher.h -- the reference's ORBmatcher (include/ORBmatcher.h) as far as this backend carries it: SearchForTriangulation
-// (src/ORBmatcher.cpp:760-955, monocular) over vba_search_triangulation.  The other searches stay matcher code of the caller.
+// (src/ORBmatcher.cpp:760-955, monocular) over vba_search_triangulation and both Fuse overloads (:958-1254, monocular) over vba_fuse.
+// The other searches stay matcher code of the caller.
 #pragma once
 #include <utility>
 #include <vector>
@@ -20,6 +21,16 @@ public:
                                const bool bOnlyStereo);
     // the epipole of :768-775 in float32: the centre of pKF1 in the image of pKF2
     static void Epipole(KeyFrame* pKF1, KeyFrame* pKF2, float& ex, float& ey);
+    // src/ORBmatcher.cpp:958-1119: vpMapPoints projected into pKF; a point whose best keypoint has a map point replaces it or is
+    // replaced by it (the one with more observations stays), otherwise it gains the observation.  ONE vba_fuse call for the search,
+    // then the reference's apply loop in list order on the live map; the loop tests :983 again in front of each point, because an
+    // earlier point of the same call may have made a later one bad or put it into the keyframe.  Returns nFused, -1 when the
+    // backend failed or pKF has a stereo keypoint (this backend is monocular), with a message on std::cerr
+    int Fuse(KeyFrame* pKF, const std::vector<MapPoint*>& vpMapPoints, const float th = 3.0);
+    // src/ORBmatcher.cpp:1123-1254: the same search under the Sim3 pose Scw (decomposed in float32 as :1134-1138), without the
+    // reprojection gate; a point whose best keypoint has a good map point is recorded in vpReplacePoint[iMP] instead of replaced.
+    // vba_fuse applies the level range check of :1027 here, too (include/vislam_ba.h).  A NULL entry of vpPoints is skipped
+    int Fuse(KeyFrame* pKF, const Mat4f& Scw, const std::vector<MapPoint*>& vpPoints, float th, std::vector<MapPoint*>& vpReplacePoint);
 
 protected:
     float mfNNratio;

@@ -542,6 +542,85 @@ int fc_create_new_map_points_matched(void* m, long kf, const long* neigh, int n_
     }
     return nnew;
 }
+// ---- map-point fusion (ORBmatcher::Fuse, LocalMapping::SearchInNeighbors) ----
+// what Fuse reads of a keyframe beside the keypoints: N x 32 descriptor bytes, the image bounds and the grid, which is assigned here
+// as Frame::AssignFeaturesToGrid does; N becomes the number of keypoints the keyframe holds
+int fc_kf_set_fuse_data(void* m, long kf, const unsigned char* desc, int min_x, int max_x, int min_y, int max_y, int cols, int rows) {
+    KeyFrame* k = reinterpret_cast<FcMap*>(m)->kfs.at(kf).get();
+    k->N = (int)k->mvKeysUn.size();
+    k->mDescriptors.assign(desc, desc + 32 * (size_t)k->N);
+    k->mnMinX = min_x; k->mnMaxX = max_x; k->mnMinY = min_y; k->mnMaxY = max_y;
+    k->mnGridCols = cols; k->mnGridRows = rows;
+    k->AssignFeaturesToGrid();
+    return k->N;
+}
+// the grid in CSR form: cell (ix, iy) at ix * rows + iy; returns the number of listed keypoints
+int fc_kf_grid(void* m, long kf, int* cell_begin, int* cell_feat, float* inv_wh) {
+    KeyFrame* k = reinterpret_cast<FcMap*>(m)->kfs.at(kf).get();
+    int n = 0, c = 0;
+    cell_begin[0] = 0;
+    for (int ix = 0; ix < k->mnGridCols; ix++)
+        for (int iy = 0; iy < k->mnGridRows; iy++) {
+            for (size_t idx : k->mGrid[(size_t)ix][(size_t)iy]) cell_feat[n++] = (int)idx;
+            cell_begin[++c] = n;
+        }
+    inv_wh[0] = k->mfGridElementWidthInv; inv_wh[1] = k->mfGridElementHeightInv;
+    return n;
+}
+int fc_kf_set_uright(void* m, long kf, int idx, float ur) {
+    reinterpret_cast<FcMap*>(m)->kfs.at(kf)->mvuRight.at(idx) = ur;
+    return 0;
+}
+// what Fuse reads of a map point beside its position; nObs becomes the number of its observations, and the point joins the map
+int fc_mp_set_fuse_data(void* m, long mp, const float* normal, float min_distance, float max_distance, const unsigned char* desc) {
+    FcMap* M = reinterpret_cast<FcMap*>(m);
+    MapPoint* p = M->mps.at(mp).get();
+    std::memcpy(p->mNormalVector, normal, 12);
+    p->mfMinDistance = min_distance; p->mfMaxDistance = max_distance;
+    std::memcpy(p->mDescriptor, desc, 32);
+    p->nObs = (int)p->mObservations.size();
+    p->mpMap = &M->map;
+    M->map.AddMapPoint(p);
+    return 0;
+}
+static std::vector<MapPoint*> point_list(FcMap* M, const long* ids, int n) {
+    std::vector<MapPoint*> v;
+    for (int i = 0; i < n; i++) v.push_back(ids[i] >= 0 ? M->mps.at(ids[i]).get() : nullptr);
+    return v;
+}
+// ORBmatcher::Fuse(pKF, vpMapPoints, th); an id of -1 is a NULL entry
+int fc_fuse(void* m, long kf, const long* mp_ids, int n, float th) {
+    FcMap* M = reinterpret_cast<FcMap*>(m);
+    ORBmatcher matcher;
+    return matcher.Fuse(M->kfs.at(kf).get(), point_list(M, mp_ids, n), th);
+}
+// ORBmatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint): replace_ids [n] comes back with the ids of vpReplacePoint (-1: NULL)
+int fc_fuse_sim3(void* m, long kf, const float* Scw16, const long* mp_ids, int n, float th, long* replace_ids) {
+    FcMap* M = reinterpret_cast<FcMap*>(m);
+    Mat4f S; std::memcpy(S.data(), Scw16, 64);
+    std::vector<MapPoint*> rep((size_t)n, nullptr);
+    ORBmatcher matcher;
+    const int r = matcher.Fuse(M->kfs.at(kf).get(), S, point_list(M, mp_ids, n), th, rep);
+    for (int i = 0; i < n; i++) replace_ids[i] = rep[(size_t)i] ? (long)rep[(size_t)i]->mnId : -1;
+    return r;
+}
+int fc_search_in_neighbors(void* m, long kf, const long* targets, int n) {
+    FcMap* M = reinterpret_cast<FcMap*>(m);
+    std::vector<KeyFrame*> v;
+    for (int i = 0; i < n; i++) v.push_back(M->kfs.at(targets[i]).get());
+    return M->lm.SearchInNeighbors(M->kfs.at(kf).get(), v);
+}
+// out5: bad, the id of mpReplaced (-1: NULL), nObs, the ComputeDistinctiveDescriptors counter, 1 if the map still lists the point
+int fc_mp_fuse_state(void* m, long mp, long* out5) {
+    FcMap* M = reinterpret_cast<FcMap*>(m);
+    MapPoint* p = M->mps.at(mp).get();
+    out5[0] = p->mbBad ? 1 : 0;
+    out5[1] = p->mpReplaced ? (long)p->mpReplaced->mnId : -1;
+    out5[2] = p->nObs;
+    out5[3] = p->nDescriptorUpdates;
+    out5[4] = (long)std::count(M->map.mspMapPoints.begin(), M->map.mspMapPoints.end(), p);
+    return 0;
+}
 // ---- essential graph ----
 // spanning tree, loop edges and the ordered covisibility list (descending weights) of one keyframe
 int fc_kf_set_graph(void* m, long kf, long parent, const long* children, int n_children, const long* loop_edges, int n_loop,

@@ -120,6 +120,9 @@ public:
     std::vector<MapPoint*> GetAllMapPoints() { return mspMapPoints; }    // include/Map.h:45
     long unsigned int GetMaxKFid() { return mnMaxKFid; }                 // include/Map.h:50
     void AddMapPoint(MapPoint* pMP) { mspMapPoints.push_back(pMP); }     // src/Map.cpp (a std::set there)
+    void EraseMapPoint(MapPoint* pMP) {                                  // src/Map.cpp: the point leaves the set, it is not deleted
+        mspMapPoints.erase(std::remove(mspMapPoints.begin(), mspMapPoints.end(), pMP), mspMapPoints.end());
+    }
     long unsigned int mnMaxKFid = 0;
     std::vector<KeyFrame*> mspKeyFrames;
     std::vector<MapPoint*> mspMapPoints;
@@ -144,6 +147,11 @@ public:
     int CreateNewMapPoints(KeyFrame* pKF, const std::vector<KeyFrame*>& vpNeighKFs, Map* pMap, std::list<MapPoint*>& lpRecentAddedMapPoints);
     // src/LocalMapping.cpp:1659-1680: K1^-T [t12]x R12 K2^-1 with analytic K inverses, FP64 products, the result held as float32
     static Mat3f ComputeF12(KeyFrame* pKF1, KeyFrame* pKF2);
+    // src/LocalMapping.cpp:1588-1632, steps 2 and 3 of SearchInNeighbors for pKF (= mpCurrentKeyFrame) and the target keyframes the
+    // caller chose (step 1, :1554-1582): ORBmatcher::Fuse of pKF's map points into every target, then of the targets' map points
+    // into pKF, one vba_fuse call per Fuse call, in order (LocalMapping.cpp).  Returns the fused points of all calls, -1 when the
+    // backend failed (the Fuse calls in front of the failing one stay applied)
+    int SearchInNeighbors(KeyFrame* pKF, const std::vector<KeyFrame*>& vpTargetKFs);
 };
 
 class KeyFrame {
@@ -214,6 +222,32 @@ public:
         SetPose(T);
     }
     void AddMapPoint(MapPoint* pMP, const size_t& idx) { mvpMapPoints[idx] = pMP; }   // src/KeyFrame.cpp
+    // what ORBmatcher::Fuse reads and writes (include/KeyFrame.h:240-245, :289-300, :322; src/KeyFrame.cpp:560-610, :1119-1122)
+    int mnGridCols = 64, mnGridRows = 48;                                 // FRAME_GRID_COLS, FRAME_GRID_ROWS
+    float mfGridElementWidthInv = 0, mfGridElementHeightInv = 0;
+    int mnMinX = 0, mnMinY = 0, mnMaxX = 0, mnMaxY = 0;
+    int mnScaleLevels = 8;
+    float mfLogScaleFactor = std::log(1.2f);
+    std::vector<std::vector<std::vector<size_t>>> mGrid;                  // [col][row] keypoint indices
+    long unsigned int mnFuseTargetForKF = 0;
+    bool IsInImage(const float& x, const float& y) const { return (x >= mnMinX && x < mnMaxX && y >= mnMinY && y < mnMaxY); }
+    MapPoint* GetMapPoint(const size_t& idx) { return mvpMapPoints[idx]; }
+    void ReplaceMapPointMatch(const size_t& idx, MapPoint* pMP) { mvpMapPoints[idx] = pMP; }
+    void EraseMapPointMatch(const size_t& idx) { mvpMapPoints[idx] = nullptr; }
+    std::set<MapPoint*> GetMapPoints();   // the points that are neither NULL nor bad (below MapPoint)
+    // Frame::AssignFeaturesToGrid with PosInGrid (src/Frame.cpp): round() of the float32 cell coordinate, a keypoint outside the grid
+    // is in no cell
+    void AssignFeaturesToGrid() {
+        mfGridElementWidthInv = (float)mnGridCols / (float)(mnMaxX - mnMinX);
+        mfGridElementHeightInv = (float)mnGridRows / (float)(mnMaxY - mnMinY);
+        mGrid.assign((size_t)mnGridCols, std::vector<std::vector<size_t>>((size_t)mnGridRows));
+        for (size_t i = 0; i < mvKeysUn.size(); i++) {
+            const int posX = (int)std::round((mvKeysUn[i].pt.x - mnMinX) * mfGridElementWidthInv);
+            const int posY = (int)std::round((mvKeysUn[i].pt.y - mnMinY) * mfGridElementHeightInv);
+            if (posX < 0 || posX >= mnGridCols || posY < 0 || posY >= mnGridRows) continue;
+            mGrid[(size_t)posX][(size_t)posY].push_back(i);
+        }
+    }
     // src/KeyFrame.cpp:1163-1195 in float32 like cv::Mat (below MapPoint).  Without a single map point the reference indexes an empty
     // vector; here that case returns -1 (every baseline ratio is then below the gate of CreateNewMapPoints)
     float ComputeSceneMedianDepth(const int q);
@@ -282,6 +316,18 @@ public:
         return it == mObservations.end() ? -1 : (int)it->second;
     }
     void UpdateNormalAndDepth() { ++nNormalUpdates; }  // bookkeeping of the map, out of scope
+    // what ORBmatcher::Fuse reads and writes (src/MapPoint.cpp)
+    void GetNormal(double n[3]) const { for (int i = 0; i < 3; i++) n[i] = mNormalVector[i]; }
+    float GetMinDistanceInvariance() const { return 0.8f * mfMinDistance; }
+    float GetMaxDistanceInvariance() const { return 1.2f * mfMaxDistance; }
+    const unsigned char* GetDescriptor() const { return mDescriptor; }
+    bool IsInKeyFrame(KeyFrame* pKF) { return mObservations.count(pKF) != 0; }
+    int Observations() { return nObs; }
+    MapPoint* GetReplaced() { return mpReplaced; }
+    void IncreaseVisible(int n = 1) { mnVisible += n; }
+    void IncreaseFound(int n = 1) { mnFound += n; }
+    void ComputeDistinctiveDescriptors() { ++nDescriptorUpdates; }   // a counter, like UpdateNormalAndDepth
+    void Replace(MapPoint* pMP);                                      // src/MapPoint.cpp:245-292 (below)
 
     mapMapPointObs mObservations;
     KeyFrame* mpRefKF = nullptr;
@@ -289,6 +335,14 @@ public:
     bool mbBad = false;
     int nNormalUpdates = 0;
     int nObs = 0;
+    float mNormalVector[3] = {0, 0, 0};
+    float mfMinDistance = 0, mfMaxDistance = 0;
+    unsigned char mDescriptor[32] = {0};
+    int mnVisible = 1, mnFound = 1;
+    int nDescriptorUpdates = 0;
+    long unsigned int mnFuseCandidateForKF = 0;   // include/MapPoint.h:149
+    MapPoint* mpReplaced = nullptr;
+    Map* mpMap = nullptr;
     float mPosGBA[3] = {0, 0, 0};          // include/MapPoint.h:90-91
     long unsigned int mnBAGlobalForKF = 0;
 };
@@ -387,6 +441,33 @@ inline float KeyFrame::ComputeSceneMedianDepth(const int q) {
 inline void KeyFrame::EraseMapPointMatch(MapPoint* pMP) {
     const int idx = pMP->GetIndexInKeyFrame(this);
     if (idx >= 0) mvpMapPoints[idx] = nullptr;
+}
+inline std::set<MapPoint*> KeyFrame::GetMapPoints() {   // src/KeyFrame.cpp:590-605
+    std::set<MapPoint*> s;
+    for (MapPoint* pMP : mvpMapPoints)
+        if (pMP && !pMP->isBad()) s.insert(pMP);
+    return s;
+}
+inline void MapPoint::Replace(MapPoint* pMP) {
+    if (pMP->mnId == this->mnId) return;
+    const mapMapPointObs obs = mObservations;
+    mObservations.clear();
+    mbBad = true;
+    const int nvisible = mnVisible, nfound = mnFound;
+    mpReplaced = pMP;
+    for (mapMapPointObs::const_iterator mit = obs.begin(), mend = obs.end(); mit != mend; mit++) {
+        KeyFrame* pKF = mit->first;
+        if (!pMP->IsInKeyFrame(pKF)) {
+            pKF->ReplaceMapPointMatch(mit->second, pMP);
+            pMP->AddObservation(pKF, mit->second);
+        } else {
+            pKF->EraseMapPointMatch(mit->second);
+        }
+    }
+    pMP->IncreaseFound(nfound);
+    pMP->IncreaseVisible(nvisible);
+    pMP->ComputeDistinctiveDescriptors();
+    if (mpMap) mpMap->EraseMapPoint(this);
 }
 
 }  // namespace ORB_SLAM2

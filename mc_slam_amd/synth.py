@@ -914,3 +914,95 @@ def synth_match_pair(seed, n_true=60, n_distract1=20, n_distract2=20, n_nodes=12
                                 epipole=np.array([float(ex), float(ey)]), th_low=th_low, check_orientation=check_orientation,
                                 truth=dict(pair=np.stack([inv1[:n_true], inv2[:n_true]], axis=1), shared=shared,
                                            pose=(Rcw1, tcw1, Rcw2, tcw2, K)))
+
+
+# ---------------------------------------------------------------- projection search for map-point fusion (vba_fuse)
+FUSE_KINDS = ("match", "far_desc", "random", "behind", "outside", "distance", "angle", "level_high", "skip")
+
+
+def fuse_scene(seed, n_keys=1000, n_pt=600, n_levels=8, scale_factor=1.2, flip_bits=12, width=640, height=480, cols=64, rows=48,
+               mix=(0.62, 0.06, 0.1, 0.04, 0.04, 0.04, 0.04, 0.03, 0.03), noise=0.4, th=3.0, th_low=50, check_reproj=True):
+    """One ORBmatcher::Fuse call, every input rounded through float32 as the reference holds it.  A keyframe with a random pose, a
+    pinhole camera of width x height pixels, n_keys keypoints at random pixels with random 256-bit descriptors and octaves, the
+    cols x rows grid assigned as Frame::AssignFeaturesToGrid does (abi.grid_csr).  n_pt map points, each of one kind, with the
+    shares of `mix` (FUSE_KINDS):
+      match       the back-projection of one keypoint (every keypoint once before any is taken twice) 2-10 m deep, noise pixels of noise
+                  times its level's scale, the keypoint's descriptor with flip_bits flipped bits
+      far_desc    the same with 90 flipped bits
+      random      a random pixel, depth and descriptor (no keypoint in the area, or none similar)
+      behind      behind the camera;  outside  in front of it but out of the image
+      distance    a distance range that does not hold the point;  angle  a normal that looks away
+      level_high  a distance between 0.84 and 0.99 of mfMinDistance: the predicted level is n_levels
+      skip        a match that the caller marks as skipped
+    Normal and distances come from a reference view 0.1-0.5 m from the keyframe's centre, which saw the point at the keypoint's
+    octave: normal = the unit vector from it, mfMaxDistance = its distance times that level's scale, mfMinDistance = mfMaxDistance
+    over the last level's scale, dist_min / dist_max = 0.8f / 1.2f times those (MapPoint.cpp).  truth: kind [n_pt] (index into
+    FUSE_KINDS), key [n_pt] (the keypoint of a match, far_desc or skip, else -1)."""
+    r = np.random.default_rng(seed)
+    f32 = lambda a: np.asarray(a, dtype=np.float32)
+    scale, sigma2 = level_tables(n_levels, scale_factor)
+    inv_sigma2 = (np.float32(1.0) / f32(sigma2)).astype(np.float64)
+    log_sf = float(np.float32(np.log(np.float32(scale_factor))))
+    K = f32([0.72 * width, 0.72 * width, 0.5 * width - 0.5, 0.5 * height - 0.5]).astype(np.float64)
+    Rm = so3_exp(r.normal(size=3) * 0.4)
+    Cw = r.uniform(-2, 2, 3)
+    Rcw = f32(Rm).astype(np.float64)
+    tcw = f32(-(Rcw @ Cw)).astype(np.float64)
+    Ow = (-(f32(Rcw).T @ f32(tcw))).astype(np.float64)                      # GetCameraCenter in float32
+    bounds = np.array([0.0, float(width), 0.0, float(height)])
+    inv_w = float(np.float32(cols) / np.float32(bounds[1] - bounds[0]))
+    inv_h = float(np.float32(rows) / np.float32(bounds[3] - bounds[2]))
+    uv = f32(np.stack([r.uniform(0, width - 1, n_keys), r.uniform(0, height - 1, n_keys)], axis=1)).astype(np.float64)
+    oct_p = np.array([35, 25, 15, 10, 6, 4, 3, 2] + [1] * 56)[:n_levels].astype(float)
+    octv = r.choice(n_levels, size=n_keys, p=oct_p / oct_p.sum()).astype(np.uint8)
+    desc = r.integers(0, 256, (n_keys, 32), dtype=np.uint8)
+    cell_begin, cell_feat = abi.grid_csr(uv, bounds, cols, rows, inv_w, inv_h)
+
+    kind = r.choice(len(FUSE_KINDS), size=n_pt, p=np.asarray(mix, dtype=float) / np.sum(mix))
+    free = list(r.permutation(n_keys))
+    key = np.full(n_pt, -1)
+    pos, normal = np.zeros((n_pt, 3)), np.zeros((n_pt, 3))
+    dmin, dmax, pmax = np.zeros(n_pt), np.zeros(n_pt), np.zeros(n_pt)
+    pdesc = r.integers(0, 256, (n_pt, 32), dtype=np.uint8)
+    skip = np.zeros(n_pt, dtype=np.uint8)
+    top = np.float32(scale[n_levels - 1])
+    for i in range(n_pt):
+        kd = FUSE_KINDS[kind[i]]
+        depth = r.uniform(2, 10)
+        lev = int(r.choice(n_levels, p=oct_p / oct_p.sum()))
+        px = np.array([r.uniform(0, width - 1), r.uniform(0, height - 1)])
+        if kd in ("match", "far_desc", "skip") and n_keys > 0:
+            if not free:
+                free = list(r.permutation(n_keys))                            # a second round: two points of the call share a keypoint
+            k = int(free.pop())
+            key[i] = k
+            lev = int(octv[k])
+            px = uv[k] + r.normal(size=2) * noise * scale[lev]
+            bits = np.unpackbits(desc[k])
+            which = r.permutation(256)[:90 if kd == "far_desc" else flip_bits]
+            bits[which] ^= 1
+            pdesc[i] = np.packbits(bits)
+        if kd == "behind":
+            depth = -depth
+        if kd == "outside":
+            px = np.array([width + r.uniform(5, 200), r.uniform(0, height - 1)]) if r.random() < 0.5 else np.array([r.uniform(0, width - 1), -r.uniform(5, 200)])
+        Xc = depth * np.array([(px[0] - K[2]) / K[0], (px[1] - K[3]) / K[1], 1.0])
+        Xw = f32(Rm.T @ Xc + Cw).astype(np.float64)
+        off = r.normal(size=3)
+        Cref = Cw + off / np.linalg.norm(off) * r.uniform(0.1, 0.5)
+        if kd == "angle":
+            Cref = Xw + (Xw - Cw) * r.uniform(1.0, 1.2)                       # the reference view looks at it from the other side
+        dref = np.linalg.norm(Xw - Cref)
+        mx = np.float32(dref) * np.float32(scale[lev])                         # UpdateNormalAndDepth
+        if kd == "distance":
+            mx = np.float32(dref) * np.float32(r.choice([0.3, 3.0 * float(top)]))   # the range ends below or starts above the point
+        if kd == "level_high":
+            mx = np.float32(np.linalg.norm(Xw - Ow) / r.uniform(0.84, 0.99)) * top   # dist3D = 0.84 .. 0.99 of mfMinDistance
+        mn = mx / top
+        pos[i], normal[i] = Xw, f32((Xw - Cref) / dref)
+        pmax[i], dmax[i], dmin[i] = mx, np.float32(1.2) * mx, np.float32(0.8) * mn
+        skip[i] = kd == "skip"
+    return abi.FuseProblem(Rcw=Rcw, tcw=tcw, Ow=Ow, K=K, bounds=bounds, desc=desc, uv=uv, oct=octv, scale=scale, inv_level_sigma2=inv_sigma2,
+                           log_scale_factor=log_sf, grid_cols=cols, grid_rows=rows, grid_inv_w=inv_w, grid_inv_h=inv_h, cell_begin=cell_begin,
+                           cell_feat=cell_feat, pos=pos, normal=normal, dist_min=dmin, dist_max=dmax, pred_max=pmax, pt_desc=pdesc, skip=skip,
+                           th=th, th_low=th_low, check_reproj=check_reproj, truth=dict(kind=kind, key=key))
