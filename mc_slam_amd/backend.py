@@ -21,6 +21,20 @@ EXPORTS = ["vba_create", "vba_destroy", "vba_last_error", "vba_solve", "vba_batc
            "vba_batch_set_depth", "vba_batch_submit", "vba_batch_submit_b", "vba_batch_poll", "vba_batch_wait", "vba_sim3_optimize",
            "vba_posegraph_optimize", "vba_sim3_ransac", "vba_triangulate", "vba_two_view_init", "vba_search_triangulation", "vba_fuse"]
 
+# The small-problem entry points, all of the shape fn(handle, n, problems, results).  kind -> (library function, problem struct,
+# result struct, result buffer of one problem -- called with the problem and the extra arguments of its pack --, whether the call
+# works on private copies of the problems)
+_SMALL = {
+    "pose": ("vba_pose_optimize", abi.vba_frame_problem, abi.vba_frame_result, abi.FrameResultBuf, False),
+    "sim3": ("vba_sim3_optimize", abi.vba_sim3_problem, abi.vba_sim3_result, abi.Sim3ResultBuf, False),
+    "sim3_ransac": ("vba_sim3_ransac", abi.vba_sim3_ransac_problem, abi.vba_sim3_ransac_result, abi.Sim3RansacResultBuf, False),
+    "triangulate": ("vba_triangulate", abi.vba_triangulate_problem, abi.vba_triangulate_result, abi.TriangulateResultBuf, False),
+    "two_view": ("vba_two_view_init", abi.vba_two_view_problem, abi.vba_two_view_result, abi.TwoViewResultBuf, False),
+    "search_triangulation": ("vba_search_triangulation", abi.vba_search_tri_problem, abi.vba_search_tri_result, abi.SearchTriResultBuf, False),
+    "fuse": ("vba_fuse", abi.vba_fuse_problem, abi.vba_fuse_result, abi.FuseResultBuf, False),
+    "posegraph": ("vba_posegraph_optimize", abi.vba_posegraph_problem, abi.vba_posegraph_result, lambda p: abi.vba_posegraph_result(), True),
+}
+
 
 def load_library(hooks=False):
     """dlopen the in-tree HIP library and declare every entry point of include/vislam_ba.h.  hooks=True: the flavour with the
@@ -48,19 +62,8 @@ def load_library(hooks=False):
     lib.vba_batch_solve_b.argtypes = [C.c_void_p, C.c_int32, PP, PR, C.c_void_p]
     _pd, _pi = C.POINTER(C.c_double), C.POINTER(C.c_int32)
     lib.vba_preintegrate.argtypes = [C.c_void_p, C.c_int32, _pi, _pd, _pd, _pd, C.c_double, C.c_double, _pd, _pd, _pd]
-    lib.vba_pose_optimize.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.POINTER(abi.vba_frame_problem)), C.POINTER(C.POINTER(abi.vba_frame_result))]
-    lib.vba_sim3_optimize.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.POINTER(abi.vba_sim3_problem)), C.POINTER(C.POINTER(abi.vba_sim3_result))]
-    lib.vba_sim3_ransac.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.POINTER(abi.vba_sim3_ransac_problem)),
-                                    C.POINTER(C.POINTER(abi.vba_sim3_ransac_result))]
-    lib.vba_triangulate.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.POINTER(abi.vba_triangulate_problem)),
-                                    C.POINTER(C.POINTER(abi.vba_triangulate_result))]
-    lib.vba_two_view_init.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.POINTER(abi.vba_two_view_problem)),
-                                      C.POINTER(C.POINTER(abi.vba_two_view_result))]
-    lib.vba_search_triangulation.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.POINTER(abi.vba_search_tri_problem)),
-                                             C.POINTER(C.POINTER(abi.vba_search_tri_result))]
-    lib.vba_fuse.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.POINTER(abi.vba_fuse_problem)), C.POINTER(C.POINTER(abi.vba_fuse_result))]
-    lib.vba_posegraph_optimize.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.POINTER(abi.vba_posegraph_problem)),
-                                           C.POINTER(C.POINTER(abi.vba_posegraph_result))]
+    for fn, problem, result, _, _ in _SMALL.values():
+        getattr(lib, fn).argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.POINTER(problem)), C.POINTER(C.POINTER(result))]
     lib.vba_set_profile.argtypes = [C.c_void_p, C.c_int32]
     lib.vba_get_profile.argtypes = [C.c_void_p, C.POINTER(abi.vba_profile)]
     lib.vba_batch_set_depth.argtypes = [C.c_void_p, C.c_int32]
@@ -235,14 +238,29 @@ class LocalBA:
             raise self._err("vba_preintegrate")
         return meas, cov.reshape(E, 9, 9), (info.reshape(E, 9, 9) if want_info else None)
 
+    # ---- the small-problem entry points: a batch of independent problems per call.  <topic>_pack makes the ctypes views once,
+    # <topic>_call runs the library on them (again and again in a benchmark), <topic>_reset puts back what a call updated in place
+    @staticmethod
+    def _small_pack(kind, problems, *buf_args):
+        """(n, problem structs, result buffers, the two pointer arrays, problems[, private copies]): the ctypes views of a list of
+        the kind's abi problems, kept alive by the returned tuple"""
+        _, problem, result, make_buf, copied = _SMALL[kind]
+        n = len(problems)
+        own = [p.copy() for p in problems] if copied else problems
+        structs = [p.as_struct() for p in own]
+        bufs = [make_buf(p, *buf_args) for p in own]
+        pp = (C.POINTER(problem) * n)(*[C.pointer(s) for s in structs])
+        rr = (C.POINTER(result) * n)(*[C.pointer(getattr(b, "s", b)) for b in bufs])
+        return (n, structs, bufs, pp, rr, problems) + ((own,) if copied else ())
+
+    def _small_call(self, kind, packed):
+        fn = _SMALL[kind][0]
+        if getattr(self.lib, fn)(self.h, packed[0], packed[3], packed[4]) != 0:
+            raise self._err(fn)
+
+    # vba_pose_optimize: abi.FrameProblem
     def pose_pack(self, frames):
-        """ctypes views of a list of abi.FrameProblem for vba_pose_optimize (kept alive by the returned tuple)"""
-        n = len(frames)
-        structs = [f.as_struct() for f in frames]
-        bufs = [abi.FrameResultBuf(f) for f in frames]
-        pp = (C.POINTER(abi.vba_frame_problem) * n)(*[C.pointer(s) for s in structs])
-        rr = (C.POINTER(abi.vba_frame_result) * n)(*[C.pointer(b.s) for b in bufs])
-        return n, structs, bufs, pp, rr, frames
+        return self._small_pack("pose", frames)
 
     def pose_reset(self, packed):
         """vba_pose_optimize updates nav in place: put the frames' initial states back before the next run"""
@@ -250,8 +268,7 @@ class LocalBA:
             C.memmove(C.addressof(s) + abi.vba_frame_problem.nav.offset, f.nav.ctypes.data, 8 * abi.NAV_STRIDE)
 
     def pose_call(self, packed):
-        if self.lib.vba_pose_optimize(self.h, packed[0], packed[3], packed[4]) != 0:
-            raise self._err("vba_pose_optimize")
+        self._small_call("pose", packed)
 
     def pose_run(self, packed):
         self.pose_reset(packed)
@@ -263,15 +280,9 @@ class LocalBA:
         self.pose_run(packed)
         return [b.get(s) for b, s in zip(packed[2], packed[1])]
 
-    # ---- loop-closure Sim3 refinement (vba_sim3_optimize): a batch of independent candidates per call ----
+    # loop-closure Sim3 refinement (vba_sim3_optimize): abi.Sim3Problem
     def sim3_pack(self, problems, want_chi2=True):
-        """ctypes views of a list of abi.Sim3Problem for vba_sim3_optimize (kept alive by the returned tuple)"""
-        n = len(problems)
-        structs = [p.as_struct() for p in problems]
-        bufs = [abi.Sim3ResultBuf(p, want_chi2) for p in problems]
-        pp = (C.POINTER(abi.vba_sim3_problem) * n)(*[C.pointer(s) for s in structs])
-        rr = (C.POINTER(abi.vba_sim3_result) * n)(*[C.pointer(b.s) for b in bufs])
-        return n, structs, bufs, pp, rr, problems
+        return self._small_pack("sim3", problems, want_chi2)
 
     def sim3_reset(self, packed):
         """vba_sim3_optimize updates S12 in place: put the initial estimates back before the next run"""
@@ -279,8 +290,7 @@ class LocalBA:
             C.memmove(C.addressof(s) + abi.vba_sim3_problem.S12.offset, p.S12.ctypes.data, 64)
 
     def sim3_call(self, packed):
-        if self.lib.vba_sim3_optimize(self.h, packed[0], packed[3], packed[4]) != 0:
-            raise self._err("vba_sim3_optimize")
+        self._small_call("sim3", packed)
 
     def sim3_optimize(self, problems, want_chi2=True):
         """vba_sim3_optimize on a list of abi.Sim3Problem (left untouched): list of abi.Sim3Result with the refined S12"""
@@ -288,15 +298,9 @@ class LocalBA:
         self.sim3_call(packed)
         return [b.get(s) for b, s in zip(packed[2], packed[1])]
 
-    # ---- loop-candidate Sim3 RANSAC (vba_sim3_ransac): the hypotheses of a batch of independent candidates per call ----
+    # loop-candidate Sim3 RANSAC (vba_sim3_ransac): abi.Sim3RansacProblem
     def sim3_ransac_pack(self, problems, want_counts=True):
-        """ctypes views of a list of abi.Sim3RansacProblem for vba_sim3_ransac (kept alive by the returned tuple)"""
-        n = len(problems)
-        structs = [p.as_struct() for p in problems]
-        bufs = [abi.Sim3RansacResultBuf(p, want_counts) for p in problems]
-        pp = (C.POINTER(abi.vba_sim3_ransac_problem) * n)(*[C.pointer(s) for s in structs])
-        rr = (C.POINTER(abi.vba_sim3_ransac_result) * n)(*[C.pointer(b.s) for b in bufs])
-        return n, structs, bufs, pp, rr, problems
+        return self._small_pack("sim3_ransac", problems, want_counts)
 
     def sim3_ransac_reset(self, packed):
         """vba_sim3_ransac updates best_inliers / best_S12 in place: put the solvers' states back before the next run"""
@@ -305,8 +309,7 @@ class LocalBA:
             s.best_S12[:] = p.best_S12.tolist()
 
     def sim3_ransac_call(self, packed):
-        if self.lib.vba_sim3_ransac(self.h, packed[0], packed[3], packed[4]) != 0:
-            raise self._err("vba_sim3_ransac")
+        self._small_call("sim3_ransac", packed)
 
     def sim3_ransac(self, problems, want_counts=True):
         """vba_sim3_ransac on a list of abi.Sim3RansacProblem (left untouched): list of abi.Sim3RansacResult, each with the
@@ -315,97 +318,62 @@ class LocalBA:
         self.sim3_ransac_call(packed)
         return [b.get(s) for b, s in zip(packed[2], packed[1])]
 
-    # ---- two-view triangulation of new map points (vba_triangulate): the matches of a batch of keyframe pairs per call ----
+    # two-view triangulation of new map points (vba_triangulate): abi.TriangulateProblem, one keyframe pair each
     def triangulate_pack(self, problems):
-        """ctypes views of a list of abi.TriangulateProblem for vba_triangulate (kept alive by the returned tuple)"""
-        n = len(problems)
-        structs = [p.as_struct() for p in problems]
-        bufs = [abi.TriangulateResultBuf(p) for p in problems]
-        pp = (C.POINTER(abi.vba_triangulate_problem) * n)(*[C.pointer(s) for s in structs])
-        rr = (C.POINTER(abi.vba_triangulate_result) * n)(*[C.pointer(b.s) for b in bufs])
-        return n, structs, bufs, pp, rr, problems
+        return self._small_pack("triangulate", problems)
 
     def triangulate_call(self, packed):
-        if self.lib.vba_triangulate(self.h, packed[0], packed[3], packed[4]) != 0:
-            raise self._err("vba_triangulate")
+        self._small_call("triangulate", packed)
 
     def triangulate(self, problems):
-        """vba_triangulate on a list of abi.TriangulateProblem (one keyframe pair each): list of abi.TriangulateResult"""
+        """vba_triangulate on a list of abi.TriangulateProblem: list of abi.TriangulateResult"""
         packed = self.triangulate_pack(problems)
         self.triangulate_call(packed)
         return [b.get() for b in packed[2]]
 
-    # ---- monocular two-view initialisation (vba_two_view_init): a batch of frame pairs per call ----
+    # monocular two-view initialisation (vba_two_view_init): abi.TwoViewProblem, one frame pair each
     def two_view_pack(self, problems, want_scores=True, fill=0):
-        """ctypes views of a list of abi.TwoViewProblem for vba_two_view_init (kept alive by the returned tuple)"""
-        n = len(problems)
-        structs = [p.as_struct() for p in problems]
-        bufs = [abi.TwoViewResultBuf(p, want_scores, fill) for p in problems]
-        pp = (C.POINTER(abi.vba_two_view_problem) * n)(*[C.pointer(s) for s in structs])
-        rr = (C.POINTER(abi.vba_two_view_result) * n)(*[C.pointer(b.s) for b in bufs])
-        return n, structs, bufs, pp, rr, problems
+        return self._small_pack("two_view", problems, want_scores, fill)
 
     def two_view_call(self, packed):
-        if self.lib.vba_two_view_init(self.h, packed[0], packed[3], packed[4]) != 0:
-            raise self._err("vba_two_view_init")
+        self._small_call("two_view", packed)
 
     def two_view_init(self, problems, want_scores=True, fill=0):
-        """vba_two_view_init on a list of abi.TwoViewProblem (one frame pair each): list of abi.TwoViewResult"""
+        """vba_two_view_init on a list of abi.TwoViewProblem: list of abi.TwoViewResult"""
         packed = self.two_view_pack(problems, want_scores, fill)
         self.two_view_call(packed)
         return [b.get() for b in packed[2]]
 
-    # ---- matching for triangulation (vba_search_triangulation): a batch of keyframe pairs per call ----
+    # matching for triangulation (vba_search_triangulation): abi.SearchTriProblem, one keyframe pair each
     def search_triangulation_pack(self, problems):
-        """ctypes views of a list of abi.SearchTriProblem for vba_search_triangulation (kept alive by the returned tuple)"""
-        n = len(problems)
-        structs = [p.as_struct() for p in problems]
-        bufs = [abi.SearchTriResultBuf(p) for p in problems]
-        pp = (C.POINTER(abi.vba_search_tri_problem) * n)(*[C.pointer(s) for s in structs])
-        rr = (C.POINTER(abi.vba_search_tri_result) * n)(*[C.pointer(b.s) for b in bufs])
-        return n, structs, bufs, pp, rr, problems
+        return self._small_pack("search_triangulation", problems)
 
     def search_triangulation_call(self, packed):
-        if self.lib.vba_search_triangulation(self.h, packed[0], packed[3], packed[4]) != 0:
-            raise self._err("vba_search_triangulation")
+        self._small_call("search_triangulation", packed)
 
     def search_triangulation(self, problems):
-        """vba_search_triangulation on a list of abi.SearchTriProblem (one keyframe pair each): list of abi.SearchTriResult"""
+        """vba_search_triangulation on a list of abi.SearchTriProblem: list of abi.SearchTriResult"""
         packed = self.search_triangulation_pack(problems)
         self.search_triangulation_call(packed)
         return [b.get() for b in packed[2]]
 
-    # ---- projection search for map-point fusion (vba_fuse): a batch of (keyframe, point list) problems per call ----
+    # projection search for map-point fusion (vba_fuse): abi.FuseProblem, one keyframe and one point list each
     def fuse_pack(self, problems):
-        """ctypes views of a list of abi.FuseProblem for vba_fuse (kept alive by the returned tuple)"""
-        n = len(problems)
-        structs = [p.as_struct() for p in problems]
-        bufs = [abi.FuseResultBuf(p) for p in problems]
-        pp = (C.POINTER(abi.vba_fuse_problem) * n)(*[C.pointer(s) for s in structs])
-        rr = (C.POINTER(abi.vba_fuse_result) * n)(*[C.pointer(b.s) for b in bufs])
-        return n, structs, bufs, pp, rr, problems
+        return self._small_pack("fuse", problems)
 
     def fuse_call(self, packed):
-        if self.lib.vba_fuse(self.h, packed[0], packed[3], packed[4]) != 0:
-            raise self._err("vba_fuse")
+        self._small_call("fuse", packed)
 
     def fuse(self, problems):
-        """vba_fuse on a list of abi.FuseProblem (one keyframe and one point list each): list of abi.FuseResult"""
+        """vba_fuse on a list of abi.FuseProblem: list of abi.FuseResult"""
         packed = self.fuse_pack(problems)
         self.fuse_call(packed)
         return [b.get() for b in packed[2]]
 
-    # ---- essential-graph optimisation (vba_posegraph_optimize): a batch of independent Sim3 pose graphs per call ----
+    # essential-graph optimisation (vba_posegraph_optimize): abi.PoseGraphProblem, independent Sim3 pose graphs.  The call updates
+    # S and pt of the pack's private copies in place
     def posegraph_pack(self, problems):
-        """private copies of a list of abi.PoseGraphProblem and the ctypes views vba_posegraph_optimize needs (kept alive by the
-        returned tuple); the call updates the copies' S and pt in place"""
-        n = len(problems)
-        own = [p.copy() for p in problems]
-        structs = [p.as_struct() for p in own]
-        res = [abi.vba_posegraph_result() for _ in own]
-        pp = (C.POINTER(abi.vba_posegraph_problem) * n)(*[C.pointer(s) for s in structs])
-        rr = (C.POINTER(abi.vba_posegraph_result) * n)(*[C.pointer(r) for r in res])
-        return n, structs, res, pp, rr, problems, own
+        return self._small_pack("posegraph", problems)
 
     def posegraph_reset(self, packed):
         """put the initial estimates and points back before the next run"""
@@ -414,8 +382,7 @@ class LocalBA:
             q.pt[...] = p.pt
 
     def posegraph_call(self, packed):
-        if self.lib.vba_posegraph_optimize(self.h, packed[0], packed[3], packed[4]) != 0:
-            raise self._err("vba_posegraph_optimize")
+        self._small_call("posegraph", packed)
 
     def posegraph_optimize(self, problems):
         """vba_posegraph_optimize on copies of a list of abi.PoseGraphProblem: list of abi.PoseGraphResult"""

@@ -33,21 +33,6 @@
 #define FU_COS 27
 #define FU_CHI2 28
 
-struct FuBatch {
-    const FuDesc* desc;
-    const FuTile* tile;          // [tiles]
-    const FuKey* key;            // keypoint records of all problems
-    const FuPoint* pt;           // point records of all problems
-    const int* cell_begin;       // cell_begin of all problems
-    const int* cell_feat;        // cell_feat of all problems
-    const double* lev;           // level tables of all problems: scale [n_levels] inv_level_sigma2 [n_levels]
-    int* best_idx;               // [total points]
-    unsigned short* best_dist;   // ...
-    signed char* level;          // ...
-    double* uv;                  // [total points][2]
-    unsigned char* state;        // [total points]
-};
-
 __global__ void __launch_bounds__(FU_NT) k_fuse(FuBatch B) {
 #pragma clang fp contract(off)
     __shared__ double sc[VBA_FU_CONST];

@@ -154,4 +154,39 @@ inline void unpack_fuse(vba_fuse_result* R, const FuDesc& d, const int32_t* best
     R->n_found = found;
 }
 
+// One call (a fresh object each): what the driver (run_small, vba_host_small.h) and the sanitizer harness (run_call,
+// tests/host_check.h) run.  bind is the only place that maps the arena's regions to the kernel's pointers
+struct FuseCall {
+    int n = 0;
+    FuseTotals T;
+    FuseArena A = FuseArena(0, FuseTotals());
+    int prepare(int n_problems, const vba_fuse_problem* const* in, const vba_fuse_result* const* out, std::string& err) {
+        n = n_problems;
+        if (check_fuse(n, in, out, T, err)) return 1;
+        A = FuseArena((size_t)n, T);
+        return 0;
+    }
+    const ArenaLayout& layout() const { return A.L; }
+    size_t download_bytes() const { return A.L.back_bytes(); }
+    size_t grid() const { return T.tiles; }   // k_fuse: one workgroup per tile; a call whose problems all have no points has nothing to search
+    FuDesc* desc(void* hin) const { return at<FuDesc>(hin, A.desc); }
+    void describe(const vba_fuse_problem* const* in, void* hin) const { describe_fuse(n, in, desc(hin), at<FuTile>(hin, A.tile)); }
+    const char* pack(int f, const vba_fuse_problem* P, void* hin) const {
+        pack_fuse(P, desc(hin)[f], at<FuKey>(hin, A.key), at<FuPoint>(hin, A.pt), at<int32_t>(hin, A.cell), at<int32_t>(hin, A.feat), at<double>(hin, A.lev));
+        return nullptr;
+    }
+    FuBatch bind(void* base) const {
+        FuBatch B;
+        B.desc = desc(base); B.tile = at<FuTile>(base, A.tile); B.key = at<FuKey>(base, A.key); B.pt = at<FuPoint>(base, A.pt);
+        B.cell_begin = at<int>(base, A.cell); B.cell_feat = at<int>(base, A.feat); B.lev = at<double>(base, A.lev);
+        B.best_idx = at<int>(base, A.best_idx); B.best_dist = at<unsigned short>(base, A.best_dist); B.level = at<signed char>(base, A.level);
+        B.uv = at<double>(base, A.uv); B.state = at<unsigned char>(base, A.state);
+        return B;
+    }
+    void unpack(int f, vba_fuse_problem*, vba_fuse_result* R, void* hin, void* hout) const {
+        unpack_fuse(R, desc(hin)[f], at<int32_t>(hout, A.L.in_back(A.best_idx)), at<uint16_t>(hout, A.L.in_back(A.best_dist)),
+                    at<int8_t>(hout, A.L.in_back(A.level)), at<double>(hout, A.L.in_back(A.uv)), at<unsigned char>(hout, A.L.in_back(A.state)));
+    }
+};
+
 }  // namespace vba_host

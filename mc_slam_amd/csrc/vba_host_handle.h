@@ -83,6 +83,9 @@ struct SideArena {
     hipError_t ensure(const vba_host::ArenaLayout& L) { return ensure(L, L.back_bytes()); }
     void release() { dev.release(); in.release(); out.release(); }
 };
+// vba_preintegrate (dev only), vba_pose_optimize, vba_sim3_optimize, vba_sim3_ransac, vba_triangulate, vba_two_view_init,
+// vba_search_triangulation, vba_fuse, vba_posegraph_optimize
+enum Side { SIDE_PREINT, SIDE_POSE, SIDE_SIM3, SIDE_RANSAC, SIDE_TRI, SIDE_TWO_VIEW, SIDE_SEARCH_TRI, SIDE_FUSE, SIDE_POSEGRAPH, SIDE_N };
 
 // Growable array in pinned host memory with the few std::vector members the upload / download code uses.  The staging
 // arrays of a handle persist from call to call, so the H2D / D2H copies are true DMA transfers (no pageable bounce
@@ -198,7 +201,7 @@ struct Handle {
     bool owns_streams = true;
     std::string err;
     DevBuf buf[BUF_N];
-    SideArena preint, pose, sim3, pg, ransac, tri, tv, st, fu;   // vba_preintegrate (dev only), vba_pose_optimize, vba_sim3_optimize, vba_posegraph_optimize, vba_sim3_ransac, vba_triangulate, vba_two_view_init, vba_search_triangulation, vba_fuse
+    SideArena side[SIDE_N];       // one per small-problem entry point
     // small batches (UploadPlan::arena_on): every host-built array of an upload goes through ONE pinned arena and ONE H2D copy
     struct Pending { int id; const void* src; size_t bytes; };
     std::vector<Pending> pending;

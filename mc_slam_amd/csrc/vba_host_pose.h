@@ -8,6 +8,7 @@
 
 #include <cmath>
 #include <cstring>
+#include <string>
 #include <utility>
 
 namespace vba_host {
@@ -125,5 +126,39 @@ inline void unpack_frame(vba_frame_problem* F, vba_frame_result* R, const FrameD
     if (R->outlier_last)
         for (int i = 0; i < d.n_last; i++) R->outlier_last[i] = lvl[d.last0 + i];
 }
+
+// One call (a fresh object each): what the driver (run_small, vba_host_small.h) and the sanitizer harness (run_call,
+// tests/host_check.h) run.  bind is the only place that maps the arena's regions to the kernel's pointers
+struct PoseCall {
+    int n = 0;
+    size_t n_tot = 0;
+    PoseArena A = PoseArena(0, 0);
+    int prepare(int n_frames, const vba_frame_problem* const* in, const vba_frame_result* const* out, std::string& err) {
+        n = n_frames;
+        if (const char* m = check_pose(n, in, out, n_tot)) { err = m; return 1; }
+        A = PoseArena((size_t)n, n_tot);
+        return 0;
+    }
+    const ArenaLayout& layout() const { return A.L; }
+    size_t download_bytes() const { return A.L.back_bytes(); }
+    size_t grid() const { return (size_t)n; }   // k_pose_opt: one workgroup per frame
+    FrameDesc* desc(void* hin) const { return at<FrameDesc>(hin, A.desc); }
+    void describe(const vba_frame_problem* const* in, void* hin) const { describe_pose(n, in, desc(hin)); }
+    // not nullptr: why the frame is refused after all
+    const char* pack(int f, const vba_frame_problem* F, void* hin) const {
+        return pack_frame(F, desc(hin)[f], at<double>(hin, A.pw), at<double>(hin, A.uv), at<double>(hin, A.w)) ? nullptr
+                                                                                                             : "imu_cov_pvphi is singular or not finite";
+    }
+    PoseBatch bind(void* base) const {
+        PoseBatch B;
+        B.desc = desc(base); B.out = at<FrameOut>(base, A.out); B.pw = at<double>(base, A.pw); B.uv = at<double>(base, A.uv);
+        B.w = at<double>(base, A.w); B.err = at<double>(base, A.err); B.lvl = at<unsigned char>(base, A.lvl);
+        B.n_frames = n;
+        return B;
+    }
+    void unpack(int f, vba_frame_problem* F, vba_frame_result* R, void* hin, void* hout) const {
+        unpack_frame(F, R, desc(hin)[f], at<FrameOut>(hout, A.L.in_back(A.out))[f], at<unsigned char>(hout, A.L.in_back(A.lvl)));
+    }
+};
 
 }  // namespace vba_host

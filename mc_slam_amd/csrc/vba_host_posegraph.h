@@ -156,8 +156,11 @@ inline int build_posegraph(const vba_posegraph_problem* P, PoseGraphLayout& L, s
 }
 
 // One call: the layout and descriptor of every graph and the arena [upload | back | work].  The staging block [desc | estimates |
-// measurements | index lists | points] goes up in one copy, [out | estimates | points] come back in one.
+// measurements | index lists | points] goes up in one copy, [out | estimates | points] come back in one.  One object per call:
+// prepare, then describe, pack (any g on any thread), bind, and unpack once the back section is in hout
 struct PoseGraphCall {
+    bool debug = false;   // set before prepare: graph 0 stops after the solve of its first trial and nothing is written back (hooks flavour)
+    int n = 0;
     std::vector<PoseGraphLayout> lay;
     std::vector<PgDesc> desc;
     size_t npt = 0;   // map points of the call
@@ -165,80 +168,107 @@ struct PoseGraphCall {
     size_t o_desc, o_Sin, o_meas, o_ei, o_ej, o_free, o_vert, o_first, o_last, o_roff, o_incb, o_inc, o_plo, o_phi, o_pb, o_pe, o_pt, o_ref;   // upload
     size_t o_out, o_S, o_pto;                                                                                                                // back
     size_t o_Sbk, o_err, o_J, o_H, o_F, o_Ld, o_b, o_w, o_y, o_x;                                                                            // work
+
+    // 0: every graph is usable and the arena is laid out; otherwise err says which graph is not and why
+    int prepare(int n_graphs, const vba_posegraph_problem* const* in, const vba_posegraph_result* const* res, std::string& err) {
+        n = n_graphs;
+        lay.resize(n);
+        desc.resize(n);
+        size_t nv = 0, ne = 0, nf = 0, nenv = 0, ninc = 0, npair = 0, npe = 0;
+        for (int g = 0; g < n; g++) {
+            const std::string who = "graph " + std::to_string(g) + ": ";
+            if (!in[g] || !res[g]) { err = who + "NULL problem or result"; return 1; }
+            if (build_posegraph(in[g], lay[g], err, (long long)nenv)) { err = who + err; return 1; }
+            const vba_posegraph_problem* P = in[g];
+            const PoseGraphLayout& G = lay[g];
+            PgDesc& d = desc[g];
+            std::memset(&d, 0, sizeof d);
+            d.nv = P->n_vertices; d.ne = P->n_edges; d.nf = G.n_free; d.npair = (int)G.pair_lo.size();
+            d.fix_scale = P->fix_scale ? 1 : 0; d.its = P->its; d.n_pt = P->n_pt; d.debug = (debug && g == 0) ? 1 : 0;
+            d.lambda_init = P->lambda_init;
+            d.v0 = (long long)nv; d.e0 = (long long)ne; d.f0 = (long long)nf; d.r0 = (long long)nf + g; d.env0 = (long long)nenv;
+            d.inc0 = (long long)ninc; d.pair0 = (long long)npair; d.pb0 = (long long)npair + g; d.pe0 = (long long)npe; d.pt0 = (long long)npt;
+            nv += (size_t)d.nv; ne += (size_t)d.ne; nf += (size_t)d.nf; nenv += (size_t)G.env_blocks; ninc += G.inc.size();
+            npair += G.pair_lo.size(); npe += G.pair_edge.size(); npt += (size_t)d.n_pt;
+        }
+        auto take = [this](size_t bytes) { return L.take(bytes + 8); };
+        const size_t G = (size_t)n;
+        o_desc = take(sizeof(PgDesc) * G); o_Sin = take(64 * nv); o_meas = take(64 * ne); o_ei = take(4 * ne); o_ej = take(4 * ne);
+        o_free = take(4 * nv); o_vert = take(4 * nf); o_first = take(4 * nf); o_last = take(4 * nf); o_roff = take(4 * (nf + G));
+        o_incb = take(4 * (nf + G)); o_inc = take(4 * ninc); o_plo = take(4 * npair); o_phi = take(4 * npair);
+        o_pb = take(4 * (npair + G)); o_pe = take(4 * npe); o_pt = take(24 * npt); o_ref = take(4 * npt);
+        L.end_upload();
+        o_out = take(sizeof(PgOut) * G); o_S = take(64 * nv); o_pto = take(24 * npt);
+        L.end_back();
+        o_Sbk = take(64 * nv); o_err = take(56 * ne); o_J = take(784 * ne); o_H = take(392 * nenv); o_F = take(392 * nenv);
+        o_Ld = take(392 * nf); o_b = take(56 * nf); o_w = take(56 * nf); o_y = take(56 * nf); o_x = take(56 * nf);
+        return 0;
+    }
+    const ArenaLayout& layout() const { return L; }
+    size_t download_bytes() const { return L.back_bytes(); }
+    size_t grid() const { return (size_t)n; }   // k_posegraph_opt: one workgroup per graph
+
+    // the descriptors were complete with prepare: they go in as one block
+    void describe(const vba_posegraph_problem* const*, void* hin) const { std::memcpy(at<char>(hin, o_desc), desc.data(), sizeof(PgDesc) * (size_t)n); }
+    // graph g into the staging block: its slices of the concatenated arrays
+    const char* pack(int g, const vba_posegraph_problem* P, void* hin) const {
+        const PoseGraphLayout& G = lay[g];
+        const PgDesc& d = desc[g];
+        auto put = [hin](size_t o, size_t off, const void* src, size_t bytes) { if (bytes) std::memcpy(at<char>(hin, o + off), src, bytes); };
+        put(o_Sin, 64 * (size_t)d.v0, P->S, 64 * (size_t)d.nv);
+        put(o_meas, 64 * (size_t)d.e0, P->edge_S, 64 * (size_t)d.ne);
+        put(o_ei, 4 * (size_t)d.e0, P->edge_i, 4 * (size_t)d.ne);
+        put(o_ej, 4 * (size_t)d.e0, P->edge_j, 4 * (size_t)d.ne);
+        put(o_free, 4 * (size_t)d.v0, G.free_of.data(), 4 * (size_t)d.nv);
+        put(o_vert, 4 * (size_t)d.f0, G.vert_of.data(), 4 * (size_t)d.nf);
+        put(o_first, 4 * (size_t)d.f0, G.first.data(), 4 * (size_t)d.nf);
+        put(o_last, 4 * (size_t)d.f0, G.last_row.data(), 4 * (size_t)d.nf);
+        put(o_roff, 4 * (size_t)d.r0, G.row_off.data(), 4 * ((size_t)d.nf + 1));
+        put(o_incb, 4 * (size_t)d.r0, G.inc_begin.data(), 4 * ((size_t)d.nf + 1));
+        put(o_inc, 4 * (size_t)d.inc0, G.inc.data(), 4 * G.inc.size());
+        put(o_plo, 4 * (size_t)d.pair0, G.pair_lo.data(), 4 * G.pair_lo.size());
+        put(o_phi, 4 * (size_t)d.pair0, G.pair_hi.data(), 4 * G.pair_hi.size());
+        put(o_pb, 4 * (size_t)d.pb0, G.pair_begin.data(), 4 * G.pair_begin.size());
+        put(o_pe, 4 * (size_t)d.pe0, G.pair_edge.data(), 4 * G.pair_edge.size());
+        put(o_pt, 24 * (size_t)d.pt0, P->pt, 24 * (size_t)d.n_pt);
+        int* ref = at<int>(hin, o_ref) + d.pt0;
+        for (int p = 0; p < d.n_pt; p++) ref[p] = (int)d.v0 + P->pt_ref[p];   // index into the concatenated vertices
+        return nullptr;
+    }
+    PgBatch bind(void* base) const {
+        PgBatch B;
+        auto d = [base](size_t o) { return at<double>(base, o); };
+        auto i = [base](size_t o) { return at<int>(base, o); };
+        B.desc = at<PgDesc>(base, o_desc);
+        B.out = at<PgOut>(base, o_out);
+        B.Sin = d(o_Sin); B.meas = d(o_meas); B.ei = i(o_ei); B.ej = i(o_ej); B.free_of = i(o_free);
+        B.vert_of = i(o_vert); B.first = i(o_first); B.last_row = i(o_last); B.row_off = i(o_roff); B.inc_begin = i(o_incb);
+        B.inc = i(o_inc); B.pair_lo = i(o_plo); B.pair_hi = i(o_phi); B.pair_begin = i(o_pb); B.pair_edge = i(o_pe);
+        B.pt_in = d(o_pt); B.pt_ref = i(o_ref);
+        B.S = d(o_S); B.Sbk = d(o_Sbk); B.err = d(o_err); B.J = d(o_J); B.H = d(o_H); B.F = d(o_F); B.Ld = d(o_Ld);
+        B.b = d(o_b); B.w = d(o_w); B.y = d(o_y); B.x = d(o_x); B.pt_out = d(o_pto);
+        B.n_pt_total = (long long)npt;
+        return B;
+    }
+    void unpack(int g, vba_posegraph_problem* P, vba_posegraph_result* R, void*, void* hout) const {
+        if (debug) return;   // the caller's arrays are left untouched
+        const PgDesc& d = desc[g];
+        const PgOut& r = at<PgOut>(hout, L.in_back(o_out))[g];
+        R->status = r.status; R->its_done = r.its_done; R->lm_trials = r.lm_trials; R->stop = r.stop;
+        R->chi2_initial = r.chi2_initial; R->chi2_final = r.chi2_final; R->lambda_final = r.lambda_final;
+        if (d.nv) std::memcpy(P->S, at<double>(hout, L.in_back(o_S)) + 8 * (size_t)d.v0, 64 * (size_t)d.nv);   // fixed vertices: the input, bit for bit
+        if (d.n_pt) std::memcpy(P->pt, at<double>(hout, L.in_back(o_pto)) + 3 * (size_t)d.pt0, 24 * (size_t)d.n_pt);
+    }
 };
 
-// 0: every graph is usable and C describes the call; otherwise err says which graph is not and why.  debug: graph 0 stops after
-// the solve of its first trial (hooks flavour)
+// the two steps of a call under their earlier names
 inline int describe_posegraph(int n_graphs, const vba_posegraph_problem* const* in, const vba_posegraph_result* const* out, bool debug,
                               PoseGraphCall& C, std::string& err) {
     C = PoseGraphCall();
-    C.lay.resize(n_graphs);
-    C.desc.resize(n_graphs);
-    size_t nv = 0, ne = 0, nf = 0, nenv = 0, ninc = 0, npair = 0, npe = 0, npt = 0;
-    for (int g = 0; g < n_graphs; g++) {
-        const std::string who = "graph " + std::to_string(g) + ": ";
-        if (!in[g] || !out[g]) { err = who + "NULL problem or result"; return 1; }
-        if (build_posegraph(in[g], C.lay[g], err, (long long)nenv)) { err = who + err; return 1; }
-        const vba_posegraph_problem* P = in[g];
-        const PoseGraphLayout& L = C.lay[g];
-        PgDesc& d = C.desc[g];
-        std::memset(&d, 0, sizeof d);
-        d.nv = P->n_vertices; d.ne = P->n_edges; d.nf = L.n_free; d.npair = (int)L.pair_lo.size();
-        d.fix_scale = P->fix_scale ? 1 : 0; d.its = P->its; d.n_pt = P->n_pt; d.debug = (debug && g == 0) ? 1 : 0;
-        d.lambda_init = P->lambda_init;
-        d.v0 = (long long)nv; d.e0 = (long long)ne; d.f0 = (long long)nf; d.r0 = (long long)nf + g; d.env0 = (long long)nenv;
-        d.inc0 = (long long)ninc; d.pair0 = (long long)npair; d.pb0 = (long long)npair + g; d.pe0 = (long long)npe; d.pt0 = (long long)npt;
-        nv += (size_t)d.nv; ne += (size_t)d.ne; nf += (size_t)d.nf; nenv += (size_t)L.env_blocks; ninc += L.inc.size();
-        npair += L.pair_lo.size(); npe += L.pair_edge.size(); npt += (size_t)d.n_pt;
-    }
-    C.npt = npt;
-    ArenaLayout& A = C.L;
-    auto take = [&A](size_t bytes) { return A.take(bytes + 8); };
-    const size_t G = (size_t)n_graphs;
-    C.o_desc = take(sizeof(PgDesc) * G); C.o_Sin = take(64 * nv); C.o_meas = take(64 * ne); C.o_ei = take(4 * ne); C.o_ej = take(4 * ne);
-    C.o_free = take(4 * nv); C.o_vert = take(4 * nf); C.o_first = take(4 * nf); C.o_last = take(4 * nf); C.o_roff = take(4 * (nf + G));
-    C.o_incb = take(4 * (nf + G)); C.o_inc = take(4 * ninc); C.o_plo = take(4 * npair); C.o_phi = take(4 * npair);
-    C.o_pb = take(4 * (npair + G)); C.o_pe = take(4 * npe); C.o_pt = take(24 * npt); C.o_ref = take(4 * npt);
-    A.end_upload();
-    C.o_out = take(sizeof(PgOut) * G); C.o_S = take(64 * nv); C.o_pto = take(24 * npt);
-    A.end_back();
-    C.o_Sbk = take(64 * nv); C.o_err = take(56 * ne); C.o_J = take(784 * ne); C.o_H = take(392 * nenv); C.o_F = take(392 * nenv);
-    C.o_Ld = take(392 * nf); C.o_b = take(56 * nf); C.o_w = take(56 * nf); C.o_y = take(56 * nf); C.o_x = take(56 * nf);
-    return 0;
+    C.debug = debug;
+    return C.prepare(n_graphs, in, out, err);
 }
-
-// graph g into the staging block hin: its slices of the concatenated arrays (the descriptors go in as one block)
-inline void pack_posegraph(const PoseGraphCall& C, int g, const vba_posegraph_problem* P, char* hin) {
-    const PoseGraphLayout& L = C.lay[g];
-    const PgDesc& d = C.desc[g];
-    auto put = [hin](size_t o, size_t at, const void* src, size_t bytes) { if (bytes) std::memcpy(hin + o + at, src, bytes); };
-    put(C.o_Sin, 64 * (size_t)d.v0, P->S, 64 * (size_t)d.nv);
-    put(C.o_meas, 64 * (size_t)d.e0, P->edge_S, 64 * (size_t)d.ne);
-    put(C.o_ei, 4 * (size_t)d.e0, P->edge_i, 4 * (size_t)d.ne);
-    put(C.o_ej, 4 * (size_t)d.e0, P->edge_j, 4 * (size_t)d.ne);
-    put(C.o_free, 4 * (size_t)d.v0, L.free_of.data(), 4 * (size_t)d.nv);
-    put(C.o_vert, 4 * (size_t)d.f0, L.vert_of.data(), 4 * (size_t)d.nf);
-    put(C.o_first, 4 * (size_t)d.f0, L.first.data(), 4 * (size_t)d.nf);
-    put(C.o_last, 4 * (size_t)d.f0, L.last_row.data(), 4 * (size_t)d.nf);
-    put(C.o_roff, 4 * (size_t)d.r0, L.row_off.data(), 4 * ((size_t)d.nf + 1));
-    put(C.o_incb, 4 * (size_t)d.r0, L.inc_begin.data(), 4 * ((size_t)d.nf + 1));
-    put(C.o_inc, 4 * (size_t)d.inc0, L.inc.data(), 4 * L.inc.size());
-    put(C.o_plo, 4 * (size_t)d.pair0, L.pair_lo.data(), 4 * L.pair_lo.size());
-    put(C.o_phi, 4 * (size_t)d.pair0, L.pair_hi.data(), 4 * L.pair_hi.size());
-    put(C.o_pb, 4 * (size_t)d.pb0, L.pair_begin.data(), 4 * L.pair_begin.size());
-    put(C.o_pe, 4 * (size_t)d.pe0, L.pair_edge.data(), 4 * L.pair_edge.size());
-    put(C.o_pt, 24 * (size_t)d.pt0, P->pt, 24 * (size_t)d.n_pt);
-    int* ref = at<int>(hin, C.o_ref) + d.pt0;
-    for (int p = 0; p < d.n_pt; p++) ref[p] = (int)d.v0 + P->pt_ref[p];   // index into the concatenated vertices
-}
-
-// Sf, pf: the call's estimate and point regions as they came back
-inline void unpack_posegraph(vba_posegraph_problem* P, vba_posegraph_result* R, const PgDesc& d, const PgOut& r, const double* Sf, const double* pf) {
-    R->status = r.status; R->its_done = r.its_done; R->lm_trials = r.lm_trials; R->stop = r.stop;
-    R->chi2_initial = r.chi2_initial; R->chi2_final = r.chi2_final; R->lambda_final = r.lambda_final;
-    if (d.nv) std::memcpy(P->S, Sf + 8 * (size_t)d.v0, 64 * (size_t)d.nv);   // fixed vertices: the input, bit for bit
-    if (d.n_pt) std::memcpy(P->pt, pf + 3 * (size_t)d.pt0, 24 * (size_t)d.n_pt);
-}
+inline void pack_posegraph(const PoseGraphCall& C, int g, const vba_posegraph_problem* P, char* hin) { C.pack(g, P, hin); }
 
 // the envelope blocks of one graph (env, [env_blocks][49]) expanded to the dense symmetric H, [7 n_free]^2 row-major
 inline void expand_envelope(const PoseGraphLayout& L, const double* env, double* H) {

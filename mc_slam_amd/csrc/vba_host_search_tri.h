@@ -183,4 +183,39 @@ inline void unpack_search_tri(vba_search_tri_result* R, const StDesc& d, const S
     }
 }
 
+// One call (a fresh object each): what the driver (run_small, vba_host_small.h) and the sanitizer harness (run_call,
+// tests/host_check.h) run.  bind is the only place that maps the arena's regions to the kernel's pointers
+struct SearchTriCall {
+    int n = 0;
+    SearchTriTotals T;
+    SearchTriArena A = SearchTriArena(0, SearchTriTotals());
+    int prepare(int n_pairs, const vba_search_tri_problem* const* in, const vba_search_tri_result* const* out, std::string& err) {
+        n = n_pairs;
+        if (check_search_tri(n, in, out, T, err)) return 1;
+        A = SearchTriArena((size_t)n, T);
+        return 0;
+    }
+    const ArenaLayout& layout() const { return A.L; }
+    size_t download_bytes() const { return A.L.back_bytes(); }
+    size_t grid() const { return (size_t)n; }   // k_search_tri: one workgroup per pair
+    StDesc* desc(void* hin) const { return at<StDesc>(hin, A.desc); }
+    void describe(const vba_search_tri_problem* const* in, void* hin) const { describe_search_tri(n, in, desc(hin)); }
+    const char* pack(int f, const vba_search_tri_problem* P, void* hin) const {
+        pack_search_tri(P, desc(hin)[f], at<StKey>(hin, A.key1), at<StKey>(hin, A.key2), at<StQuery>(hin, A.query), at<int32_t>(hin, A.feat),
+                        at<double>(hin, A.lev));
+        return nullptr;
+    }
+    StBatch bind(void* base) const {
+        StBatch B;
+        B.desc = desc(base); B.key1 = at<StKey>(base, A.key1); B.key2 = at<StKey>(base, A.key2); B.query = at<StQuery>(base, A.query);
+        B.feat = at<int>(base, A.feat); B.lev = at<double>(base, A.lev); B.out = at<StOut>(base, A.out); B.match12 = at<int>(base, A.match12);
+        B.best_dist = at<unsigned char>(base, A.best_dist); B.state = at<unsigned char>(base, A.state);
+        return B;
+    }
+    void unpack(int f, vba_search_tri_problem*, vba_search_tri_result* R, void* hin, void* hout) const {
+        unpack_search_tri(R, desc(hin)[f], at<StOut>(hout, A.L.in_back(A.out))[f], at<int32_t>(hout, A.L.in_back(A.match12)),
+                          at<unsigned char>(hout, A.L.in_back(A.best_dist)), at<unsigned char>(hout, A.L.in_back(A.state)));
+    }
+};
+
 }  // namespace vba_host

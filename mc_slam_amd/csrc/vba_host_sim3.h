@@ -91,4 +91,38 @@ inline void unpack_sim3(vba_sim3_problem* P, vba_sim3_result* R, const Sim3Desc&
     for (size_t i = 0; i < n && R->chi2_21; i++) R->chi2_21[i] = cc[2 * (o + i) + 1];
 }
 
+// One call (a fresh object each): what the driver (run_small, vba_host_small.h) and the sanitizer harness (run_call,
+// tests/host_check.h) run.  bind is the only place that maps the arena's regions to the kernel's pointers
+struct Sim3Call {
+    int n = 0;
+    size_t n_tot = 0;
+    bool want_chi2 = false;
+    Sim3Arena A = Sim3Arena(0, 0);
+    int prepare(int n_problems, const vba_sim3_problem* const* in, const vba_sim3_result* const* out, std::string& err) {
+        n = n_problems;
+        if (check_sim3(n, in, out, n_tot, want_chi2, err)) return 1;
+        A = Sim3Arena((size_t)n, n_tot);
+        return 0;
+    }
+    const ArenaLayout& layout() const { return A.L; }
+    size_t download_bytes() const { return A.download_bytes(want_chi2); }
+    size_t grid() const { return (size_t)n; }   // k_sim3_opt: one workgroup per candidate
+    Sim3Desc* desc(void* hin) const { return at<Sim3Desc>(hin, A.desc); }
+    void describe(const vba_sim3_problem* const* in, void* hin) const { describe_sim3(n, in, desc(hin)); }
+    const char* pack(int f, const vba_sim3_problem* P, void* hin) const {
+        pack_sim3(P, desc(hin)[f], at<double>(hin, A.p), at<double>(hin, A.uv), at<double>(hin, A.w));
+        return nullptr;
+    }
+    Sim3Batch bind(void* base) const {
+        Sim3Batch B;
+        B.desc = desc(base); B.out = at<Sim3Out>(base, A.out); B.p = at<double>(base, A.p); B.uv = at<double>(base, A.uv);
+        B.w = at<double>(base, A.w); B.c = at<double>(base, A.c); B.flag = at<unsigned char>(base, A.flag);
+        return B;
+    }
+    void unpack(int f, vba_sim3_problem* P, vba_sim3_result* R, void* hin, void* hout) const {
+        unpack_sim3(P, R, desc(hin)[f], at<Sim3Out>(hout, A.L.in_back(A.out))[f], at<unsigned char>(hout, A.L.in_back(A.flag)),
+                    at<double>(hout, A.L.in_back(A.c)));
+    }
+};
+
 }  // namespace vba_host

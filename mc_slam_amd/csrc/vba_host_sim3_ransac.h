@@ -107,4 +107,38 @@ inline void unpack_sim3_ransac(vba_sim3_ransac_problem* P, vba_sim3_ransac_resul
     if (R->hyp_inliers && nh) std::memcpy(R->hyp_inliers, cnt + (size_t)d.hyp0, 4 * nh);
 }
 
+// One call (a fresh object each): what the driver (run_small, vba_host_small.h) and the sanitizer harness (run_call,
+// tests/host_check.h) run.  bind is the only place that maps the arena's regions to the kernel's pointers
+struct RansacCall {
+    int n = 0;
+    size_t n_tot = 0, h_tot = 0;
+    bool want_counts = false;
+    RansacArena A = RansacArena(0, 0, 0);
+    int prepare(int n_problems, const vba_sim3_ransac_problem* const* in, const vba_sim3_ransac_result* const* out, std::string& err) {
+        n = n_problems;
+        if (check_sim3_ransac(n, in, out, n_tot, h_tot, want_counts, err)) return 1;
+        A = RansacArena((size_t)n, n_tot, h_tot);
+        return 0;
+    }
+    const ArenaLayout& layout() const { return A.L; }
+    size_t download_bytes() const { return A.download_bytes(want_counts); }
+    size_t grid() const { return (size_t)n; }   // k_sim3_ransac: one workgroup per candidate
+    RansacDesc* desc(void* hin) const { return at<RansacDesc>(hin, A.desc); }
+    void describe(const vba_sim3_ransac_problem* const* in, void* hin) const { describe_sim3_ransac(n, in, desc(hin)); }
+    const char* pack(int f, const vba_sim3_ransac_problem* P, void* hin) const {
+        pack_sim3_ransac(P, desc(hin)[f], at<double>(hin, A.p), at<double>(hin, A.gate), at<int32_t>(hin, A.sample));
+        return nullptr;
+    }
+    RansacBatch bind(void* base) const {
+        RansacBatch B;
+        B.desc = desc(base); B.out = at<RansacOut>(base, A.out); B.p = at<double>(base, A.p); B.gate = at<double>(base, A.gate);
+        B.sample = at<int>(base, A.sample); B.hyp = at<double>(base, A.hyp); B.cnt = at<int>(base, A.cnt); B.flag = at<unsigned char>(base, A.flag);
+        return B;
+    }
+    void unpack(int f, vba_sim3_ransac_problem* P, vba_sim3_ransac_result* R, void* hin, void* hout) const {
+        unpack_sim3_ransac(P, R, desc(hin)[f], at<RansacOut>(hout, A.L.in_back(A.out))[f], at<unsigned char>(hout, A.L.in_back(A.flag)),
+                           at<int32_t>(hout, A.L.in_back(A.cnt)));
+    }
+};
+
 }  // namespace vba_host

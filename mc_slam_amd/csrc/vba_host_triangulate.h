@@ -115,4 +115,36 @@ inline void unpack_triangulate(vba_triangulate_result* R, const TriDesc& d, cons
     R->n_accepted = acc;
 }
 
+// One call (a fresh object each): what the driver (run_small, vba_host_small.h) and the sanitizer harness (run_call,
+// tests/host_check.h) run.  bind is the only place that maps the arena's regions to the kernel's pointers
+struct TriCall {
+    int n = 0;
+    size_t n_tot = 0, l_tot = 0, n_blocks = 0;
+    TriArena A = TriArena(0, 0, 0, 0);
+    int prepare(int n_pairs, const vba_triangulate_problem* const* in, const vba_triangulate_result* const* out, std::string& err) {
+        n = n_pairs;
+        if (check_triangulate(n, in, out, n_tot, l_tot, n_blocks, err)) return 1;
+        A = TriArena((size_t)n, n_tot, l_tot, n_blocks);
+        return 0;
+    }
+    const ArenaLayout& layout() const { return A.L; }
+    size_t download_bytes() const { return A.L.back_bytes(); }
+    size_t grid() const { return n_blocks; }   // k_triangulate: one lane per match; a call without a single match launches nothing
+    TriDesc* desc(void* hin) const { return at<TriDesc>(hin, A.desc); }
+    void describe(const vba_triangulate_problem* const* in, void* hin) const { describe_triangulate(n, in, desc(hin), at<TriBlock>(hin, A.blk)); }
+    const char* pack(int f, const vba_triangulate_problem* P, void* hin) const {
+        pack_triangulate(P, desc(hin)[f], at<double>(hin, A.lev), at<double>(hin, A.uv), at<unsigned char>(hin, A.oct));
+        return nullptr;
+    }
+    TriBatch bind(void* base) const {
+        TriBatch B;
+        B.desc = desc(base); B.blk = at<TriBlock>(base, A.blk); B.lev = at<double>(base, A.lev); B.uv = at<double>(base, A.uv);
+        B.oct = at<unsigned char>(base, A.oct); B.x3d = at<double>(base, A.x3d); B.reason = at<unsigned char>(base, A.reason);
+        return B;
+    }
+    void unpack(int f, vba_triangulate_problem*, vba_triangulate_result* R, void* hin, void* hout) const {
+        unpack_triangulate(R, desc(hin)[f], at<double>(hout, A.L.in_back(A.x3d)), at<unsigned char>(hout, A.L.in_back(A.reason)));
+    }
+};
+
 }  // namespace vba_host

@@ -131,4 +131,43 @@ inline void unpack_two_view(vba_two_view_result* R, const TvDesc& d, const TvOut
     if (R->hyp_score_f && nh) std::memcpy(R->hyp_score_f, sf + (size_t)d.hyp0, 8 * nh);
 }
 
+// One call (a fresh object each): what the driver (run_small, vba_host_small.h) and the sanitizer harness (run_call,
+// tests/host_check.h) run.  bind is the only place that maps the arena's regions to the kernel's pointers
+struct TwoViewCall {
+    int n = 0;
+    TwoViewTotals T;
+    TwoViewArena A = TwoViewArena(0, TwoViewTotals());
+    int prepare(int n_problems, const vba_two_view_problem* const* in, const vba_two_view_result* const* out, std::string& err) {
+        n = n_problems;
+        if (check_two_view(n, in, out, T, err)) return 1;
+        A = TwoViewArena((size_t)n, T);
+        return 0;
+    }
+    const ArenaLayout& layout() const { return A.L; }
+    size_t download_bytes() const { return A.download_bytes(T.want_scores); }
+    size_t grid() const { return (size_t)n; }   // k_two_view: one workgroup per pair
+    TvDesc* desc(void* hin) const { return at<TvDesc>(hin, A.desc); }
+    void describe(const vba_two_view_problem* const* in, void* hin) const { describe_two_view(n, in, desc(hin)); }
+    const char* pack(int f, const vba_two_view_problem* P, void* hin) const {
+        pack_two_view(P, desc(hin)[f], at<double>(hin, A.uv1), at<double>(hin, A.uv2), at<int32_t>(hin, A.match), at<int32_t>(hin, A.sets));
+        return nullptr;
+    }
+    TvBatch bind(void* base) const {
+        TvBatch B;
+        B.desc = desc(base); B.uv1 = at<double>(base, A.uv1); B.uv2 = at<double>(base, A.uv2); B.match = at<int>(base, A.match);
+        B.sets = at<int>(base, A.sets); B.out = at<TvOut>(base, A.out); B.flag_h = at<unsigned char>(base, A.flag_h);
+        B.flag_f = at<unsigned char>(base, A.flag_f); B.tri = at<unsigned char>(base, A.tri); B.x3d = at<double>(base, A.x3d);
+        B.score_h = at<double>(base, A.score_h); B.score_f = at<double>(base, A.score_f); B.hyp_h = at<double>(base, A.hyp_h);
+        B.hyp_f = at<double>(base, A.hyp_f); B.rt_state = at<unsigned char>(base, A.rt_state); B.rt_cos = at<double>(base, A.rt_cos);
+        B.rt_x = at<double>(base, A.rt_x);
+        return B;
+    }
+    void unpack(int f, vba_two_view_problem*, vba_two_view_result* R, void* hin, void* hout) const {
+        auto u8 = [&](size_t o) { return at<unsigned char>(hout, A.L.in_back(o)); };
+        auto f64 = [&](size_t o) { return at<double>(hout, A.L.in_back(o)); };
+        unpack_two_view(R, desc(hin)[f], at<TvOut>(hout, A.L.in_back(A.out))[f], u8(A.flag_h), u8(A.flag_f), u8(A.tri), f64(A.x3d), f64(A.score_h),
+                        f64(A.score_f));
+    }
+};
+
 }  // namespace vba_host

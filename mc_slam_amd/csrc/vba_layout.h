@@ -90,8 +90,8 @@ struct WinCtrl {
     double trace[VBA_TRACE];
 };
 
-// ---- the small-problem entry points: per-item descriptor (host -> device) and result record (device -> host); the *Batch
-// structs of device pointers stay with their kernels
+// ---- the small-problem entry points: per-item descriptor (host -> device), result record (device -> host) and the *Batch of
+// device pointers a kernel takes as its argument (filled by bind() of the topic's call object, vba_host_<topic>.h)
 // vba_pose_optimize (vba_pose.h)
 struct FrameDesc {
     int last_is_frame, compute_marg, n_obs, n_last;
@@ -112,6 +112,14 @@ struct FrameOut {
     double nav[22];
     double marg[225];
 };
+struct PoseBatch {
+    const FrameDesc* desc;
+    FrameOut* out;
+    const double *pw, *uv, *w;   // [total obs] current-frame observations first, then the last frames'
+    double* err;                 // [total obs][2] stored _error of every mono edge
+    unsigned char* lvl;          // [total obs] g2o level (1 = outlier, outside the active set)
+    int n_frames;
+};
 // vba_sim3_optimize (vba_sim3.h)
 struct Sim3Desc {
     int n_pairs, fix_scale;
@@ -128,6 +136,17 @@ struct Sim3Out {
     double S[8];
 };
 static_assert(sizeof(Sim3Desc) == 176 && sizeof(Sim3Out) == 112, "scripts/sim3_bench.py derives the copied bytes from these sizes");
+struct Sim3Batch {
+    const Sim3Desc* desc;
+    Sim3Out* out;
+    // per-pair arrays, the two sides of a pair interleaved (five base pointers instead of eleven: the kernel is short of scalar
+    // registers, and a lane fetches both sides with one wide load)
+    const double* p;           // [total pairs][6] P1c, P2c
+    const double* uv;          // [total pairs][4] uv1, uv2
+    const double* w;           // [total pairs][2] w1, w2
+    double* c;                 // [total pairs][2] chi2 of e12 and e21 at the last evaluation
+    unsigned char* flag;       // [total pairs] 1 = the pair left the problem (g2o: both edges removed)
+};
 // vba_sim3_ransac (vba_sim3_ransac.h)
 struct RansacDesc {
     int n_pairs, fix_scale, min_inliers, n_hyp, best_inliers;
@@ -143,6 +162,16 @@ struct RansacOut {
 };
 #define VBA_RANSAC_HYP 32      // doubles per hypothesis record (device only): sR12 (9) t12 (3) sR21 (9) t21 (3) t (3) q (4) s (1)
 static_assert(sizeof(RansacDesc) == 104 && sizeof(RansacOut) == 160, "scripts/sim3_ransac_bench.py derives the copied bytes from these sizes");
+struct RansacBatch {
+    const RansacDesc* desc;
+    RansacOut* out;
+    const double* p;           // [total pairs][6] P1c, P2c
+    const double* gate;        // [total pairs][2] max_err1, max_err2
+    const int* sample;         // [total hypotheses][3]
+    double* hyp;               // [total hypotheses][VBA_RANSAC_HYP] device only
+    int* cnt;                  // [total hypotheses] inlier count of every hypothesis
+    unsigned char* flag;       // [total pairs] inlier flags of the hit
+};
 // vba_triangulate (vba_triangulate.h)
 #define VBA_TRI_CONST 41       // doubles of a pair's constants: Rcw1 (9) tcw1 (3) Ow1 (3) K1 (4), the same of keyframe 2, ratio_factor cos_max chi2_th
 #define VBA_TRI_LEVELS 64      // most pyramid levels of a keyframe
@@ -157,6 +186,15 @@ struct TriBlock {
     int pair, first;           // the pair of a workgroup and its first match inside the pair
 };
 static_assert(sizeof(TriDesc) == 360 && sizeof(TriBlock) == 8, "scripts/triangulate_bench.py derives the copied bytes from these sizes");
+struct TriBatch {
+    const TriDesc* desc;
+    const TriBlock* blk;         // [workgroups] the pair of a workgroup and its first match inside the pair
+    const double* lev;           // level tables of all pairs: sigma2_1 [n_levels1] scale_1 [n_levels1] sigma2_2 [n_levels2] scale_2 [n_levels2]
+    const double* uv;            // [total matches][4] u1 v1 u2 v2
+    const unsigned char* oct;    // [total matches][2] octave in keyframe 1 / 2
+    double* x3d;                 // [total matches][3]
+    unsigned char* reason;       // [total matches]
+};
 // vba_two_view_init (vba_two_view.h)
 struct TvDesc {
     long long key1_0, key2_0, match0, hyp0;   // offsets of the pair's keypoints, matches and hypotheses in the concatenated arrays
@@ -173,6 +211,25 @@ struct TvOut {
 #define VBA_TV_HYP_F 9         // doubles per F hypothesis record (device only): F21
 #define VBA_TV_RT 8            // most (R, t) hypotheses of a pair: the per-(hypothesis, match) regions hold this many per match
 static_assert(sizeof(TvDesc) == 104 && sizeof(TvOut) == 400, "scripts/two_view_bench.py derives the copied bytes from these sizes");
+struct TvBatch {
+    const TvDesc* desc;
+    const double* uv1;           // [total keypoints of frames 1][2]
+    const double* uv2;           // [total keypoints of frames 2][2]
+    const int* match;            // [total matches][2]
+    const int* sets;             // [total hypotheses][8]
+    TvOut* out;
+    unsigned char* flag_h;       // [total matches] inlier flags of the best H / F hypothesis
+    unsigned char* flag_f;
+    unsigned char* tri;          // [total keypoints of frames 1]
+    double* x3d;                 // [total keypoints of frames 1][3]
+    double* score_h;             // [total hypotheses]
+    double* score_f;
+    double* hyp_h;               // [total hypotheses][VBA_TV_HYP_H] device only
+    double* hyp_f;               // [total hypotheses][VBA_TV_HYP_F] device only
+    unsigned char* rt_state;     // [VBA_TV_RT * total matches] device only: 0 rejected, 1 counted, 2 counted and flagged
+    double* rt_cos;              // [VBA_TV_RT * total matches] device only
+    double* rt_x;                // [VBA_TV_RT * total matches][3] device only
+};
 // vba_search_triangulation (vba_search_tri.h)
 #define VBA_ST_NT 256          // lanes of the one workgroup of a pair
 #define VBA_ST_HISTO 30        // HISTO_LENGTH (src/ORBmatcher.cpp:42)
@@ -203,6 +260,18 @@ struct StOut {
 };
 static_assert(sizeof(StKey) == 64 && sizeof(StQuery) == 16 && sizeof(StDesc) == 160 && sizeof(StOut) == 144,
               "scripts/search_tri_bench.py derives the copied bytes from these sizes");
+struct StBatch {
+    const StDesc* desc;
+    const StKey* key1;           // keypoint records of keyframe 1 of all pairs
+    const StKey* key2;           // ... of keyframe 2
+    const StQuery* query;        // [total keypoints of keyframe 1] the first n_q of a pair's region (at key1_0) are used
+    const int* feat;             // node_feat_2 of all pairs
+    const double* lev;           // level tables of all pairs: level_sigma2_2 [n_levels2] scale_2 [n_levels2]
+    StOut* out;                  // [pairs]
+    int* match12;                // [total keypoints of keyframe 1]
+    unsigned char* best_dist;    // ...
+    unsigned char* state;        // ...
+};
 // vba_fuse (vba_fuse.h)
 #define VBA_FU_NT 256          // lanes of a workgroup = most points of a tile
 #define VBA_FU_CONST 29        // doubles of a problem's constants: Rcw (9) tcw (3) Ow (3) K (4) bounds (4) grid_inv_w grid_inv_h
@@ -232,6 +301,20 @@ struct FuDesc {
 };
 static_assert(sizeof(FuKey) == 64 && sizeof(FuPoint) == 128 && sizeof(FuTile) == 8 && sizeof(FuDesc) == 304,
               "scripts/fuse_bench.py derives the copied bytes from these sizes");
+struct FuBatch {
+    const FuDesc* desc;
+    const FuTile* tile;          // [tiles]
+    const FuKey* key;            // keypoint records of all problems
+    const FuPoint* pt;           // point records of all problems
+    const int* cell_begin;       // cell_begin of all problems
+    const int* cell_feat;        // cell_feat of all problems
+    const double* lev;           // level tables of all problems: scale [n_levels] inv_level_sigma2 [n_levels]
+    int* best_idx;               // [total points]
+    unsigned short* best_dist;   // ...
+    signed char* level;          // ...
+    double* uv;                  // [total points][2]
+    unsigned char* state;        // [total points]
+};
 // vba_posegraph_optimize (vba_posegraph.h)
 struct PgDesc {
     int nv, ne, nf, npair;
@@ -243,4 +326,29 @@ struct PgDesc {
 struct PgOut {
     int status, its_done, lm_trials, stop;
     double chi2_initial, chi2_final, lambda_final;
+};
+struct PgBatch {
+    const PgDesc* desc;
+    PgOut* out;
+    const double* Sin;       // [vertices][8] t(3) q(4, xyzw) s: the initial estimates
+    const double* meas;      // [edges][8] Sji
+    const int *ei, *ej;      // [edges] vertex 0 / vertex 1
+    const int* free_of;      // [vertices] free index or -1
+    const int *vert_of, *first, *last_row;   // [free]
+    const int *row_off, *inc_begin;          // [free + graphs]
+    const int* inc;
+    const int *pair_lo, *pair_hi;            // [pairs]
+    const int* pair_begin;                   // [pairs + graphs]
+    const int* pair_edge;
+    const double* pt_in;     // [points][3]
+    const int* pt_ref;       // [points] index into the concatenated vertices
+    double* S;               // [vertices][8] the estimates (copied back)
+    double* Sbk;             // [vertices][8] push() / pop()
+    double* err;             // [edges][7]
+    double* J;               // [edges][2][49] J_i, J_j row-major (error component, direction)
+    double *H, *F;           // [envelope blocks][49]
+    double* Ld;              // [free][49] factor of the diagonal blocks: unit lower L with D on the diagonal
+    double *b, *w, *y, *x;   // [free][7]
+    double* pt_out;          // [points][3]
+    long long n_pt_total;
 };

@@ -11,15 +11,6 @@
 #include "vba_device.h"
 #include "vba_layout.h"
 
-struct PoseBatch {
-    const FrameDesc* desc;
-    FrameOut* out;
-    const double *pw, *uv, *w;   // [total obs] current-frame observations first, then the last frames'
-    double* err;                 // [total obs][2] stored _error of every mono edge
-    unsigned char* lvl;          // [total obs] g2o level (1 = outlier, outside the active set)
-    int n_frames;
-};
-
 #define PO_N 30
 // LDS layout (doubles)
 #define PO_A 0                  // damped copy / Cholesky factor (30x30); the Gauss-Jordan workspace [30][60] of the marginals

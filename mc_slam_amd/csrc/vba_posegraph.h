@@ -31,32 +31,6 @@
 
 #define PG_NT 256
 
-struct PgBatch {
-    const PgDesc* desc;
-    PgOut* out;
-    const double* Sin;       // [vertices][8] t(3) q(4, xyzw) s: the initial estimates
-    const double* meas;      // [edges][8] Sji
-    const int *ei, *ej;      // [edges] vertex 0 / vertex 1
-    const int* free_of;      // [vertices] free index or -1
-    const int *vert_of, *first, *last_row;   // [free]
-    const int *row_off, *inc_begin;          // [free + graphs]
-    const int* inc;
-    const int *pair_lo, *pair_hi;            // [pairs]
-    const int* pair_begin;                   // [pairs + graphs]
-    const int* pair_edge;
-    const double* pt_in;     // [points][3]
-    const int* pt_ref;       // [points] index into the concatenated vertices
-    double* S;               // [vertices][8] the estimates (copied back)
-    double* Sbk;             // [vertices][8] push() / pop()
-    double* err;             // [edges][7]
-    double* J;               // [edges][2][49] J_i, J_j row-major (error component, direction)
-    double *H, *F;           // [envelope blocks][49]
-    double* Ld;              // [free][49] factor of the diagonal blocks: unit lower L with D on the diagonal
-    double *b, *w, *y, *x;   // [free][7]
-    double* pt_out;          // [points][3]
-    long long n_pt_total;
-};
-
 DEVI Sim3State pg_load(const double* p) {
     Sim3State S;
 #pragma unroll

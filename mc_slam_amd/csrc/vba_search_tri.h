@@ -26,19 +26,6 @@
 #define ST_CHI2 11
 #define ST_R2 12
 
-struct StBatch {
-    const StDesc* desc;
-    const StKey* key1;           // keypoint records of keyframe 1 of all pairs
-    const StKey* key2;           // ... of keyframe 2
-    const StQuery* query;        // [total keypoints of keyframe 1] the first n_q of a pair's region (at key1_0) are used
-    const int* feat;             // node_feat_2 of all pairs
-    const double* lev;           // level tables of all pairs: level_sigma2_2 [n_levels2] scale_2 [n_levels2]
-    StOut* out;                  // [pairs]
-    int* match12;                // [total keypoints of keyframe 1]
-    unsigned char* best_dist;    // ...
-    unsigned char* state;        // ...
-};
-
 // :898-901 in float32, these three operations and C round (half away from zero)
 DEVI int st_bin(float angle1, float angle2) {
     float rot = angle1 - angle2;

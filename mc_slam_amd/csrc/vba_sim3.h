@@ -23,18 +23,6 @@
 #include "vba_layout.h"
 #include "vba_pose.h"   // po_wave_sum
 
-struct Sim3Batch {
-    const Sim3Desc* desc;
-    Sim3Out* out;
-    // per-pair arrays, the two sides of a pair interleaved (five base pointers instead of eleven: the kernel is short of scalar
-    // registers, and a lane fetches both sides with one wide load)
-    const double* p;           // [total pairs][6] P1c, P2c
-    const double* uv;          // [total pairs][4] uv1, uv2
-    const double* w;           // [total pairs][2] w1, w2
-    double* c;                 // [total pairs][2] chi2 of e12 and e21 at the last evaluation
-    unsigned char* flag;       // [total pairs] 1 = the pair left the problem (g2o: both edges removed)
-};
-
 struct Sim3State { double q[4], t[3], s; };
 
 // Sum over the wave that leaves the SAME bits in every lane without a closing broadcast: the 16 lanes of a row by data-parallel-

@@ -28,17 +28,6 @@
 #define RS_NT 256
 #define RS_SWEEPS 8   // cyclic Jacobi sweeps over the six off-diagonal entries of N (4x4 converges quadratically: 5-6 suffice in FP64)
 
-struct RansacBatch {
-    const RansacDesc* desc;
-    RansacOut* out;
-    const double* p;           // [total pairs][6] P1c, P2c
-    const double* gate;        // [total pairs][2] max_err1, max_err2
-    const int* sample;         // [total hypotheses][3]
-    double* hyp;               // [total hypotheses][VBA_RANSAC_HYP] device only
-    int* cnt;                  // [total hypotheses] inlier count of every hypothesis
-    unsigned char* flag;       // [total pairs] inlier flags of the hit
-};
-
 // one Jacobi rotation in the (P, Q) plane of the symmetric A (both triangles kept), accumulated into V (columns = eigenvectors)
 template <int P, int Q>
 DEVI void rs_rotate(double (&A)[4][4], double (&V)[4][4]) {

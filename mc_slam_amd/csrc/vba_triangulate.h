@@ -23,16 +23,6 @@
 #define TR_NT VBA_TRI_NT
 #define TR_SWEEPS 8   // cyclic sweeps over the six column pairs (4 columns converge quadratically: 5-6 suffice in FP64)
 
-struct TriBatch {
-    const TriDesc* desc;
-    const TriBlock* blk;         // [workgroups] the pair of a workgroup and its first match inside the pair
-    const double* lev;           // level tables of all pairs: sigma2_1 [n_levels1] scale_1 [n_levels1] sigma2_2 [n_levels2] scale_2 [n_levels2]
-    const double* uv;            // [total matches][4] u1 v1 u2 v2
-    const unsigned char* oct;    // [total matches][2] octave in keyframe 1 / 2
-    double* x3d;                 // [total matches][3]
-    unsigned char* reason;       // [total matches]
-};
-
 // one rotation in the plane of columns P, Q of U that makes them orthogonal, accumulated into V (columns = right singular vectors)
 template <int P, int Q>
 DEVI void tr_rotate(double (&U)[4][4], double (&V)[4][4]) {

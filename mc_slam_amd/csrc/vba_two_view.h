@@ -35,26 +35,6 @@
 #define TV_SWEEPS 10    // round-robin sweeps over the 36 column pairs of a 9-column A
 #define TV_SWEEPS3 8    // cyclic sweeps over the three column pairs of a 3x3
 
-struct TvBatch {
-    const TvDesc* desc;
-    const double* uv1;           // [total keypoints of frames 1][2]
-    const double* uv2;           // [total keypoints of frames 2][2]
-    const int* match;            // [total matches][2]
-    const int* sets;             // [total hypotheses][8]
-    TvOut* out;
-    unsigned char* flag_h;       // [total matches] inlier flags of the best H / F hypothesis
-    unsigned char* flag_f;
-    unsigned char* tri;          // [total keypoints of frames 1]
-    double* x3d;                 // [total keypoints of frames 1][3]
-    double* score_h;             // [total hypotheses]
-    double* score_f;
-    double* hyp_h;               // [total hypotheses][VBA_TV_HYP_H] device only
-    double* hyp_f;               // [total hypotheses][VBA_TV_HYP_F] device only
-    unsigned char* rt_state;     // [VBA_TV_RT * total matches] device only: 0 rejected, 1 counted, 2 counted and flagged
-    double* rt_cos;              // [VBA_TV_RT * total matches] device only
-    double* rt_x;                // [VBA_TV_RT * total matches][3] device only
-};
-
 DEVI double tv_sel3(int k, double a0, double a1, double a2) { return (k == 0) ? a0 : (k == 1) ? a1 : a2; }
 DEVI double tv_det3(const double* m) {
     return (m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6])) + m[2] * (m[3] * m[7] - m[4] * m[6]);

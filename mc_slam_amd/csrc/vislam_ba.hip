@@ -1,11 +1,14 @@
 // vislam_ba.hip -- C-ABI (include/vislam_ba.h) of the MI355X local-BA backend, one translation unit: the kernel headers, the host
-// side by topic (vba_host_structure.h / vba_host_posegraph.h: the plain-C++ structure builds, vba_host_handle.h: handle and buffers,
-// vba_host_upload.h: H2D + structure build, vba_host_run.h: the lock-step launch schedule of the two-stage solve and the download,
-// vba_host_batch.h: lanes and tickets, vba_host_small.h: the small-problem entry points over their plain-C++ halves
-// vba_host_pose.h / vba_host_sim3.h / vba_host_sim3_ransac.h / vba_host_triangulate.h / vba_host_two_view.h / vba_host_search_tri.h / vba_host_fuse.h / vba_host_posegraph.h, vba_host_hooks.h), and below the extern "C"
-// entry points: vba_create / destroy / last_error, vba_solve*, vba_batch_upload / run / download / solve*, vba_batch_set_depth /
-// submit* / poll / wait, vba_preintegrate, vba_pose_optimize, vba_triangulate (new map points), vba_two_view_init (monocular initialisation), vba_search_triangulation (the matcher in front of vba_triangulate), vba_fuse (the projection search of map-point fusion), vba_sim3_ransac, vba_sim3_optimize, vba_posegraph_optimize (the last
-// three are the solver stages of loop closing), vba_host_threads, vba_set_profile / get_profile.
+// side by topic, and below the extern "C" entry points.
+//   the solve     vba_host_structure.h (plain-C++ structure build), vba_host_handle.h (handle and buffers), vba_host_upload.h (H2D +
+//                 structure build), vba_host_run.h (the lock-step launch schedule of the two-stage solve and the download),
+//                 vba_host_batch.h (lanes and tickets): vba_create / destroy / last_error, vba_solve*, vba_batch_upload / run /
+//                 download / solve*, vba_batch_set_depth / submit* / poll / wait
+//   small problems  vba_host_small.h: one driver over the plain-C++ call object of each topic (vba_host_<topic>.h).  Tracking:
+//                 vba_preintegrate, vba_pose_optimize.  Initialisation: vba_two_view_init.  Local mapping:
+//                 vba_search_triangulation (the matcher in front of) vba_triangulate, vba_fuse.  Loop closing: vba_sim3_ransac,
+//                 vba_sim3_optimize, vba_posegraph_optimize
+//   the rest      vba_host_hooks.h (vba_debug_*, hooks flavour), vba_host_threads, vba_set_profile / get_profile
 //
 // Host-side control flow restated from src/Optimizer.cpp:453-517 (two-stage protocol) and
 // Thirdparty/g2o/g2o/core/sparse_optimizer.cpp:354-419 (optimize loop); all per-iteration decisions are taken
@@ -35,6 +38,14 @@
 #include "vba_host_batch.h"
 #include "vba_host_small.h"
 #include "vba_host_hooks.h"
+
+namespace {
+// the handle of an entry point that needs it idle; nullptr (the entry point returns -1) for no handle or one with tickets in flight
+Handle* idle_handle(void* handle) {
+    Handle* h = reinterpret_cast<Handle*>(handle);
+    return (h && !async_busy(h)) ? h : nullptr;
+}
+}  // namespace
 
 extern "C" {
 
@@ -66,7 +77,7 @@ int vba_destroy(void* handle) {
 #ifdef VBA_TEST_HOOKS
     for (auto& b : h->cap) b.release();
 #endif
-    for (SideArena* a : {&h->preint, &h->pose, &h->sim3, &h->pg, &h->ransac, &h->tri, &h->tv, &h->st, &h->fu}) a->release();
+    for (auto& a : h->side) a.release();
     for (auto e : h->evt_pool) (void)hipEventDestroy(e);
     if (h->up_done) (void)hipEventDestroy(h->up_done);
     if (h->owns_streams)
@@ -83,24 +94,20 @@ const char* vba_last_error(void* handle) {
 }
 
 int vba_batch_upload(void* handle, int32_t n, vba_problem* const* problems) {
-    Handle* h = reinterpret_cast<Handle*>(handle);
-    if (!h || async_busy(h)) return -1;
-    return do_upload(h, n, problems);
+    Handle* h = idle_handle(handle);
+    return h ? do_upload(h, n, problems) : -1;
 }
 int vba_batch_run(void* handle, const volatile int* stop_flag) {
-    Handle* h = reinterpret_cast<Handle*>(handle);
-    if (!h || async_busy(h)) return -1;
-    return do_run(h, stop_int(stop_flag));
+    Handle* h = idle_handle(handle);
+    return h ? do_run(h, stop_int(stop_flag)) : -1;
 }
 int vba_batch_run_b(void* handle, const volatile unsigned char* stop_flag) {
-    Handle* h = reinterpret_cast<Handle*>(handle);
-    if (!h || async_busy(h)) return -1;
-    return do_run(h, stop_byte(stop_flag));
+    Handle* h = idle_handle(handle);
+    return h ? do_run(h, stop_byte(stop_flag)) : -1;
 }
 int vba_batch_download(void* handle, int32_t n, vba_problem* const* inout, vba_result* const* out) {
-    Handle* h = reinterpret_cast<Handle*>(handle);
-    if (!h || async_busy(h)) return -1;
-    return do_download(h, n, inout, out);
+    Handle* h = idle_handle(handle);
+    return h ? do_download(h, n, inout, out) : -1;
 }
 int vba_solve(void* handle, vba_problem* inout, vba_result* out, const volatile int* stop_flag) { return solve_one(handle, inout, out, stop_int(stop_flag)); }
 int vba_solve_b(void* handle, vba_problem* inout, vba_result* out, const volatile unsigned char* stop_flag) { return solve_one(handle, inout, out, stop_byte(stop_flag)); }
@@ -112,8 +119,8 @@ int vba_batch_solve_b(void* handle, int32_t n, vba_problem* const* inout, vba_re
 }
 
 int vba_batch_set_depth(void* handle, int32_t depth) {
-    Handle* h = reinterpret_cast<Handle*>(handle);
-    if (!h || async_busy(h)) return -1;
+    Handle* h = idle_handle(handle);
+    if (!h) return -1;
     if (depth < 1 || depth > 4) return fail(h, "vba_batch_set_depth: depth must be 1..4");
     if (h->as) {   // idle: the workers leave, arenas beyond the new depth free their device buffers and staging
         AsyncState& A = *h->as;
@@ -165,57 +172,48 @@ int vba_host_threads(void) { return host_threads(); }
 int vba_preintegrate(void* handle, int32_t n_edges, const int32_t* sample_begin, const double* gyr, const double* acc,
                      const double* dt, double gyr_meas_cov, double acc_meas_cov, double* imu_meas, double* cov_pvphi,
                      double* imu_info_prv) {
-    Handle* h = reinterpret_cast<Handle*>(handle);
-    if (!h || async_busy(h)) return -1;
-    return preintegrate(h, n_edges, sample_begin, gyr, acc, dt, gyr_meas_cov, acc_meas_cov, imu_meas, cov_pvphi, imu_info_prv);
+    Handle* h = idle_handle(handle);
+    return h ? preintegrate(h, n_edges, sample_begin, gyr, acc, dt, gyr_meas_cov, acc_meas_cov, imu_meas, cov_pvphi, imu_info_prv) : -1;
 }
 int vba_pose_optimize(void* handle, int32_t n_frames, vba_frame_problem* const* inout, vba_frame_result* const* out) {
-    Handle* h = reinterpret_cast<Handle*>(handle);
-    if (!h || async_busy(h)) return -1;
-    return pose_optimize(h, n_frames, inout, out);
+    Handle* h = idle_handle(handle);
+    return h ? pose_optimize(h, n_frames, inout, out) : -1;
 }
 int vba_sim3_optimize(void* handle, int32_t n_problems, vba_sim3_problem* const* inout, vba_sim3_result* const* out) {
-    Handle* h = reinterpret_cast<Handle*>(handle);
-    if (!h || async_busy(h)) return -1;
-    return sim3_optimize(h, n_problems, inout, out);
+    Handle* h = idle_handle(handle);
+    return h ? sim3_optimize(h, n_problems, inout, out) : -1;
 }
 int vba_sim3_ransac(void* handle, int32_t n_problems, vba_sim3_ransac_problem* const* inout, vba_sim3_ransac_result* const* out) {
-    Handle* h = reinterpret_cast<Handle*>(handle);
-    if (!h || async_busy(h)) return -1;
-    return sim3_ransac(h, n_problems, inout, out);
+    Handle* h = idle_handle(handle);
+    return h ? sim3_ransac(h, n_problems, inout, out) : -1;
 }
 int vba_triangulate(void* handle, int32_t n_pairs, vba_triangulate_problem* const* in, vba_triangulate_result* const* out) {
-    Handle* h = reinterpret_cast<Handle*>(handle);
-    if (!h || async_busy(h)) return -1;
-    return triangulate(h, n_pairs, in, out);
+    Handle* h = idle_handle(handle);
+    return h ? triangulate(h, n_pairs, in, out) : -1;
 }
 int vba_two_view_init(void* handle, int32_t n_problems, vba_two_view_problem* const* in, vba_two_view_result* const* out) {
-    Handle* h = reinterpret_cast<Handle*>(handle);
-    if (!h || async_busy(h)) return -1;
-    return two_view_init(h, n_problems, in, out);
+    Handle* h = idle_handle(handle);
+    return h ? two_view_init(h, n_problems, in, out) : -1;
 }
 int vba_search_triangulation(void* handle, int32_t n_pairs, vba_search_tri_problem* const* in, vba_search_tri_result* const* out) {
-    Handle* h = reinterpret_cast<Handle*>(handle);
-    if (!h || async_busy(h)) return -1;
-    return search_triangulation(h, n_pairs, in, out);
+    Handle* h = idle_handle(handle);
+    return h ? search_triangulation(h, n_pairs, in, out) : -1;
 }
 int vba_fuse(void* handle, int32_t n_problems, vba_fuse_problem* const* in, vba_fuse_result* const* out) {
-    Handle* h = reinterpret_cast<Handle*>(handle);
-    if (!h || async_busy(h)) return -1;
-    return fuse(h, n_problems, in, out);
+    Handle* h = idle_handle(handle);
+    return h ? fuse(h, n_problems, in, out) : -1;
 }
 int vba_posegraph_optimize(void* handle, int32_t n_graphs, vba_posegraph_problem* const* inout, vba_posegraph_result* const* out) {
-    Handle* h = reinterpret_cast<Handle*>(handle);
-    if (!h || async_busy(h)) return -1;
-    return posegraph_run(h, n_graphs, inout, out, nullptr);
+    Handle* h = idle_handle(handle);
+    return h ? posegraph_run(h, n_graphs, inout, out, nullptr) : -1;
 }
 
 #ifdef VBA_TEST_HOOKS
 // test hook (not part of include/vislam_ba.h): H (dense, [7 n_free]^2 row-major), b and the x of the first trial of the first
 // iteration of one graph, as k_posegraph_opt formed them; the graph's arrays are left untouched
 int vba_debug_posegraph_system(void* handle, vba_posegraph_problem* graph, double* H, double* b, double* x) {
-    Handle* h = reinterpret_cast<Handle*>(handle);
-    if (!h || async_busy(h)) return -1;
+    Handle* h = idle_handle(handle);
+    if (!h) return -1;
     if (!graph || !H || !b || !x) return fail(h, "vba_debug_posegraph_system: bad arguments");
     PgDebug dbg{H, b, x};
     vba_posegraph_result r;
@@ -225,8 +223,8 @@ int vba_debug_posegraph_system(void* handle, vba_posegraph_problem* graph, doubl
 #endif
 
 int vba_set_profile(void* handle, int32_t enable) {
-    Handle* h = reinterpret_cast<Handle*>(handle);
-    if (!h || async_busy(h)) return -1;
+    Handle* h = idle_handle(handle);
+    if (!h) return -1;
     h->profile = enable != 0;
     return 0;
 }

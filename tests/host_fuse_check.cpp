@@ -1,10 +1,8 @@
 // Sanitizer harness of the host half of vba_fuse (mc_slam_amd/csrc/vba_host_fuse.h, vba_host_arena.h): plain C++, built by
 // tests/test_host_fuse.py with g++ -fsanitize=address,undefined.
 //   host_fuse_check <file>...     one line per file: "ok key value ..." or "error <message>"
-// check, describe and pack run as the driver runs them -- above 256 problems on several threads, as small_pack_threads does -- into
-// malloc'ed blocks of exactly upload_bytes(); unpack reads a block of exactly back_bytes() and writes result arrays of exactly the
-// caller's sizes, so any overrun is an ASan report.  Every array of the callers is a heap block of its exact size, too.
-// Checksums: sum of (2 i + 1) * word i over the 64-bit words of a region's payload (padded with zeros to whole words), mod 2^64.
+// FuseCall runs as the library's driver runs it (run_call, tests/host_check.h); every array of the callers is a heap block of its
+// exact size, so any overrun is an ASan report.  bind_<field>: where the kernel's argument points, as an offset into the arena.
 // Files (little-endian, written by the test): i32 n, then per problem i32 hd[13] = n_keys len_keys n_pt len_pt n_levels lv grid_cols
 // grid_rows len_cell len_feat th_low check_reproj nulls, f64 c[29] (Rcw tcw Ow K bounds grid_inv_w grid_inv_h log_scale_factor th
 // cos_view chi2_reproj), u8 desc[len_keys][32], f64 uv[len_keys][2], u8 oct[len_keys], f64 scale[lv] inv_level_sigma2[lv],
@@ -14,27 +12,9 @@
 // the result
 #include "../mc_slam_amd/csrc/vba_host_fuse.h"
 
-#include <cstdio>
-#include <cstdlib>
-#include <thread>
-#include <vector>
+#include "host_check.h"
 
 using namespace vba_host;
-
-struct Heap {   // exact-size heap blocks, freed at the end of a file
-    std::vector<void*> all;
-    template <class T> T* get(size_t n) { void* p = malloc(n * sizeof(T) + (n == 0)); all.push_back(p); return static_cast<T*>(p); }
-    template <class T> T* read(FILE* f, size_t n, bool& ok) { T* p = get<T>(n); ok = ok && (n == 0 || fread(p, sizeof(T), n, f) == n); return p; }
-    ~Heap() { for (void* p : all) free(p); }
-};
-
-static unsigned long long checksum(const void* p, size_t bytes) {
-    std::vector<unsigned long long> w((bytes + 7) / 8, 0);
-    if (bytes) std::memcpy(w.data(), p, bytes);
-    unsigned long long s = 0;
-    for (size_t i = 0; i < w.size(); i++) s += (2 * i + 1) * w[i];
-    return s;
-}
 
 static void fuse_file(FILE* f) {
     Heap H;
@@ -82,46 +62,36 @@ static void fuse_file(FILE* f) {
         rr[k] = (nl & 16) ? nullptr : &R[k];
     }
     if (!ok) { printf("error load\n"); return; }
-    FuseTotals T;
-    std::string err;
-    if (check_fuse(n, pp.data(), rr.data(), T, err)) { printf("error %s\n", err.c_str()); return; }
-    const FuseArena A(n, T);
-    void* hin = H.get<char>(A.L.upload_bytes());
-    FuDesc* desc = at<FuDesc>(hin, A.desc);
-    const size_t n_tiles = describe_fuse(n, pp.data(), desc, at<FuTile>(hin, A.tile));
-    auto pack = [&](int k) {
-        pack_fuse(pp[k], desc[k], at<FuKey>(hin, A.key), at<FuPoint>(hin, A.pt), at<int32_t>(hin, A.cell), at<int32_t>(hin, A.feat), at<double>(hin, A.lev));
-    };
-    if (n >= 256) {   // the threaded path: problem k goes to thread k mod 4
-        std::vector<std::thread> th;
-        for (int t = 0; t < 4; t++) th.emplace_back([&, t] { for (int k = t; k < n; k += 4) pack(k); });
-        for (auto& t : th) t.join();
-    } else
-        for (int k = 0; k < n; k++) pack(k);
-    printf("ok keys %zu pts %zu cells %zu feat_tot %zu lev_tot %zu tiles %zu n_tiles %zu upload %zu back %zu total %zu desc %zu tile %zu key %zu pt %zu cell %zu feat %zu lev %zu "
-           "best_idx %zu best_dist %zu level %zu uv %zu state %zu",
-           T.keys, T.pts, T.cells, T.feat, T.lev, T.tiles, n_tiles, A.L.upload_bytes(), A.L.back_bytes(), A.L.total_bytes(), A.desc, A.tile, A.key, A.pt, A.cell,
-           A.feat, A.lev, A.best_idx, A.best_dist, A.level, A.uv, A.state);
-    printf(" sum_desc %llu sum_tile %llu sum_key %llu sum_pt %llu sum_cell %llu sum_feat %llu sum_lev %llu", checksum(desc, sizeof(FuDesc) * n),
-           checksum(at<char>(hin, A.tile), sizeof(FuTile) * T.tiles), checksum(at<char>(hin, A.key), sizeof(FuKey) * T.keys),
-           checksum(at<char>(hin, A.pt), sizeof(FuPoint) * T.pts), checksum(at<char>(hin, A.cell), 4 * T.cells), checksum(at<char>(hin, A.feat), 4 * T.feat),
-           checksum(at<char>(hin, A.lev), 8 * T.lev));
-    // what came back: point i of the call has best_idx = i mod 7 - 1, best_dist = i mod 257, level = i mod 200 - 128, uv = (i / 4, -i / 8),
-    // state = i mod 9
-    void* hout = H.get<char>(A.L.back_bytes());
-    int32_t* bi = at<int32_t>(hout, A.L.in_back(A.best_idx));
-    uint16_t* bd = at<uint16_t>(hout, A.L.in_back(A.best_dist));
-    int8_t* lv = at<int8_t>(hout, A.L.in_back(A.level));
-    double* uv = at<double>(hout, A.L.in_back(A.uv));
-    unsigned char* st = at<unsigned char>(hout, A.L.in_back(A.state));
-    for (size_t i = 0; i < T.pts; i++) {
-        bi[i] = (int32_t)(i % 7) - 1; bd[i] = (uint16_t)(i % 257); lv[i] = (int8_t)((int)(i % 200) - 128); uv[2 * i] = (double)i / 4; uv[2 * i + 1] = -(double)i / 8;
-        st[i] = (unsigned char)(i % 9);
-    }
+    FuseCall C;
+    const bool ran = run_call(H, C, n, pp.data(), rr.data(), [&](const FuBatch& B, void* hin) {
+        printf("ok keys %zu pts %zu cells %zu feat_tot %zu lev_tot %zu tiles %zu n_tiles %zu upload %zu back %zu total %zu desc %zu tile %zu key %zu pt %zu cell %zu feat %zu lev %zu "
+               "best_idx %zu best_dist %zu level %zu uv %zu state %zu",
+               C.T.keys, C.T.pts, C.T.cells, C.T.feat, C.T.lev, C.T.tiles, C.grid(), C.A.L.upload_bytes(), C.A.L.back_bytes(), C.A.L.total_bytes(), C.A.desc, C.A.tile, C.A.key, C.A.pt, C.A.cell,
+               C.A.feat, C.A.lev, C.A.best_idx, C.A.best_dist, C.A.level, C.A.uv, C.A.state);
+        PRINT_BIND(B, hin, desc); PRINT_BIND(B, hin, tile); PRINT_BIND(B, hin, key); PRINT_BIND(B, hin, pt); PRINT_BIND(B, hin, cell_begin);
+        PRINT_BIND(B, hin, cell_feat); PRINT_BIND(B, hin, lev); PRINT_BIND(B, hin, best_idx); PRINT_BIND(B, hin, best_dist); PRINT_BIND(B, hin, level);
+        PRINT_BIND(B, hin, uv); PRINT_BIND(B, hin, state);
+        printf(" sum_desc %llu sum_tile %llu sum_key %llu sum_pt %llu sum_cell %llu sum_feat %llu sum_lev %llu", checksum(at<char>(hin, C.A.desc), sizeof(FuDesc) * n),
+               checksum(at<char>(hin, C.A.tile), sizeof(FuTile) * C.T.tiles), checksum(at<char>(hin, C.A.key), sizeof(FuKey) * C.T.keys),
+               checksum(at<char>(hin, C.A.pt), sizeof(FuPoint) * C.T.pts), checksum(at<char>(hin, C.A.cell), 4 * C.T.cells), checksum(at<char>(hin, C.A.feat), 4 * C.T.feat),
+               checksum(at<char>(hin, C.A.lev), 8 * C.T.lev));
+    }, [&](void* hout) {
+        // what came back: point i of the call has best_idx = i mod 7 - 1, best_dist = i mod 257, level = i mod 200 - 128, uv = (i / 4, -i / 8),
+        // state = i mod 9
+        int32_t* bi = at<int32_t>(hout, C.A.L.in_back(C.A.best_idx));
+        uint16_t* bd = at<uint16_t>(hout, C.A.L.in_back(C.A.best_dist));
+        int8_t* lv = at<int8_t>(hout, C.A.L.in_back(C.A.level));
+        double* uv = at<double>(hout, C.A.L.in_back(C.A.uv));
+        unsigned char* st = at<unsigned char>(hout, C.A.L.in_back(C.A.state));
+        for (size_t i = 0; i < C.T.pts; i++) {
+            bi[i] = (int32_t)(i % 7) - 1; bd[i] = (uint16_t)(i % 257); lv[i] = (int8_t)((int)(i % 200) - 128); uv[2 * i] = (double)i / 4; uv[2 * i + 1] = -(double)i / 8;
+            st[i] = (unsigned char)(i % 9);
+        }
+    });
+    if (!ran) return;
     long long s_found = 0, s_status = 0, s_bi = 0, s_bd = 0, s_lv = 0, s_st = 0;
     double s_uv = 0;
     for (int k = 0; k < n; k++) {
-        unpack_fuse(rr[k], desc[k], bi, bd, lv, uv, st);
         s_found += R[k].n_found * (long long)(k + 1);
         s_status += R[k].status;
         for (size_t i = 0; i < len_pt[k] && (size_t)P[k].n_pt == len_pt[k]; i++) {
@@ -133,12 +103,4 @@ static void fuse_file(FILE* f) {
            (long long)(s_uv * 8));
 }
 
-int main(int argc, char** argv) {
-    for (int a = 1; a < argc; a++) {
-        FILE* f = fopen(argv[a], "rb");
-        if (!f) { printf("error load\n"); continue; }
-        fuse_file(f);
-        fclose(f);
-    }
-    return 0;
-}
+int main(int argc, char** argv) { return for_each_file(argc, argv, 1, fuse_file); }

@@ -8,8 +8,8 @@
 // mutate: 0 nothing, 1 n_vertices = -1, 2 n_edges = -1, 3 n_pt = -1, 4 S = NULL, 5 edge_S = NULL, 6 pt = NULL, 7 fixed = NULL.
 #include "../mc_slam_amd/csrc/vba_host_posegraph.h"
 
-#include <cstdio>
-#include <cstring>
+#include "host_check.h"
+
 #include <set>
 
 template <class T>
@@ -113,8 +113,8 @@ struct Graph {
     }
 };
 
-// --call <file>...: the files as the graphs of ONE call -- its sizes and the offset of every region of the arena, in arena order;
-// the staging block is a heap block of exactly upload_bytes(), so a packing overrun is an ASan report
+// --call <file>...: the files as the graphs of ONE call, PoseGraphCall run as the library's driver runs it (run_call,
+// tests/host_check.h) -- its sizes, the offset of every region of the arena in arena order, and where the kernel's argument points
 static void one_call(int n, char** files) {
     std::vector<Graph> G(n);
     std::vector<vba_posegraph_problem*> pp(n);
@@ -124,24 +124,50 @@ static void one_call(int n, char** files) {
         if (!G[g].load(files[g])) { printf("error load\n"); return; }
         pp[g] = &G[g].P; rr[g] = &R[g];
     }
+    Heap H;
     vba_host::PoseGraphCall C;
-    std::string err;
-    if (vba_host::describe_posegraph(n, pp.data(), rr.data(), false, C, err)) { printf("error %s\n", err.c_str()); return; }
-    std::vector<char> heap_in(C.L.upload_bytes());   // exactly the upload section
-    for (int g = 0; g < n; g++) vba_host::pack_posegraph(C, g, pp[g], heap_in.data());
-    size_t nv = 0, ne = 0, nf = 0, nenv = 0, ninc = 0, npair = 0, npe = 0;
+    size_t nv = 0;
+    const bool ran = run_call(H, C, n, pp.data(), rr.data(), [&](const PgBatch& B, void* hin) {
+        size_t ne = 0, nf = 0, nenv = 0, ninc = 0, npair = 0, npe = 0;
+        for (int g = 0; g < n; g++) {
+            const vba_host::PoseGraphLayout& L = C.lay[g];
+            nv += G[g].P.n_vertices; ne += G[g].P.n_edges; nf += L.n_free; nenv += L.env_blocks; ninc += L.inc.size(); npair += L.pair_lo.size(); npe += L.pair_edge.size();
+        }
+        printf("call nv %zu ne %zu nf %zu nenv %zu ninc %zu npair %zu npe %zu npt %zu upload %zu back %zu total %zu offsets", nv, ne, nf, nenv, ninc, npair, npe, C.npt,
+               C.L.upload_bytes(), C.L.back_bytes(), C.L.total_bytes());
+        for (size_t o : {C.o_desc, C.o_Sin, C.o_meas, C.o_ei, C.o_ej, C.o_free, C.o_vert, C.o_first, C.o_last, C.o_roff, C.o_incb, C.o_inc, C.o_plo, C.o_phi, C.o_pb,
+                         C.o_pe, C.o_pt, C.o_ref, C.o_out, C.o_S, C.o_pto, C.o_Sbk, C.o_err, C.o_J, C.o_H, C.o_F, C.o_Ld, C.o_b, C.o_w, C.o_y, C.o_x})
+            printf(" %zu", o);
+        // the last point reference of the last graph, as packed: an index into the concatenated vertices
+        printf(" last_ref %d", C.npt ? vba_host::at<int>(hin, C.o_ref)[C.npt - 1] : -1);
+        // where every pointer of the kernel's argument points, in arena order
+        printf(" bind");
+        for (const void* p : {(const void*)B.desc, (const void*)B.Sin, (const void*)B.meas, (const void*)B.ei, (const void*)B.ej, (const void*)B.free_of,
+                              (const void*)B.vert_of, (const void*)B.first, (const void*)B.last_row, (const void*)B.row_off, (const void*)B.inc_begin,
+                              (const void*)B.inc, (const void*)B.pair_lo, (const void*)B.pair_hi, (const void*)B.pair_begin, (const void*)B.pair_edge,
+                              (const void*)B.pt_in, (const void*)B.pt_ref, (const void*)B.out, (const void*)B.S, (const void*)B.pt_out, (const void*)B.Sbk,
+                              (const void*)B.err, (const void*)B.J, (const void*)B.H, (const void*)B.F, (const void*)B.Ld, (const void*)B.b, (const void*)B.w,
+                              (const void*)B.y, (const void*)B.x})
+            printf(" %zu", (size_t)((const char*)p - (const char*)hin));
+        printf(" n_pt_total %lld", B.n_pt_total);
+    }, [&](void* hout) {
+        // what came back: graph g stopped after g iterations, double j of the estimates is j, double j of the points is -j
+        PgOut* res = vba_host::at<PgOut>(hout, C.L.in_back(C.o_out));
+        double* S = vba_host::at<double>(hout, C.L.in_back(C.o_S));
+        double* pt = vba_host::at<double>(hout, C.L.in_back(C.o_pto));
+        for (int g = 0; g < n; g++) { std::memset(&res[g], 0, sizeof res[g]); res[g].its_done = g; }
+        for (size_t j = 0; j < 8 * nv; j++) S[j] = (double)j;
+        for (size_t j = 0; j < 3 * C.npt; j++) pt[j] = -(double)j;
+    });
+    if (!ran) return;
+    double s_S = 0, s_pt = 0;
+    long long s_its = 0;
     for (int g = 0; g < n; g++) {
-        const vba_host::PoseGraphLayout& L = C.lay[g];
-        nv += G[g].P.n_vertices; ne += G[g].P.n_edges; nf += L.n_free; nenv += L.env_blocks; ninc += L.inc.size(); npair += L.pair_lo.size(); npe += L.pair_edge.size();
+        s_its += R[g].its_done;
+        for (double v : G[g].S) s_S += v;
+        for (double v : G[g].pt) s_pt += v;
     }
-    printf("call nv %zu ne %zu nf %zu nenv %zu ninc %zu npair %zu npe %zu npt %zu upload %zu back %zu total %zu offsets", nv, ne, nf, nenv, ninc, npair, npe, C.npt,
-           C.L.upload_bytes(), C.L.back_bytes(), C.L.total_bytes());
-    for (size_t o : {C.o_desc, C.o_Sin, C.o_meas, C.o_ei, C.o_ej, C.o_free, C.o_vert, C.o_first, C.o_last, C.o_roff, C.o_incb, C.o_inc, C.o_plo, C.o_phi, C.o_pb,
-                     C.o_pe, C.o_pt, C.o_ref, C.o_out, C.o_S, C.o_pto, C.o_Sbk, C.o_err, C.o_J, C.o_H, C.o_F, C.o_Ld, C.o_b, C.o_w, C.o_y, C.o_x})
-        printf(" %zu", o);
-    // the last point reference of the last graph, as packed: an index into the concatenated vertices
-    if (C.npt) printf(" last_ref %d", vba_host::at<int>(heap_in.data(), C.o_ref)[C.npt - 1]);
-    printf("\n");
+    printf(" got_its %lld got_S %.0f got_pt %.0f\n", s_its, s_S, s_pt);
 }
 
 // --expand <file>: envelope block q holds 100 q + 7 a + k + 1 at (a, k) below the diagonal; the dense expansion, row by row

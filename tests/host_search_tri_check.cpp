@@ -1,12 +1,9 @@
 // Sanitizer harness of the host half of vba_search_triangulation (mc_slam_amd/csrc/vba_host_search_tri.h, vba_host_arena.h): plain
 // C++, built by tests/test_host_search_tri.py with g++ -fsanitize=address,undefined.
 //   host_search_tri_check <file>...     one line per file: "ok key value ..." or "error <message>"
-// check, describe and pack (with the node join) run as the driver runs them -- above 256 pairs on several threads, as
-// small_pack_threads does -- into malloc'ed blocks of exactly upload_bytes(); unpack reads a block of exactly back_bytes() and writes
-// result arrays of exactly the caller's sizes, so any overrun is an ASan report.  Every array of the callers is a heap block of its
-// exact size, too.
-// Checksums: sum of (2 i + 1) * word i over the 64-bit words of a region's payload (padded with zeros to whole words), mod 2^64;
-// sum_query runs over the used query slots of all pairs, one after the other.
+// SearchTriCall (with the node join) runs as the library's driver runs it (run_call, tests/host_check.h); every array of the
+// callers is a heap block of its exact size, so any overrun is an ASan report.  bind_<field>: where the kernel's argument points, as
+// an offset into the arena.  sum_query runs over the used query slots of all pairs, one after the other.
 // Files (little-endian, written by the test): i32 n, then per pair i32 hd[15] = n_keys1 len1 n_keys2 len2 n_nodes1 nn1 nf1 n_nodes2
 // nn2 nf2 n_levels2 lv th_low check_orientation nulls, f64 c[13] (F12 epipole chi2_epi epipole_r2), then per side u8 desc[len][32]
 // has_mp[len], f64 uv[len][2], f32 angle[len], u32 node_id[nn], i32 node_begin[nn + 1] node_feat[nf], after side 2
@@ -15,28 +12,9 @@
 // 2048 oct2
 #include "../mc_slam_amd/csrc/vba_host_search_tri.h"
 
-#include <cstdio>
-#include <cstdlib>
-#include <thread>
-#include <vector>
+#include "host_check.h"
 
 using namespace vba_host;
-
-struct Heap {   // exact-size heap blocks, freed at the end of a file
-    std::vector<void*> all;
-    template <class T> T* get(size_t n) { void* p = malloc(n * sizeof(T) + (n == 0)); all.push_back(p); return static_cast<T*>(p); }
-    template <class T> T* read(FILE* f, size_t n, bool& ok) { T* p = get<T>(n); ok = ok && (n == 0 || fread(p, sizeof(T), n, f) == n); return p; }
-    ~Heap() { for (void* p : all) free(p); }
-};
-
-static unsigned long long checksum(const void* p, size_t bytes, unsigned long long* pos = nullptr) {
-    std::vector<unsigned long long> w((bytes + 7) / 8, 0);
-    if (bytes) std::memcpy(w.data(), p, bytes);
-    unsigned long long s = 0, i0 = pos ? *pos : 0;
-    for (size_t i = 0; i < w.size(); i++) s += (2 * (i0 + i) + 1) * w[i];
-    if (pos) *pos += w.size();
-    return s;
-}
 
 static void st_file(FILE* f) {
     Heap H;
@@ -82,49 +60,43 @@ static void st_file(FILE* f) {
         rr[k] = (nl & 16) ? nullptr : &R[k];
     }
     if (!ok) { printf("error load\n"); return; }
-    SearchTriTotals T;
-    std::string err;
-    if (check_search_tri(n, pp.data(), rr.data(), T, err)) { printf("error %s\n", err.c_str()); return; }
-    const SearchTriArena A(n, T);
-    void* hin = H.get<char>(A.L.upload_bytes());
-    StDesc* desc = at<StDesc>(hin, A.desc);
-    describe_search_tri(n, pp.data(), desc);
-    auto pack = [&](int k) {
-        pack_search_tri(pp[k], desc[k], at<StKey>(hin, A.key1), at<StKey>(hin, A.key2), at<StQuery>(hin, A.query), at<int32_t>(hin, A.feat), at<double>(hin, A.lev));
-    };
-    if (n >= 256) {   // the threaded path: pair k goes to thread k mod 4
-        std::vector<std::thread> th;
-        for (int t = 0; t < 4; t++) th.emplace_back([&, t] { for (int k = t; k < n; k += 4) pack(k); });
-        for (auto& t : th) t.join();
-    } else
-        for (int k = 0; k < n; k++) pack(k);
-    printf("ok k1 %zu k2 %zu feat_tot %zu lev_tot %zu upload %zu back %zu total %zu desc %zu key1 %zu key2 %zu query %zu feat %zu lev %zu out %zu match12 %zu best_dist %zu state %zu",
-           T.k1, T.k2, T.feat, T.lev, A.L.upload_bytes(), A.L.back_bytes(), A.L.total_bytes(), A.desc, A.key1, A.key2, A.query, A.feat, A.lev, A.out, A.match12,
-           A.best_dist, A.state);
-    unsigned long long sq = 0, pos = 0;
-    long long nq = 0;
-    for (int k = 0; k < n; k++) {
-        sq += checksum(at<StQuery>(hin, A.query) + desc[k].key1_0, sizeof(StQuery) * (size_t)desc[k].n_q, &pos);
-        nq += desc[k].n_q;
-    }
-    printf(" n_q %lld sum_query %llu sum_desc %llu sum_key1 %llu sum_key2 %llu sum_feat %llu sum_lev %llu", nq, sq, checksum(desc, sizeof(StDesc) * n),
-           checksum(at<char>(hin, A.key1), sizeof(StKey) * T.k1), checksum(at<char>(hin, A.key2), sizeof(StKey) * T.k2), checksum(at<char>(hin, A.feat), 4 * T.feat),
-           checksum(at<char>(hin, A.lev), 8 * T.lev));
-    // what came back: keypoint i of the call has match12 = i mod 5 - 1 (-1 for every fifth), best_dist = i mod 251, state = i mod 5; pair k
-    // reports hist[b] = k + b, ind = (k, -1, k + 1), n_before_filter = 2 k, and n_matches = the entries >= 0 of its match12
-    void* hout = H.get<char>(A.L.back_bytes());
-    StOut* res = at<StOut>(hout, A.L.in_back(A.out));
-    int32_t* m12 = at<int32_t>(hout, A.L.in_back(A.match12));
-    unsigned char* bd = at<unsigned char>(hout, A.L.in_back(A.best_dist));
-    unsigned char* st = at<unsigned char>(hout, A.L.in_back(A.state));
-    for (size_t i = 0; i < T.k1; i++) { m12[i] = (int32_t)(i % 5) - 1; bd[i] = (unsigned char)(i % 251); st[i] = (unsigned char)(i % 5); }
+    SearchTriCall C;
+    const bool ran = run_call(H, C, n, pp.data(), rr.data(), [&](const StBatch& B, void* hin) {
+        const StDesc* desc = at<StDesc>(hin, C.A.desc);
+        printf("ok k1 %zu k2 %zu feat_tot %zu lev_tot %zu upload %zu back %zu total %zu desc %zu key1 %zu key2 %zu query %zu feat %zu lev %zu out %zu match12 %zu best_dist %zu state %zu",
+               C.T.k1, C.T.k2, C.T.feat, C.T.lev, C.A.L.upload_bytes(), C.A.L.back_bytes(), C.A.L.total_bytes(), C.A.desc, C.A.key1, C.A.key2, C.A.query, C.A.feat, C.A.lev, C.A.out, C.A.match12,
+               C.A.best_dist, C.A.state);
+        PRINT_BIND(B, hin, desc); PRINT_BIND(B, hin, key1); PRINT_BIND(B, hin, key2); PRINT_BIND(B, hin, query); PRINT_BIND(B, hin, feat); PRINT_BIND(B, hin, lev);
+        PRINT_BIND(B, hin, out); PRINT_BIND(B, hin, match12); PRINT_BIND(B, hin, best_dist); PRINT_BIND(B, hin, state);
+        unsigned long long sq = 0, pos = 0;
+        long long nq = 0;
+        for (int k = 0; k < n; k++) {
+            sq += checksum(at<StQuery>(hin, C.A.query) + desc[k].key1_0, sizeof(StQuery) * (size_t)desc[k].n_q, &pos);
+            nq += desc[k].n_q;
+        }
+        printf(" n_q %lld sum_query %llu sum_desc %llu sum_key1 %llu sum_key2 %llu sum_feat %llu sum_lev %llu", nq, sq, checksum(desc, sizeof(StDesc) * n),
+               checksum(at<char>(hin, C.A.key1), sizeof(StKey) * C.T.k1), checksum(at<char>(hin, C.A.key2), sizeof(StKey) * C.T.k2), checksum(at<char>(hin, C.A.feat), 4 * C.T.feat),
+               checksum(at<char>(hin, C.A.lev), 8 * C.T.lev));
+    }, [&](void* hout) {
+        // what came back: keypoint i of the call has match12 = i mod 5 - 1 (-1 for every fifth), best_dist = i mod 251, state = i mod 5; pair k
+        // reports hist[b] = k + b, ind = (k, -1, k + 1), n_before_filter = 2 k, and n_matches = the entries >= 0 of its match12
+        StOut* res = at<StOut>(hout, C.A.L.in_back(C.A.out));
+        int32_t* m12 = at<int32_t>(hout, C.A.L.in_back(C.A.match12));
+        unsigned char* bd = at<unsigned char>(hout, C.A.L.in_back(C.A.best_dist));
+        unsigned char* st = at<unsigned char>(hout, C.A.L.in_back(C.A.state));
+        for (size_t i = 0; i < C.T.k1; i++) { m12[i] = (int32_t)(i % 5) - 1; bd[i] = (unsigned char)(i % 251); st[i] = (unsigned char)(i % 5); }
+        size_t key1_0 = 0;
+        for (int k = 0; k < n; k++) {
+            res[k].status = 0; res[k].n_before_filter = 2 * k; res[k].n_matches = 0;
+            for (int i = 0; i < P[k].n_keys1; i++) res[k].n_matches += m12[key1_0 + i] >= 0;
+            for (int b = 0; b < VBA_ST_HISTO; b++) res[k].hist[b] = k + b;
+            res[k].ind[0] = k; res[k].ind[1] = -1; res[k].ind[2] = k + 1;
+            key1_0 += (size_t)P[k].n_keys1;
+        }
+    });
+    if (!ran) return;
     long long s_n = 0, s_status = 0, s_m12 = 0, s_bd = 0, s_st = 0, s_pairs = 0, s_hist = 0, s_ind = 0;
     for (int k = 0; k < n; k++) {
-        res[k].status = 0; res[k].n_before_filter = 2 * k; res[k].n_matches = 0;
-        for (int i = 0; i < desc[k].n_keys1; i++) res[k].n_matches += m12[desc[k].key1_0 + i] >= 0;
-        for (int b = 0; b < VBA_ST_HISTO; b++) res[k].hist[b] = k + b;
-        res[k].ind[0] = k; res[k].ind[1] = -1; res[k].ind[2] = k + 1;
-        unpack_search_tri(rr[k], desc[k], res[k], m12, bd, st);
         s_n += R[k].n_matches * (long long)(k + 1) + R[k].n_before_filter;
         s_status += R[k].status;
         for (int b = 0; b < VBA_ST_HISTO; b++) s_hist += R[k].hist[b];
@@ -136,12 +108,4 @@ static void st_file(FILE* f) {
            s_pairs, s_hist, s_ind);
 }
 
-int main(int argc, char** argv) {
-    for (int a = 1; a < argc; a++) {
-        FILE* f = fopen(argv[a], "rb");
-        if (!f) { printf("error load\n"); continue; }
-        st_file(f);
-        fclose(f);
-    }
-    return 0;
-}
+int main(int argc, char** argv) { return for_each_file(argc, argv, 1, st_file); }

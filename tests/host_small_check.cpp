@@ -3,10 +3,9 @@
 //   host_small_check sim3 <file>...     one line per file: "ok key value ..." or "error <message>"
 //   host_small_check pose <file>...     the same
 //   host_small_check inverse <file>...  "ok <n*n values>" or "singular"
-// check, describe and pack run as the drivers run them, into malloc'ed blocks of exactly upload_bytes(); unpack reads a block of
-// exactly the downloaded bytes and writes result arrays of exactly the caller's sizes, so any overrun is an ASan report.
-// Every array of the callers is a heap block of its exact size, too.  Checksums: sum of (2 i + 1) * word i over the 64-bit words of
-// a region's payload, mod 2^64.
+// Sim3Call and PoseCall run as the library's driver runs them (run_call, tests/host_check.h); every array of the callers is a heap
+// block of its exact size, so any overrun is an ASan report.  bind_<field>: where the kernel's argument points, as an offset into
+// the arena.
 // Files (little-endian, written by the test):
 //   sim3: i32 n, then per problem i32 n_pairs len fix_scale its1 its2_bad its2_clean min_inliers nulls want_chi2, f64 S12[8] K1[4]
 //         K2[4] th2 huber, f64 p1c[len][3] p2c[len][3] uv1[len][2] uv2[len][2] w1[len] w2[len].  n_pairs is the field, len the arrays;
@@ -19,25 +18,9 @@
 #include "../mc_slam_amd/csrc/vba_host_pose.h"
 #include "../mc_slam_amd/csrc/vba_host_sim3.h"
 
-#include <cstdio>
-#include <cstdlib>
-#include <memory>
-#include <vector>
+#include "host_check.h"
 
 using namespace vba_host;
-
-struct Heap {   // exact-size heap blocks, freed at the end of a file
-    std::vector<void*> all;
-    template <class T> T* get(size_t n) { void* p = malloc(n * sizeof(T) + (n == 0)); all.push_back(p); return static_cast<T*>(p); }
-    template <class T> T* read(FILE* f, size_t n, bool& ok) { T* p = get<T>(n); ok = ok && (n == 0 || fread(p, sizeof(T), n, f) == n); return p; }
-    ~Heap() { for (void* p : all) free(p); }
-};
-
-static unsigned long long checksum(const void* p, size_t bytes) {
-    unsigned long long s = 0, w;
-    for (size_t i = 0; i < bytes / 8; i++) { std::memcpy(&w, static_cast<const char*>(p) + 8 * i, 8); s += (2 * i + 1) * w; }
-    return s;
-}
 
 static void sim3_file(FILE* f) {
     Heap H;
@@ -70,31 +53,27 @@ static void sim3_file(FILE* f) {
         rr[k] = &R[k];
     }
     if (!ok) { printf("error load\n"); return; }
-    size_t n_tot = 0;
-    bool want_chi2 = false;
-    std::string err;
-    if (check_sim3(n, pp.data(), rr.data(), n_tot, want_chi2, err)) { printf("error %s\n", err.c_str()); return; }
-    const Sim3Arena A(n, n_tot);
-    void* hin = H.get<char>(A.L.upload_bytes());
-    Sim3Desc* desc = at<Sim3Desc>(hin, A.desc);
-    describe_sim3(n, pp.data(), desc);
-    for (int k = 0; k < n; k++) pack_sim3(pp[k], desc[k], at<double>(hin, A.p), at<double>(hin, A.uv), at<double>(hin, A.w));
-    printf("ok n_tot %zu want_chi2 %d upload %zu back %zu total %zu download %zu desc %zu p %zu uv %zu w %zu out %zu flag %zu c %zu", n_tot, (int)want_chi2,
-           A.L.upload_bytes(), A.L.back_bytes(), A.L.total_bytes(), A.download_bytes(want_chi2), A.desc, A.p, A.uv, A.w, A.out, A.flag, A.c);
-    printf(" sum_desc %llu sum_p %llu sum_uv %llu sum_w %llu", checksum(desc, sizeof(Sim3Desc) * n), checksum(at<char>(hin, A.p), 48 * n_tot),
-           checksum(at<char>(hin, A.uv), 32 * n_tot), checksum(at<char>(hin, A.w), 16 * n_tot));
-    // what came back: out record k says k, pair i is flagged when i is odd, its chi2 are 2 i and 2 i + 1
-    void* hout = H.get<char>(A.download_bytes(want_chi2));
-    Sim3Out* res = at<Sim3Out>(hout, A.L.in_back(A.out));
-    unsigned char* flag = at<unsigned char>(hout, A.L.in_back(A.flag));
-    double* cc = at<double>(hout, A.L.in_back(A.c));
-    for (int k = 0; k < n; k++) { std::memset(&res[k], 0, sizeof res[k]); res[k].n_inliers = k; for (int q = 0; q < 8; q++) res[k].S[q] = k + q; }
-    for (size_t i = 0; i < n_tot; i++) flag[i] = i & 1;
-    for (size_t i = 0; i < 2 * n_tot && want_chi2; i++) cc[i] = (double)i;
+    Sim3Call C;
+    const bool ran = run_call(H, C, n, pp.data(), rr.data(), [&](const Sim3Batch& B, void* hin) {
+        printf("ok n_tot %zu want_chi2 %d upload %zu back %zu total %zu download %zu desc %zu p %zu uv %zu w %zu out %zu flag %zu c %zu", C.n_tot, (int)C.want_chi2,
+               C.A.L.upload_bytes(), C.A.L.back_bytes(), C.A.L.total_bytes(), C.download_bytes(), C.A.desc, C.A.p, C.A.uv, C.A.w, C.A.out, C.A.flag, C.A.c);
+        PRINT_BIND(B, hin, desc); PRINT_BIND(B, hin, out); PRINT_BIND(B, hin, p); PRINT_BIND(B, hin, uv); PRINT_BIND(B, hin, w); PRINT_BIND(B, hin, c);
+        PRINT_BIND(B, hin, flag);
+        printf(" sum_desc %llu sum_p %llu sum_uv %llu sum_w %llu", checksum(at<char>(hin, C.A.desc), sizeof(Sim3Desc) * n), checksum(at<char>(hin, C.A.p), 48 * C.n_tot),
+               checksum(at<char>(hin, C.A.uv), 32 * C.n_tot), checksum(at<char>(hin, C.A.w), 16 * C.n_tot));
+    }, [&](void* hout) {
+        // what came back: out record k says k, pair i is flagged when i is odd, its chi2 are 2 i and 2 i + 1
+        Sim3Out* res = at<Sim3Out>(hout, C.A.L.in_back(C.A.out));
+        unsigned char* flag = at<unsigned char>(hout, C.A.L.in_back(C.A.flag));
+        double* cc = at<double>(hout, C.A.L.in_back(C.A.c));
+        for (int k = 0; k < n; k++) { std::memset(&res[k], 0, sizeof res[k]); res[k].n_inliers = k; for (int q = 0; q < 8; q++) res[k].S[q] = k + q; }
+        for (size_t i = 0; i < C.n_tot; i++) flag[i] = i & 1;
+        for (size_t i = 0; i < 2 * C.n_tot && C.want_chi2; i++) cc[i] = (double)i;
+    });
+    if (!ran) return;
     unsigned long long s_in = 0, s_flag = 0;
     double s_12 = 0, s_21 = 0, s_S = 0;
     for (int k = 0; k < n; k++) {
-        unpack_sim3(pp[k], rr[k], desc[k], res[k], flag, cc);
         s_in += R[k].n_inliers; s_S += P[k].S12[7];
         for (int i = 0; i < P[k].n_pairs; i++) {
             s_flag += R[k].outlier[i];
@@ -136,54 +115,50 @@ static void pose_file(FILE* f) {
         rr[k] = &R[k];
     }
     if (!ok) { printf("error load\n"); return; }
-    size_t n_tot = 0;
-    if (const char* m = check_pose(n, pp.data(), rr.data(), n_tot)) { printf("error %s\n", m); return; }
-    const PoseArena A(n, n_tot);
-    void* hin = H.get<char>(A.L.upload_bytes());
-    FrameDesc* desc = at<FrameDesc>(hin, A.desc);
-    describe_pose(n, pp.data(), desc);
-    for (int k = 0; k < n; k++)
-        if (!pack_frame(pp[k], desc[k], at<double>(hin, A.pw), at<double>(hin, A.uv), at<double>(hin, A.w))) {
-            printf("error imu_cov_pvphi is singular or not finite\n");
-            return;
+    PoseCall C;
+    const bool ran = run_call(H, C, n, pp.data(), rr.data(), [&](const PoseBatch& B, void* hin) {
+        const FrameDesc* desc = at<FrameDesc>(hin, C.A.desc);
+        printf("ok n_tot %zu upload %zu back %zu total %zu desc %zu pw %zu uv %zu w %zu out %zu lvl %zu err %zu n_frames %d", C.n_tot, C.A.L.upload_bytes(), C.A.L.back_bytes(),
+               C.A.L.total_bytes(), C.A.desc, C.A.pw, C.A.uv, C.A.w, C.A.out, C.A.lvl, C.A.err, B.n_frames);
+        PRINT_BIND(B, hin, desc); PRINT_BIND(B, hin, out); PRINT_BIND(B, hin, pw); PRINT_BIND(B, hin, uv); PRINT_BIND(B, hin, w); PRINT_BIND(B, hin, err);
+        PRINT_BIND(B, hin, lvl);
+        printf(" sum_pw %llu sum_uv %llu sum_w %llu", checksum(at<char>(hin, C.A.pw), 24 * C.n_tot), checksum(at<char>(hin, C.A.uv), 16 * C.n_tot),
+               checksum(at<char>(hin, C.A.w), 8 * C.n_tot));
+        // the descriptors: the integers, and a checksum over the fields a frame's values are copied into
+        unsigned long long s_int = 0, s_val = 0;
+        double info_err = 0;
+        for (int k = 0; k < n; k++) {
+            const FrameDesc& d = desc[k];
+            const int iv[8] = {d.last_is_frame, d.compute_marg, d.n_obs, d.n_last, d.obs0, d.last0, d.pad0, d.pad1};
+            for (int q = 0; q < 8; q++) s_int += (unsigned long long)(8 * k + q + 1) * (unsigned)iv[q];
+            std::vector<double> v;
+            auto add = [&v](const double* p, size_t m) { v.insert(v.end(), p, p + m); };
+            add(d.nav, 22); add(d.nav_last, 22); add(d.prior_nav, 22); add(d.K, 4); add(d.tcb, 3); add(d.g, 3); add(d.meas, 61); add(d.prior_info, 225);
+            add(&d.inv_bg, 1); add(&d.inv_ba, 1); add(&d.hub_prior, 1); add(&d.hub_pvr, 1); add(&d.hub_bias, 1); add(&d.hub_mono, 1);
+            s_val += (unsigned long long)(k + 1) * checksum(v.data(), 8 * v.size());
+            for (int i = 0; i < 9 && d.last_is_frame != VBA_FRAME_VISION; i++)     // info_pvr * cov = I, to rounding
+                for (int j = 0; j < 9; j++) {
+                    double s = 0;
+                    for (int q = 0; q < 9; q++) s += d.info_pvr[9 * i + q] * P[k].imu_cov_pvphi[9 * q + j];
+                    info_err = std::max(info_err, std::fabs(s - (i == j)));
+                }
         }
-    printf("ok n_tot %zu upload %zu back %zu total %zu desc %zu pw %zu uv %zu w %zu out %zu lvl %zu err %zu", n_tot, A.L.upload_bytes(), A.L.back_bytes(),
-           A.L.total_bytes(), A.desc, A.pw, A.uv, A.w, A.out, A.lvl, A.err);
-    printf(" sum_pw %llu sum_uv %llu sum_w %llu", checksum(at<char>(hin, A.pw), 24 * n_tot), checksum(at<char>(hin, A.uv), 16 * n_tot),
-           checksum(at<char>(hin, A.w), 8 * n_tot));
-    // the descriptors: the integers, and a checksum over the fields a frame's values are copied into
-    unsigned long long s_int = 0, s_val = 0;
-    double info_err = 0;
-    for (int k = 0; k < n; k++) {
-        const FrameDesc& d = desc[k];
-        const int iv[8] = {d.last_is_frame, d.compute_marg, d.n_obs, d.n_last, d.obs0, d.last0, d.pad0, d.pad1};
-        for (int q = 0; q < 8; q++) s_int += (unsigned long long)(8 * k + q + 1) * (unsigned)iv[q];
-        std::vector<double> v;
-        auto add = [&v](const double* p, size_t m) { v.insert(v.end(), p, p + m); };
-        add(d.nav, 22); add(d.nav_last, 22); add(d.prior_nav, 22); add(d.K, 4); add(d.tcb, 3); add(d.g, 3); add(d.meas, 61); add(d.prior_info, 225);
-        add(&d.inv_bg, 1); add(&d.inv_ba, 1); add(&d.hub_prior, 1); add(&d.hub_pvr, 1); add(&d.hub_bias, 1); add(&d.hub_mono, 1);
-        s_val += (unsigned long long)(k + 1) * checksum(v.data(), 8 * v.size());
-        for (int i = 0; i < 9 && d.last_is_frame != VBA_FRAME_VISION; i++)     // info_pvr * cov = I, to rounding
-            for (int j = 0; j < 9; j++) {
-                double s = 0;
-                for (int q = 0; q < 9; q++) s += d.info_pvr[9 * i + q] * P[k].imu_cov_pvphi[9 * q + j];
-                info_err = std::max(info_err, std::fabs(s - (i == j)));
-            }
-    }
-    printf(" sum_int %llu sum_val %llu info_err %.3g", s_int, s_val, info_err);
-    // what came back: out record k says k, observation i is an outlier when i is odd
-    void* hout = H.get<char>(A.L.back_bytes());
-    FrameOut* res = at<FrameOut>(hout, A.L.in_back(A.out));
-    unsigned char* lvl = at<unsigned char>(hout, A.L.in_back(A.lvl));
-    for (int k = 0; k < n; k++) { std::memset(&res[k], 0, sizeof res[k]); res[k].n_inliers = k; for (int q = 0; q < 22; q++) res[k].nav[q] = k + q; }
-    for (size_t i = 0; i < n_tot; i++) lvl[i] = i & 1;
+        printf(" sum_int %llu sum_val %llu info_err %.3g", s_int, s_val, info_err);
+    }, [&](void* hout) {
+        // what came back: out record k says k, observation i is an outlier when i is odd
+        FrameOut* res = at<FrameOut>(hout, C.A.L.in_back(C.A.out));
+        unsigned char* lvl = at<unsigned char>(hout, C.A.L.in_back(C.A.lvl));
+        for (int k = 0; k < n; k++) { std::memset(&res[k], 0, sizeof res[k]); res[k].n_inliers = k; for (int q = 0; q < 22; q++) res[k].nav[q] = k + q; }
+        for (size_t i = 0; i < C.n_tot; i++) lvl[i] = i & 1;
+    });
+    if (!ran) return;
     unsigned long long s_in = 0, s_out = 0, s_last = 0;
     double s_nav = 0;
     for (int k = 0; k < n; k++) {
-        unpack_frame(pp[k], rr[k], desc[k], res[k], lvl);
+        const int n_last = P[k].last_is_frame == VBA_FRAME_FRAME ? P[k].n_obs_last : 0;
         s_in += R[k].n_inliers; s_nav += P[k].nav[21];
         for (int i = 0; i < P[k].n_obs; i++) s_out += R[k].outlier[i];
-        for (int i = 0; i < desc[k].n_last; i++) s_last += R[k].outlier_last[i];
+        for (int i = 0; i < n_last; i++) s_last += R[k].outlier_last[i];
     }
     printf(" got_inliers %llu got_nav21 %.0f got_outlier %llu got_outlier_last %llu\n", s_in, s_nav, s_out, s_last);
 }
@@ -202,14 +177,8 @@ static void inverse_file(FILE* f) {
 int main(int argc, char** argv) {
     if (argc < 2) return 2;
     const std::string mode = argv[1];
-    for (int a = 2; a < argc; a++) {
-        FILE* f = fopen(argv[a], "rb");
-        if (!f) { printf("error load\n"); continue; }
-        if (mode == "sim3") sim3_file(f);
-        else if (mode == "pose") pose_file(f);
-        else if (mode == "inverse") inverse_file(f);
-        else { fclose(f); return 2; }
-        fclose(f);
-    }
-    return 0;
+    if (mode == "sim3") return for_each_file(argc, argv, 2, sim3_file);
+    if (mode == "pose") return for_each_file(argc, argv, 2, pose_file);
+    if (mode == "inverse") return for_each_file(argc, argv, 2, inverse_file);
+    return 2;
 }

@@ -1,38 +1,17 @@
 // Sanitizer harness of the host half of vba_two_view_init (mc_slam_amd/csrc/vba_host_two_view.h, vba_host_arena.h): plain C++,
 // built by tests/test_host_two_view.py with g++ -fsanitize=address,undefined.
 //   host_two_view_check <file>...     one line per file: "ok key value ..." or "error <message>"
-// check, describe and pack run as the driver runs them -- above 256 pairs on several threads, as small_pack_threads does -- into
-// malloc'ed blocks of exactly upload_bytes(); unpack reads a block of exactly the downloaded bytes and writes result arrays of
-// exactly the caller's sizes, so any overrun is an ASan report.  Every array of the callers is a heap block of its exact size, too.
-// Checksums: sum of (2 i + 1) * word i over the 64-bit words of a region's payload (padded with zeros to whole words), mod 2^64.
+// TwoViewCall runs as the library's driver runs it (run_call, tests/host_check.h); every array of the callers is a heap block of
+// its exact size, so any overrun is an ASan report.  bind_<field>: where the kernel's argument points, as an offset into the arena.
 // Files (little-endian, written by the test): i32 n, then per pair i32 n_keys1 len1 n_keys2 len2 n_matches lenm n_hyp lenh nulls
 // min_triangulated, f64 K[4] sigma min_parallax, f64 uv1[len1][2] uv2[len2][2], i32 match[lenm][2] sets[lenh][8].  n_* are the
 // fields, len* the arrays; nulls: 1 uv2, 2 inlier_f, 4 the problem itself, 8 sets, 16 the result, 32 x3d, 64 match, 128 both
 // hyp_score arrays (legal), 256 triangulated, 512 uv1, 1024 inlier_h = NULL
 #include "../mc_slam_amd/csrc/vba_host_two_view.h"
 
-#include <cstdio>
-#include <cstdlib>
-#include <thread>
-#include <vector>
+#include "host_check.h"
 
 using namespace vba_host;
-
-struct Heap {   // exact-size heap blocks, freed at the end of a file
-    std::vector<void*> all;
-    template <class T> T* get(size_t n) { void* p = malloc(n * sizeof(T) + (n == 0)); all.push_back(p); return static_cast<T*>(p); }
-    template <class T> T* fill(size_t n, T v) { T* p = get<T>(n); for (size_t i = 0; i < n; i++) p[i] = v; return p; }
-    template <class T> T* read(FILE* f, size_t n, bool& ok) { T* p = get<T>(n); ok = ok && (n == 0 || fread(p, sizeof(T), n, f) == n); return p; }
-    ~Heap() { for (void* p : all) free(p); }
-};
-
-static unsigned long long checksum(const void* p, size_t bytes) {
-    std::vector<unsigned long long> w((bytes + 7) / 8, 0);
-    if (bytes) std::memcpy(w.data(), p, bytes);
-    unsigned long long s = 0;
-    for (size_t i = 0; i < w.size(); i++) s += (2 * i + 1) * w[i];
-    return s;
-}
 
 static void tv_file(FILE* f) {
     Heap H;
@@ -76,54 +55,47 @@ static void tv_file(FILE* f) {
         rr[k] = (nulls & 16) ? nullptr : &R[k];
     }
     if (!ok) { printf("error load\n"); return; }
-    TwoViewTotals T;
-    std::string err;
-    if (check_two_view(n, pp.data(), rr.data(), T, err)) { printf("error %s\n", err.c_str()); return; }
-    const TwoViewArena A(n, T);
-    void* hin = H.get<char>(A.L.upload_bytes());
-    TvDesc* desc = at<TvDesc>(hin, A.desc);
-    describe_two_view(n, pp.data(), desc);
-    auto pack = [&](int k) { pack_two_view(pp[k], desc[k], at<double>(hin, A.uv1), at<double>(hin, A.uv2), at<int32_t>(hin, A.match), at<int32_t>(hin, A.sets)); };
-    if (n >= 256) {   // the threaded path: pair k goes to thread k mod 4
-        std::vector<std::thread> th;
-        for (int t = 0; t < 4; t++) th.emplace_back([&, t] { for (int k = t; k < n; k += 4) pack(k); });
-        for (auto& t : th) t.join();
-    } else
-        for (int k = 0; k < n; k++) pack(k);
-    const size_t down = A.download_bytes(T.want_scores);
-    printf("ok k1 %zu k2 %zu m %zu h %zu want %d upload %zu back %zu down %zu total %zu", T.k1, T.k2, T.m, T.h, (int)T.want_scores, A.L.upload_bytes(),
-           A.L.back_bytes(), down, A.L.total_bytes());
-    printf(" desc %zu uv1 %zu uv2 %zu match %zu sets %zu out %zu flag_h %zu flag_f %zu tri %zu x3d %zu score_h %zu score_f %zu hyp_h %zu hyp_f %zu rt_state %zu rt_cos %zu rt_x %zu",
-           A.desc, A.uv1, A.uv2, A.match, A.sets, A.out, A.flag_h, A.flag_f, A.tri, A.x3d, A.score_h, A.score_f, A.hyp_h, A.hyp_f, A.rt_state, A.rt_cos, A.rt_x);
-    printf(" sum_desc %llu sum_uv1 %llu sum_uv2 %llu sum_match %llu sum_sets %llu", checksum(desc, sizeof(TvDesc) * n), checksum(at<char>(hin, A.uv1), 16 * T.k1),
-           checksum(at<char>(hin, A.uv2), 16 * T.k2), checksum(at<char>(hin, A.match), 8 * T.m), checksum(at<char>(hin, A.sets), 32 * T.h));
-    // what came back: pair k is ok when k is odd; flag_h[i] = i % 2, flag_f[i] = (i % 3 == 0), tri[j] = j % 2, double j of x3d is j,
-    // score_h[h] = h, score_f[h] = 2 h (i, j, h count through the call)
-    void* hout = H.get<char>(down);
-    TvOut* res = at<TvOut>(hout, A.L.in_back(A.out));
-    unsigned char* fh = at<unsigned char>(hout, A.L.in_back(A.flag_h));
-    unsigned char* ff = at<unsigned char>(hout, A.L.in_back(A.flag_f));
-    unsigned char* tri = at<unsigned char>(hout, A.L.in_back(A.tri));
-    double* x3d = at<double>(hout, A.L.in_back(A.x3d));
-    double* sh = at<double>(hout, A.L.in_back(A.score_h));   // beyond `down` without score arrays: never touched then
-    double* sf = at<double>(hout, A.L.in_back(A.score_f));
-    for (int k = 0; k < n; k++) {
-        std::memset(&res[k], 0, sizeof(TvOut));
-        res[k].ok = k % 2; res[k].model = 1 + k % 2; res[k].reason = k % 6; res[k].best_hyp_h = k; res[k].best_hyp_f = -1; res[k].n_rt = 4; res[k].best_rt = 3;
-        res[k].n_inliers_h = 2 * k; res[k].n_inliers_f = 3 * k;
-        for (int i = 0; i < 8; i++) { res[k].rt_good[i] = k + i; res[k].rt_parallax[i] = 0.5 * i; }
-        res[k].score_h = 1.5; res[k].score_f = 2.5; res[k].rh = 0.375;
-        for (int i = 0; i < 9; i++) { res[k].H21[i] = i; res[k].F21[i] = -i; res[k].R21[i] = 10 + i; }
-        for (int i = 0; i < 3; i++) res[k].t21[i] = 20 + i;
-    }
-    for (size_t i = 0; i < T.m; i++) { fh[i] = (unsigned char)(i % 2); ff[i] = (unsigned char)(i % 3 == 0); }
-    for (size_t j = 0; j < T.k1; j++) tri[j] = (unsigned char)(j % 2);
-    for (size_t j = 0; j < 3 * T.k1; j++) x3d[j] = (double)j;
-    if (T.want_scores) for (size_t h = 0; h < T.h; h++) { sh[h] = (double)h; sf[h] = 2.0 * h; }
+    TwoViewCall C;
+    const bool ran = run_call(H, C, n, pp.data(), rr.data(), [&](const TvBatch& B, void* hin) {
+        printf("ok k1 %zu k2 %zu m %zu h %zu want %d upload %zu back %zu down %zu total %zu", C.T.k1, C.T.k2, C.T.m, C.T.h, (int)C.T.want_scores, C.A.L.upload_bytes(),
+               C.A.L.back_bytes(), C.download_bytes(), C.A.L.total_bytes());
+        printf(" desc %zu uv1 %zu uv2 %zu match %zu sets %zu out %zu flag_h %zu flag_f %zu tri %zu x3d %zu score_h %zu score_f %zu hyp_h %zu hyp_f %zu rt_state %zu rt_cos %zu rt_x %zu",
+               C.A.desc, C.A.uv1, C.A.uv2, C.A.match, C.A.sets, C.A.out, C.A.flag_h, C.A.flag_f, C.A.tri, C.A.x3d, C.A.score_h, C.A.score_f, C.A.hyp_h, C.A.hyp_f, C.A.rt_state, C.A.rt_cos, C.A.rt_x);
+        PRINT_BIND(B, hin, desc); PRINT_BIND(B, hin, uv1); PRINT_BIND(B, hin, uv2); PRINT_BIND(B, hin, match); PRINT_BIND(B, hin, sets); PRINT_BIND(B, hin, out);
+        PRINT_BIND(B, hin, flag_h); PRINT_BIND(B, hin, flag_f); PRINT_BIND(B, hin, tri); PRINT_BIND(B, hin, x3d); PRINT_BIND(B, hin, score_h);
+        PRINT_BIND(B, hin, score_f); PRINT_BIND(B, hin, hyp_h); PRINT_BIND(B, hin, hyp_f); PRINT_BIND(B, hin, rt_state); PRINT_BIND(B, hin, rt_cos);
+        PRINT_BIND(B, hin, rt_x);
+        printf(" sum_desc %llu sum_uv1 %llu sum_uv2 %llu sum_match %llu sum_sets %llu", checksum(at<char>(hin, C.A.desc), sizeof(TvDesc) * n),
+               checksum(at<char>(hin, C.A.uv1), 16 * C.T.k1), checksum(at<char>(hin, C.A.uv2), 16 * C.T.k2), checksum(at<char>(hin, C.A.match), 8 * C.T.m),
+               checksum(at<char>(hin, C.A.sets), 32 * C.T.h));
+    }, [&](void* hout) {
+        // what came back: pair k is ok when k is odd; flag_h[i] = i % 2, flag_f[i] = (i % 3 == 0), tri[j] = j % 2, double j of x3d is j,
+        // score_h[h] = h, score_f[h] = 2 h (i, j, h count through the call)
+        TvOut* res = at<TvOut>(hout, C.A.L.in_back(C.A.out));
+        unsigned char* fh = at<unsigned char>(hout, C.A.L.in_back(C.A.flag_h));
+        unsigned char* ff = at<unsigned char>(hout, C.A.L.in_back(C.A.flag_f));
+        unsigned char* tri = at<unsigned char>(hout, C.A.L.in_back(C.A.tri));
+        double* x3d = at<double>(hout, C.A.L.in_back(C.A.x3d));
+        double* sh = at<double>(hout, C.A.L.in_back(C.A.score_h));   // beyond the downloaded bytes without score arrays: never touched then
+        double* sf = at<double>(hout, C.A.L.in_back(C.A.score_f));
+        for (int k = 0; k < n; k++) {
+            std::memset(&res[k], 0, sizeof(TvOut));
+            res[k].ok = k % 2; res[k].model = 1 + k % 2; res[k].reason = k % 6; res[k].best_hyp_h = k; res[k].best_hyp_f = -1; res[k].n_rt = 4; res[k].best_rt = 3;
+            res[k].n_inliers_h = 2 * k; res[k].n_inliers_f = 3 * k;
+            for (int i = 0; i < 8; i++) { res[k].rt_good[i] = k + i; res[k].rt_parallax[i] = 0.5 * i; }
+            res[k].score_h = 1.5; res[k].score_f = 2.5; res[k].rh = 0.375;
+            for (int i = 0; i < 9; i++) { res[k].H21[i] = i; res[k].F21[i] = -i; res[k].R21[i] = 10 + i; }
+            for (int i = 0; i < 3; i++) res[k].t21[i] = 20 + i;
+        }
+        for (size_t i = 0; i < C.T.m; i++) { fh[i] = (unsigned char)(i % 2); ff[i] = (unsigned char)(i % 3 == 0); }
+        for (size_t j = 0; j < C.T.k1; j++) tri[j] = (unsigned char)(j % 2);
+        for (size_t j = 0; j < 3 * C.T.k1; j++) x3d[j] = (double)j;
+        if (C.T.want_scores) for (size_t h = 0; h < C.T.h; h++) { sh[h] = (double)h; sf[h] = 2.0 * h; }
+    });
+    if (!ran) return;
     long long s_ok = 0, s_head = 0, s_fh = 0, s_ff = 0, s_tri = 0;
     double s_x = 0, s_R = 0, s_sc = 0, s_mat = 0;
     for (int k = 0; k < n; k++) {
-        unpack_two_view(rr[k], desc[k], res[k], fh, ff, tri, x3d, sh, sf);
         const vba_two_view_result& r = R[k];
         s_ok += r.ok;
         s_head += r.status + r.model + r.reason + r.best_hyp_h + r.best_hyp_f + r.n_inliers_h + r.n_inliers_f + r.n_rt + r.best_rt + r.rt_good[7];
@@ -137,12 +109,4 @@ static void tv_file(FILE* f) {
            s_R, s_sc, s_mat);
 }
 
-int main(int argc, char** argv) {
-    for (int a = 1; a < argc; a++) {
-        FILE* f = fopen(argv[a], "rb");
-        if (!f) { printf("error load\n"); continue; }
-        tv_file(f);
-        fclose(f);
-    }
-    return 0;
-}
+int main(int argc, char** argv) { return for_each_file(argc, argv, 1, tv_file); }

@@ -2,16 +2,14 @@
 and point records, the grid copy, write-back with n_found) under AddressSanitizer + UBSan (CPU only).  The harness
 (tests/host_fuse_check.cpp) packs into heap blocks of exactly the arena's sizes; every expected offset below is restated from the
 sizes alone and the packed regions are compared with records built in NumPy through an order-sensitive checksum."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 from mc_slam_amd import synth
 import fuse_cases as cases_mod
+import host_check_lib as hc
+from host_check_lib import checksum, up
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DESC = np.dtype([("off", "<i8", 5), ("i", "<i4", 8), ("c", "<f8", 29)])
 KEY = np.dtype([("d", "u1", 32), ("u", "<f8"), ("v", "<f8"), ("oct", "u1"), ("pad", "u1", 15)])
 PT = np.dtype([("d", "u1", 32), ("pos", "<f8", 3), ("normal", "<f8", 3), ("dist", "<f8", 3), ("skip", "<i4"), ("pad", "<i4", 5)])
@@ -19,37 +17,7 @@ PT = np.dtype([("d", "u1", 32), ("pos", "<f8", 3), ("normal", "<f8", 3), ("dist"
 
 @pytest.fixture(scope="module")
 def checker(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("hf") / "host_fuse_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-pthread", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           "-fno-omit-frame-pointer", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "host_fuse_check.cpp"),
-                           "-o", exe])
-    return exe
-
-
-def _run(checker, files):
-    r = subprocess.run([checker] + files, capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"), timeout=300)
-    assert r.returncode == 0 and "ERROR" not in r.stderr and "runtime error" not in r.stderr, (r.stdout[-500:], r.stderr[-2000:])
-    lines = r.stdout.strip().splitlines()
-    assert len(lines) == len(files), lines
-    return lines
-
-
-def _fields(line):
-    assert line.startswith("ok "), line
-    t = line.split()
-    return {k: int(v) for k, v in zip(t[1::2], t[2::2])}
-
-
-def up(b):
-    return (b + 255) // 256 * 256
-
-
-def checksum(*arrays):
-    """sum of (2 i + 1) * word i over the 64-bit words of the arrays' bytes (padded with zeros to whole words), mod 2^64"""
-    b = b"".join(np.ascontiguousarray(a).tobytes() for a in arrays)
-    w = np.frombuffer(b + b"\0" * (-len(b) % 8), dtype="<u8")
-    with np.errstate(over="ignore"):
-        return int((w * (2 * np.arange(len(w), dtype=np.uint64) + 1)).sum(dtype=np.uint64))
+    return hc.build(tmp_path_factory, "host_fuse_check", pthread=True)
 
 
 def consts(p):
@@ -99,8 +67,8 @@ def test_offsets_tiles_packing_and_write_back(checker, tmp_path):
     for k, ps in enumerate(batches):
         files.append(str(tmp_path / ("b%d.fu" % k)))
         _write(files[-1], [(p, {}) for p in ps])
-    for ps, line in zip(batches, _run(checker, files)):
-        f = _fields(line)
+    for ps, line in zip(batches, hc.run(checker, files, len(files))):
+        f = hc.fields(line)
         n = len(ps)
         nk, npt = sum(p.n_keys for p in ps), sum(p.n_pt for p in ps)
         nc, ft, lv = sum(len(p.cell_begin) for p in ps), sum(len(p.cell_feat) for p in ps), sum(2 * p.n_levels for p in ps)
@@ -114,6 +82,9 @@ def test_offsets_tiles_packing_and_write_back(checker, tmp_path):
             offs.append(o)
             o += up(b)
         assert [f[k] for k in ("desc", "tile", "key", "pt", "cell", "feat", "lev", "best_idx", "best_dist", "level", "uv", "state")] == offs
+        # FuBatch reads every region where it is: the two grid copies are the pair that a swap would not show on the CPU otherwise
+        hc.assert_bound(f, [("cell_begin", "cell"), ("cell_feat", "feat")] +
+                        [(k, k) for k in ("desc", "tile", "key", "pt", "lev", "best_idx", "best_dist", "level", "uv", "state")])
         assert f["upload"] == offs[7] and f["back"] == o - offs[7] and f["total"] == o
         d = np.zeros(n, dtype=DESC)
         ok = op = oc = of = ol = 0
@@ -217,7 +188,7 @@ def test_refusals(checker, tmp_path, change, message):
         bad = bad.copy(cell_feat=a)
     path = str(tmp_path / "r.fu")
     _write(path, [(good, {}), (bad, o)])
-    assert _run(checker, [path]) == ["error " + message]
+    assert hc.run(checker, [path], 1) == ["error " + message]
 
 
 def test_legal_edges(checker, tmp_path):
@@ -231,5 +202,5 @@ def test_legal_edges(checker, tmp_path):
     g = synth.fuse_scene(9, n_keys=20, n_pt=300, cols=65536, rows=1)
     path = str(tmp_path / "e.fu")
     _write(path, [(e, dict(nulls=2 | 32 | 256 | 512 | 2048)), (k, dict(nulls=1 | 128 | 1024)), (b, {}), (g, {})])
-    f = _fields(_run(checker, [path])[0])
+    f = hc.fields(hc.run(checker, [path], 1)[0])
     assert (f["keys"], f["pts"], f["lev_tot"], f["tiles"], f["cells"]) == (e.n_keys + 30 + 20, k.n_pt + 10 + 300, 16 + 16 + 128 + 16, 1 + 1 + 2, 2 * 3073 + 3073 + 65537)

@@ -3,23 +3,19 @@ under AddressSanitizer + UBSan (CPU only).  Every expectation below is derived f
 prefix sums, the rows of the reduced system from the layout rules of the three elimination orders restated here -- and the two
 encodings of a dof's position (the descriptor fields the kernels read, and vpos_host) are compared entry by entry."""
 import os
-import subprocess
 
 import pytest
 
 from mc_slam_amd import abi, synth
+import host_check_lib as hc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NB = 32
 ORDERS = [None, 0, 1, 2]      # VBA_ORDER unset (the library's choice) and the three orders forced
 
 
 @pytest.fixture(scope="module")
 def checker(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("hl") / "host_layout_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
-                           "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "host_layout_check.cpp"), "-o", exe])
-    return exe
+    return hc.build(tmp_path_factory, "host_layout_check")
 
 
 @pytest.fixture(scope="module")
@@ -46,13 +42,11 @@ BATCHES = [["idp12", "idp9", "idp70", "c3", "idp4"], ["idp9", "idp4"], ["se3", "
 
 
 def _run(checker, args, order=None):
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1")
+    env = dict(os.environ)
     env.pop("VBA_ORDER", None)
     if order is not None:
         env["VBA_ORDER"] = str(order)
-    r = subprocess.run([checker] + args, capture_output=True, text=True, env=env, timeout=600)
-    assert r.returncode == 0 and "ERROR" not in r.stderr and "runtime error" not in r.stderr, (r.stdout[-500:], r.stderr[-2000:])
-    return r.stdout.strip().splitlines()
+    return hc.run(checker, args, env=env, timeout=600)
 
 
 def _fields(line):

@@ -8,6 +8,7 @@ import subprocess
 import pytest
 
 import plan_cases as pc
+import host_check_lib as hc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mc_slam_amd", "csrc")
@@ -16,10 +17,7 @@ SIZES = [1, 3, 4, 7, 8, 9, 15, 16, 63, 64, 65, 255, 256, 300]
 
 @pytest.fixture(scope="module")
 def checker(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("hp") / "host_plan_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
-                           "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "host_plan_check.cpp"), "-o", exe])
-    return exe
+    return hc.build(tmp_path_factory, "host_plan_check")
 
 
 def _run(checker, tmp_path, lines):

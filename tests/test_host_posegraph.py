@@ -1,7 +1,6 @@
 """The host half of vba_posegraph_optimize (validation, free-vertex numbering, block envelope, owner lists) under
 AddressSanitizer + UBSan (CPU only): every graph of the GPU tests, every bad input of the entry point, and a 5 000-vertex graph
 with a 40-keyframe band.  The harness (tests/host_posegraph_check.cpp) checks the envelope invariants itself."""
-import os
 import subprocess
 
 import numpy as np
@@ -9,17 +8,14 @@ import pytest
 
 import posegraph_cases as pc
 from mc_slam_amd import abi
+import host_check_lib as hc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MUTATE = dict(n_vertices_neg=1, n_edges_neg=2, n_pt_neg=3, S_null=4, edge_S_null=5, pt_null=6, fixed_null=7)
 
 
 @pytest.fixture(scope="module")
 def checker(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("pg") / "host_posegraph_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
-                           "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "host_posegraph_check.cpp"), "-o", exe])
-    return exe
+    return hc.build(tmp_path_factory, "host_posegraph_check", pthread=True)
 
 
 def _write(path, p, mutate=0, env_before=0):
@@ -37,16 +33,7 @@ def _run(checker, tmp_path, items):
         f = str(tmp_path / ("g%d.pg" % i))
         _write(f, p, mutate, env_before)
         files.append(f)
-    r = subprocess.run([checker] + files, capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"), timeout=300)
-    assert r.returncode == 0 and "ERROR" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-2000:]
-    lines = r.stdout.strip().splitlines()
-    assert len(lines) == len(items)
-    return lines
-
-
-def _fields(line):
-    assert line.startswith("ok "), line
-    return {k: int(v) for k, v in zip(line.split()[1::2], line.split()[2::2])}
+    return hc.run(checker, files, len(items))
 
 
 def _big(n=5000, band=40, n_loop=8):
@@ -66,7 +53,7 @@ def _big(n=5000, band=40, n_loop=8):
 def test_every_gpu_graph_has_a_consistent_envelope(checker, tmp_path):
     names = pc.CASES + ["REJECT"]
     ps = [pc.case(n) for n in names]
-    got = dict(zip(names, map(_fields, _run(checker, tmp_path, ps))))
+    got = dict(zip(names, map(hc.fields, _run(checker, tmp_path, ps))))
     for n, p in zip(names, ps):
         f = got[n]
         assert f["n_free"] == int((p.fixed == 0).sum())
@@ -82,7 +69,7 @@ def test_every_gpu_graph_has_a_consistent_envelope(checker, tmp_path):
 
 def test_five_thousand_vertices_fit_the_bound_eight_times(checker, tmp_path):
     p = _big()
-    f = _fields(_run(checker, tmp_path, [p])[0])
+    f = hc.fields(_run(checker, tmp_path, [p])[0])
     assert f["n_free"] == 4999 and f["widest"] == 4999
     assert f["env"] * 8 <= 2 ** 21
     line = _run(checker, tmp_path, [(p, 0, 2 ** 21 - f["env"] + 1)])[0]                 # the bound holds for the whole call
@@ -131,9 +118,7 @@ def test_arena_of_a_two_graph_call(checker, tmp_path):
     for i, p in enumerate(ps):
         files.append(str(tmp_path / ("c%d.pg" % i)))
         _write(files[-1], p)
-    r = subprocess.run([checker, "--call"] + files, capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"), timeout=300)
-    assert r.returncode == 0 and "ERROR" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-2000:]
-    t = r.stdout.split()
+    t = hc.run(checker, ["--call"] + files, 1)[0].split()
     assert t[0] == "call" and t[23] == "offsets"
     got = {k: int(v) for k, v in zip(t[1:23:2], t[2:23:2])}
     offs = [int(v) for v in t[24:55]]
@@ -153,6 +138,10 @@ def test_arena_of_a_two_graph_call(checker, tmp_path):
     assert offs == want[:31].tolist()                                                              # and exactly where they were
     assert (got["upload"], got["back"], got["total"]) == (want[18], want[21] - want[18], want[31])
     assert t[55] == "last_ref" and int(t[56]) == ps[0].n_vertices + int(ps[1].pt_ref[-1])
+    # PgBatch reads every region where it is, and knows the call's points
+    assert t[57] == "bind" and [int(v) for v in t[58:89]] == offs and t[89:91] == ["n_pt_total", str(npt)]
+    # the write-back of a synthetic result (see the harness): graph g says g, the estimates come back as 0, 1, 2, ..., the points as -0, -1, ...
+    assert t[91:] == ["got_its", "1", "got_S", str(8 * nv * (8 * nv - 1) // 2), "got_pt", str(-(3 * npt * (3 * npt - 1) // 2))]
 
 
 def test_dense_expansion_of_a_three_vertex_envelope(checker, tmp_path):
@@ -163,9 +152,7 @@ def test_dense_expansion_of_a_three_vertex_envelope(checker, tmp_path):
     assert sizes["nf"] == 3 and first.tolist() == [0, 0, 1]
     f = str(tmp_path / "e.pg")
     _write(f, p)
-    r = subprocess.run([checker, "--expand", f], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"), timeout=60)
-    assert r.returncode == 0 and "ERROR" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-2000:]
-    t = r.stdout.split()
+    t = hc.run(checker, ["--expand", f], 1)[0].split()
     assert t[:3] == ["expand", "n_free", "3"] and [int(v) for v in t[4:7]] == first.tolist() and t[7] == "H"
     H = np.array(t[8:], dtype=float).reshape(21, 21)
     assert np.array_equal(H, H.T)

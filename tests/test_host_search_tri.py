@@ -3,17 +3,15 @@ node join with its query list, the interleaved keypoint records, write-back with
 (CPU only).  The harness (tests/host_search_tri_check.cpp) packs into heap blocks of exactly the arena's sizes; every expected
 offset below is restated from the sizes alone, the packed regions are compared with records built in NumPy through an
 order-sensitive checksum, and the query list with the yardstick's node join (tests/search_tri_ref.py)."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 from mc_slam_amd import synth
 import search_tri_cases as cases_mod
 import search_tri_ref as ref_mod
+import host_check_lib as hc
+from host_check_lib import checksum, up
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DESC = np.dtype([("off", "<i8", 4), ("i", "<i4", 6), ("c", "<f8", 13)])
 KEY = np.dtype([("d", "u1", 32), ("u", "<f8"), ("v", "<f8"), ("angle", "<f4"), ("oct", "u1"), ("role", "u1"), ("pad", "u1", 10)])
 OUT_BYTES = 144
@@ -21,37 +19,7 @@ OUT_BYTES = 144
 
 @pytest.fixture(scope="module")
 def checker(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("hs") / "host_search_tri_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-pthread", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           "-fno-omit-frame-pointer", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "host_search_tri_check.cpp"),
-                           "-o", exe])
-    return exe
-
-
-def _run(checker, files):
-    r = subprocess.run([checker] + files, capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"), timeout=300)
-    assert r.returncode == 0 and "ERROR" not in r.stderr and "runtime error" not in r.stderr, (r.stdout[-500:], r.stderr[-2000:])
-    lines = r.stdout.strip().splitlines()
-    assert len(lines) == len(files), lines
-    return lines
-
-
-def _fields(line):
-    assert line.startswith("ok "), line
-    t = line.split()
-    return {k: int(v) for k, v in zip(t[1::2], t[2::2])}
-
-
-def up(b):
-    return (b + 255) // 256 * 256
-
-
-def checksum(*arrays):
-    """sum of (2 i + 1) * word i over the 64-bit words of the arrays' bytes (padded with zeros to whole words), mod 2^64"""
-    b = b"".join(np.ascontiguousarray(a).tobytes() for a in arrays)
-    w = np.frombuffer(b + b"\0" * (-len(b) % 8), dtype="<u8")
-    with np.errstate(over="ignore"):
-        return int((w * (2 * np.arange(len(w), dtype=np.uint64) + 1)).sum(dtype=np.uint64))
+    return hc.build(tmp_path_factory, "host_search_tri_check", pthread=True)
 
 
 def consts(p):
@@ -104,8 +72,8 @@ def test_offsets_join_packing_and_write_back(checker, tmp_path):
     for k, ps in enumerate(batches):
         files.append(str(tmp_path / ("b%d.st" % k)))
         _write(files[-1], [(p, {}) for p in ps])
-    for ps, line in zip(batches, _run(checker, files)):
-        f = _fields(line)
+    for ps, line in zip(batches, hc.run(checker, files, len(files))):
+        f = hc.fields(line)
         n = len(ps)
         k1, k2 = sum(p.n_keys1 for p in ps), sum(p.n_keys2 for p in ps)
         ft, lv = sum(len(p.node_feat2) for p in ps), sum(2 * p.n_levels2 for p in ps)
@@ -116,6 +84,7 @@ def test_offsets_join_packing_and_write_back(checker, tmp_path):
             offs.append(o)
             o += up(b)
         assert [f[k] for k in ("desc", "key1", "key2", "query", "feat", "lev", "out", "match12", "best_dist", "state")] == offs
+        hc.assert_bound(f, [(k, k) for k in ("desc", "key1", "key2", "query", "feat", "lev", "out", "match12", "best_dist", "state")])   # StBatch reads every region where it is
         assert f["upload"] == offs[6] and f["back"] == o - offs[6] and f["total"] == o
         # the join against the yardstick's, and the packed regions
         joins = [ref_mod.node_join(p) for p in ps]
@@ -221,7 +190,7 @@ def test_refusals(checker, tmp_path, change, message):
         bad = bad.copy(**{name: a})
     path = str(tmp_path / "r.st")
     _write(path, [(good, {}), (bad, o)])
-    assert _run(checker, [path]) == ["error " + message]
+    assert hc.run(checker, [path], 1) == ["error " + message]
 
 
 def test_legal_edges(checker, tmp_path):
@@ -235,5 +204,5 @@ def test_legal_edges(checker, tmp_path):
     b = _with(b, oct2=(5, 63))
     path = str(tmp_path / "e.st")
     _write(path, [(a, dict(nulls=64)), (e, dict(nulls=2 | 32 | 1024)), (b, {})])
-    f = _fields(_run(checker, [path])[0])
+    f = hc.fields(hc.run(checker, [path], 1)[0])
     assert (f["k1"], f["lev_tot"]) == (a.n_keys1 + b.n_keys1, 16 + 16 + 128)

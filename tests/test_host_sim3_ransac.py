@@ -2,52 +2,20 @@
 write-back) under AddressSanitizer + UBSan (CPU only).  The harness (tests/host_sim3_ransac_check.cpp) packs into heap blocks of
 exactly the arena's sizes; every expected offset below is restated from the sizes alone, and the packed regions are compared with
 the interleaving done in NumPy through an order-sensitive checksum."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 from mc_slam_amd import synth
+import host_check_lib as hc
+from host_check_lib import checksum, up
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DESC = np.dtype([("i", "<i4", 6), ("pair0", "<i8"), ("hyp0", "<i8"), ("K1", "<f8", 4), ("K2", "<f8", 4)])
 OUT, HYP = 160, 32 * 8
 
 
 @pytest.fixture(scope="module")
 def checker(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("hr") / "host_sim3_ransac_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-pthread", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           "-fno-omit-frame-pointer", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "host_sim3_ransac_check.cpp"),
-                           "-o", exe])
-    return exe
-
-
-def _run(checker, files):
-    r = subprocess.run([checker] + files, capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"), timeout=300)
-    assert r.returncode == 0 and "ERROR" not in r.stderr and "runtime error" not in r.stderr, (r.stdout[-500:], r.stderr[-2000:])
-    lines = r.stdout.strip().splitlines()
-    assert len(lines) == len(files), lines
-    return lines
-
-
-def _fields(line):
-    assert line.startswith("ok "), line
-    t = line.split()
-    return {k: int(v) for k, v in zip(t[1::2], t[2::2])}
-
-
-def up(b):
-    return (b + 255) // 256 * 256
-
-
-def checksum(*arrays):
-    """sum of (2 i + 1) * word i over the 64-bit words of the arrays' bytes (padded with zeros to whole words), mod 2^64"""
-    b = b"".join(np.ascontiguousarray(a).tobytes() for a in arrays)
-    w = np.frombuffer(b + b"\0" * (-len(b) % 8), dtype="<u8")
-    with np.errstate(over="ignore"):
-        return int((w * (2 * np.arange(len(w), dtype=np.uint64) + 1)).sum(dtype=np.uint64))
+    return hc.build(tmp_path_factory, "host_sim3_ransac_check", pthread=True)
 
 
 def _write(path, items):
@@ -82,8 +50,8 @@ def test_offsets_packing_and_write_back(checker, tmp_path, want):
     for k, ps in enumerate(batches):
         files.append(str(tmp_path / ("b%d.rs" % k)))
         _write(files[-1], [(p, dict(want=want)) for p in ps])
-    for ps, line in zip(batches, _run(checker, files)):
-        f = _fields(line)
+    for ps, line in zip(batches, hc.run(checker, files, len(files))):
+        f = hc.fields(line)
         n, n_tot, h_tot = len(ps), sum(p.n_pairs for p in ps), sum(p.n_hyp for p in ps)
         assert (f["n_tot"], f["h_tot"], f["want"]) == (n_tot, h_tot, want)
         # the arena, restated from the sizes: four upload regions, three back regions, one device-only region
@@ -92,6 +60,7 @@ def test_offsets_packing_and_write_back(checker, tmp_path, want):
             offs.append(o)
             o += up(b)
         assert [f[k] for k in ("desc", "p", "gate", "sample", "out", "flag", "cnt", "hyp")] == offs
+        hc.assert_bound(f, [(k, k) for k in ("desc", "out", "p", "gate", "sample", "hyp", "cnt", "flag")])   # RansacBatch reads every region where it is
         assert f["upload"] == offs[4] and f["back"] == offs[7] - offs[4] and f["total"] == o
         assert f["download"] == (f["back"] if want else offs[6] - offs[4])
         # the packed regions
@@ -162,7 +131,7 @@ def test_refusals(checker, tmp_path, change, message):
         bad = bad.copy(max_err1=a)
     path = str(tmp_path / "r.rs")
     _write(path, [(good, {}), (bad, o)])
-    assert _run(checker, [path]) == ["error " + message]
+    assert hc.run(checker, [path], 1) == ["error " + message]
 
 
 def test_legal_edges(checker, tmp_path):
@@ -170,5 +139,5 @@ def test_legal_edges(checker, tmp_path):
     a, b, c = _batch([(5, 0), (4, 3), (0, 0)], 7)
     path = str(tmp_path / "e.rs")
     _write(path, [(a, dict(want=0)), (b, dict(min_inliers=50)), (c, dict(want=0))])
-    f = _fields(_run(checker, [path])[0])
+    f = hc.fields(hc.run(checker, [path], 1)[0])
     assert f["want"] == 1 and f["download"] == f["back"] and f["got_cnt"] == 0 + 1 + 2

@@ -2,50 +2,20 @@
 refusals, arena offsets, packing, write-back, inverse_host) under AddressSanitizer + UBSan (CPU only).  The harness
 (tests/host_small_check.cpp) packs into heap blocks of exactly the arena's sizes; every expected offset below is restated from the
 sizes alone, and the packed regions are compared with the interleaving done in NumPy through an order-sensitive checksum."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 from mc_slam_amd import abi, synth
+import host_check_lib as hc
+from host_check_lib import checksum, up
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIM3_DESC = np.dtype([("i", "<i4", 6), ("pair0", "<i8"), ("S", "<f8", 8), ("K1", "<f8", 4), ("K2", "<f8", 4), ("th2", "<f8"), ("huber", "<f8")])
 SIM3_OUT, FRAME_DESC, FRAME_OUT = 112, 32 + 8 * (3 * 22 + 19 + 61 + 81 + 225 + 6), 32 + 8 * (4 + 22 + 225)
 
 
 @pytest.fixture(scope="module")
 def checker(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("hs") / "host_small_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
-                           "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "host_small_check.cpp"), "-o", exe])
-    return exe
-
-
-def _run(checker, mode, files):
-    r = subprocess.run([checker, mode] + files, capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"), timeout=300)
-    assert r.returncode == 0 and "ERROR" not in r.stderr and "runtime error" not in r.stderr, (r.stdout[-500:], r.stderr[-2000:])
-    lines = r.stdout.strip().splitlines()
-    assert len(lines) == len(files), lines
-    return lines
-
-
-def _fields(line):
-    assert line.startswith("ok "), line
-    t = line.split()
-    return {k: (float(v) if k == "info_err" else int(v)) for k, v in zip(t[1::2], t[2::2])}
-
-
-def up(b):
-    return (b + 255) // 256 * 256
-
-
-def checksum(*arrays):
-    """sum of (2 i + 1) * word i over the 64-bit words of the arrays' bytes, mod 2^64"""
-    w = np.frombuffer(b"".join(np.ascontiguousarray(a).tobytes() for a in arrays), dtype="<u8")
-    with np.errstate(over="ignore"):
-        return int((w * (2 * np.arange(len(w), dtype=np.uint64) + 1)).sum(dtype=np.uint64))
+    return hc.build(tmp_path_factory, "host_small_check", pthread=True)
 
 
 # ---------------------------------------------------------------------------------------------------------------- sim3
@@ -75,14 +45,15 @@ def test_sim3_offsets_packing_and_write_back(checker, tmp_path, want_chi2):
     for k, ps in enumerate(batches):
         files.append(str(tmp_path / ("b%d.s3" % k)))
         _write_sim3(files[-1], [(p, dict(want_chi2=want_chi2)) for p in ps])
-    for ps, line in zip(batches, _run(checker, "sim3", files)):
-        f = _fields(line)
+    for ps, line in zip(batches, hc.run(checker, ["sim3"] + files, len(files))):
+        f = hc.fields(line)
         n, n_tot = len(ps), sum(p.n_pairs for p in ps)
         # today's formulas: [desc | p | uv | w] up, [out | flag | c] back, no device-only region
         sizes = [up(SIM3_DESC.itemsize * n), up((6 * n_tot + 6) * 8), up((4 * n_tot + 4) * 8), up((2 * n_tot + 2) * 8),
                  up(SIM3_OUT * n), up(n_tot + 1), up((2 * n_tot + 2) * 8)]
         offs = np.concatenate([[0], np.cumsum(sizes)])
         assert [f[k] for k in ("desc", "p", "uv", "w", "out", "flag", "c")] == offs[:7].tolist()
+        hc.assert_bound(f, [(k, k) for k in ("desc", "out", "p", "uv", "w", "c", "flag")])                 # Sim3Batch reads every region where it is
         assert (f["n_tot"], f["want_chi2"], f["upload"], f["back"], f["total"]) == (n_tot, want_chi2, offs[4], offs[7] - offs[4], offs[7])
         assert f["download"] == (offs[7] if want_chi2 else offs[6]) - offs[4]         # chi2 comes back only when a caller asked for it
         d = np.zeros(n, dtype=SIM3_DESC)
@@ -123,15 +94,15 @@ def test_sim3_refusals_carry_todays_messages(checker, tmp_path):
     for k, (bad, _) in enumerate(cases):
         files.append(str(tmp_path / ("r%d.s3" % k)))
         _write_sim3(files[-1], [good, bad])
-    for (_, msg), line in zip(cases, _run(checker, "sim3", files)):
+    for (_, msg), line in zip(cases, hc.run(checker, ["sim3"] + files, len(files))):
         assert line == "error problem 1: " + msg
     # a NULL array is no refusal while n_pairs is 0; scale before quaternion, as the entry point orders them
     q = synth.make_sim3_pair(7, 0)
     _write_sim3(files[0], [(q, dict(nulls=1)), (p.copy(S12=np.r_[p.S12[:3], 0, 0, 0, 0, 0.0]), {})])
-    assert _run(checker, "sim3", files[:1]) == ["error problem 1: scale of S12 is not positive"]
+    assert hc.run(checker, ["sim3"] + files[:1], 1) == ["error problem 1: scale of S12 is not positive"]
     raw = open(files[1], "rb").read()
     open(files[1], "wb").write(raw[:len(raw) // 2])                                   # a truncated file: refused by the reader
-    assert _run(checker, "sim3", files[1:2]) == ["error load"]
+    assert hc.run(checker, ["sim3"] + files[1:2], 1) == ["error load"]
 
 
 # ---------------------------------------------------------------------------------------------------------------- pose
@@ -177,8 +148,8 @@ def test_pose_offsets_packing_and_write_back(checker, tmp_path, frames):
         files.append(str(tmp_path / ("b%d.fr" % k)))
         _write_pose(files[-1], [(f, {}) for f in fs])
     hub = [float(np.float32(np.sqrt(x))) for x in (30.5779, 21.666, 16.812, 5.991)]
-    for fs, line in zip(batches, _run(checker, "pose", files)):
-        f = _fields(line)
+    for fs, line in zip(batches, hc.run(checker, ["pose"] + files, len(files))):
+        f = hc.fields(line, floats=("info_err",))
         n = len(fs)
         n_last = [g.n_obs_last if g.last_is_frame == 1 else 0 for g in fs]
         n_tot = sum(g.n_obs for g in fs) + sum(n_last)
@@ -186,6 +157,8 @@ def test_pose_offsets_packing_and_write_back(checker, tmp_path, frames):
         sizes = [up(FRAME_DESC * n), up((3 * n_tot + 3) * 8), up((2 * n_tot + 2) * 8), up((n_tot + 1) * 8), up(FRAME_OUT * n), up(n_tot + 1), up((2 * n_tot + 2) * 8)]
         offs = np.concatenate([[0], np.cumsum(sizes)])
         assert [f[k] for k in ("desc", "pw", "uv", "w", "out", "lvl", "err")] == offs[:7].tolist()
+        hc.assert_bound(f, [(k, k) for k in ("desc", "out", "pw", "uv", "w", "err", "lvl")])             # PoseBatch reads every region where it is
+        assert f["n_frames"] == n
         assert (f["n_tot"], f["upload"], f["back"], f["total"]) == (n_tot, offs[4], offs[6] - offs[4], offs[7])
         # a frame's observations, then its last frame's
         assert f["sum_pw"] == checksum(*[a for g, nl in zip(fs, n_last) for a in (g.obs_pw, g.last_pw[:nl])])
@@ -227,13 +200,13 @@ def test_pose_refusals_carry_todays_messages(checker, tmp_path, frames):
     for k, (bad, _) in enumerate(cases):
         files.append(str(tmp_path / ("r%d.fr" % k)))
         _write_pose(files[-1], [(fr, {}), bad])
-    for (_, msg), line in zip(cases, _run(checker, "pose", files)):
+    for (_, msg), line in zip(cases, hc.run(checker, ["pose"] + files, len(files))):
         assert line == "error " + msg
     # what is no refusal: a negative n_obs_last and NULL last arrays where no last frame is read, a singular covariance in a vision-only frame
     vis = _cut(frames[2], 31)
     vis.imu_cov_pvphi = np.zeros((9, 9))
     _write_pose(files[0], [(kf, dict(n_obs_last=-5, nulls=2)), (vis, {}), (_cut(frames[1], 0, 0), dict(nulls=1 | 2))])
-    assert _fields(_run(checker, "pose", files[:1])[0])["n_tot"] == 62
+    assert hc.fields(hc.run(checker, ["pose"] + files[:1], 1)[0], floats=("info_err",))["n_tot"] == 62
 
 
 # ------------------------------------------------------------------------------------------------------------- inverse
@@ -250,7 +223,7 @@ def test_inverse_host(checker, tmp_path):
     for k, M in enumerate(mats):
         files.append(str(tmp_path / ("m%d.bin" % k)))
         open(files[-1], "wb").write(np.array([len(M)], dtype="<i4").tobytes() + M.astype("<f8").tobytes())
-    lines = _run(checker, "inverse", files)
+    lines = hc.run(checker, ["inverse"] + files, len(files))
     got = np.array(lines[0].split()[1:], dtype=float).reshape(9, 9)
     want = np.linalg.inv(A)
     err = np.abs(got - want).max() / np.abs(want).max()

@@ -8,16 +8,13 @@ import numpy as np
 import pytest
 
 from mc_slam_amd import abi, synth
+import host_check_lib as hc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def checker(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("hs") / "host_structure_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
-                           "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "host_structure_check.cpp"), "-o", exe])
-    return exe
+    return hc.build(tmp_path_factory, "host_structure_check")
 
 
 def _run(checker, tmp_path, probs):
@@ -26,11 +23,7 @@ def _run(checker, tmp_path, probs):
         f = str(tmp_path / ("w%d.vbap" % i))
         abi.save_problem(f, p)
         files.append(f)
-    r = subprocess.run([checker] + files, capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"), timeout=300)
-    assert r.returncode == 0 and "ERROR" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-2000:]
-    lines = r.stdout.strip().splitlines()
-    assert len(lines) == len(probs)
-    return lines
+    return hc.run(checker, files, len(probs))
 
 
 def _shuffle(p, seed):

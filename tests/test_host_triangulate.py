@@ -2,52 +2,20 @@
 block-to-pair map, packing, write-back) under AddressSanitizer + UBSan (CPU only).  The harness (tests/host_triangulate_check.cpp)
 packs into heap blocks of exactly the arena's sizes; every expected offset below is restated from the sizes alone, and the packed
 regions are compared with the interleaving done in NumPy through an order-sensitive checksum."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 from mc_slam_amd import synth
+import host_check_lib as hc
+from host_check_lib import checksum, up
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DESC = np.dtype([("match0", "<i8"), ("lev0", "<i8"), ("i", "<i4", 4), ("c", "<f8", 41)])
 NT = 256
 
 
 @pytest.fixture(scope="module")
 def checker(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("ht") / "host_triangulate_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-pthread", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           "-fno-omit-frame-pointer", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "host_triangulate_check.cpp"),
-                           "-o", exe])
-    return exe
-
-
-def _run(checker, files):
-    r = subprocess.run([checker] + files, capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"), timeout=300)
-    assert r.returncode == 0 and "ERROR" not in r.stderr and "runtime error" not in r.stderr, (r.stdout[-500:], r.stderr[-2000:])
-    lines = r.stdout.strip().splitlines()
-    assert len(lines) == len(files), lines
-    return lines
-
-
-def _fields(line):
-    assert line.startswith("ok "), line
-    t = line.split()
-    return {k: int(v) for k, v in zip(t[1::2], t[2::2])}
-
-
-def up(b):
-    return (b + 255) // 256 * 256
-
-
-def checksum(*arrays):
-    """sum of (2 i + 1) * word i over the 64-bit words of the arrays' bytes (padded with zeros to whole words), mod 2^64"""
-    b = b"".join(np.ascontiguousarray(a).tobytes() for a in arrays)
-    w = np.frombuffer(b + b"\0" * (-len(b) % 8), dtype="<u8")
-    with np.errstate(over="ignore"):
-        return int((w * (2 * np.arange(len(w), dtype=np.uint64) + 1)).sum(dtype=np.uint64))
+    return hc.build(tmp_path_factory, "host_triangulate_check", pthread=True)
 
 
 def consts(p):
@@ -91,8 +59,8 @@ def test_offsets_packing_block_map_and_write_back(checker, tmp_path):
     for k, ps in enumerate(batches):
         files.append(str(tmp_path / ("b%d.tr" % k)))
         _write(files[-1], [(p, {}) for p in ps])
-    for ps, line in zip(batches, _run(checker, files)):
-        f = _fields(line)
+    for ps, line in zip(batches, hc.run(checker, files, len(files))):
+        f = hc.fields(line)
         n, n_tot = len(ps), sum(p.n_matches for p in ps)
         l_tot = sum(2 * (p.n_levels1 + p.n_levels2) for p in ps)
         n_blocks = sum((p.n_matches + NT - 1) // NT for p in ps)
@@ -103,6 +71,7 @@ def test_offsets_packing_block_map_and_write_back(checker, tmp_path):
             offs.append(o)
             o += up(b)
         assert [f[k] for k in ("desc", "blk", "lev", "uv", "oct", "x3d", "reason")] == offs
+        hc.assert_bound(f, [(k, k) for k in ("desc", "blk", "lev", "uv", "oct", "x3d", "reason")])   # TriBatch reads every region where it is
         assert f["upload"] == offs[5] and f["back"] == o - offs[5] and f["total"] == o
         # the packed regions
         d = np.zeros(n, dtype=DESC)
@@ -180,7 +149,7 @@ def test_refusals(checker, tmp_path, change, message):
         bad = bad.copy(**change["copy"])
     path = str(tmp_path / "r.tr")
     _write(path, [(good, {}), (bad, o)])
-    assert _run(checker, [path]) == ["error " + message]
+    assert hc.run(checker, [path], 1) == ["error " + message]
 
 
 def test_legal_edges(checker, tmp_path):
@@ -190,5 +159,5 @@ def test_legal_edges(checker, tmp_path):
     b = synth.make_triangulate(8, 5).copy(level_sigma2_1=s * s, scale_1=s, oct1=np.array([63, 0, 1, 63, 7], dtype=np.uint8))
     path = str(tmp_path / "e.tr")
     _write(path, [(a, dict(nulls=1 | 2 | 32)), (b, {})])
-    f = _fields(_run(checker, [path])[0])
+    f = hc.fields(hc.run(checker, [path], 1)[0])
     assert (f["n_tot"], f["n_blocks"], f["l_tot"]) == (5, 1, 2 * 16 + 2 * 72)

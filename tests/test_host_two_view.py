@@ -2,52 +2,20 @@
 write-back) under AddressSanitizer + UBSan (CPU only).  The harness (tests/host_two_view_check.cpp) is a stand-alone program: it
 packs into heap blocks of exactly the arena's sizes; every expected offset below is restated from the sizes alone, and the packed
 regions are compared with NumPy's concatenation through an order-sensitive checksum."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 from mc_slam_amd import synth
+import host_check_lib as hc
+from host_check_lib import checksum, up
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DESC = np.dtype([("off", "<i8", 4), ("i", "<i4", 6), ("c", "<f8", 6)])
 OUT_BYTES = 400
 
 
 @pytest.fixture(scope="module")
 def checker(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("htv") / "host_two_view_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-pthread", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           "-fno-omit-frame-pointer", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "host_two_view_check.cpp"),
-                           "-o", exe])
-    return exe
-
-
-def _run(checker, files):
-    r = subprocess.run([checker] + files, capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"), timeout=300)
-    assert r.returncode == 0 and "ERROR" not in r.stderr and "runtime error" not in r.stderr, (r.stdout[-500:], r.stderr[-2000:])
-    lines = r.stdout.strip().splitlines()
-    assert len(lines) == len(files), lines
-    return lines
-
-
-def _fields(line):
-    assert line.startswith("ok "), line
-    t = line.split()
-    return {k: float(v) if "." in v else int(v) for k, v in zip(t[1::2], t[2::2])}
-
-
-def up(b):
-    return (b + 255) // 256 * 256
-
-
-def checksum(*arrays):
-    """sum of (2 i + 1) * word i over the 64-bit words of the arrays' bytes (padded with zeros to whole words), mod 2^64"""
-    b = b"".join(np.ascontiguousarray(a).tobytes() for a in arrays)
-    w = np.frombuffer(b + b"\0" * (-len(b) % 8), dtype="<u8")
-    with np.errstate(over="ignore"):
-        return int((w * (2 * np.arange(len(w), dtype=np.uint64) + 1)).sum(dtype=np.uint64))
+    return hc.build(tmp_path_factory, "host_two_view_check", pthread=True)
 
 
 def _write(path, items):
@@ -86,8 +54,8 @@ def test_offsets_packing_and_write_back(checker, tmp_path, nulls):
     for k, ps in enumerate(batches):
         files.append(str(tmp_path / ("b%d.tv" % k)))
         _write(files[-1], [(p, dict(nulls=nulls)) for p in ps])
-    for ps, line in zip(batches, _run(checker, files)):
-        f = _fields(line)
+    for ps, line in zip(batches, hc.run(checker, files, len(files))):
+        f = hc.fields(line, floats=("got_mat",))
         n = len(ps)
         k1, k2, m, h = (sum(getattr(p, a) for p in ps) for a in ("n_keys1", "n_keys2", "n_matches", "n_hyp"))
         assert (f["k1"], f["k2"], f["m"], f["h"], f["want"]) == (k1, k2, m, h, int(nulls == 0))
@@ -100,6 +68,7 @@ def test_offsets_packing_and_write_back(checker, tmp_path, nulls):
             o += up(b)
         names = ("desc", "uv1", "uv2", "match", "sets", "out", "flag_h", "flag_f", "tri", "x3d", "score_h", "score_f", "hyp_h", "hyp_f", "rt_state", "rt_cos", "rt_x")
         assert [f[k] for k in names] == offs
+        hc.assert_bound(f, [(k, k) for k in names])   # TvBatch reads every region where it is
         assert f["upload"] == offs[5] and f["back"] == offs[12] - offs[5] and f["total"] == o
         assert f["down"] == (f["back"] if nulls == 0 else offs[10] - offs[5])       # the score regions stay on the device unless asked for
         # the packed regions
@@ -193,7 +162,7 @@ def test_refusals(checker, tmp_path, change, message):
         bad = bad.copy(**change["copy"])
     path = str(tmp_path / "r.tv")
     _write(path, [(good, {}), (bad, o)])
-    assert _run(checker, [path]) == ["error " + message]
+    assert hc.run(checker, [path], 1) == ["error " + message]
 
 
 def test_legal_edges(checker, tmp_path):
@@ -204,5 +173,5 @@ def test_legal_edges(checker, tmp_path):
     e = a.copy(uv1=np.zeros((0, 2)), uv2=np.zeros((0, 2)))
     path = str(tmp_path / "e.tv")
     _write(path, [(a, dict(nulls=2 | 64 | 1024 | 8 | 128)), (b, dict(nulls=8)), (c, {}), (e, dict(nulls=1 | 2 | 8 | 32 | 64 | 128 | 256 | 512 | 1024))])
-    f = _fields(_run(checker, [path])[0])
+    f = hc.fields(hc.run(checker, [path], 1)[0], floats=("got_mat",))
     assert (f["k1"], f["m"], f["h"]) == (a.n_keys1 + b.n_keys1 + c.n_keys1, 13, 0)
