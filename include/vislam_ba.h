@@ -123,7 +123,7 @@ typedef struct vba_profile {
     double total_ms;             /* first launch -> last launch of the run */
     double factor_flops;         /* FP64 flop the factorisation class executed on MFMA: 2*32^3 per tile product of the
                                     symbolic tile lists, per solve (structurally zero tiles are never touched) */
-    int64_t kernel_launches;     /* kernel launches the last vba_batch_run / vba_solve / vba_sim3_optimize / vba_sim3_ransac / vba_triangulate / vba_two_view_init (at most 2) / vba_search_triangulation / vba_fuse / vba_posegraph_optimize enqueued (filled with or without profiling) */
+    int64_t kernel_launches;     /* kernel launches the last vba_batch_run / vba_solve / vba_sim3_optimize / vba_sim3_ransac / vba_triangulate / vba_two_view_init (at most 2) / vba_search_triangulation / vba_fuse / vba_search_by_sim3 / vba_posegraph_optimize enqueued (filled with or without profiling) */
 } vba_profile;
 
 /* One handle per host thread / GPU; owns device buffers and a stream.  Errors: nonzero return, message
@@ -178,7 +178,7 @@ int vba_batch_solve_b(void *handle, int32_t n_windows, vba_problem *const *inout
  *           every later one, those submitted afterwards included, with the same message: no GPU work starts for them (earlier
  *           tickets finish).  Waiting on an unknown or retired ticket returns -1.
  *   handle  while any ticket is submitted and not yet waited for, every synchronous entry point of the handle (vba_solve*,
- *           vba_batch_upload / run / download / solve*, vba_pose_optimize, vba_sim3_optimize, vba_sim3_ransac, vba_triangulate, vba_two_view_init, vba_search_triangulation, vba_fuse, vba_posegraph_optimize, vba_preintegrate, vba_set_profile,
+ *           vba_batch_upload / run / download / solve*, vba_pose_optimize, vba_sim3_optimize, vba_sim3_ransac, vba_triangulate, vba_two_view_init, vba_search_triangulation, vba_fuse, vba_search_by_sim3, vba_posegraph_optimize, vba_preintegrate, vba_set_profile,
  *           vba_batch_set_depth) returns -1 with "asynchronous batches pending: wait for them first"; afterwards the handle
  *           works synchronously as before.  vba_destroy finishes pending tickets (their results land) before it frees.
  *           Profiling (vba_set_profile) covers synchronous calls only.  One caller thread at a time, as everywhere. */
@@ -601,6 +601,101 @@ typedef struct vba_fuse_result {
  * non-finite pose, intrinsic, bound, pixel, level table, position, normal, distance or threshold.  A problem's outputs do not depend
  * on where it stands in the batch. */
 int vba_fuse(void *handle, int32_t n_problems, vba_fuse_problem *const *in, vba_fuse_result *const *out);
+
+/* ---- Sim3 projection matching for loop candidates ----
+ * ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) (src/ORBmatcher.cpp:1258-1496) with
+ * KeyFrame::GetFeaturesInArea (src/KeyFrame.cpp:1071-1115), IsInImage (:1119-1122) and MapPoint::PredictScale
+ * (src/MapPoint.cpp:529-540), monocular: the call LoopClosing::ComputeSim3 makes between Sim3Solver::iterate (vba_sim3_ransac) and
+ * Optimizer::OptimizeSim3 (vba_sim3_optimize) (src/LoopClosing.cpp:390).  One problem is one keyframe pair with its Sim3; one call
+ * takes any number of pairs, ragged, in one kernel launch (256 queries per workgroup).  Both projection searches (:1310-1392 and
+ * :1398-1475) read static data only, so every keypoint that has a usable map point and no prior match is an independent query; the
+ * agreement loop (:1480-1493) runs on the host in the write-back.  The reference is restated as it stands, direction 1 (keyframe 1
+ * into keyframe 2) with the line numbers below, direction 2 alike with the sides exchanged:
+ *   transform   p3Dc1 = R1w p + t1w, p3Dc2 = sR21 p3Dc1 + t21 (:1321-1322), with sR12 = s12 R12, sR21 = (1 / s12) R12^T and
+ *               t21 = -sR21 t12 formed once per pair on the host in the order :1277-1279 write them
+ *   gates       z < 0 leaves (:1325); z == 0 passes, u and v are infinite or NaN and the point leaves at IsInImage of the TARGET
+ *               keyframe, written as the positive conjunction u >= minX && u < maxX && v >= minY && v < maxY (:1337).  The
+ *               projection uses K of pKF1 in BOTH directions, as the reference does (:1262-1265, :1333, :1420).
+ *               dist3D = |p3Dc2| outside [dist_min, dist_max] (:1345),
+ *               nPredictedLevel = ceil(log(pred_max / dist3D) / log_scale_factor of the target) outside 0 .. n_levels - 1 of the target
+ *   area        GetFeaturesInArea(u, v, th * scale[level]) of the target literally: floor for the first cell and CEIL for the last
+ *               one, the four early returns, the clamps to the grid, fabs(dx) < r && fabs(dy) < r.  Candidates come in cell order
+ *               (ix outer, iy inner) and inside a cell in list order
+ *   candidate   skipped when kpLevel < nPredictedLevel - 1 || kpLevel > nPredictedLevel (:1374), nothing else: there is no
+ *               viewing-angle gate and no reprojection gate here.  dist < bestDist is strict (:1381), so among equal distances the
+ *               first in walk order wins.  Target keypoints are never filtered by has_pt or matched
+ * One deviation: the reference reads mvScaleFactors[nPredictedLevel] unchecked (:1354, :1439) and PredictScale does not clamp, so it
+ * can read outside the vector.  vba_search_by_sim3 leaves with state 6 instead, as vba_fuse does.
+ * `state` says where a keypoint left its loop, numbered in the order of the reference's exits, the same in both directions:
+ *   0  bestDist <= th_high (:1388): match holds bestIdx
+ *   1  no usable point (has_pt == 0: !pMP or pMP->isBad(), :1314-1318)
+ *   2  already matched (:1314)
+ *   3  z < 0 (:1325)
+ *   4  not in the image of the target keyframe (:1337)
+ *   5  dist3D outside [dist_min, dist_max] (:1345)
+ *   6  predicted level outside 0 .. n_levels - 1 of the target (the deviation)
+ *   7  no keypoint in the area (:1359)
+ *   8  keypoints in the area but none at or under th_high; best_dist is what the loop left (256 when every candidate failed the
+ *      level test)
+ * All floating point is FP64 on the float32 inputs widened; the reference computes in float32 (gives
+ * the measured difference).  No floating-point value is returned. */
+typedef struct vba_search_sim3_kf {
+    double Rcw[9], tcw[3];           /* row-major GetRotation(), GetTranslation() */
+    double bounds[4];                /* mnMinX mnMaxX mnMinY mnMaxY */
+    int32_t n_keys;                  /* N = GetMapPointMatches().size() */
+    int32_t n_levels;                /* mnScaleLevels, 1 .. 64 */
+    const uint8_t *desc;             /* [n_keys][32] mDescriptors */
+    const double *uv;                /* [n_keys][2] mvKeysUn[idx].pt */
+    const uint8_t *oct;              /* [n_keys] mvKeysUn[idx].octave */
+    const double *scale;             /* [n_levels] mvScaleFactors (:1354) */
+    double log_scale_factor;         /* mfLogScaleFactor */
+    int32_t grid_cols, grid_rows;    /* mnGridCols, mnGridRows; >= 1, cols * rows <= 65536 */
+    double grid_inv_w, grid_inv_h;   /* mfGridElementWidthInv, mfGridElementHeightInv */
+    const int32_t *cell_begin;       /* [cols * rows + 1] as in vba_fuse_problem */
+    const int32_t *cell_feat;        /* keypoint indices in the order mGrid[ix][iy] holds them; each keypoint at most once */
+    /* the keyframe's own map points, GetMapPointMatches(), per keypoint */
+    const uint8_t *has_pt;           /* [n_keys] non-zero: pMP && !pMP->isBad() */
+    const uint8_t *matched;          /* [n_keys] non-zero: vbAlreadyMatched1 (kf1) / vbAlreadyMatched2 (kf2), built as :1291-1301 do,
+                                        GetIndexInKeyFrame included */
+    const double *pos;               /* [n_keys][3] GetWorldPos(); read only where has_pt */
+    const double *dist_min, *dist_max; /* [n_keys] GetMinDistanceInvariance(), GetMaxDistanceInvariance(); read only where has_pt */
+    const double *pred_max;          /* [n_keys] mfMaxDistance, which PredictScale reads; read only where has_pt */
+    const uint8_t *pt_desc;          /* [n_keys][32] GetDescriptor(); read only where has_pt */
+} vba_search_sim3_kf;
+
+typedef struct vba_search_sim3_problem {
+    vba_search_sim3_kf kf1, kf2;
+    double K[4];                     /* fx fy cx cy of pKF1, used in both directions */
+    double s12, R12[9], t12[3];      /* the Sim3: s12 finite and positive, R12 row-major */
+    double th;                       /* the radius factor, 7.5 at the call site */
+    int32_t th_high;                 /* TH_HIGH = 100 (:1388); 0 .. 256 */
+} vba_search_sim3_problem;
+
+typedef struct vba_search_sim3_result {
+    int32_t status;           /* VBA_OK */
+    int32_t n_found;          /* nFound of :1478-1493 (counted on the host) */
+    int32_t *match1;          /* [kf1.n_keys] caller-allocated: vnMatch1, a keypoint of keyframe 2 or -1 */
+    int32_t *match2;          /* [kf2.n_keys] caller-allocated: vnMatch2, a keypoint of keyframe 1 or -1 */
+    uint16_t *best_dist1;     /* [kf1.n_keys] caller-allocated: bestDist; 256 where the loop left INT_MAX or was not reached */
+    uint16_t *best_dist2;     /* [kf2.n_keys] */
+    int8_t *level1;           /* [kf1.n_keys] caller-allocated: nPredictedLevel for the states 0, 7 and 8, the out-of-range value itself
+                                 clamped to int8 for state 6, -128 otherwise */
+    int8_t *level2;           /* [kf2.n_keys] */
+    uint8_t *state1;          /* [kf1.n_keys] caller-allocated: the codes above */
+    uint8_t *state2;          /* [kf2.n_keys] */
+    int32_t *match12;         /* [kf1.n_keys] caller-allocated: the keypoint of keyframe 2 both directions agree on (:1480-1493) or -1; the
+                                 caller does vpMatches12[i1] = vpMapPoints2[match12[i1]] */
+} vba_search_sim3_result;
+
+/* Synchronous, like vba_fuse; -1 while asynchronous tickets are pending.  n_pairs == 0 returns 0; n_keys == 0 on either side is
+ * legal.  A bad pair fails the whole call before any GPU work, with nothing written, as "vba_search_by_sim3: pair K: <why>" through
+ * vba_last_error: a NULL problem or result; for either side ("keyframe 1: ..." / "keyframe 2: ...") everything vba_fuse refuses for
+ * its keyframe (a negative count, a NULL array with a non-zero count -- the result arrays of a side are required when its n_keys
+ * > 0 --, n_levels outside 1 .. 64, an octave >= n_levels, grid sizes outside their range, a cell_begin that does not start at 0,
+ * decreases or ends above n_keys, a cell_feat entry out of range or listed twice, a non-finite pose, bound, cell size, pixel or level
+ * table) and a non-finite position or distance where has_pt is set; s12 not finite or not positive; a non-finite R12, t12, K or th;
+ * th_high outside 0 .. 256.  A pair's outputs do not depend on where it stands in the batch. */
+int vba_search_by_sim3(void *handle, int32_t n_pairs, vba_search_sim3_problem *const *in, vba_search_sim3_result *const *out);
 
 /* ---- essential-graph optimisation (Sim3 pose graph) ----
  * Optimizer::OptimizeEssentialGraph(Map*, KeyFrame* pLoopKF, KeyFrame* pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections,

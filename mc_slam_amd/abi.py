@@ -1097,6 +1097,168 @@ class FuseResultBuf:
         return FuseResult(self.s.status, self.s.n_found, self.bi[:n].copy(), self.bd[:n].copy(), self.lv[:n].copy(), self.uv[:n].copy(), self.st[:n].copy())
 
 
+# ---- Sim3 projection matching (include/vislam_ba.h: vba_search_sim3_problem / vba_search_sim3_result) ----
+class vba_search_sim3_kf(C.Structure):
+    _fields_ = [
+        ("Rcw", C.c_double * 9), ("tcw", C.c_double * 3), ("bounds", C.c_double * 4), ("n_keys", C.c_int32), ("n_levels", C.c_int32),
+        ("desc", _pu8), ("uv", _pd), ("oct", _pu8), ("scale", _pd), ("log_scale_factor", C.c_double), ("grid_cols", C.c_int32),
+        ("grid_rows", C.c_int32), ("grid_inv_w", C.c_double), ("grid_inv_h", C.c_double), ("cell_begin", _pi), ("cell_feat", _pi),
+        ("has_pt", _pu8), ("matched", _pu8), ("pos", _pd), ("dist_min", _pd), ("dist_max", _pd), ("pred_max", _pd), ("pt_desc", _pu8),
+    ]
+
+
+class vba_search_sim3_problem(C.Structure):
+    _fields_ = [("kf1", vba_search_sim3_kf), ("kf2", vba_search_sim3_kf), ("K", C.c_double * 4), ("s12", C.c_double), ("R12", C.c_double * 9),
+                ("t12", C.c_double * 3), ("th", C.c_double), ("th_high", C.c_int32)]
+
+
+class vba_search_sim3_result(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_found", C.c_int32), ("match1", _pi), ("match2", _pi), ("best_dist1", _pu16), ("best_dist2", _pu16),
+                ("level1", _pi8), ("level2", _pi8), ("state1", _pu8), ("state2", _pu8), ("match12", _pi)]
+
+
+(SS_FOUND, SS_NO_POINT, SS_MATCHED, SS_BEHIND, SS_NOT_IN_IMAGE, SS_DISTANCE, SS_LEVEL, SS_EMPTY_AREA, SS_NO_MATCH) = range(9)
+
+
+@dataclass
+class SearchSim3KF:
+    """One keyframe of a SearchBySim3 call as flat arrays: as a search target (pose, bounds, keypoints, scale table, grid in CSR
+    form) and as a source (its own map points, per keypoint)."""
+    Rcw: np.ndarray                # [3,3]
+    tcw: np.ndarray                # [3]
+    bounds: np.ndarray             # [4] mnMinX mnMaxX mnMinY mnMaxY
+    desc: np.ndarray               # [n_keys,32] uint8
+    uv: np.ndarray                 # [n_keys,2]
+    oct: np.ndarray                # [n_keys] uint8
+    scale: np.ndarray              # [n_levels]
+    log_scale_factor: float
+    grid_cols: int
+    grid_rows: int
+    grid_inv_w: float
+    grid_inv_h: float
+    cell_begin: np.ndarray         # [cols * rows + 1] int32
+    cell_feat: np.ndarray          # int32
+    has_pt: np.ndarray             # [n_keys] uint8
+    matched: np.ndarray            # [n_keys] uint8
+    pos: np.ndarray                # [n_keys,3]
+    dist_min: np.ndarray           # [n_keys]
+    dist_max: np.ndarray           # [n_keys]
+    pred_max: np.ndarray           # [n_keys]
+    pt_desc: np.ndarray            # [n_keys,32] uint8
+
+    def __post_init__(self):
+        u8 = lambda a, shape: np.ascontiguousarray(a, dtype=np.uint8).reshape(shape)
+        self.Rcw = _f64(self.Rcw, (3, 3)); self.tcw = _f64(self.tcw, (3,)); self.bounds = _f64(self.bounds, (4,))
+        self.desc = u8(self.desc, (-1, 32)); self.oct = u8(self.oct, (-1,)); self.uv = _f64(self.uv, (-1, 2))
+        self.scale = _f64(self.scale, (-1,))
+        self.cell_begin = _i32(self.cell_begin).reshape(-1); self.cell_feat = _i32(self.cell_feat).reshape(-1)
+        self.has_pt = u8(self.has_pt, (-1,)); self.matched = u8(self.matched, (-1,))
+        self.pos = _f64(self.pos, (-1, 3))
+        self.dist_min = _f64(self.dist_min, (-1,)); self.dist_max = _f64(self.dist_max, (-1,)); self.pred_max = _f64(self.pred_max, (-1,))
+        self.pt_desc = u8(self.pt_desc, (-1, 32))
+
+    n_keys = property(lambda self: self.desc.shape[0])
+    n_levels = property(lambda self: self.scale.shape[0])
+
+    def copy(self, **changes):
+        import copy as _c
+        q = _c.copy(self)
+        for k, v in changes.items():
+            setattr(q, k, v)
+        q.__post_init__()
+        return q
+
+    def fill(self, s: vba_search_sim3_kf):
+        p = lambda a, t: a.ctypes.data_as(t)
+        s.Rcw[:] = self.Rcw.ravel().tolist(); s.tcw[:] = self.tcw.tolist(); s.bounds[:] = self.bounds.tolist()
+        s.n_keys, s.n_levels = self.n_keys, self.n_levels
+        s.desc, s.uv, s.oct, s.scale = p(self.desc, _pu8), p(self.uv, _pd), p(self.oct, _pu8), p(self.scale, _pd)
+        s.log_scale_factor = float(self.log_scale_factor)
+        s.grid_cols, s.grid_rows, s.grid_inv_w, s.grid_inv_h = int(self.grid_cols), int(self.grid_rows), float(self.grid_inv_w), float(self.grid_inv_h)
+        s.cell_begin, s.cell_feat = p(self.cell_begin, _pi), p(self.cell_feat, _pi)
+        s.has_pt, s.matched, s.pos = p(self.has_pt, _pu8), p(self.matched, _pu8), p(self.pos, _pd)
+        s.dist_min, s.dist_max, s.pred_max, s.pt_desc = p(self.dist_min, _pd), p(self.dist_max, _pd), p(self.pred_max, _pd), p(self.pt_desc, _pu8)
+
+
+@dataclass
+class SearchSim3Problem:
+    """One ORBmatcher::SearchBySim3 call (src/ORBmatcher.cpp:1258-1496): two keyframes and the Sim3 between them."""
+    kf1: SearchSim3KF
+    kf2: SearchSim3KF
+    K: np.ndarray                  # [4] fx fy cx cy of keyframe 1
+    s12: float
+    R12: np.ndarray                # [3,3]
+    t12: np.ndarray                # [3]
+    th: float = 7.5
+    th_high: int = 100
+    truth: dict = field(default_factory=dict)
+
+    def __post_init__(self):
+        self.K = _f64(self.K, (4,)); self.R12 = _f64(self.R12, (3, 3)); self.t12 = _f64(self.t12, (3,))
+
+    def copy(self, **changes):
+        """a copy with fields replaced; kf1 / kf2 take a SearchSim3KF or a dict of changes to the keyframe"""
+        import copy as _c
+        q = _c.copy(self)
+        for k, v in changes.items():
+            setattr(q, k, getattr(self, k).copy(**v) if k in ("kf1", "kf2") and isinstance(v, dict) else v)
+        q.__post_init__()
+        return q
+
+    def as_struct(self) -> vba_search_sim3_problem:
+        s = vba_search_sim3_problem()
+        self.kf1.fill(s.kf1); self.kf2.fill(s.kf2)
+        s.K[:] = self.K.tolist(); s.R12[:] = self.R12.ravel().tolist(); s.t12[:] = self.t12.tolist()
+        s.s12, s.th, s.th_high = float(self.s12), float(self.th), int(self.th_high)
+        return s
+
+
+@dataclass
+class SearchSim3Result:
+    status: int
+    n_found: int
+    match1: np.ndarray              # [n_keys1] int32
+    match2: np.ndarray              # [n_keys2] int32
+    best_dist1: np.ndarray          # uint16
+    best_dist2: np.ndarray
+    level1: np.ndarray              # int8
+    level2: np.ndarray
+    state1: np.ndarray              # uint8
+    state2: np.ndarray
+    match12: np.ndarray             # [n_keys1] int32
+
+
+class SearchSim3ResultBuf:
+    """Caller-allocated result storage of one pair."""
+
+    def __init__(self, p: SearchSim3Problem):
+        self.n = (p.kf1.n_keys, p.kf2.n_keys)
+        m = [max(k, 1) for k in self.n]
+        self.ma = [np.full(k, -7, dtype=np.int32) for k in m]
+        self.bd = [np.full(k, 7, dtype=np.uint16) for k in m]
+        self.lv = [np.full(k, 77, dtype=np.int8) for k in m]
+        self.st = [np.full(k, 255, dtype=np.uint8) for k in m]
+        self.m12 = np.full(m[0], -7, dtype=np.int32)
+        s = self.s = vba_search_sim3_result()
+        s.status, s.n_found = -7, -7
+        s.match1, s.match2 = (a.ctypes.data_as(_pi) for a in self.ma)
+        s.best_dist1, s.best_dist2 = (a.ctypes.data_as(_pu16) for a in self.bd)
+        s.level1, s.level2 = (a.ctypes.data_as(_pi8) for a in self.lv)
+        s.state1, s.state2 = (a.ctypes.data_as(_pu8) for a in self.st)
+        s.match12 = self.m12.ctypes.data_as(_pi)
+
+    def untouched(self):
+        """nothing was written since construction"""
+        return (self.s.status == -7 and self.s.n_found == -7 and (self.m12 == -7).all() and all((a == -7).all() for a in self.ma) and
+                all((a == 7).all() for a in self.bd) and all((a == 77).all() for a in self.lv) and all((a == 255).all() for a in self.st))
+
+    def get(self) -> SearchSim3Result:
+        n1, n2 = self.n
+        return SearchSim3Result(self.s.status, self.s.n_found, self.ma[0][:n1].copy(), self.ma[1][:n2].copy(), self.bd[0][:n1].copy(),
+                                self.bd[1][:n2].copy(), self.lv[0][:n1].copy(), self.lv[1][:n2].copy(), self.st[0][:n1].copy(),
+                                self.st[1][:n2].copy(), self.m12[:n1].copy())
+
+
 # ---- essential-graph optimisation (include/vislam_ba.h: vba_posegraph_problem / vba_posegraph_result) ----
 class vba_posegraph_problem(C.Structure):
     _fields_ = [

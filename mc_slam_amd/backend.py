@@ -19,7 +19,8 @@ _libs = {}
 EXPORTS = ["vba_create", "vba_destroy", "vba_last_error", "vba_solve", "vba_batch_upload", "vba_batch_run",
            "vba_batch_download", "vba_batch_solve", "vba_solve_b", "vba_batch_run_b", "vba_batch_solve_b", "vba_preintegrate", "vba_pose_optimize", "vba_problem_save", "vba_problem_load", "vba_problem_free", "vba_set_profile", "vba_get_profile", "vba_host_threads",
            "vba_batch_set_depth", "vba_batch_submit", "vba_batch_submit_b", "vba_batch_poll", "vba_batch_wait", "vba_sim3_optimize",
-           "vba_posegraph_optimize", "vba_sim3_ransac", "vba_triangulate", "vba_two_view_init", "vba_search_triangulation", "vba_fuse"]
+           "vba_posegraph_optimize", "vba_sim3_ransac", "vba_triangulate", "vba_two_view_init", "vba_search_triangulation", "vba_fuse",
+           "vba_search_by_sim3"]
 
 # The small-problem entry points, all of the shape fn(handle, n, problems, results).  kind -> (library function, problem struct,
 # result struct, result buffer of one problem -- called with the problem and the extra arguments of its pack --, whether the call
@@ -32,6 +33,7 @@ _SMALL = {
     "two_view": ("vba_two_view_init", abi.vba_two_view_problem, abi.vba_two_view_result, abi.TwoViewResultBuf, False),
     "search_triangulation": ("vba_search_triangulation", abi.vba_search_tri_problem, abi.vba_search_tri_result, abi.SearchTriResultBuf, False),
     "fuse": ("vba_fuse", abi.vba_fuse_problem, abi.vba_fuse_result, abi.FuseResultBuf, False),
+    "search_by_sim3": ("vba_search_by_sim3", abi.vba_search_sim3_problem, abi.vba_search_sim3_result, abi.SearchSim3ResultBuf, False),
     "posegraph": ("vba_posegraph_optimize", abi.vba_posegraph_problem, abi.vba_posegraph_result, lambda p: abi.vba_posegraph_result(), True),
 }
 
@@ -368,6 +370,19 @@ class LocalBA:
         """vba_fuse on a list of abi.FuseProblem: list of abi.FuseResult"""
         packed = self.fuse_pack(problems)
         self.fuse_call(packed)
+        return [b.get() for b in packed[2]]
+
+    # Sim3 projection matching for loop candidates (vba_search_by_sim3): abi.SearchSim3Problem, one keyframe pair each
+    def search_by_sim3_pack(self, problems):
+        return self._small_pack("search_by_sim3", problems)
+
+    def search_by_sim3_call(self, packed):
+        self._small_call("search_by_sim3", packed)
+
+    def search_by_sim3(self, problems):
+        """vba_search_by_sim3 on a list of abi.SearchSim3Problem: list of abi.SearchSim3Result"""
+        packed = self.search_by_sim3_pack(problems)
+        self.search_by_sim3_call(packed)
         return [b.get() for b in packed[2]]
 
     # essential-graph optimisation (vba_posegraph_optimize): abi.PoseGraphProblem, independent Sim3 pose graphs.  The call updates

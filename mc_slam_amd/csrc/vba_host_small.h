@@ -1,5 +1,5 @@
 // vba_host_small.h -- host side of the library, part 5: the small-problem entry points.  vba_preintegrate copies straight from and
-// to the caller's arrays.  The other eight are one driver, run_small, over the call object of their topic (PoseCall, Sim3Call, ...:
+// to the caller's arrays.  The other nine are one driver, run_small, over the call object of their topic (PoseCall, Sim3Call, ...:
 // plain C++, vba_host_<topic>.h), which knows what is refused, the arena, the packing, the kernel's argument and the write-back;
 // what an entry point adds here is the launch of its kernel.  No entry point shares its arena (Handle::side) with another.
 #pragma once
@@ -10,6 +10,7 @@
 #include "vba_host_two_view.h"
 #include "vba_host_search_tri.h"
 #include "vba_host_fuse.h"
+#include "vba_host_search_sim3.h"
 #include "vba_host_posegraph.h"
 
 namespace {
@@ -138,6 +139,14 @@ int fuse(Handle* h, int32_t n_problems, vba_fuse_problem* const* in, vba_fuse_re
     vba_host::FuseCall C;
     return run_small(h, SIDE_FUSE, "vba_fuse", C, n_problems, in, out,
                      [h](const FuBatch& B, unsigned g) { VBA_LAUNCH(k_fuse, dim3(g), dim3(FU_NT), 0, h->stream, B); });
+}
+
+// Both projection searches of ORBmatcher::SearchBySim3 (src/ORBmatcher.cpp:1258-1496, monocular) for a batch of keyframe pairs; the
+// agreement loop runs in the write-back
+int search_by_sim3(Handle* h, int32_t n_pairs, vba_search_sim3_problem* const* in, vba_search_sim3_result* const* out) {
+    vba_host::SearchSim3Call C;
+    return run_small(h, SIDE_SEARCH_SIM3, "vba_search_by_sim3", C, n_pairs, in, out,
+                     [h](const SsBatch& B, unsigned g) { VBA_LAUNCH(k_search_sim3, dim3(g), dim3(SS_NT), 0, h->stream, B); });
 }
 
 // what vba_debug_posegraph_system asks of a run: graph 0 stops after the solve of its first trial, and H, b, x come back

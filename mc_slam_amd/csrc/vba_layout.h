@@ -315,6 +315,42 @@ struct FuBatch {
     double* uv;                  // [total points][2]
     unsigned char* state;        // [total points]
 };
+// vba_search_by_sim3 (vba_search_sim3.h); the target side of a direction reuses FuKey
+#define VBA_SS_NT 256          // lanes of a workgroup = most queries of a tile
+#define VBA_SS_CONST 36        // doubles of a direction's constants: R_src (9) t_src (3) sR (9) t (3) K (4) bounds of the target (4)
+                               // grid_inv_w grid_inv_h log_scale_factor of the target, th
+struct alignas(16) SsQuery {   // one keypoint of the source side with a usable, unmatched map point, 96 bytes
+    unsigned int d[8];         // GetDescriptor()
+    double pos[3];
+    double dist_min, dist_max, pred_max;
+    int idx;                   // the keypoint's index in its keyframe
+    int pad[3];
+};
+struct SsTile {                // one workgroup: the queries first .. first + 255 of direction dir (0: 1 -> 2, 1: 2 -> 1) of pair
+    int pair, dir, first, pad;
+};
+struct SsDir {                 // one direction of one pair, at [2 * pair + dir]
+    long long q0, key0, cell0, feat0, lev0;   // offsets of its query records (and outputs) and of the TARGET's keypoint records, cell_begin
+                                              // copy, cell_feat copy and scale table in the concatenated arrays
+    int n_q, n_keys, n_levels, th_high;       // n_keys, n_levels, cols, rows: the target's
+    int cols, rows, pad[2];
+    double c[VBA_SS_CONST];
+};
+static_assert(sizeof(SsQuery) == 96 && sizeof(SsTile) == 16 && sizeof(SsDir) == 360,
+              "scripts/search_sim3_bench.py derives the copied bytes from these sizes");
+struct SsBatch {
+    const SsDir* dir;            // [2 * pairs]
+    const SsTile* tile;          // [tiles]
+    const FuKey* key;            // keypoint records of all pairs: keyframe 1 of pair 0, keyframe 2 of pair 0, ...
+    const SsQuery* query;        // query records of all pairs: direction 0 of pair 0, direction 1 of pair 0, ...
+    const int* cell_begin;       // cell_begin of all keyframes
+    const int* cell_feat;        // cell_feat of all keyframes
+    const double* lev;           // scale tables of all keyframes
+    int* match;                  // [total queries]
+    unsigned short* best_dist;   // ...
+    signed char* level;          // ...
+    unsigned char* state;        // ...
+};
 // vba_posegraph_optimize (vba_posegraph.h)
 struct PgDesc {
     int nv, ne, nf, npair;

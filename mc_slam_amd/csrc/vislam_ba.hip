@@ -7,7 +7,7 @@
 //   small problems  vba_host_small.h: one driver over the plain-C++ call object of each topic (vba_host_<topic>.h).  Tracking:
 //                 vba_preintegrate, vba_pose_optimize.  Initialisation: vba_two_view_init.  Local mapping:
 //                 vba_search_triangulation (the matcher in front of) vba_triangulate, vba_fuse.  Loop closing: vba_sim3_ransac,
-//                 vba_sim3_optimize, vba_posegraph_optimize
+//                 vba_search_by_sim3, vba_sim3_optimize, vba_posegraph_optimize
 //   the rest      vba_host_hooks.h (vba_debug_*, hooks flavour), vba_host_threads, vba_set_profile / get_profile
 //
 // Host-side control flow restated from src/Optimizer.cpp:453-517 (two-stage protocol) and
@@ -27,6 +27,7 @@
 #include "vba_two_view.h"
 #include "vba_search_tri.h"
 #include "vba_fuse.h"
+#include "vba_search_sim3.h"
 #include "vba_posegraph.h"
 #include "vba_structure.h"
 #include "vba_pcg.h"
@@ -202,6 +203,10 @@ int vba_search_triangulation(void* handle, int32_t n_pairs, vba_search_tri_probl
 int vba_fuse(void* handle, int32_t n_problems, vba_fuse_problem* const* in, vba_fuse_result* const* out) {
     Handle* h = idle_handle(handle);
     return h ? fuse(h, n_problems, in, out) : -1;
+}
+int vba_search_by_sim3(void* handle, int32_t n_pairs, vba_search_sim3_problem* const* in, vba_search_sim3_result* const* out) {
+    Handle* h = idle_handle(handle);
+    return h ? search_by_sim3(h, n_pairs, in, out) : -1;
 }
 int vba_posegraph_optimize(void* handle, int32_t n_graphs, vba_posegraph_problem* const* inout, vba_posegraph_result* const* out) {
     Handle* h = idle_handle(handle);

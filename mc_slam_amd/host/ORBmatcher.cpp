@@ -2,7 +2,9 @@
 // keyframe pair as flat arrays (descriptors, map-point flags, the feature vectors in CSR form, keypoints, the level tables of
 // keyframe 2), the epipole in float32 as :768-775, ONE call, vMatchedPairs from the result.  And both ORBmatcher::Fuse overloads
 // (:958-1254, monocular) over vba_fuse: the keyframe with its grid in CSR form and the point list as flat arrays, ONE call for the
-// search, then the reference's apply loop in list order on the live map.
+// search, then the reference's apply loop in list order on the live map.  And ORBmatcher::SearchBySim3 (:1258-1496, monocular) over
+// vba_search_by_sim3: both keyframes as flat arrays with their own map points per keypoint, the vbAlreadyMatched flags of
+// :1291-1301, ONE call, vpMatches12 from the agreed matches.
 #include "ORBmatcher.h"
 
 #include <cstring>
@@ -283,6 +285,124 @@ int ORBmatcher::Fuse(KeyFrame* pKF, const Mat4f& Scw, const std::vector<MapPoint
         nFused++;
     }
     return nFused;
+}
+
+namespace {
+// one keyframe's side of a vba_search_sim3_problem: the keyframe as a search target and its own map points per keypoint
+struct Sim3Side {
+    std::vector<double> uv, scale, pos, dmin, dmax, pmax;
+    std::vector<uint8_t> oct, has_pt, pt_desc;
+    std::vector<int32_t> cell_begin, cell_feat;
+    bool fill(const char* who, KeyFrame* pKF, const std::vector<MapPoint*>& pts, const std::vector<uint8_t>& matched, vba_search_sim3_kf& S) {
+        const size_t nk = (size_t)pKF->N;
+        if (nk != pKF->mvKeysUn.size() || pKF->mDescriptors.size() != 32 * nk || pts.size() != nk || pKF->mvuRight.size() != nk) {
+            std::cerr << who << ": N, mvKeysUn, mvuRight, mvpMapPoints and mDescriptors of a keyframe disagree" << std::endl;
+            return false;
+        }
+        if (pKF->mnScaleLevels < 1 || pKF->mvScaleFactors.size() != (size_t)pKF->mnScaleLevels) {
+            std::cerr << who << ": mnScaleLevels and mvScaleFactors of a keyframe disagree" << std::endl;
+            return false;
+        }
+        if (pKF->mnGridCols < 1 || pKF->mnGridRows < 1 || pKF->mGrid.size() != (size_t)pKF->mnGridCols) {
+            std::cerr << who << ": a keyframe has no grid" << std::endl;
+            return false;
+        }
+        uv.resize(2 * nk); oct.resize(nk); has_pt.assign(nk, 0); pos.assign(3 * nk, 0.0); dmin.assign(nk, 0.0); dmax.assign(nk, 0.0); pmax.assign(nk, 0.0);
+        pt_desc.assign(32 * nk, 0);
+        for (size_t i = 0; i < nk; i++) {
+            const KeyPoint& kp = pKF->mvKeysUn[i];
+            if (pKF->mvuRight[i] >= 0) {
+                std::cerr << who << ": a keyframe has a stereo keypoint (the backend is monocular)" << std::endl;
+                return false;
+            }
+            if (kp.octave < 0 || kp.octave > 255) {   // the ABI carries octaves as uint8; the library checks them against n_levels
+                std::cerr << who << ": a keypoint's octave is outside 0 .. 255" << std::endl;
+                return false;
+            }
+            uv[2 * i] = kp.pt.x; uv[2 * i + 1] = kp.pt.y; oct[i] = (uint8_t)kp.octave;
+            MapPoint* pMP = pts[i];
+            if (!pMP || pMP->isBad()) continue;       // :1314-1318
+            has_pt[i] = 1;
+            pMP->GetWorldPos(&pos[3 * i]);
+            dmin[i] = pMP->GetMinDistanceInvariance(); dmax[i] = pMP->GetMaxDistanceInvariance(); pmax[i] = pMP->mfMaxDistance;
+            std::memcpy(&pt_desc[32 * i], pMP->GetDescriptor(), 32);
+        }
+        cell_begin.assign(1, 0);
+        for (int ix = 0; ix < pKF->mnGridCols; ix++)
+            for (int iy = 0; iy < pKF->mnGridRows; iy++) {
+                if (pKF->mGrid[(size_t)ix].size() != (size_t)pKF->mnGridRows) {
+                    std::cerr << who << ": a keyframe has no grid" << std::endl;
+                    return false;
+                }
+                for (size_t idx : pKF->mGrid[(size_t)ix][(size_t)iy]) cell_feat.push_back((int32_t)idx);
+                cell_begin.push_back((int32_t)cell_feat.size());
+            }
+        scale.assign(pKF->mvScaleFactors.begin(), pKF->mvScaleFactors.end());
+        pKF->GetRotation(S.Rcw); pKF->GetTranslation(S.tcw);
+        S.bounds[0] = pKF->mnMinX; S.bounds[1] = pKF->mnMaxX; S.bounds[2] = pKF->mnMinY; S.bounds[3] = pKF->mnMaxY;
+        S.n_keys = pKF->N; S.n_levels = pKF->mnScaleLevels;
+        S.desc = pKF->mDescriptors.data(); S.uv = uv.data(); S.oct = oct.data(); S.scale = scale.data();
+        S.log_scale_factor = pKF->mfLogScaleFactor;
+        S.grid_cols = pKF->mnGridCols; S.grid_rows = pKF->mnGridRows;
+        S.grid_inv_w = pKF->mfGridElementWidthInv; S.grid_inv_h = pKF->mfGridElementHeightInv;
+        S.cell_begin = cell_begin.data(); S.cell_feat = cell_feat.data();
+        S.has_pt = has_pt.data(); S.matched = matched.data(); S.pos = pos.data();
+        S.dist_min = dmin.data(); S.dist_max = dmax.data(); S.pred_max = pmax.data(); S.pt_desc = pt_desc.data();
+        return true;
+    }
+};
+}  // namespace
+
+void ORBmatcher::AlreadyMatched(KeyFrame* pKF1, KeyFrame* pKF2, const std::vector<MapPoint*>& vpMatches12, std::vector<uint8_t>& vb1,
+                                std::vector<uint8_t>& vb2) {
+    const int N1 = (int)pKF1->mvpMapPoints.size(), N2 = (int)pKF2->mvpMapPoints.size();
+    vb1.assign((size_t)N1, 0); vb2.assign((size_t)N2, 0);
+    for (int i = 0; i < N1 && i < (int)vpMatches12.size(); i++) {   // :1291-1301
+        MapPoint* pMP = vpMatches12[(size_t)i];
+        if (pMP) {
+            vb1[(size_t)i] = 1;
+            const int idx2 = pMP->GetIndexInKeyFrame(pKF2);
+            if (idx2 >= 0 && idx2 < N2) vb2[(size_t)idx2] = 1;
+        }
+    }
+}
+
+int ORBmatcher::SearchBySim3(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoint*>& vpMatches12, const float& s12, const Mat3f& R12,
+                             const std::array<float, 3>& t12, const float th) {
+    const char* who = "ORBmatcher::SearchBySim3";
+    const std::vector<MapPoint*> vpMapPoints1 = pKF1->GetMapPointMatches(), vpMapPoints2 = pKF2->GetMapPointMatches();
+    const size_t N1 = vpMapPoints1.size(), N2 = vpMapPoints2.size();
+    if (vpMatches12.size() != N1) {
+        std::cerr << who << ": vpMatches12 must have one entry per keypoint of pKF1" << std::endl;
+        return -1;
+    }
+    std::vector<uint8_t> vb1, vb2;
+    AlreadyMatched(pKF1, pKF2, vpMatches12, vb1, vb2);
+    vba_search_sim3_problem P{};
+    Sim3Side s1, s2;
+    if (!s1.fill(who, pKF1, vpMapPoints1, vb1, P.kf1) || !s2.fill(who, pKF2, vpMapPoints2, vb2, P.kf2)) return -1;
+    P.K[0] = pKF1->fx; P.K[1] = pKF1->fy; P.K[2] = pKF1->cx; P.K[3] = pKF1->cy;   // :1262-1265: pKF1's, in both directions
+    P.s12 = s12;
+    for (int i = 0; i < 9; i++) P.R12[i] = R12[(size_t)i];
+    for (int i = 0; i < 3; i++) P.t12[i] = t12[(size_t)i];
+    P.th = th; P.th_high = TH_HIGH;
+    std::vector<int32_t> match1(N1), match2(N2), match12(N1);
+    std::vector<uint16_t> dist1(N1), dist2(N2);
+    std::vector<int8_t> level1(N1), level2(N2);
+    std::vector<uint8_t> state1(N1), state2(N2);
+    vba_search_sim3_result R{};
+    R.match1 = match1.data(); R.match2 = match2.data(); R.best_dist1 = dist1.data(); R.best_dist2 = dist2.data();
+    R.level1 = level1.data(); R.level2 = level2.data(); R.state1 = state1.data(); R.state2 = state2.data(); R.match12 = match12.data();
+    vba_search_sim3_problem* pp = &P;
+    vba_search_sim3_result* pr = &R;
+    void* h = Optimizer::BackendHandle();
+    if (!h || vba_search_by_sim3(h, 1, &pp, &pr) != 0) {
+        std::cerr << who << ": " << (h ? vba_last_error(h) : "no HIP device (the backend has no CPU path)") << std::endl;
+        return -1;
+    }
+    for (size_t i1 = 0; i1 < N1; i1++)
+        if (match12[i1] >= 0) vpMatches12[i1] = vpMapPoints2[(size_t)match12[i1]];   // :1489
+    return R.n_found;
 }
 
 }  // namespace ORB_SLAM2

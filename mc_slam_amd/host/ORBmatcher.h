@@ -1,7 +1,9 @@
 // ORBmatcher.h -- the reference's ORBmatcher (include/ORBmatcher.h) as far as this backend carries it: SearchForTriangulation
-// (src/ORBmatcher.cpp:760-955, monocular) over vba_search_triangulation and both Fuse overloads (:958-1254, monocular) over vba_fuse.
-// The other searches stay matcher code of the caller.
+// (src/ORBmatcher.cpp:760-955, monocular) over vba_search_triangulation, both Fuse overloads (:958-1254, monocular) over vba_fuse and
+// SearchBySim3 (:1258-1496, monocular) over vba_search_by_sim3.  The other searches stay matcher code of the caller.
 #pragma once
+#include <array>
+#include <cstdint>
 #include <utility>
 #include <vector>
 
@@ -12,6 +14,7 @@ namespace ORB_SLAM2 {
 class ORBmatcher {
 public:
     static const int TH_LOW = 50;         // src/ORBmatcher.cpp:41
+    static const int TH_HIGH = 100;       // :41
     static const int HISTO_LENGTH = 30;   // :42
     ORBmatcher(float nnratio = 0.6, bool checkOri = true) : mfNNratio(nnratio), mbCheckOrientation(checkOri) {}
     // Matches between the keypoints of pKF1 and pKF2 that have no map point, inside shared vocabulary nodes and under the epipolar
@@ -31,6 +34,17 @@ public:
     // reprojection gate; a point whose best keypoint has a good map point is recorded in vpReplacePoint[iMP] instead of replaced.
     // vba_fuse applies the level range check of :1027 here, too (include/vislam_ba.h).  A NULL entry of vpPoints is skipped
     int Fuse(KeyFrame* pKF, const Mat4f& Scw, const std::vector<MapPoint*>& vpPoints, float th, std::vector<MapPoint*>& vpReplacePoint);
+    // src/ORBmatcher.cpp:1258-1496: the map points of pKF1 projected into pKF2 through the inverse of the Sim3 (s12, R12 row-major,
+    // t12), those of pKF2 into pKF1 through the Sim3, both with the intrinsics of pKF1 as the reference does; where both directions
+    // agree, vpMatches12[i1] becomes the map point of pKF2.  vpMatches12 has one entry per keypoint of pKF1; its non-NULL entries
+    // are the prior matches (:1291-1301).  ONE vba_search_by_sim3 call.  Returns nFound, -1 when the backend failed, vpMatches12 has
+    // the wrong size or a keyframe has a stereo keypoint (this backend is monocular), with a message on std::cerr
+    int SearchBySim3(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoint*>& vpMatches12, const float& s12, const Mat3f& R12,
+                     const std::array<float, 3>& t12, const float th);
+    // vbAlreadyMatched1 / vbAlreadyMatched2 of :1287-1301: a keypoint of pKF1 with a prior match, and the keypoint of pKF2 where
+    // GetIndexInKeyFrame finds that match
+    static void AlreadyMatched(KeyFrame* pKF1, KeyFrame* pKF2, const std::vector<MapPoint*>& vpMatches12, std::vector<uint8_t>& vb1,
+                               std::vector<uint8_t>& vb2);
 
 protected:
     float mfNNratio;

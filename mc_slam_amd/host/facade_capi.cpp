@@ -621,6 +621,28 @@ int fc_mp_fuse_state(void* m, long mp, long* out5) {
     out5[4] = (long)std::count(M->map.mspMapPoints.begin(), M->map.mspMapPoints.end(), p);
     return 0;
 }
+// ---- Sim3 projection matching (ORBmatcher::SearchBySim3) ----
+// ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th): match_ids [n] holds the ids of vpMatches12 (-1: NULL) and
+// comes back with those after the call
+int fc_search_by_sim3(void* m, long kf1, long kf2, long* match_ids, int n, float s12, const float* R9, const float* t3, float th) {
+    FcMap* M = reinterpret_cast<FcMap*>(m);
+    std::vector<MapPoint*> v = point_list(M, match_ids, n);
+    Mat3f R; std::memcpy(R.data(), R9, 36);
+    const std::array<float, 3> t = {{t3[0], t3[1], t3[2]}};
+    ORBmatcher matcher;
+    const int r = matcher.SearchBySim3(M->kfs.at(kf1).get(), M->kfs.at(kf2).get(), v, s12, R, t, th);
+    for (int i = 0; i < n; i++) match_ids[i] = v[(size_t)i] ? (long)v[(size_t)i]->mnId : -1;
+    return r;
+}
+// the vbAlreadyMatched flags of src/ORBmatcher.cpp:1287-1301 (no GPU needed): flags1 [N1], flags2 [N2]
+int fc_search_by_sim3_flags(void* m, long kf1, long kf2, const long* match_ids, int n, unsigned char* flags1, unsigned char* flags2) {
+    FcMap* M = reinterpret_cast<FcMap*>(m);
+    std::vector<uint8_t> vb1, vb2;
+    ORBmatcher::AlreadyMatched(M->kfs.at(kf1).get(), M->kfs.at(kf2).get(), point_list(M, match_ids, n), vb1, vb2);
+    std::memcpy(flags1, vb1.data(), vb1.size());
+    std::memcpy(flags2, vb2.data(), vb2.size());
+    return (int)vb1.size();
+}
 // ---- essential graph ----
 // spanning tree, loop edges and the ordered covisibility list (descending weights) of one keyframe
 int fc_kf_set_graph(void* m, long kf, long parent, const long* children, int n_children, const long* loop_edges, int n_loop,

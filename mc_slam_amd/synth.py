@@ -1006,3 +1006,139 @@ def fuse_scene(seed, n_keys=1000, n_pt=600, n_levels=8, scale_factor=1.2, flip_b
                            log_scale_factor=log_sf, grid_cols=cols, grid_rows=rows, grid_inv_w=inv_w, grid_inv_h=inv_h, cell_begin=cell_begin,
                            cell_feat=cell_feat, pos=pos, normal=normal, dist_min=dmin, dist_max=dmax, pred_max=pmax, pt_desc=pdesc, skip=skip,
                            th=th, th_low=th_low, check_reproj=check_reproj, truth=dict(kind=kind, key=key))
+
+
+# ---------------------------------------------------------------- Sim3 projection matching (vba_search_by_sim3)
+SIM3_SEARCH_KINDS = ("match", "matched", "no_pt1", "no_pt2", "far_desc", "behind", "outside", "distance", "level_high")
+
+
+def sim3_search_scene(seed, n_keys1=1000, n_keys2=1000, n_common=400, n_levels=(8, 8), scale_factor=1.2, flip_bits=12, size=((640, 480), (640, 480)),
+                      grid=((64, 48), (64, 48)), mix=(0.6, 0.08, 0.04, 0.04, 0.05, 0.04, 0.05, 0.05, 0.05), noise=0.4, s12=1.1, th=7.5, th_high=100,
+                      extra_points=0.15):
+    """One ORBmatcher::SearchBySim3 call, every input rounded through float32 as the reference holds it.  Two keyframes with
+    different poses, images of size[k] pixels with grids of grid[k] cells and n_levels[k] levels, one pinhole camera (that of
+    keyframe 1, used in both directions as the reference does), and a Sim3 with s12 != 1 (p_c1 = s12 R12 p_c2 + t12; log(s12) must
+    not be a multiple of log(scale_factor)).  n_common physical features are each present as ONE MAP POINT PER KEYFRAME: the point
+    of keyframe 2 lies at a random pixel of image 2, 2-10 deep, and the point of keyframe 1 is that point pushed through the Sim3,
+    so the two map copies disagree in world space as they do before a loop is closed.  Each keyframe has a keypoint at the
+    projection of its own point plus noise pixels times its level's scale; the two keypoint descriptors are flip_bits apart and
+    each point's descriptor is that of its own keypoint.  Octaves: oct2 = oct1 + ceil(log(s12) / log(scale_factor)) - 1 and
+    mfMaxDistance = distance * scale[oct] * factor^e with e drawn so that both predicted levels accept the other keypoint.
+    Every feature is of one kind, with the shares of `mix` (SIM3_SEARCH_KINDS):
+      match       as above;  matched  the same, already matched (vbAlreadyMatched set on both sides)
+      no_pt1      keyframe 1 has no usable point on its keypoint;  no_pt2  keyframe 2 has none
+      far_desc    the two keypoint descriptors are 120 bits apart
+      behind      behind both cameras;  outside  in front but 80-200 pixels out of both images
+      distance    distance ranges that do not hold the points
+      level_high  mfMaxDistance = distance in the target * factor^(n_levels of the target - 0.5): the predicted level is the
+                  target's n_levels (state 6 when the source has at least as many levels; otherwise the range gate catches it)
+    The other keypoints of both keyframes are distractors at random pixels with random descriptors; a share extra_points of them
+    carries a random map point.  truth: kind [n_common] (index into SIM3_SEARCH_KINDS), key1 / key2 [n_common] (the feature's
+    keypoint in each keyframe)."""
+    r = np.random.default_rng(seed)
+    f32 = lambda a: np.asarray(a, dtype=np.float32)
+    f64 = lambda a: f32(a).astype(np.float64)
+    n_keys = (n_keys1, n_keys2)
+    n_common = min(n_common, n_keys1, n_keys2)
+    logsf = float(np.log(scale_factor))
+    log_sf = float(np.float32(np.log(np.float32(scale_factor))))
+    (w1, h1) = size[0]
+    K = f64([0.72 * w1, 0.72 * w1, 0.5 * w1 - 0.5, 0.5 * h1 - 0.5])
+    scales = [level_tables(n_levels[k], scale_factor)[0] for k in range(2)]
+    Rm = [so3_exp(r.normal(size=3) * 0.4) for _ in range(2)]
+    Cw = [r.uniform(-2, 2, 3) for _ in range(2)]
+    Rcw = [f64(Rm[k]) for k in range(2)]
+    tcw = [f64(-(Rcw[k] @ Cw[k])) for k in range(2)]
+    s12 = float(np.float32(s12))
+    R12 = f64(so3_exp(r.normal(size=3) * 0.02))
+    t12 = f64(r.normal(size=3) * 0.05)
+    delta = np.log(s12) / logsf
+    kshift = int(np.ceil(delta)) - 1
+    frac = delta - kshift
+
+    kind = r.choice(len(SIM3_SEARCH_KINDS), size=n_common, p=np.asarray(mix, dtype=float) / np.sum(mix))
+    perm = [r.permutation(n_keys[k]) for k in range(2)]
+    key = [perm[k][:n_common] for k in range(2)]
+    uv = [np.stack([r.uniform(0, size[k][0] - 1, n_keys[k]), r.uniform(0, size[k][1] - 1, n_keys[k])], axis=1) for k in range(2)]
+    desc = [r.integers(0, 256, (n_keys[k], 32), dtype=np.uint8) for k in range(2)]
+    octv = []
+    for k in range(2):
+        oct_p = np.array([35, 25, 15, 10, 6, 4, 3, 2] + [1] * 56)[:n_levels[k]].astype(float)
+        octv.append(r.choice(n_levels[k], size=n_keys[k], p=oct_p / oct_p.sum()).astype(np.uint8))
+    has = [(r.random(n_keys[k]) < extra_points).astype(np.uint8) for k in range(2)]
+    matched = [np.zeros(n_keys[k], dtype=np.uint8) for k in range(2)]
+    pos = [np.zeros((n_keys[k], 3)) for k in range(2)]
+    dmin, dmax, pmax = ([np.zeros(n_keys[k]) for k in range(2)] for _ in range(3))
+    pdesc = [r.integers(0, 256, (n_keys[k], 32), dtype=np.uint8) for k in range(2)]
+    tops = [np.float32(scales[k][-1]) for k in range(2)]
+
+    def ray(px):
+        return np.array([(px[0] - K[2]) / K[0], (px[1] - K[3]) / K[1], 1.0])
+
+    def project(c):
+        return np.array([K[0] * c[0] / c[2] + K[2], K[1] * c[1] / c[2] + K[3]])
+
+    def set_point(k, i, c, mx):
+        """the map point of keypoint i of keyframe k at c in its camera, with mfMaxDistance mx"""
+        pos[k][i] = f64(Rm[k].T @ c + Cw[k])
+        mx = np.float32(mx)
+        pmax[k][i], dmax[k][i], dmin[k][i] = mx, np.float32(1.2) * mx, np.float32(0.8) * (mx / tops[k])
+
+    # the distractors' points: a random pixel and depth in their own camera, seen at their keypoint's octave
+    for k in range(2):
+        for i in np.nonzero(has[k])[0]:
+            c = r.uniform(2, 10) * ray(uv[k][i] + r.normal(size=2) * 3)
+            set_point(k, i, c, np.linalg.norm(c) * scales[k][octv[k][i]])
+
+    lo, hi = max(0, -kshift), min(n_levels[0] - 2, n_levels[1] - 2 - kshift)
+    for f in range(n_common):
+        kd = SIM3_SEARCH_KINDS[kind[f]]
+        i1, i2 = int(key[0][f]), int(key[1][f])
+        o1 = int(r.integers(lo, max(lo, min(hi, 3)) + 1))
+        o2 = min(max(o1 + kshift, 0), n_levels[1] - 1)
+        octv[0][i1], octv[1][i2] = o1, o2
+        depth = r.uniform(2, 10)
+        px2 = np.array([r.uniform(30, size[1][0] - 31), r.uniform(30, size[1][1] - 31)])
+        if kd == "outside":
+            off = r.uniform(80, 200)
+            px2 = np.array([max(size[0][0], size[1][0]) + off, px2[1]]) if r.random() < 0.5 else np.array([px2[0], -off])
+        if kd == "behind":
+            depth = -depth
+        c2 = depth * ray(px2)
+        c1 = s12 * (R12 @ c2) + t12
+        d1, d2 = np.linalg.norm(c1), np.linalg.norm(c2)
+        mx1 = d1 * scales[0][o1] * scale_factor ** (-frac + r.uniform(-0.35, 0.35))
+        mx2 = d2 * scales[1][o2] * scale_factor ** (frac + r.uniform(-0.35, 0.35))
+        if kd == "distance":
+            far = r.random() < 0.5
+            mx1 = d2 * (3.0 * float(tops[0]) if far else 0.3)                # the range ends below or starts above the point
+            mx2 = d1 * (3.0 * float(tops[1]) if far else 0.3)
+        if kd == "level_high":
+            mx1 = d2 * scale_factor ** (n_levels[1] - 0.5)
+            mx2 = d1 * scale_factor ** (n_levels[0] - 0.5)
+        set_point(0, i1, c1, mx1)
+        set_point(1, i2, c2, mx2)
+        has[0][i1], has[1][i2] = kd != "no_pt1", kd != "no_pt2"
+        if kd == "matched":
+            matched[0][i1] = matched[1][i2] = 1
+        if kd not in ("behind", "outside"):
+            uv[0][i1] = project(c1) + r.normal(size=2) * noise * scales[0][o1]
+            uv[1][i2] = project(c2) + r.normal(size=2) * noise * scales[1][o2]
+        bits = np.unpackbits(desc[0][i1])
+        bits[r.permutation(256)[:120 if kd == "far_desc" else flip_bits]] ^= 1
+        desc[1][i2] = np.packbits(bits)
+        pdesc[0][i1], pdesc[1][i2] = desc[0][i1], desc[1][i2]
+
+    kfs = []
+    for k in range(2):
+        w, h = size[k]
+        cols, rows = grid[k]
+        bounds = np.array([0.0, float(w), 0.0, float(h)])
+        inv_w, inv_h = float(np.float32(cols) / np.float32(w)), float(np.float32(rows) / np.float32(h))
+        uvk = f64(uv[k])
+        cb, cf = abi.grid_csr(uvk, bounds, cols, rows, inv_w, inv_h)
+        kfs.append(abi.SearchSim3KF(Rcw=Rcw[k], tcw=tcw[k], bounds=bounds, desc=desc[k], uv=uvk, oct=octv[k], scale=scales[k], log_scale_factor=log_sf,
+                                    grid_cols=cols, grid_rows=rows, grid_inv_w=inv_w, grid_inv_h=inv_h, cell_begin=cb, cell_feat=cf, has_pt=has[k],
+                                    matched=matched[k], pos=pos[k], dist_min=dmin[k], dist_max=dmax[k], pred_max=pmax[k], pt_desc=pdesc[k]))
+    return abi.SearchSim3Problem(kf1=kfs[0], kf2=kfs[1], K=K, s12=s12, R12=R12, t12=t12, th=th, th_high=th_high,
+                                 truth=dict(kind=kind, key1=key[0].copy(), key2=key[1].copy()))

@@ -1,0 +1,286 @@
+"""The cases of the vba_search_by_sim3 tests: hand-made pairs and synthetic ones (mc_slam_amd.synth.sim3_search_scene), the smallest
+shapes at which the kernel can still go wrong.  cases() builds every pair once; ref(name, dtype, form) is the yardstick's answer
+(tests/search_sim3_ref.py), computed once and shared by the tests (treat both as read-only).
+
+The hand-made pairs use K = (50, 50, 40, 30) and th = 3.  Keyframe 1 has an 80 x 60 image with bounds (0, 80, 0, 60), an 8 x 6 grid
+(cells of 10 pixels) and four levels; KEYFRAME 2 DIFFERS IN ALL THREE: bounds (4, 76, 6, 54), a 6 x 4 grid (cells of 12 pixels) and
+five levels, so a kernel that reads the wrong side's table changes an answer.  Both keyframes have general poses and the Sim3 has
+a general rotation, a translation and s12 = 1.25 (z_zero: identities and s12 = 2, so that its zeros are exact).
+
+A hand-made pair is written per direction by a function gen(G) of the TARGET's geometry G, which returns the target's keypoints
+and the queries as (u, v, z, ...) IN THE TARGET CAMERA; build() calls it for both directions, pulls every query back through the
+Sim3 and the source pose to its world position, and hangs it on a carrier keypoint of the source keyframe.  Carriers sit 1.5
+pixels above maxY, which rounds to row `rows`: they are in no cell, as in the reference, and never a candidate; the `agree` case,
+whose keypoints are source and target at once, is written out by hand instead.  mfMaxDistance = dist3D * 1.2^(level - 0.5), so
+that PredictScale gives `level` with half a level to spare, and the distance range is [0.1, 10] dist3D.  Apart from z_zero no case
+puts a quantity on a threshold: tests/test_search_sim3_ref.py asserts the margins.
+
+vba_search_by_sim3 returns no floating-point value, so there is no tolerance here: every output is compared for equality."""
+import functools
+
+import numpy as np
+
+from mc_slam_amd import abi, synth
+from fuse_cases import base_desc, flip
+import search_sim3_ref as ref_mod
+
+K_HAND = np.array([50.0, 50.0, 40.0, 30.0])
+LOG_SF = float(np.float32(np.log(np.float32(1.2))))
+GEOM = [dict(bounds=(0.0, 80.0, 0.0, 60.0), cols=8, rows=6, nl=4), dict(bounds=(4.0, 76.0, 6.0, 54.0), cols=6, rows=4, nl=5)]
+
+
+def _rot(axis, a):
+    c, s = np.cos(a), np.sin(a)
+    i, j = [(1, 2), (2, 0), (0, 1)][axis]
+    R = np.eye(3)
+    R[i, i], R[i, j], R[j, i], R[j, j] = c, -s, s, c
+    return R
+
+
+GENERAL = dict(R1=_rot(2, 0.3), t1=np.array([0.1, -0.2, 0.3]), R2=_rot(1, -0.2), t2=np.array([-0.3, 0.1, 0.2]),
+               R12=_rot(0, 0.25) @ _rot(2, -0.4), t12=np.array([0.2, -0.1, 0.15]), s12=1.25)
+IDENTITY = dict(R1=np.eye(3), t1=np.zeros(3), R2=np.eye(3), t2=np.zeros(3), R12=np.eye(3), t12=np.zeros(3), s12=2.0)
+D = [base_desc(500 + i) for i in range(16)]
+
+
+def key(u, v, oct, desc, pt=None):
+    return dict(u=u, v=v, oct=oct, desc=desc, pt=pt)
+
+
+def query(u, v, z, desc, level=0, matched=0, dmin=0.1, dmax=10.0, c=None):
+    """a map point that lies at (u, v) and depth z in the TARGET camera (c: its coordinates there, instead)"""
+    c = np.array([(u - K_HAND[2]) / K_HAND[0] * z, (v - K_HAND[3]) / K_HAND[1] * z, z]) if c is None else np.asarray(c, dtype=float)
+    d = float(np.linalg.norm(c))
+    return dict(c=c, dist_min=dmin * d, dist_max=dmax * d, pred_max=max(d, 1.0) * 1.2 ** (level - 0.5), desc=desc, matched=matched)
+
+
+def _world(side, c, T):
+    """the world position of a point of keyframe `side` that the search puts at c in the other camera"""
+    if side == 0:                                     # c = sR21 (R1 X + t1) + t21, so R1 X + t1 = s12 R12 c + t12
+        return T["R1"].T @ (T["s12"] * (T["R12"] @ c) + T["t12"] - T["t1"])
+    return T["R2"].T @ (T["R12"].T @ (c - T["t12"]) / T["s12"] - T["t2"])
+
+
+def _kf(side, keys, T, insert_order=None):
+    G = GEOM[side]
+    b = G["bounds"]
+    inv_w, inv_h = G["cols"] / (b[1] - b[0]), G["rows"] / (b[3] - b[2])
+    n = len(keys)
+    uv = np.array([[k["u"], k["v"]] for k in keys], dtype=float).reshape(-1, 2)
+    order = list(range(n)) if insert_order is None else list(insert_order)
+    begin, feat = abi.grid_csr(uv[order], b, G["cols"], G["rows"], inv_w, inv_h)
+    feat = np.asarray(order, dtype=np.int32)[feat]
+    pos, dist, pdesc = np.zeros((n, 3)), np.zeros((n, 3)), np.zeros((n, 32), dtype=np.uint8)
+    has, matched = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+    for i, k in enumerate(keys):
+        q = k["pt"]
+        if q is None:
+            pos[i], dist[i] = np.nan, np.nan          # read only where has_pt: a read shows as a changed state
+            continue
+        has[i], matched[i], pdesc[i] = 1, q["matched"], q["desc"]
+        pos[i] = q["c"] if T is IDENTITY else _world(side, q["c"], T)   # IDENTITY: c is the world position itself, see _z_zero
+        dist[i] = (q["dist_min"], q["dist_max"], q["pred_max"])
+    return abi.SearchSim3KF(Rcw=T["R%d" % (side + 1)], tcw=T["t%d" % (side + 1)], bounds=b, desc=np.array([k["desc"] for k in keys], dtype=np.uint8).reshape(-1, 32),
+                            uv=uv, oct=np.array([k["oct"] for k in keys], dtype=np.uint8), scale=synth.level_tables(G["nl"])[0], log_scale_factor=LOG_SF,
+                            grid_cols=G["cols"], grid_rows=G["rows"], grid_inv_w=inv_w, grid_inv_h=inv_h, cell_begin=begin, cell_feat=feat,
+                            has_pt=has, matched=matched, pos=pos, dist_min=dist[:, 0], dist_max=dist[:, 1], pred_max=dist[:, 2], pt_desc=pdesc)
+
+
+def pair(keys1, keys2, T=GENERAL, order1=None, order2=None, th=3.0, th_high=100):
+    return abi.SearchSim3Problem(kf1=_kf(0, keys1, T, order1), kf2=_kf(1, keys2, T, order2), K=K_HAND, s12=T["s12"], R12=T["R12"], t12=T["t12"],
+                                 th=th, th_high=th_high)
+
+
+def build(gen, T=GENERAL, descending=False, extra=(0, 0), **kw):
+    """the pair of gen(G) -> (target keypoints, queries[, expected answers]) for both directions; extra[s] more keypoints without a
+    point on side s.  Returns (pair, expect) with expect[d] = the answers of direction d as gen gave them (or None)"""
+    out = [gen(GEOM[1]), gen(GEOM[0])]                # direction 0 searches keyframe 2, direction 1 keyframe 1
+    keys, expect = [], []
+    for s in range(2):
+        targets, queries = out[1 - s][0], out[s][1]   # side s is the target of direction 1 - s and the source of direction s
+        b = GEOM[s]["bounds"]
+        carriers = [key(b[0] + 2.5 + (3.1 * k) % (b[1] - b[0] - 5), b[3] - 1.5, 0, D[15], pt=q) for k, q in enumerate(queries)]
+        spare = [key(b[0] + 3.5 + (2.7 * k) % (b[1] - b[0] - 5), b[3] - 1.2, 0, D[14]) for k in range(extra[s])]
+        keys.append(list(targets) + carriers + spare)
+        expect.append(out[s][2] if len(out[s]) > 2 else None)
+    od = lambda s: range(len(keys[s]) - 1, -1, -1) if descending else None
+    return pair(keys[0], keys[1], T, od(0), od(1), **kw), expect
+
+
+def fillers(G):
+    x0, x1, y0, y1 = G["bounds"]
+    return [key(x0 + 5, y0 + 5, 0, D[8]), key(x1 - 9, y0 + 5, 1, D[9]), key(x1 - 9, y1 - 9, 0, D[10]), key(x0 + 30, y1 - 16, 2, D[11])]
+
+
+def _micro(G):
+    """four targets and one query per state 0 and 3 .. 8, one carrier already matched (state 2); the targets have no point (state 1).
+    expect: query -> (state, match, best_dist, level)"""
+    x0, x1, y0, y1 = G["bounds"]
+    nl = G["nl"]
+    targets = [key(x0 + 20, y0 + 20, 0, flip(D[0], 5)),          # 0: the match of query 0
+               key(x0 + 22, y0 + 20, 0, flip(D[0], 9)),          # 1: in its area too, farther in Hamming distance
+               key(x0 + 51, y0 + 31, 1, flip(D[1], 110)),        # 2: the only candidate of query 6, 110 bits off
+               key(x0 + 52, y0 + 11, 0, D[2])] + fillers(G)      # 3: in the area of query 7 with its exact descriptor, two levels below it
+    queries = [query(x0 + 20.5, y0 + 20.5, 4.0, D[0], level=0),                  # 0: found
+               query(x0 + 36.5, y0 + 24.5, -5.0, D[6]),                          # 1: behind
+               query(x1 + 5.0, y0 + 24.5, 4.0, D[6]),                            # 2: right of the target's image
+               query(x0 + 36.5, y0 + 24.5, 4.0, D[6], dmin=2.0),                 # 3: nearer than dist_min
+               query(x0 + 36.5, y0 + 24.5, 4.0, D[6], level=nl),                 # 4: level n_levels of the target
+               query(x0 + 10.5, y0 + 38.5, 4.0, D[6], level=0),                  # 5: nothing within 3 pixels
+               query(x0 + 50.5, y0 + 30.5, 4.0, D[1], level=1),                  # 6: a candidate, but 110 > th_high
+               query(x0 + 50.5, y0 + 10.5, 4.0, D[2], level=2),                  # 7: a keypoint in the area, none at its levels
+               query(x0 + 20.5, y0 + 20.5, 4.0, D[0], level=0, matched=1)]       # 8: already matched
+    expect = [(0, 0, 5, 0), (3, -1, 256, -128), (4, -1, 256, -128), (5, -1, 256, -128), (6, -1, 256, nl), (7, -1, 256, 0), (8, -1, 110, 1),
+              (8, -1, 256, 2), (2, -1, 256, -128)]
+    return targets, queries, expect
+
+
+def _tie_cells(G):
+    """query 0 (level 3, radius 5.184): two keypoints in neighbouring columns, both 8 bits off: the earlier column wins although its
+    index is larger.  query 1: keypoints 5 and 3 in one cell, both 6 bits off; the grid was filled in descending index order, so
+    the cell lists 5 in front of 3 and 5 wins"""
+    x0, x1, y0, y1 = G["bounds"]
+    xa, xb = (36.0, 34.0) if G["cols"] == 8 else (38.0, 32.0)      # columns 4 and 3 of keyframe 1, 3 and 2 of keyframe 2
+    targets = [key(x0 + 5, y0 + 5, 0, D[8]), key(x1 - 9, y0 + 5, 1, D[9]), key(xa, 30, 3, flip(D[0], 8, 40)), key(61, 30.5, 0, flip(D[1], 6, 90)),
+               key(x1 - 9, y1 - 9, 0, D[10]), key(60, 30, 0, flip(D[1], 6)), key(x0 + 30, y1 - 16, 2, D[11]), key(xb, 30, 3, flip(D[0], 8))]
+    queries = [query(35.2, 30.2, 4.0, D[0], level=3), query(60.4, 30.2, 4.0, D[1], level=0)]
+    return targets, queries, [(0, 7, 8, 3), (0, 5, 6, 0)]
+
+
+def _z_zero(G):
+    """z exactly 0 in the source camera, on and off the axis, with identities and s12 = 2 all the way: z stays 0 in the target
+    camera, invz is infinite, u and v are infinite or NaN and the point leaves at IsInImage; -0.0 likewise"""
+    x0, x1, y0, y1 = G["bounds"]
+    pos = [(0, 0, 0), (1, 0, 0), (1, 2, 0), (-1, 0, 0), (0, -3, 0), (-2, -1, -0.0), (0, 0, -0.0)]
+    queries = [dict(query(0, 0, 1.0, D[6]), c=np.array(q, dtype=float)) for q in pos]
+    s = 2.0 if G["nl"] == 5 else 0.5                              # the target camera sees the source's coordinates over or times s12
+    queries.append(dict(query(x0 + 20.5, y0 + 20.5, 4.0, D[0], level=0), c=s * query(x0 + 20.5, y0 + 20.5, 4.0, D[0])["c"]))
+    return [key(x0 + 20, y0 + 20, 0, flip(D[0], 5))] + fillers(G), queries, [(4, -1, 256, -128)] * 7 + [(0, 0, 5, 0)]
+
+
+def _level_edges(G):
+    """predicted levels -1, 0, last and last + 1 of the target; a query of level 2 with candidates at the levels 0, 1, 2 and 3, of
+    which the outer two are nearer in Hamming distance; one keypoint of level 1 under queries of the levels 0, 1, 2 and 3 (a
+    candidate for the middle two only)"""
+    x0, x1, y0, y1 = G["bounds"]
+    last = G["nl"] - 1
+    targets = [key(x0 + 20, y0 + 14, 0, flip(D[0], 7)), key(x0 + 56, y0 + 14, last, flip(D[1], 7)), key(x0 + 55, y0 + 15, last - 1, flip(D[1], 9)),
+               key(x0 + 35, y0 + 33, 0, flip(D[2], 1)), key(x0 + 37, y0 + 33, 1, flip(D[2], 10)), key(x0 + 36, y0 + 31, 2, flip(D[2], 12)),
+               key(x0 + 37, y0 + 31, 3, flip(D[2], 2)), key(x0 + 16, y0 + 35, 1, flip(D[3], 3))] + fillers(G)
+    queries = [query(x0 + 20.4, y0 + 14.3, 4.0, D[0], level=-1), query(x0 + 20.4, y0 + 14.3, 4.0, D[0], level=0),
+               query(x0 + 56.4, y0 + 14.3, 4.0, D[1], level=last), query(x0 + 56.4, y0 + 14.3, 4.0, D[1], level=last + 1),
+               query(x0 + 36.3, y0 + 32.2, 4.0, D[2], level=2), query(x0 + 16.3, y0 + 35.4, 4.0, D[3], level=0),
+               query(x0 + 16.3, y0 + 35.4, 4.0, D[3], level=1), query(x0 + 16.3, y0 + 35.4, 4.0, D[3], level=2), query(x0 + 16.3, y0 + 35.4, 4.0, D[3], level=3)]
+    expect = [(6, -1, 256, -1), (0, 0, 7, 0), (0, 1, 7, last), (6, -1, 256, last + 1), (0, 4, 10, 2), (8, -1, 256, 0), (0, 7, 3, 1), (0, 7, 3, 2),
+              (8, -1, 256, 3)]
+    return targets, queries, expect
+
+
+def _border(G):
+    """projections whose cell ranges clamp at 0 and at the last column and row.  A keypoint within half a cell of maxX or maxY
+    rounds to column `cols` or row `rows` and is in no cell, as in the reference"""
+    x0, x1, y0, y1 = G["bounds"]
+    targets = [key(x0 + 1, y0 + 1, 0, flip(D[0], 4)), key(x1 - 6.5, y1 - 6.5, 3, flip(D[1], 4)), key(x1 - 1, y1 - 1, 0, D[2]), key(x0 + 2, y1 - 6.5, 0, flip(D[3], 4)),
+               key(x1 - 3, y0 + 2, 0, D[4]), key(x1 - 6.5, y0 + 1.5, 0, flip(D[4], 4))] + fillers(G)
+    queries = [query(x0 + 0.6, y0 + 0.7, 4.0, D[0], level=0), query(x1 - 6.1, y1 - 6.2, 4.0, D[1], level=3), query(x1 - 0.6, y1 - 0.7, 4.0, D[2], level=0),
+               query(x0 + 1.7, y1 - 6.1, 4.0, D[3], level=1), query(x1 - 5.7, y0 + 0.7, 4.0, D[4], level=0), query(x0 + 36.3, y0 + 24.4, 4.0, D[5], level=2)]
+    return targets, queries, [(0, 0, 4, 0), (0, 1, 4, 3), (7, -1, 256, 0), (0, 3, 4, 1), (0, 5, 4, 0), (7, -1, 256, 2)]
+
+
+def _border_returns(G):
+    """th = -20: the radius is negative and each of the four early returns of GetFeaturesInArea is taken in turn; the last query
+    passes all four and walks an empty range"""
+    x0, x1, y0, y1 = G["bounds"]
+    xm, ym = 0.5 * (x0 + x1) + 1.5, 0.5 * (y0 + y1) + 0.4
+    queries = [query(x1 - 0.7, ym, 4.0, D[0]), query(x0 + 2.3, ym, 4.0, D[0]), query(xm, y1 - 0.7, 4.0, D[0]), query(xm, y0 + 2.3, 4.0, D[0]),
+               query(xm, ym, 4.0, D[0])]
+    return [key(xm - 0.5, ym - 0.4, 0, D[0])] + fillers(G), queries, [(7, -1, 256, 0)] * 5
+
+
+def _agree():
+    """the agreement loop (:1480-1493) on keypoints that are source and target at once, all at level 0.  a / A: a mutual match.
+    b -> B while B -> b2.  c -> C, which has no point.  d -> D', which is already matched: targets are never filtered, so match1
+    points at it and match2 of it is -1.  e and e2 -> E, and E -> e2."""
+    g1, g2 = GEOM[0]["bounds"], GEOM[1]["bounds"]
+    q = lambda u, v, desc, **kw: query(u, v, 4.0, desc, level=0, **kw)
+    A, B, Cc, Dd, E = (g2[0] + 26, g2[2] + 14), (g2[0] + 46, g2[2] + 14), (g2[0] + 26, g2[2] + 30), (g2[0] + 46, g2[2] + 30), (g2[0] + 10, g2[2] + 30)
+    keys1 = [key(20, 20, 0, D[0], pt=q(A[0] + 0.3, A[1] + 0.2, D[0])),                 # 0 a
+             key(40, 20, 0, flip(D[1], 9), pt=q(B[0] + 0.3, B[1] + 0.2, D[1])),        # 1 b
+             key(42, 21, 0, flip(D[1], 2, 100)),                                      # 2 b2: nearer to B's descriptor than b, no point
+             key(20, 40, 0, D[2], pt=q(Cc[0] + 0.3, Cc[1] + 0.2, D[2])),               # 3 c
+             key(40, 40, 0, D[3], pt=q(Dd[0] + 0.3, Dd[1] + 0.2, D[3])),               # 4 d
+             key(60, 40, 0, flip(D[4], 6), pt=q(E[0] + 0.3, E[1] + 0.2, D[4])),        # 5 e
+             key(61, 41, 0, flip(D[4], 2, 100), pt=q(E[0] - 0.3, E[1] + 0.4, D[4]))]   # 6 e2
+    keys2 = [key(A[0], A[1], 0, flip(D[0], 4), pt=q(20.3, 20.2, flip(D[0], 4))),       # 0 A
+             key(B[0], B[1], 0, flip(D[1], 3), pt=q(41.2, 20.6, D[1])),                # 1 B: b is 9 bits off, b2 is 2
+             key(Cc[0], Cc[1], 0, flip(D[2], 3)),                                     # 2 C: no point
+             key(Dd[0], Dd[1], 0, flip(D[3], 3), pt=q(40.3, 40.2, D[3], matched=1)),   # 3 D'
+             key(E[0], E[1], 0, flip(D[4], 3), pt=q(60.6, 40.6, D[4]))]                # 4 E: e is 6 bits off, e2 is 2
+    expect = dict(match1=[0, 1, -1, 2, 3, 4, 4], match2=[0, 2, -1, -1, 6], match12=[0, -1, -1, -1, -1, -1, 4], n_found=2,
+                  state1=[0, 0, 1, 0, 0, 0, 0], state2=[0, 0, 1, 2, 0])
+    return pair(keys1, keys2), expect
+
+
+def agree_expect():
+    return _agree()[1]
+
+
+HAND = dict(micro=_micro, tie_cells=_tie_cells, z_zero=_z_zero, level_edges=_level_edges, border=_border, border_all=_border, border_returns=_border_returns)
+HAND_KW = dict(micro=dict(extra=(2, 3)), tie_cells=dict(descending=True), z_zero=dict(T=IDENTITY), border_all=dict(th=1000.0), border_returns=dict(th=-20.0))
+
+
+def hand_expect(name):
+    """expect[d][query] = (state, match, best_dist, level) of the hand-made case, and the index of query 0's carrier per direction"""
+    p, e = build(HAND[name], **HAND_KW.get(name, {}))
+    first = [len(HAND[name](GEOM[s])[0]) for s in range(2)]      # side s holds the targets of direction 1 - s in front of its carriers
+    return e, first
+
+
+def _count_scene(seed, n_q1, n_q2):
+    """a scene with exactly n_q1 and n_q2 queries: the first keypoints with a usable, unmatched point keep it, the others lose it"""
+    p = synth.sim3_search_scene(seed, n_keys1=max(2 * n_q1, 300), n_keys2=max(2 * n_q2, 300), n_common=150, extra_points=0.9)
+    ch = {}
+    for name, kf, n in (("kf1", p.kf1, n_q1), ("kf2", p.kf2, n_q2)):
+        live = np.nonzero((kf.has_pt != 0) & (kf.matched == 0))[0]
+        assert len(live) >= n, (name, len(live), n)
+        has = kf.has_pt.copy()
+        has[live[n:]] = 0
+        ch[name] = dict(has_pt=has)
+    return p.copy(**ch)
+
+
+@functools.lru_cache(maxsize=None)
+def cases():
+    c = {}
+    for name, gen in HAND.items():
+        c[name] = build(gen, **HAND_KW.get(name, {}))[0]
+    c["agree"] = _agree()[0]
+    c["scale_half"] = build(_micro, T=dict(GENERAL, s12=0.5))[0]             # the same geometry in the target cameras under another s12
+    c["scale_two"] = build(_micro, T=dict(GENERAL, s12=2.0))[0]
+    for n, m in ((1, 0), (255, 3), (256, 0), (257, 3), (513, 0)):
+        c["queries_%d_%d" % (n, m)] = _count_scene(600 + n, n, m)
+    c["queries_3_257"] = _count_scene(611, 3, 257)
+    s = synth.sim3_search_scene(41, n_keys1=60, n_keys2=50, n_common=30)
+    c["empty_kf1"] = synth.sim3_search_scene(42, n_keys1=0, n_keys2=50, n_common=0)
+    c["empty_kf2"] = synth.sim3_search_scene(43, n_keys1=50, n_keys2=0, n_common=0)
+    c["nothing_searchable"] = s.copy(kf1=dict(has_pt=np.zeros(60, dtype=np.uint8)), kf2=dict(matched=np.ones(50, dtype=np.uint8)))
+    c["synth_small"] = synth.sim3_search_scene(44, n_keys1=120, n_keys2=110, n_common=60, n_levels=(8, 6), size=((640, 480), (600, 440)),
+                                               grid=((64, 48), (50, 40)))
+    c["synth_mid"] = synth.sim3_search_scene(45, n_keys1=1000, n_keys2=1100, n_common=900)
+    return c
+
+
+@functools.lru_cache(maxsize=None)
+def ref(name, dtype="float64", form="seq"):
+    return ref_mod.search_sim3_ref(cases()[name], np.dtype(dtype), form)
+
+
+def check_against(what, got, want):
+    """a library result against a yardstick result: every output equal for every keypoint of both keyframes"""
+    assert got.status == 0, what
+    for k in ref_mod.INT_KEYS[1:]:
+        g, w = np.asarray(getattr(got, k)), np.asarray(want[k])
+        assert g.shape == w.shape, (what, k, g.shape, w.shape)
+        bad = np.nonzero(g != w)[0]
+        assert len(bad) == 0, (what, k, bad[:8], g[bad[:8]], w[bad[:8]])
+    assert got.n_found == want["n_found"], what
