@@ -123,7 +123,7 @@ typedef struct vba_profile {
     double total_ms;             /* first launch -> last launch of the run */
     double factor_flops;         /* FP64 flop the factorisation class executed on MFMA: 2*32^3 per tile product of the
                                     symbolic tile lists, per solve (structurally zero tiles are never touched) */
-    int64_t kernel_launches;     /* kernel launches the last vba_batch_run / vba_solve / vba_sim3_optimize / vba_sim3_ransac / vba_triangulate / vba_two_view_init (at most 2) / vba_search_triangulation / vba_fuse / vba_search_by_sim3 / vba_posegraph_optimize enqueued (filled with or without profiling) */
+    int64_t kernel_launches;     /* kernel launches the last vba_batch_run / vba_solve / vba_sim3_optimize / vba_sim3_ransac / vba_triangulate / vba_two_view_init (at most 2) / vba_search_triangulation / vba_fuse / vba_search_by_sim3 / vba_search_by_projection / vba_posegraph_optimize enqueued (filled with or without profiling) */
 } vba_profile;
 
 /* One handle per host thread / GPU; owns device buffers and a stream.  Errors: nonzero return, message
@@ -178,7 +178,7 @@ int vba_batch_solve_b(void *handle, int32_t n_windows, vba_problem *const *inout
  *           every later one, those submitted afterwards included, with the same message: no GPU work starts for them (earlier
  *           tickets finish).  Waiting on an unknown or retired ticket returns -1.
  *   handle  while any ticket is submitted and not yet waited for, every synchronous entry point of the handle (vba_solve*,
- *           vba_batch_upload / run / download / solve*, vba_pose_optimize, vba_sim3_optimize, vba_sim3_ransac, vba_triangulate, vba_two_view_init, vba_search_triangulation, vba_fuse, vba_search_by_sim3, vba_posegraph_optimize, vba_preintegrate, vba_set_profile,
+ *           vba_batch_upload / run / download / solve*, vba_pose_optimize, vba_sim3_optimize, vba_sim3_ransac, vba_triangulate, vba_two_view_init, vba_search_triangulation, vba_fuse, vba_search_by_sim3, vba_search_by_projection, vba_posegraph_optimize, vba_preintegrate, vba_set_profile,
  *           vba_batch_set_depth) returns -1 with "asynchronous batches pending: wait for them first"; afterwards the handle
  *           works synchronously as before.  vba_destroy finishes pending tickets (their results land) before it frees.
  *           Profiling (vba_set_profile) covers synchronous calls only.  One caller thread at a time, as everywhere. */
@@ -696,6 +696,121 @@ typedef struct vba_search_sim3_result {
  * table) and a non-finite position or distance where has_pt is set; s12 not finite or not positive; a non-finite R12, t12, K or th;
  * th_high outside 0 .. 256.  A pair's outputs do not depend on where it stands in the batch. */
 int vba_search_by_sim3(void *handle, int32_t n_pairs, vba_search_sim3_problem *const *in, vba_search_sim3_result *const *out);
+
+/* ---- projection matching for tracking ----
+ * The two matchers the tracking thread runs directly in front of its two PoseOptimization calls (vba_pose_optimize), monocular
+ * (mvuRight < 0, bMono == true), selected by `mode`:
+ *   VBA_SEARCH_PROJ_LAST_FRAME  ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) (src/ORBmatcher.cpp:1511-1665), the
+ *                               call of Tracking::TrackWithMotionModel (src/Tracking.cpp:1735-1804)
+ *   VBA_SEARCH_PROJ_LOCAL_MAP   Frame::isInFrustum (src/Frame.cpp:492-550) per point fused with ORBmatcher::SearchByProjection(F,
+ *                               vpMapPoints, th) (src/ORBmatcher.cpp:63-156): Tracking::SearchLocalPoints (src/Tracking.cpp:2111-2174)
+ * both over Frame::GetFeaturesInArea (src/Frame.cpp:562-620).  One problem is one frame and one ORDERED list of queries (the keypoints
+ * of the last frame, or the local map points, in the reference's loop order); one call takes any number of problems, ragged, in one
+ * kernel launch (one 256-lane workgroup per problem).  The queries of a problem are not independent: a query skips the keypoints
+ * that hold a point with Observations() > 0, among them those an earlier query of the same call has claimed (:113-115, :1596-1598),
+ * and then claims its own (:150, :1623).  The kernel resolves that with an order-preserving conflict pass whose result is the
+ * sequential one: claim[k] is the smallest index of a blocking query (q_blocks) whose current result is keypoint k, query q treats k
+ * as taken iff occupied[k] || claim[k] < q, and rounds of (every query walks against the table of the round before; the table is
+ * rebuilt) run until a round changes nothing.  `rounds` counts them, the detecting round included; it is at most n_q + 1
+ * (has the proof).  The reference is restated as it stands:
+ *   last frame  x3Dc = Rcw p + tcw; invzc = 1 / z < 0 leaves (:1553); u = fx * xc * invzc + cx, v alike; u < minX || u > maxX ||
+ *               v < minY || v > maxY leaves (:1559-1562); radius = th * scale[q_oct] (:1567); GetFeaturesInArea(u, v, radius,
+ *               q_oct - 1, q_oct + 1) (:1580, neither bForward nor bBackward with bMono); a taken keypoint is skipped; dist < bestDist is
+ *               strict (:1613); bestDist <= th_high matches (:1621); the bin of :1628-1633 in float32 with C round
+ *   local map   Pc = Rcw p + tcw; PcZ < 0 leaves (:506); the same projection and bounds tests (:513-516); dist = |p - Ow| outside
+ *               [q_dist_min, q_dist_max] (:525); viewCos = PO . Pn / dist < cos_view (:532); nPredictedLevel =
+ *               ceil(log(q_pred_max / dist) / log_scale_factor) outside 0 .. n_levels - 1 (:537); r = RadiusByViewingCos(viewCos) (2.5
+ *               when viewCos > 0.998, else 4.0), r *= th only when th != 1.0 (:67, :88); GetFeaturesInArea(u, v, r * scale[level],
+ *               level - 1, level) (:93); best and second best as :129-141; bestDist <= th_high (:145) and then the ratio test
+ *               bestLevel == bestLevel2 && bestDist > nn_ratio * bestDist2 with the product in float32 (:147)
+ *   area        Frame::GetFeaturesInArea literally: floor for the first cell and CEIL for the last one, the four early returns, the
+ *               clamps to the grid, bCheckLevels = minLevel > 0 || maxLevel >= 0, the level test INSIDE the cell loop (so an area
+ *               that holds keypoints of other levels only is empty), fabs(dx) < r && fabs(dy) < r.  Candidates come in cell order
+ *               (ix outer, iy inner) and inside a cell in list order
+ * One deviation: the reference's bounds tests are written as u < min || u > max, which a NaN projection (z == 0 with xc == 0)
+ * passes, to reach an int cast of NaN inside GetFeaturesInArea.  Here a non-finite u or v leaves with state 3.  (With th_high = 256 a
+ * query whose candidates are all taken would index mvpMapPoints with -1 in the reference; here it leaves as bestDist > th_high does.)
+ * `state` says where a query left, numbered in the order of the reference's exits.  Last-frame mode:
+ *   0  matched and kept        1  skipped (q_skip)      2  invzc < 0 (:1553)      3  outside the image (:1559-1562)
+ *   4  no keypoint in the area (:1582)      5  bestDist > th_high (:1621), every candidate taken included
+ *   6  matched, then dropped by the orientation filter (:1651-1661)
+ * Local-map mode:
+ *   0  matched      1  skipped (q_skip)      2  PcZ < 0 (:506)      3  outside the image (:513-516)      4  distance (:525)
+ *   5  viewCos < cos_view (:532)      6  level outside 0 .. n_levels - 1 (:537)      7  area empty (:96)
+ *   8  bestDist > th_high (:145)      9  failed the ratio test (:147)
+ * In local-map mode the states 0 and 7 .. 9 are exactly the points for which isInFrustum returned true (IncreaseVisible,
+ * src/Tracking.cpp:2154).  Everything but the ratio test and the bin is FP64 on the float32 inputs widened; the reference computes in
+ * float32 (gives the measured margins). */
+#define VBA_SEARCH_PROJ_LAST_FRAME 0
+#define VBA_SEARCH_PROJ_LOCAL_MAP 1
+#define VBA_SEARCH_PROJ_MAX_KEYS 16384   /* the claim table of a frame lives in LDS */
+typedef struct vba_search_proj_problem {
+    int32_t mode;                    /* VBA_SEARCH_PROJ_LAST_FRAME or VBA_SEARCH_PROJ_LOCAL_MAP */
+    int32_t check_orientation;       /* mbCheckOrientation (:1626, :1643); last-frame mode only */
+    double Rcw[9], tcw[3];           /* row-major mTcw rotation and translation (:1521-1522) / mRcw, mtcw (Frame.cpp:500) */
+    double Ow[3];                    /* mOw (Frame.cpp:523); local-map mode only */
+    double K[4];                     /* fx fy cx cy */
+    double bounds[4];                /* mnMinX mnMaxX mnMinY mnMaxY */
+    int32_t n_keys;                  /* CurrentFrame.N; at most VBA_SEARCH_PROJ_MAX_KEYS */
+    int32_t n_levels;                /* mnScaleLevels, 1 .. 64 */
+    const uint8_t *desc;             /* [n_keys][32] mDescriptors */
+    const double *uv;                /* [n_keys][2] mvKeysUn[idx].pt */
+    const uint8_t *oct;              /* [n_keys] mvKeysUn[idx].octave */
+    const float *angle;              /* [n_keys] mvKeysUn[idx].angle in [0, 360) (:1628); read with check_orientation only */
+    const double *scale;             /* [n_levels] mvScaleFactors (:93, :1567) */
+    double log_scale_factor;         /* mfLogScaleFactor (Frame.cpp:536); local-map mode only */
+    int32_t grid_cols, grid_rows;    /* FRAME_GRID_COLS, FRAME_GRID_ROWS (64 x 48); >= 1, cols * rows <= 65536 */
+    double grid_inv_w, grid_inv_h;   /* mfGridElementWidthInv, mfGridElementHeightInv */
+    const int32_t *cell_begin;       /* [cols * rows + 1] as in vba_fuse_problem */
+    const int32_t *cell_feat;        /* keypoint indices in the order mGrid[ix][iy] holds them; each keypoint at most once */
+    const uint8_t *occupied;         /* [n_keys] non-zero: mvpMapPoints[idx] && mvpMapPoints[idx]->Observations() > 0 before the call */
+    int32_t n_q;                     /* LastFrame.N / vpMapPoints.size(): the queries in the reference's loop order */
+    int32_t th_high;                 /* TH_HIGH = 100 (:145, :1621); 0 .. 256 */
+    const double *q_pos;             /* [n_q][3] GetWorldPos() */
+    const uint8_t *q_desc;           /* [n_q][32] GetDescriptor() */
+    const uint8_t *q_skip;           /* [n_q] non-zero: last-frame mode, no point or mvbOutlier (:1540-1542); local-map mode, the caller's
+                                        tests of src/Tracking.cpp:2145-2148 (mnLastFrameSeen == mnId, isBad) */
+    const uint8_t *q_blocks;         /* [n_q] non-zero: pMP->Observations() > 0, so the keypoint this query claims is taken for later ones */
+    const uint8_t *q_oct;            /* [n_q] LastFrame.mvKeys[i].octave (:1564), < n_levels; last-frame mode only */
+    const float *q_angle;            /* [n_q] LastFrame.mvKeysUn[i].angle in [0, 360) (:1628); last-frame mode with check_orientation only */
+    const double *q_normal;          /* [n_q][3] GetNormal(); local-map mode only, as the next three */
+    const double *q_dist_min, *q_dist_max; /* [n_q] GetMinDistanceInvariance(), GetMaxDistanceInvariance() as the reference returns them */
+    const double *q_pred_max;        /* [n_q] mfMaxDistance, which PredictScale reads */
+    double th;                       /* the radius factor: 15 and 30 at the retry (Tracking.cpp:1752-1766) / 1 or 5 (:2163-2169) */
+    float nn_ratio;                  /* mfNNratio, 0.8f at Tracking.cpp:2162; local-map mode only */
+    double cos_view;                 /* 0.5 (Tracking.cpp:2151); local-map mode only */
+} vba_search_proj_problem;
+
+typedef struct vba_search_proj_result {
+    int32_t status;           /* VBA_OK */
+    int32_t n_matches;        /* the return value of the function */
+    int32_t n_before_filter;  /* nmatches in front of the orientation filter (:1643); n_matches without one */
+    int32_t hist[30];         /* rotHist[i].size() in front of the filter (zeros without check_orientation) */
+    int32_t ind[3];           /* ind1 .. ind3 of ComputeThreeMaxima, -1 as the reference leaves them (and without check_orientation) */
+    int32_t rounds;           /* rounds of the conflict pass, 1 .. n_q + 1 */
+    int32_t *best_idx;        /* [n_q] caller-allocated: bestIdx as the candidate loop left it, -1 without a candidate */
+    uint16_t *best_dist;      /* [n_q] caller-allocated: bestDist; 256 = none */
+    uint16_t *best_dist2;     /* [n_q] caller-allocated: bestDist2 (local-map mode; 256 in last-frame mode) */
+    int8_t *level;            /* [n_q] caller-allocated: local-map mode, nPredictedLevel (mnTrackScaleLevel) for the states 0 and 7 .. 9, the
+                                 out-of-range value itself clamped to int8 for state 6; -128 otherwise and in last-frame mode */
+    double *view_cos;         /* [n_q] caller-allocated: local-map mode, mTrackViewCos for the states 0 and 5 .. 9; NaN otherwise */
+    double *uv;               /* [n_q][2] caller-allocated: the projection (mTrackProjX / Y) for every state but 1 and 2, NaN there */
+    uint8_t *bin;             /* [n_q] caller-allocated: the histogram bin of a match (states 0 and 6) with check_orientation; 255 = none */
+    uint8_t *state;           /* [n_q] caller-allocated: the codes above */
+    int32_t *key_match;       /* [n_keys] caller-allocated: what the function leaves in mvpMapPoints, as a query index: -1 untouched,
+                                 -2 cleared by the orientation filter (:1657), else the last query that wrote the keypoint */
+} vba_search_proj_result;
+
+/* Synchronous, like vba_fuse; -1 while asynchronous tickets are pending.  n_problems == 0 returns 0; a problem with n_q == 0 or
+ * n_keys == 0 is legal.  A bad problem fails the whole call before any GPU work, with nothing written, as
+ * "vba_search_by_projection: problem K: <why>" through vba_last_error: a NULL problem or result, an unknown mode, a negative count,
+ * n_keys above VBA_SEARCH_PROJ_MAX_KEYS, a NULL array with a non-zero count (the per-query result arrays are required when n_q > 0,
+ * key_match when n_keys > 0; the arrays of the other mode may be NULL), n_levels outside 1 .. 64, an octave >= n_levels, th_high
+ * outside 0 .. 256, grid sizes outside their range, a cell_begin that does not start at 0, decreases or ends above n_keys, a
+ * cell_feat entry out of range or listed twice, with check_orientation an angle outside [0, 360), any non-finite pose, intrinsic,
+ * bound, pixel, level table, position, normal, distance or threshold that the mode reads.  A problem's outputs do not depend on
+ * where it stands in the batch. */
+int vba_search_by_projection(void *handle, int32_t n_problems, vba_search_proj_problem *const *in, vba_search_proj_result *const *out);
 
 /* ---- essential-graph optimisation (Sim3 pose graph) ----
  * Optimizer::OptimizeEssentialGraph(Map*, KeyFrame* pLoopKF, KeyFrame* pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections,

@@ -1259,6 +1259,180 @@ class SearchSim3ResultBuf:
                                 self.st[1][:n2].copy(), self.m12[:n1].copy())
 
 
+# ---- projection matching for tracking (include/vislam_ba.h: vba_search_proj_problem / vba_search_proj_result) ----
+_pf = C.POINTER(C.c_float)
+SEARCH_PROJ_LAST_FRAME, SEARCH_PROJ_LOCAL_MAP = 0, 1
+SEARCH_PROJ_MAX_KEYS = 16384
+
+
+class vba_search_proj_problem(C.Structure):
+    _fields_ = [
+        ("mode", C.c_int32), ("check_orientation", C.c_int32), ("Rcw", C.c_double * 9), ("tcw", C.c_double * 3), ("Ow", C.c_double * 3),
+        ("K", C.c_double * 4), ("bounds", C.c_double * 4), ("n_keys", C.c_int32), ("n_levels", C.c_int32), ("desc", _pu8), ("uv", _pd),
+        ("oct", _pu8), ("angle", _pf), ("scale", _pd), ("log_scale_factor", C.c_double), ("grid_cols", C.c_int32), ("grid_rows", C.c_int32),
+        ("grid_inv_w", C.c_double), ("grid_inv_h", C.c_double), ("cell_begin", _pi), ("cell_feat", _pi), ("occupied", _pu8),
+        ("n_q", C.c_int32), ("th_high", C.c_int32), ("q_pos", _pd), ("q_desc", _pu8), ("q_skip", _pu8), ("q_blocks", _pu8), ("q_oct", _pu8),
+        ("q_angle", _pf), ("q_normal", _pd), ("q_dist_min", _pd), ("q_dist_max", _pd), ("q_pred_max", _pd), ("th", C.c_double),
+        ("nn_ratio", C.c_float), ("cos_view", C.c_double),
+    ]
+
+
+class vba_search_proj_result(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_matches", C.c_int32), ("n_before_filter", C.c_int32), ("hist", C.c_int32 * 30), ("ind", C.c_int32 * 3),
+                ("rounds", C.c_int32), ("best_idx", _pi), ("best_dist", _pu16), ("best_dist2", _pu16), ("level", _pi8), ("view_cos", _pd), ("uv", _pd),
+                ("bin", _pu8), ("state", _pu8), ("key_match", _pi)]
+
+
+# the states of the two modes
+(SPL_MATCHED, SPL_SKIPPED, SPL_BEHIND, SPL_NOT_IN_IMAGE, SPL_EMPTY_AREA, SPL_NO_MATCH, SPL_ROTATION) = range(7)
+(SPM_MATCHED, SPM_SKIPPED, SPM_BEHIND, SPM_NOT_IN_IMAGE, SPM_DISTANCE, SPM_VIEW_ANGLE, SPM_LEVEL, SPM_EMPTY_AREA, SPM_NO_MATCH, SPM_RATIO) = range(10)
+
+
+@dataclass
+class SearchProjProblem:
+    """One call of a tracking matcher as flat arrays: one frame with its grid in CSR form and one ORDERED list of queries.  mode
+    SEARCH_PROJ_LAST_FRAME is ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) (src/ORBmatcher.cpp:1511-1665), mode
+    SEARCH_PROJ_LOCAL_MAP is Frame::isInFrustum with SearchByProjection(F, vpMapPoints, th) (:63-156).  The arrays of the other mode
+    may stay None."""
+    mode: int
+    Rcw: np.ndarray                # [3,3]
+    tcw: np.ndarray                # [3]
+    K: np.ndarray                  # [4] fx fy cx cy
+    bounds: np.ndarray             # [4] mnMinX mnMaxX mnMinY mnMaxY
+    desc: np.ndarray               # [n_keys,32] uint8
+    uv: np.ndarray                 # [n_keys,2]
+    oct: np.ndarray                # [n_keys] uint8
+    scale: np.ndarray              # [n_levels]
+    grid_cols: int
+    grid_rows: int
+    grid_inv_w: float
+    grid_inv_h: float
+    cell_begin: np.ndarray         # [cols * rows + 1] int32
+    cell_feat: np.ndarray          # int32
+    occupied: np.ndarray           # [n_keys] uint8
+    q_pos: np.ndarray              # [n_q,3]
+    q_desc: np.ndarray             # [n_q,32] uint8
+    q_skip: np.ndarray             # [n_q] uint8
+    q_blocks: np.ndarray           # [n_q] uint8
+    th: float = 15.0
+    th_high: int = 100
+    Ow: np.ndarray = None          # [3] local-map mode
+    log_scale_factor: float = 0.0
+    angle: np.ndarray = None       # [n_keys] float32, last-frame mode with check_orientation
+    q_oct: np.ndarray = None       # [n_q] uint8, last-frame mode
+    q_angle: np.ndarray = None     # [n_q] float32
+    q_normal: np.ndarray = None    # [n_q,3] local-map mode, as the next three
+    q_dist_min: np.ndarray = None
+    q_dist_max: np.ndarray = None
+    q_pred_max: np.ndarray = None
+    nn_ratio: float = 0.8
+    cos_view: float = 0.5
+    check_orientation: bool = True
+    truth: dict = field(default_factory=dict)
+
+    def __post_init__(self):
+        u8 = lambda a, shape: np.ascontiguousarray(a, dtype=np.uint8).reshape(shape)
+        opt = lambda a, f, *s: None if a is None else f(a, *s)
+        f32 = lambda a, shape: np.ascontiguousarray(a, dtype=np.float32).reshape(shape)
+        self.Rcw = _f64(self.Rcw, (3, 3)); self.tcw = _f64(self.tcw, (3,)); self.Ow = _f64(np.zeros(3) if self.Ow is None else self.Ow, (3,))
+        self.K = _f64(self.K, (4,)); self.bounds = _f64(self.bounds, (4,))
+        self.desc = u8(self.desc, (-1, 32)); self.oct = u8(self.oct, (-1,)); self.uv = _f64(self.uv, (-1, 2))
+        self.scale = _f64(self.scale, (-1,)); self.occupied = u8(self.occupied, (-1,))
+        self.cell_begin = _i32(self.cell_begin).reshape(-1); self.cell_feat = _i32(self.cell_feat).reshape(-1)
+        self.q_pos = _f64(self.q_pos, (-1, 3)); self.q_desc = u8(self.q_desc, (-1, 32))
+        self.q_skip = u8(self.q_skip, (-1,)); self.q_blocks = u8(self.q_blocks, (-1,))
+        self.angle = opt(self.angle, f32, (-1,)); self.q_angle = opt(self.q_angle, f32, (-1,)); self.q_oct = opt(self.q_oct, u8, (-1,))
+        self.q_normal = opt(self.q_normal, _f64, (-1, 3))
+        self.q_dist_min = opt(self.q_dist_min, _f64, (-1,)); self.q_dist_max = opt(self.q_dist_max, _f64, (-1,))
+        self.q_pred_max = opt(self.q_pred_max, _f64, (-1,))
+        self.nn_ratio = float(np.float32(self.nn_ratio))
+
+    n_keys = property(lambda self: self.desc.shape[0])
+    n_q = property(lambda self: self.q_pos.shape[0])
+    n_levels = property(lambda self: self.scale.shape[0])
+    local = property(lambda self: self.mode == SEARCH_PROJ_LOCAL_MAP)
+
+    def copy(self, **changes):
+        import copy as _c
+        q = _c.copy(self)
+        for k, v in changes.items():
+            setattr(q, k, v)
+        q.__post_init__()
+        return q
+
+    def as_struct(self) -> vba_search_proj_problem:
+        s = vba_search_proj_problem()
+        p = lambda a, t: None if a is None else a.ctypes.data_as(t)
+        s.mode, s.check_orientation = int(self.mode), int(bool(self.check_orientation))
+        s.Rcw[:] = self.Rcw.ravel().tolist(); s.tcw[:] = self.tcw.tolist(); s.Ow[:] = self.Ow.tolist()
+        s.K[:] = self.K.tolist(); s.bounds[:] = self.bounds.tolist()
+        s.n_keys, s.n_levels, s.n_q = self.n_keys, self.n_levels, self.n_q
+        s.desc, s.uv, s.oct, s.angle, s.scale = p(self.desc, _pu8), p(self.uv, _pd), p(self.oct, _pu8), p(self.angle, _pf), p(self.scale, _pd)
+        s.log_scale_factor = float(self.log_scale_factor)
+        s.grid_cols, s.grid_rows, s.grid_inv_w, s.grid_inv_h = int(self.grid_cols), int(self.grid_rows), float(self.grid_inv_w), float(self.grid_inv_h)
+        s.cell_begin, s.cell_feat, s.occupied = p(self.cell_begin, _pi), p(self.cell_feat, _pi), p(self.occupied, _pu8)
+        s.q_pos, s.q_desc, s.q_skip, s.q_blocks = p(self.q_pos, _pd), p(self.q_desc, _pu8), p(self.q_skip, _pu8), p(self.q_blocks, _pu8)
+        s.q_oct, s.q_angle, s.q_normal = p(self.q_oct, _pu8), p(self.q_angle, _pf), p(self.q_normal, _pd)
+        s.q_dist_min, s.q_dist_max, s.q_pred_max = p(self.q_dist_min, _pd), p(self.q_dist_max, _pd), p(self.q_pred_max, _pd)
+        s.th, s.th_high, s.nn_ratio, s.cos_view = float(self.th), int(self.th_high), float(self.nn_ratio), float(self.cos_view)
+        return s
+
+
+@dataclass
+class SearchProjResult:
+    status: int
+    n_matches: int
+    n_before_filter: int
+    hist: np.ndarray                # [30]
+    ind: np.ndarray                 # [3]
+    rounds: int
+    best_idx: np.ndarray            # [n_q] int32
+    best_dist: np.ndarray           # [n_q] uint16
+    best_dist2: np.ndarray          # [n_q] uint16
+    level: np.ndarray               # [n_q] int8
+    view_cos: np.ndarray            # [n_q]
+    uv: np.ndarray                  # [n_q,2]
+    bin: np.ndarray                 # [n_q] uint8
+    state: np.ndarray               # [n_q] uint8
+    key_match: np.ndarray           # [n_keys] int32
+
+
+class SearchProjResultBuf:
+    """Caller-allocated result storage of one problem."""
+
+    def __init__(self, p: SearchProjProblem):
+        self.n, self.nk = p.n_q, p.n_keys
+        m, mk = max(self.n, 1), max(self.nk, 1)
+        self.bi = np.full(m, -7, dtype=np.int32)
+        self.bd = np.full(m, 7, dtype=np.uint16)
+        self.bd2 = np.full(m, 7, dtype=np.uint16)
+        self.lv = np.full(m, 77, dtype=np.int8)
+        self.vc = np.full(m, -7.0)
+        self.uv = np.full((m, 2), -7.0)
+        self.bn = np.full(m, 77, dtype=np.uint8)
+        self.st = np.full(m, 255, dtype=np.uint8)
+        self.km = np.full(mk, -7, dtype=np.int32)
+        s = self.s = vba_search_proj_result()
+        s.status, s.n_matches, s.n_before_filter, s.rounds = -7, -7, -7, -7
+        s.best_idx, s.best_dist, s.best_dist2, s.level = (self.bi.ctypes.data_as(_pi), self.bd.ctypes.data_as(_pu16), self.bd2.ctypes.data_as(_pu16),
+                                                          self.lv.ctypes.data_as(_pi8))
+        s.view_cos, s.uv, s.bin, s.state, s.key_match = (self.vc.ctypes.data_as(_pd), self.uv.ctypes.data_as(_pd), self.bn.ctypes.data_as(_pu8),
+                                                         self.st.ctypes.data_as(_pu8), self.km.ctypes.data_as(_pi))
+
+    def untouched(self):
+        """nothing was written since construction"""
+        s = self.s
+        return ((s.status, s.n_matches, s.n_before_filter, s.rounds) == (-7, -7, -7, -7) and (self.bi == -7).all() and (self.bd == 7).all() and
+                (self.bd2 == 7).all() and (self.lv == 77).all() and (self.vc == -7.0).all() and (self.uv == -7.0).all() and (self.bn == 77).all() and
+                (self.st == 255).all() and (self.km == -7).all() and not any(s.hist[:]) and not any(s.ind[:]))
+
+    def get(self) -> SearchProjResult:
+        s, n = self.s, self.n
+        return SearchProjResult(s.status, s.n_matches, s.n_before_filter, np.array(s.hist[:]), np.array(s.ind[:]), s.rounds, self.bi[:n].copy(),
+                                self.bd[:n].copy(), self.bd2[:n].copy(), self.lv[:n].copy(), self.vc[:n].copy(), self.uv[:n].copy(), self.bn[:n].copy(),
+                                self.st[:n].copy(), self.km[:self.nk].copy())
+
+
 # ---- essential-graph optimisation (include/vislam_ba.h: vba_posegraph_problem / vba_posegraph_result) ----
 class vba_posegraph_problem(C.Structure):
     _fields_ = [

@@ -56,6 +56,8 @@ int make_handle(int device, Handle* parent, Handle** out) {
     // the back-substitution keeps x (nS doubles) in LDS: maps of more than ~5 600 pose dofs need more than the default 64 KiB
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_trsv), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_trsv_p), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    // the claim table of k_search_proj (VBA_SP_MAX_KEYS int32) beside its static LDS
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_search_proj), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (VBA_SP_MAX_KEYS + 1));
     (void)hipEventCreateWithFlags(&h->up_done, hipEventDisableTiming);
     memset(&h->prof, 0, sizeof h->prof);
     *out = h;

@@ -1,5 +1,5 @@
 // vba_host_small.h -- host side of the library, part 5: the small-problem entry points.  vba_preintegrate copies straight from and
-// to the caller's arrays.  The other nine are one driver, run_small, over the call object of their topic (PoseCall, Sim3Call, ...:
+// to the caller's arrays.  The other ten are one driver, run_small, over the call object of their topic (PoseCall, Sim3Call, ...:
 // plain C++, vba_host_<topic>.h), which knows what is refused, the arena, the packing, the kernel's argument and the write-back;
 // what an entry point adds here is the launch of its kernel.  No entry point shares its arena (Handle::side) with another.
 #pragma once
@@ -11,6 +11,7 @@
 #include "vba_host_search_tri.h"
 #include "vba_host_fuse.h"
 #include "vba_host_search_sim3.h"
+#include "vba_host_search_proj.h"
 #include "vba_host_posegraph.h"
 
 namespace {
@@ -147,6 +148,17 @@ int search_by_sim3(Handle* h, int32_t n_pairs, vba_search_sim3_problem* const* i
     vba_host::SearchSim3Call C;
     return run_small(h, SIDE_SEARCH_SIM3, "vba_search_by_sim3", C, n_pairs, in, out,
                      [h](const SsBatch& B, unsigned g) { VBA_LAUNCH(k_search_sim3, dim3(g), dim3(SS_NT), 0, h->stream, B); });
+}
+
+// Both tracking matchers, ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, ...) (src/ORBmatcher.cpp:1511-1665) and
+// Frame::isInFrustum with SearchByProjection(F, vpMapPoints, th) (:63-156), monocular, for a batch of (frame, ordered query list)
+// problems: the claim table of a workgroup is dynamic LDS sized to the call's largest frame; the apply loop is replayed in the
+// write-back
+int search_by_projection(Handle* h, int32_t n_problems, vba_search_proj_problem* const* in, vba_search_proj_result* const* out) {
+    vba_host::SearchProjCall C;
+    return run_small(h, SIDE_SEARCH_PROJ, "vba_search_by_projection", C, n_problems, in, out, [h, &C](const SpBatch& B, unsigned g) {
+        VBA_LAUNCH(k_search_proj, dim3(g), dim3(SP_NT), C.lds_bytes(), h->stream, B);
+    });
 }
 
 // what vba_debug_posegraph_system asks of a run: graph 0 stops after the solve of its first trial, and H, b, x come back

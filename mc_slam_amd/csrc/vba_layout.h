@@ -351,6 +351,48 @@ struct SsBatch {
     signed char* level;          // ...
     unsigned char* state;        // ...
 };
+// vba_search_by_projection (vba_search_proj.h); the frame's keypoints reuse FuKey
+#define VBA_SP_NT 256          // lanes of the one workgroup of a problem
+#define VBA_SP_MAX_KEYS 16384  // the claim table of a problem is n_keys int32 in LDS
+#define VBA_SP_CONST 28        // doubles of a problem's constants: Rcw (9) tcw (3) Ow (3) K (4) bounds (4) grid_inv_w grid_inv_h
+                               // log_scale_factor th cos_view
+struct alignas(16) SpQuery {   // one query (a keypoint of the last frame or a local map point), 112 bytes
+    unsigned int d[8];         // GetDescriptor()
+    double pos[3], normal[3];
+    double dist_min, dist_max, pred_max;
+    unsigned char skip, blocks, oct;   // oct: LastFrame.mvKeys[i].octave (last-frame mode)
+    unsigned char pad[5];
+};
+struct SpDesc {
+    long long key0, q0, cell0, feat0, lev0;   // offsets of the problem's keypoint records (and occupied flags), query records (and
+                                              // outputs), cell_begin copy, cell_feat copy and scale table in the concatenated arrays
+    int n_keys, n_q, n_levels, th_high;
+    int cols, rows, mode, pad0;
+    float nn_ratio;
+    int pad1;
+    double c[VBA_SP_CONST];
+};
+static_assert(sizeof(SpQuery) == 112 && sizeof(SpDesc) == 304, "scripts/search_proj_bench.py derives the copied bytes from these sizes");
+struct SpBatch {
+    const SpDesc* desc;
+    const FuKey* key;            // keypoint records of all problems
+    const unsigned char* occupied;   // [total keypoints]
+    const SpQuery* query;        // query records of all problems
+    const int* cell_begin;       // cell_begin of all problems
+    const int* cell_feat;        // cell_feat of all problems
+    const double* lev;           // scale tables of all problems
+    int* rounds;                 // [problems]
+    int* best_idx;               // [total queries]
+    unsigned short* best_dist;   // ...
+    unsigned short* best_dist2;  // ...
+    signed char* level;          // ...
+    double* view_cos;            // ...
+    double* uv;                  // [total queries][2]
+    unsigned char* state;        // [total queries]
+    double* rad;                 // [total queries] device only: the radius of the area
+    int* prev;                   // [total queries] device only: -2 the query never reaches the area, else the keypoint it claimed in
+                                 // the round before (-1: none)
+};
 // vba_posegraph_optimize (vba_posegraph.h)
 struct PgDesc {
     int nv, ne, nf, npair;

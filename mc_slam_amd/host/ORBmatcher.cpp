@@ -4,7 +4,10 @@
 // (:958-1254, monocular) over vba_fuse: the keyframe with its grid in CSR form and the point list as flat arrays, ONE call for the
 // search, then the reference's apply loop in list order on the live map.  And ORBmatcher::SearchBySim3 (:1258-1496, monocular) over
 // vba_search_by_sim3: both keyframes as flat arrays with their own map points per keypoint, the vbAlreadyMatched flags of
-// :1291-1301, ONE call, vpMatches12 from the agreed matches.
+// :1291-1301, ONE call, vpMatches12 from the agreed matches.  And the two tracking matchers, SearchByProjection(F, vpMapPoints, th)
+// (:63-156, fused with Frame::isInFrustum) and SearchByProjection(CurrentFrame, LastFrame, th, bMono) (:1511-1665), over
+// vba_search_by_projection: the frame with its grid in CSR form and its occupied flags, the ordered queries, ONE call, then key_match
+// applied to mvpMapPoints.
 #include "ORBmatcher.h"
 
 #include <cstring>
@@ -403,6 +406,197 @@ int ORBmatcher::SearchBySim3(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoin
     for (size_t i1 = 0; i1 < N1; i1++)
         if (match12[i1] >= 0) vpMatches12[i1] = vpMapPoints2[(size_t)match12[i1]];   // :1489
     return R.n_found;
+}
+
+namespace {
+// One vba_search_by_projection problem over a Frame: its keypoints, grid and occupied flags, and the call.  The caller fills the
+// query arrays and the mode's fields of P in front of run(); afterwards key_match is applied to F.mvpMapPoints
+struct ProjSearch {
+    vba_search_proj_problem P{};
+    vba_search_proj_result R{};
+    std::vector<double> uv, scale;
+    std::vector<uint8_t> oct, occupied;
+    std::vector<float> angle;
+    std::vector<int32_t> cell_begin, cell_feat, key_match, best_idx;
+    std::vector<uint16_t> best_dist, best_dist2;
+    std::vector<int8_t> level;
+    std::vector<double> view_cos, puv;
+    std::vector<uint8_t> bin, state;
+    bool frame(const char* who, Frame& F) {
+        const size_t nk = (size_t)F.N;
+        if (nk != F.mvKeysUn.size() || F.mDescriptors.size() != 32 * nk || F.mvpMapPoints.size() != nk || F.mvuRight.size() != nk) {
+            std::cerr << who << ": N, mvKeysUn, mvuRight, mvpMapPoints and mDescriptors of the frame disagree" << std::endl;
+            return false;
+        }
+        if (F.mnScaleLevels < 1 || F.mvScaleFactors.size() != (size_t)F.mnScaleLevels) {
+            std::cerr << who << ": mnScaleLevels and mvScaleFactors of the frame disagree" << std::endl;
+            return false;
+        }
+        if (F.mnGridCols < 1 || F.mnGridRows < 1 || F.mGrid.size() != (size_t)F.mnGridCols) {
+            std::cerr << who << ": the frame has no grid" << std::endl;
+            return false;
+        }
+        uv.resize(2 * nk); oct.resize(nk); occupied.resize(nk); angle.resize(nk);
+        for (size_t i = 0; i < nk; i++) {
+            const KeyPoint& kp = F.mvKeysUn[i];
+            if (F.mvuRight[i] >= 0) {
+                std::cerr << who << ": the frame has a stereo keypoint (the backend is monocular)" << std::endl;
+                return false;
+            }
+            if (kp.octave < 0 || kp.octave > 255) {
+                std::cerr << who << ": a keypoint's octave is outside 0 .. 255" << std::endl;
+                return false;
+            }
+            uv[2 * i] = kp.pt.x; uv[2 * i + 1] = kp.pt.y; oct[i] = (uint8_t)kp.octave; angle[i] = kp.angle;
+            occupied[i] = F.mvpMapPoints[i] && F.mvpMapPoints[i]->Observations() > 0;   // :113-115, :1596-1598 in front of the call
+        }
+        cell_begin.assign(1, 0);
+        for (int ix = 0; ix < F.mnGridCols; ix++)
+            for (int iy = 0; iy < F.mnGridRows; iy++) {
+                if (F.mGrid[(size_t)ix].size() != (size_t)F.mnGridRows) {
+                    std::cerr << who << ": the frame has no grid" << std::endl;
+                    return false;
+                }
+                for (size_t idx : F.mGrid[(size_t)ix][(size_t)iy]) cell_feat.push_back((int32_t)idx);
+                cell_begin.push_back((int32_t)cell_feat.size());
+            }
+        scale.assign(F.mvScaleFactors.begin(), F.mvScaleFactors.end());
+        P.K[0] = F.fx; P.K[1] = F.fy; P.K[2] = F.cx; P.K[3] = F.cy;
+        P.bounds[0] = F.mnMinX; P.bounds[1] = F.mnMaxX; P.bounds[2] = F.mnMinY; P.bounds[3] = F.mnMaxY;
+        P.n_keys = F.N; P.n_levels = F.mnScaleLevels;
+        P.desc = F.mDescriptors.data(); P.uv = uv.data(); P.oct = oct.data(); P.angle = angle.data(); P.scale = scale.data();
+        P.log_scale_factor = F.mfLogScaleFactor;
+        P.grid_cols = F.mnGridCols; P.grid_rows = F.mnGridRows; P.grid_inv_w = F.mfGridElementWidthInv; P.grid_inv_h = F.mfGridElementHeightInv;
+        P.cell_begin = cell_begin.data(); P.cell_feat = cell_feat.data(); P.occupied = occupied.data();
+        P.th_high = ORBmatcher::TH_HIGH;
+        key_match.assign(nk, -1);
+        R.key_match = key_match.data();
+        return true;
+    }
+    bool run(const char* who, size_t nq) {
+        P.n_q = (int32_t)nq;
+        best_idx.assign(nq, -1); best_dist.assign(nq, 256); best_dist2.assign(nq, 256); level.assign(nq, -128); view_cos.assign(nq, 0.0); puv.assign(2 * nq, 0.0);
+        bin.assign(nq, 255); state.assign(nq, 1);
+        R.best_idx = best_idx.data(); R.best_dist = best_dist.data(); R.best_dist2 = best_dist2.data(); R.level = level.data(); R.view_cos = view_cos.data();
+        R.uv = puv.data(); R.bin = bin.data(); R.state = state.data();
+        vba_search_proj_problem* pp = &P;
+        vba_search_proj_result* pr = &R;
+        void* h = Optimizer::BackendHandle();
+        if (!h || vba_search_by_projection(h, 1, &pp, &pr) != 0) {
+            std::cerr << who << ": " << (h ? vba_last_error(h) : "no HIP device (the backend has no CPU path)") << std::endl;
+            return false;
+        }
+        return true;
+    }
+    // what the function leaves in mvpMapPoints: the last query that wrote a keypoint, NULL where the orientation filter cleared it
+    void apply(Frame& F, const std::vector<MapPoint*>& queries) const {
+        for (size_t k = 0; k < key_match.size(); k++) {
+            if (key_match[k] >= 0) F.mvpMapPoints[k] = queries[(size_t)key_match[k]];
+            else if (key_match[k] == -2) F.mvpMapPoints[k] = nullptr;
+        }
+    }
+};
+
+// the per-point arrays both modes read
+struct ProjQueries {
+    std::vector<double> pos, normal, dmin, dmax, pmax;
+    std::vector<uint8_t> desc, skip, blocks;
+    explicit ProjQueries(size_t n) : pos(3 * n), normal(3 * n), dmin(n), dmax(n), pmax(n), desc(32 * n), skip(n, 1), blocks(n) {}
+    void point(size_t i, MapPoint* pMP) {
+        pMP->GetWorldPos(&pos[3 * i]);
+        pMP->GetNormal(&normal[3 * i]);
+        dmin[i] = pMP->GetMinDistanceInvariance(); dmax[i] = pMP->GetMaxDistanceInvariance(); pmax[i] = pMP->mfMaxDistance;
+        std::memcpy(&desc[32 * i], pMP->GetDescriptor(), 32);
+        blocks[i] = pMP->Observations() > 0;
+    }
+    void bind(vba_search_proj_problem& P) const {
+        P.q_pos = pos.data(); P.q_desc = desc.data(); P.q_skip = skip.data(); P.q_blocks = blocks.data();
+        P.q_normal = normal.data(); P.q_dist_min = dmin.data(); P.q_dist_max = dmax.data(); P.q_pred_max = pmax.data();
+    }
+};
+}  // namespace
+
+int SearchLocalMap(const char* who, Frame& F, const std::vector<MapPoint*>& vpMapPoints, const std::vector<uint8_t>& skip, float th, float nnratio,
+                   int* in_view) {
+    ProjSearch s;
+    if (!s.frame(who, F)) return -1;
+    const size_t n = vpMapPoints.size();
+    ProjQueries q(n);
+    for (size_t i = 0; i < n; i++) {
+        q.skip[i] = skip[i];
+        if (!skip[i]) q.point(i, vpMapPoints[i]);
+    }
+    q.bind(s.P);
+    s.P.mode = VBA_SEARCH_PROJ_LOCAL_MAP;
+    for (int i = 0; i < 9; i++) s.P.Rcw[i] = F.mRcw[i];
+    for (int i = 0; i < 3; i++) { s.P.tcw[i] = F.mtcw[i]; s.P.Ow[i] = F.mOw[i]; }
+    s.P.th = th; s.P.nn_ratio = nnratio; s.P.cos_view = 0.5;
+    if (!s.run(who, n)) return -1;
+    int seen = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (skip[i]) continue;
+        MapPoint* pMP = vpMapPoints[i];
+        const int st = s.state[i];
+        pMP->mbTrackInView = st == 0 || st >= 7;                  // Frame.cpp:494, :541-546
+        if (!pMP->mbTrackInView) continue;
+        pMP->mTrackProjX = (float)s.puv[2 * i]; pMP->mTrackProjY = (float)s.puv[2 * i + 1];
+        pMP->mnTrackScaleLevel = s.level[i]; pMP->mTrackViewCos = (float)s.view_cos[i];
+        seen++;
+    }
+    if (in_view) *in_view = seen;
+    s.apply(F, vpMapPoints);
+    return s.R.n_matches;
+}
+
+int ORBmatcher::SearchByProjection(Frame& F, const std::vector<MapPoint*>& vpMapPoints, const float th) {
+    std::vector<uint8_t> skip(vpMapPoints.size());
+    for (size_t i = 0; i < vpMapPoints.size(); i++) {
+        MapPoint* pMP = vpMapPoints[i];
+        skip[i] = !pMP || !pMP->mbTrackInView || pMP->isBad();    // :74-78
+    }
+    return SearchLocalMap("ORBmatcher::SearchByProjection", F, vpMapPoints, skip, th, mfNNratio, nullptr);
+}
+
+int ORBmatcher::SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, const float th, const bool bMono) {
+    const char* who = "ORBmatcher::SearchByProjection (last frame)";
+    if (!bMono) {
+        std::cerr << who << ": bMono is false (the backend is monocular)" << std::endl;
+        return -1;
+    }
+    const size_t n = (size_t)LastFrame.N;
+    if (LastFrame.mvpMapPoints.size() != n || LastFrame.mvbOutlier.size() != n || LastFrame.mvKeys.size() != n || LastFrame.mvKeysUn.size() != n) {
+        std::cerr << who << ": N, mvKeys, mvKeysUn, mvpMapPoints and mvbOutlier of the last frame disagree" << std::endl;
+        return -1;
+    }
+    ProjSearch s;
+    if (!s.frame(who, CurrentFrame)) return -1;
+    ProjQueries q(n);
+    std::vector<uint8_t> q_oct(n);
+    std::vector<float> q_angle(n);
+    for (size_t i = 0; i < n; i++) {
+        MapPoint* pMP = LastFrame.mvpMapPoints[i];
+        q.skip[i] = !pMP || LastFrame.mvbOutlier[i];              // :1540-1542
+        if (q.skip[i]) continue;
+        if (LastFrame.mvKeys[i].octave < 0 || LastFrame.mvKeys[i].octave > 255) {
+            std::cerr << who << ": a keypoint's octave is outside 0 .. 255" << std::endl;
+            return -1;
+        }
+        q.point(i, pMP);
+        q_oct[i] = (uint8_t)LastFrame.mvKeys[i].octave;           // :1564
+        q_angle[i] = LastFrame.mvKeysUn[i].angle;                 // :1628
+    }
+    q.bind(s.P);
+    s.P.q_oct = q_oct.data(); s.P.q_angle = q_angle.data();
+    s.P.mode = VBA_SEARCH_PROJ_LAST_FRAME;
+    s.P.check_orientation = mbCheckOrientation ? 1 : 0;
+    for (int i = 0; i < 3; i++) {                                 // :1521-1522
+        for (int j = 0; j < 3; j++) s.P.Rcw[3 * i + j] = CurrentFrame.mTcw[4 * i + j];
+        s.P.tcw[i] = CurrentFrame.mTcw[4 * i + 3];
+    }
+    s.P.th = th;
+    if (!s.run(who, n)) return -1;
+    s.apply(CurrentFrame, LastFrame.mvpMapPoints);
+    return s.R.n_matches;
 }
 
 }  // namespace ORB_SLAM2

@@ -1,6 +1,8 @@
 // ORBmatcher.h -- the reference's ORBmatcher (include/ORBmatcher.h) as far as this backend carries it: SearchForTriangulation
 // (src/ORBmatcher.cpp:760-955, monocular) over vba_search_triangulation, both Fuse overloads (:958-1254, monocular) over vba_fuse and
-// SearchBySim3 (:1258-1496, monocular) over vba_search_by_sim3.  The other searches stay matcher code of the caller.
+// SearchBySim3 (:1258-1496, monocular) over vba_search_by_sim3, and the two tracking matchers SearchByProjection(F, vpMapPoints, th)
+// (:63-156) and SearchByProjection(CurrentFrame, LastFrame, th, bMono) (:1511-1665) over vba_search_by_projection.  The other searches
+// stay matcher code of the caller.
 #pragma once
 #include <array>
 #include <cstdint>
@@ -41,6 +43,16 @@ public:
     // the wrong size or a keyframe has a stereo keypoint (this backend is monocular), with a message on std::cerr
     int SearchBySim3(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoint*>& vpMatches12, const float& s12, const Mat3f& R12,
                      const std::array<float, 3>& t12, const float th);
+    // src/ORBmatcher.cpp:63-156: the points of vpMapPoints that are in view (mbTrackInView, not bad) matched to the keypoints of F, best
+    // against second best with mfNNratio; a match is written into F.mvpMapPoints.  ONE vba_search_by_projection call in local-map
+    // mode: the entry point is fused with Frame::isInFrustum, so the projection, mnTrackScaleLevel and mTrackViewCos are formed again
+    // from F's pose (what isInFrustum(pMP, 0.5) stored for this frame) instead of read from the point.  Returns nmatches, -1 when the
+    // backend failed or F has a stereo keypoint (this backend is monocular), with a message on std::cerr
+    int SearchByProjection(Frame& F, const std::vector<MapPoint*>& vpMapPoints, const float th = 3);
+    // src/ORBmatcher.cpp:1511-1665: the map points of LastFrame projected into CurrentFrame with the octave window of the monocular
+    // case, then the orientation filter.  ONE vba_search_by_projection call in last-frame mode.  Returns nmatches, -1 when the backend
+    // failed, bMono is false or CurrentFrame has a stereo keypoint
+    int SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, const float th, const bool bMono);
     // vbAlreadyMatched1 / vbAlreadyMatched2 of :1287-1301: a keypoint of pKF1 with a prior match, and the keypoint of pKF2 where
     // GetIndexInKeyFrame finds that match
     static void AlreadyMatched(KeyFrame* pKF1, KeyFrame* pKF2, const std::vector<MapPoint*>& vpMatches12, std::vector<uint8_t>& vb1,
@@ -50,5 +62,12 @@ protected:
     float mfNNratio;
     bool mbCheckOrientation;
 };
+
+// What SearchByProjection(F, vpMapPoints, th) and Tracking::SearchLocalPoints share: ONE vba_search_by_projection call in local-map
+// mode over the points whose skip flag is 0.  On success every such point has mbTrackInView as Frame::isInFrustum(pMP, 0.5) leaves it
+// and, when in view, mTrackProjX / Y, mnTrackScaleLevel and mTrackViewCos; *in_view counts them; the matches are in F.mvpMapPoints.
+// Returns nmatches, -1 when the backend failed or F has a stereo keypoint, with a message that starts with `who` on std::cerr
+int SearchLocalMap(const char* who, Frame& F, const std::vector<MapPoint*>& vpMapPoints, const std::vector<uint8_t>& skip, float th, float nnratio,
+                   int* in_view);
 
 }  // namespace ORB_SLAM2

@@ -10,6 +10,7 @@
 #include "Sim3Solver.h"
 #include "Initializer.h"
 #include "ORBmatcher.h"
+#include "Tracking.h"
 
 using namespace ORB_SLAM2;
 
@@ -620,6 +621,87 @@ int fc_mp_fuse_state(void* m, long mp, long* out5) {
     out5[3] = p->nDescriptorUpdates;
     out5[4] = (long)std::count(M->map.mspMapPoints.begin(), M->map.mspMapPoints.end(), p);
     return 0;
+}
+// ---- projection matching for tracking (both ORBmatcher::SearchByProjection overloads, the Tracking slice) ----
+// what the tracking matchers read of a frame beside the keypoints fc_frame_add_obs gave it: the id, N x 32 descriptor bytes, the
+// keypoint angles, the image bounds and the grid, which is assigned here; eight levels of factor 1.2; mvKeys = mvKeysUn; the pose
+// parts of UpdatePoseMatrices.  N becomes the number of keypoints the frame holds
+int fc_frame_set_tracking_data(void* m, long frame, long id, const unsigned char* desc, const float* angle, float min_x, float max_x, float min_y,
+                               float max_y, int cols, int rows) {
+    Frame* f = reinterpret_cast<FcMap*>(m)->frames.at(frame).get();
+    f->mnId = (long unsigned)id;
+    f->N = (int)f->mvKeysUn.size();
+    for (int i = 0; i < f->N; i++) f->mvKeysUn[(size_t)i].angle = angle[i];
+    f->mvKeys = f->mvKeysUn;
+    f->mDescriptors.assign(desc, desc + 32 * (size_t)f->N);
+    f->mnScaleLevels = 8;
+    f->mvScaleFactors.resize(8);
+    for (int l = 0; l < 8; l++) f->mvScaleFactors[(size_t)l] = (float)std::pow(1.2, l);
+    f->mnMinX = min_x; f->mnMaxX = max_x; f->mnMinY = min_y; f->mnMaxY = max_y;
+    f->mnGridCols = cols; f->mnGridRows = rows;
+    f->AssignFeaturesToGrid();
+    f->UpdatePoseMatrices();
+    return f->N;
+}
+int fc_frame_set_outlier(void* m, long frame, int idx, int outlier) {
+    reinterpret_cast<FcMap*>(m)->frames.at(frame)->mvbOutlier.at((size_t)idx) = outlier != 0;
+    return 0;
+}
+int fc_frame_set_uright(void* m, long frame, int idx, float ur) {
+    reinterpret_cast<FcMap*>(m)->frames.at(frame)->mvuRight.at((size_t)idx) = ur;
+    return 0;
+}
+// the ids behind mvpMapPoints (-1: NULL); returns N
+int fc_frame_points(void* m, long frame, long* ids, int cap) {
+    Frame* f = reinterpret_cast<FcMap*>(m)->frames.at(frame).get();
+    for (int i = 0; i < f->N && i < cap; i++) ids[i] = f->mvpMapPoints[(size_t)i] ? (long)f->mvpMapPoints[(size_t)i]->mnId : -1;
+    return f->N;
+}
+// nObs as the test wants it (Observations() > 0 decides whether a point blocks its keypoint), mbTrackInView, mnLastFrameSeen
+int fc_mp_set_track(void* m, long mp, int n_obs, int in_view, long last_frame_seen) {
+    MapPoint* p = reinterpret_cast<FcMap*>(m)->mps.at(mp).get();
+    p->nObs = n_obs; p->mbTrackInView = in_view != 0; p->mnLastFrameSeen = (long unsigned)last_frame_seen;
+    return 0;
+}
+// out7: mbTrackInView, mTrackProjX, mTrackProjY, mnTrackScaleLevel, mTrackViewCos, mnVisible, mnLastFrameSeen
+int fc_mp_track_state(void* m, long mp, double* out7) {
+    MapPoint* p = reinterpret_cast<FcMap*>(m)->mps.at(mp).get();
+    out7[0] = p->mbTrackInView ? 1 : 0; out7[1] = p->mTrackProjX; out7[2] = p->mTrackProjY; out7[3] = p->mnTrackScaleLevel;
+    out7[4] = p->mTrackViewCos; out7[5] = p->mnVisible; out7[6] = (double)p->mnLastFrameSeen;
+    return 0;
+}
+// ORBmatcher(0.9, check_ori).SearchByProjection(CurrentFrame, LastFrame, th, bMono)
+int fc_search_by_projection_last(void* m, long cur, long last, float th, int mono, int check_ori) {
+    FcMap* M = reinterpret_cast<FcMap*>(m);
+    ORBmatcher matcher(0.9, check_ori != 0);
+    return matcher.SearchByProjection(*M->frames.at(cur), *M->frames.at(last), th, mono != 0);
+}
+// ORBmatcher(nnratio).SearchByProjection(F, vpMapPoints, th); an id of -1 is a NULL entry
+int fc_search_by_projection_map(void* m, long frame, const long* mp_ids, int n, float th, float nnratio) {
+    FcMap* M = reinterpret_cast<FcMap*>(m);
+    ORBmatcher matcher(nnratio);
+    return matcher.SearchByProjection(*M->frames.at(frame), point_list(M, mp_ids, n), th);
+}
+// Tracking::SearchLocalPoints with mCurrentFrame = the frame (copied in and back out) and mvpLocalMapPoints = the list
+int fc_search_local_points(void* m, long frame, const long* mp_ids, int n, long last_reloc_frame_id) {
+    FcMap* M = reinterpret_cast<FcMap*>(m);
+    Tracking t;
+    t.mCurrentFrame = *M->frames.at(frame);
+    t.mvpLocalMapPoints = point_list(M, mp_ids, n);
+    t.mnLastRelocFrameId = (long unsigned)last_reloc_frame_id;
+    const int r = t.SearchLocalPoints();
+    *M->frames.at(frame) = t.mCurrentFrame;
+    return r;
+}
+// the matching half of Tracking::TrackWithMotionModel
+int fc_track_motion_model_matches(void* m, long cur, long last) {
+    FcMap* M = reinterpret_cast<FcMap*>(m);
+    Tracking t;
+    t.mCurrentFrame = *M->frames.at(cur);
+    t.mLastFrame = *M->frames.at(last);
+    const int r = t.TrackWithMotionModelMatches();
+    *M->frames.at(cur) = t.mCurrentFrame;
+    return r;
 }
 // ---- Sim3 projection matching (ORBmatcher::SearchBySim3) ----
 // ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th): match_ids [n] holds the ids of vpMatches12 (-1: NULL) and

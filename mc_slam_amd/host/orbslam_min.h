@@ -341,6 +341,12 @@ public:
     int mnVisible = 1, mnFound = 1;
     int nDescriptorUpdates = 0;
     long unsigned int mnFuseCandidateForKF = 0;   // include/MapPoint.h:149
+    // what Frame::isInFrustum writes and ORBmatcher::SearchByProjection(F, vpMapPoints, th) reads (include/MapPoint.h:68-76), and the
+    // mark of Tracking::SearchLocalPoints
+    bool mbTrackInView = false;
+    float mTrackProjX = 0, mTrackProjY = 0, mTrackViewCos = 0;
+    int mnTrackScaleLevel = 0;
+    long unsigned int mnLastFrameSeen = 0;
     MapPoint* mpReplaced = nullptr;
     Map* mpMap = nullptr;
     float mPosGBA[3] = {0, 0, 0};          // include/MapPoint.h:90-91
@@ -370,6 +376,42 @@ public:
         mTcw = k.GetPose();
     }
     NavState mNavState;
+    // what the two tracking matchers, ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, ...) and (F, vpMapPoints, th), read
+    // (include/Frame.h; src/Frame.cpp:440-470, :562-620): the id, the raw keypoints, the descriptor rows, the scale table, the image
+    // bounds (static floats there), the grid and the pose parts of UpdatePoseMatrices
+    long unsigned int mnId = 0;
+    std::vector<KeyPoint> mvKeys;
+    std::vector<unsigned char> mDescriptors;              // N x 32
+    std::vector<float> mvScaleFactors;
+    int mnScaleLevels = 8;
+    float mfLogScaleFactor = std::log(1.2f);
+    float mnMinX = 0, mnMaxX = 0, mnMinY = 0, mnMaxY = 0;
+    int mnGridCols = 64, mnGridRows = 48;                 // FRAME_GRID_COLS, FRAME_GRID_ROWS
+    float mfGridElementWidthInv = 0, mfGridElementHeightInv = 0;
+    std::vector<std::vector<std::vector<size_t>>> mGrid;  // [col][row] keypoint indices
+    float mRcw[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, mtcw[3] = {0, 0, 0}, mOw[3] = {0, 0, 0};
+    void UpdatePoseMatrices() {   // src/Frame.cpp:457-463: mRcw, mtcw, mOw = -mRcw^T mtcw in float32 like cv::Mat
+        for (int i = 0; i < 3; i++) {
+            for (int j = 0; j < 3; j++) mRcw[3 * i + j] = mTcw[4 * i + j];
+            mtcw[i] = mTcw[4 * i + 3];
+        }
+        for (int i = 0; i < 3; i++) {
+            float s = 0;
+            for (int k = 0; k < 3; k++) s += mRcw[3 * k + i] * mtcw[k];
+            mOw[i] = -s;
+        }
+    }
+    void AssignFeaturesToGrid() {   // src/Frame.cpp:430-450 with PosInGrid: round() of the float32 cell coordinate
+        mfGridElementWidthInv = (float)mnGridCols / (mnMaxX - mnMinX);
+        mfGridElementHeightInv = (float)mnGridRows / (mnMaxY - mnMinY);
+        mGrid.assign((size_t)mnGridCols, std::vector<std::vector<size_t>>((size_t)mnGridRows));
+        for (size_t i = 0; i < mvKeysUn.size(); i++) {
+            const int posX = (int)std::round((mvKeysUn[i].pt.x - mnMinX) * mfGridElementWidthInv);
+            const int posY = (int)std::round((mvKeysUn[i].pt.y - mnMinY) * mfGridElementHeightInv);
+            if (posX < 0 || posX >= mnGridCols || posY < 0 || posY >= mnGridRows) continue;
+            mGrid[(size_t)posX][(size_t)posY].push_back(i);
+        }
+    }
 };
 
 inline bool cmpKeyFrameId::operator()(const KeyFrame* a, const KeyFrame* b) const { return a->mnId < b->mnId; }

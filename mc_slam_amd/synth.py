@@ -1142,3 +1142,58 @@ def sim3_search_scene(seed, n_keys1=1000, n_keys2=1000, n_common=400, n_levels=(
                                     matched=matched[k], pos=pos[k], dist_min=dmin[k], dist_max=dmax[k], pred_max=pmax[k], pt_desc=pdesc[k]))
     return abi.SearchSim3Problem(kf1=kfs[0], kf2=kfs[1], K=K, s12=s12, R12=R12, t12=t12, th=th, th_high=th_high,
                                  truth=dict(kind=kind, key1=key[0].copy(), key2=key[1].copy()))
+
+
+# ---------------------------------------------------------------- projection matching for tracking (vba_search_by_projection)
+def search_proj_scene(seed, mode, n_keys=1000, n_q=600, twins=0.3, occupied=0.1, non_blocking=0.1, th=None, th_high=100, nn_ratio=0.8,
+                      check_orientation=True, rotation=20.0, angle_noise=3.0, angle_outliers=0.1, **kw):
+    """One call of a tracking matcher (abi.SearchProjProblem of `mode`), every input rounded through float32 as the reference holds
+    it.  The frame and the queries are those of fuse_scene(seed, n_keys, n_q, **kw) -- a query of kind match projects near a keypoint
+    whose descriptor it nearly has, and with more matching queries than keypoints several queries want the same keypoint --, with what
+    the two matchers add:
+      twins         the last share `twins` of the keypoints are moved beside keypoint 0, 1, ...: up to 1.5 pixels away, the same
+                    octave, the descriptor 2-10 bits off.  A query that finds its keypoint taken then has a second candidate under
+                    th_high, and best and second best of the local-map mode lie close (the ratio test decides)
+      occupied      a random share of the keypoints held a point with observations before the call
+      non_blocking  a random share of the queries has Observations() == 0: its claim does not block
+      last frame    q_oct is the keypoint's octave for a match (one level off for a fifth of them), random otherwise; keypoint angles
+                    are uniform in [0, 360), a match's q_angle is its keypoint's plus `rotation` plus angle_noise degrees of noise, a
+                    share angle_outliers of them and every other query has a random one.  th defaults to 15 (Tracking.cpp:1754)
+      local map     th defaults to 1 (Tracking.cpp:2163)
+    truth: that of fuse_scene."""
+    f = fuse_scene(seed, n_keys=n_keys, n_pt=n_q, **kw)
+    r = np.random.default_rng(seed + 7919)
+    f32 = lambda a: np.asarray(a, dtype=np.float32)
+    desc, uv, octv = f.desc.copy(), f.uv.copy(), f.oct.copy()
+    m = min(int(n_keys * twins), n_keys // 2)
+    w, h = f.bounds[1], f.bounds[3]
+    for j in range(m):
+        k = n_keys - m + j
+        uv[k] = f32(np.clip(uv[j] + r.uniform(-1.5, 1.5, 2), 0.0, [w - 1.0, h - 1.0])).astype(np.float64)
+        octv[k] = octv[j]
+        bits = np.unpackbits(desc[j])
+        bits[r.permutation(256)[:int(r.integers(2, 11))]] ^= 1
+        desc[k] = np.packbits(bits)
+    cell_begin, cell_feat = abi.grid_csr(uv, f.bounds, f.grid_cols, f.grid_rows, f.grid_inv_w, f.grid_inv_h)
+    occ = (r.random(n_keys) < occupied).astype(np.uint8)
+    blocks = (r.random(n_q) >= non_blocking).astype(np.uint8)
+    common = dict(Rcw=f.Rcw, tcw=f.tcw, K=f.K, bounds=f.bounds, desc=desc, uv=uv, oct=octv, scale=f.scale, grid_cols=f.grid_cols, grid_rows=f.grid_rows,
+                  grid_inv_w=f.grid_inv_w, grid_inv_h=f.grid_inv_h, cell_begin=cell_begin, cell_feat=cell_feat, occupied=occ, q_pos=f.pos, q_desc=f.pt_desc,
+                  q_skip=f.skip, q_blocks=blocks, th_high=th_high, truth=f.truth)
+    if mode == abi.SEARCH_PROJ_LOCAL_MAP:
+        return abi.SearchProjProblem(mode=mode, Ow=f.Ow, log_scale_factor=f.log_scale_factor, q_normal=f.normal, q_dist_min=f.dist_min, q_dist_max=f.dist_max,
+                                     q_pred_max=f.pred_max, th=1.0 if th is None else th, nn_ratio=nn_ratio, cos_view=0.5, **common)
+    key = f.truth["key"]
+    angle = f32(r.uniform(0.0, 360.0, n_keys))
+    angle[angle >= 360.0] = 0.0
+    q_oct = r.integers(0, f.n_levels, n_q).astype(np.uint8)
+    q_angle = f32(r.uniform(0.0, 360.0, n_q))
+    for i in range(n_q):
+        if key[i] >= 0:
+            o = int(f.oct[key[i]]) + (int(r.choice([-1, 1])) if r.random() < 0.2 else 0)
+            q_oct[i] = min(max(o, 0), f.n_levels - 1)
+            if r.random() >= angle_outliers:
+                q_angle[i] = np.float32(np.mod(float(angle[key[i]]) + rotation + r.normal() * angle_noise, 360.0))
+    q_angle[q_angle >= 360.0] = 0.0
+    return abi.SearchProjProblem(mode=mode, angle=angle, q_oct=q_oct, q_angle=q_angle, th=15.0 if th is None else th,
+                                 check_orientation=check_orientation, **common)
