@@ -5,6 +5,7 @@
 #pragma once
 #include "../../include/vislam_ba.h"
 #include "vba_host_arena.h"
+#include "vba_host_keygrid.h"
 #include "vba_layout.h"
 
 #include <cmath>
@@ -29,51 +30,38 @@ inline int check_fuse(int n, const vba_fuse_problem* const* in, const vba_fuse_r
         const vba_fuse_problem* P = in[f];
         const vba_fuse_result* R = out[f];
         auto fail = [&err, f](const std::string& m) { err = "problem " + std::to_string(f) + ": " + m; return 1; };
-        auto finite = [](const double* a, size_t k) { for (size_t i = 0; i < k; i++) if (!std::isfinite(a[i])) return false; return true; };
         if (!P || !R) return fail("NULL problem or result");
         if (P->n_keys < 0) return fail("negative n_keys");
         if (P->n_pt < 0) return fail("negative n_pt");
         if (P->n_levels < 1 || P->n_levels > VBA_TRI_LEVELS) return fail("n_levels outside 1 .. 64");
         if (!P->scale || !P->inv_level_sigma2) return fail("NULL level table");
         if (P->th_low < 0 || P->th_low > 256) return fail("th_low outside 0 .. 256");
-        if (P->grid_cols < 1 || P->grid_rows < 1 || (long long)P->grid_cols * P->grid_rows > 65536) return fail("grid size outside 1 .. 65536 cells");
+        if (!grid_size_ok(*P)) return fail("grid size outside 1 .. 65536 cells");
         if (P->n_keys > 0 && (!P->desc || !P->uv || !P->oct)) return fail("NULL array with n_keys > 0");
         if (P->n_pt > 0 && (!P->pos || !P->normal || !P->dist_min || !P->dist_max || !P->pred_max || !P->pt_desc || !P->skip || !R->best_idx ||
                             !R->best_dist || !R->level || !R->uv || !R->state))
             return fail("NULL array with n_pt > 0");
         if (!P->cell_begin) return fail("NULL cell_begin");
-        if (!finite(P->Rcw, 9) || !finite(P->tcw, 3) || !finite(P->Ow, 3)) return fail("the pose is not finite");
-        if (!finite(P->K, 4)) return fail("an intrinsic is not finite");
-        if (!finite(P->bounds, 4) || !finite(&P->grid_inv_w, 1) || !finite(&P->grid_inv_h, 1)) return fail("a bound or cell size is not finite");
-        if (!finite(&P->th, 1) || !finite(&P->cos_view, 1) || !finite(&P->chi2_reproj, 1)) return fail("a threshold is not finite");
-        if (!finite(P->scale, (size_t)P->n_levels) || !finite(P->inv_level_sigma2, (size_t)P->n_levels) || !finite(&P->log_scale_factor, 1))
+        if (!all_finite(P->Rcw, 9) || !all_finite(P->tcw, 3) || !all_finite(P->Ow, 3)) return fail("the pose is not finite");
+        if (!all_finite(P->K, 4)) return fail("an intrinsic is not finite");
+        if (!all_finite(P->bounds, 4) || !all_finite(&P->grid_inv_w, 1) || !all_finite(&P->grid_inv_h, 1)) return fail("a bound or cell size is not finite");
+        if (!all_finite(&P->th, 1) || !all_finite(&P->cos_view, 1) || !all_finite(&P->chi2_reproj, 1)) return fail("a threshold is not finite");
+        if (!all_finite(P->scale, (size_t)P->n_levels) || !all_finite(P->inv_level_sigma2, (size_t)P->n_levels) || !all_finite(&P->log_scale_factor, 1))
             return fail("a level table is not finite");
         for (size_t i = 0, e = (size_t)P->n_keys; i < e; i++) {
-            if (!finite(P->uv + 2 * i, 2)) return fail("keypoint " + std::to_string(i) + ": a pixel is not finite");
-            if (P->oct[i] >= P->n_levels) return fail("keypoint " + std::to_string(i) + ": octave >= n_levels");
+            if (const char* why = keypoint_fault(*P, i)) return fail("keypoint " + std::to_string(i) + ": " + why);
         }
         for (size_t i = 0, e = (size_t)P->n_pt; i < e; i++) {
-            if (!finite(P->pos + 3 * i, 3)) return fail("point " + std::to_string(i) + ": the position is not finite");
-            if (!finite(P->normal + 3 * i, 3)) return fail("point " + std::to_string(i) + ": the normal is not finite");
-            if (!finite(P->dist_min + i, 1) || !finite(P->dist_max + i, 1) || !finite(P->pred_max + i, 1))
+            if (!all_finite(P->pos + 3 * i, 3)) return fail("point " + std::to_string(i) + ": the position is not finite");
+            if (!all_finite(P->normal + 3 * i, 3)) return fail("point " + std::to_string(i) + ": the normal is not finite");
+            if (!all_finite(P->dist_min + i, 1) || !all_finite(P->dist_max + i, 1) || !all_finite(P->pred_max + i, 1))
                 return fail("point " + std::to_string(i) + ": a distance is not finite");
         }
-        const int nc = P->grid_cols * P->grid_rows;
-        if (P->cell_begin[0] != 0) return fail("cell_begin does not start at 0");
-        for (int c = 0; c < nc; c++)
-            if (P->cell_begin[c + 1] < P->cell_begin[c]) return fail("cell_begin decreases at cell " + std::to_string(c));
-        const int nf = P->cell_begin[nc];
-        if (nf > P->n_keys) return fail("cell_begin ends above n_keys");
-        if (nf > 0 && !P->cell_feat) return fail("NULL cell_feat");
-        seen.assign((size_t)P->n_keys, 0);
-        for (int i = 0; i < nf; i++) {
-            const int a = P->cell_feat[i];
-            if (a < 0 || a >= P->n_keys) return fail("cell_feat entry " + std::to_string(i) + ": keypoint index out of range");
-            if (seen[(size_t)a]) return fail("cell_feat entry " + std::to_string(i) + ": keypoint " + std::to_string(a) + " listed twice");
-            seen[(size_t)a] = 1;
-        }
+        int nf = 0;
+        const std::string why = check_cell_lists(P->grid_cols, P->grid_rows, P->n_keys, P->cell_begin, P->cell_feat, seen, nf);
+        if (!why.empty()) return fail(why);
         T.keys += (size_t)P->n_keys; T.pts += (size_t)P->n_pt;
-        T.cells += (size_t)nc + 1; T.feat += (size_t)nf;
+        T.cells += grid_cells(*P) + 1; T.feat += (size_t)nf;
         T.lev += 2 * (size_t)P->n_levels; T.tiles += fuse_tiles(P->n_pt);
     }
     return 0;
@@ -99,11 +87,10 @@ struct FuseArena {
 inline size_t describe_fuse(int n, const vba_fuse_problem* const* in, FuDesc* desc, FuTile* tile) {
     size_t k = 0, p = 0, c = 0, ft = 0, lv = 0, nt = 0;
     for (int f = 0; f < n; f++) {
-        const int nc = in[f]->grid_cols * in[f]->grid_rows;
         desc[f].key0 = (long long)k; desc[f].pt0 = (long long)p; desc[f].cell0 = (long long)c; desc[f].feat0 = (long long)ft; desc[f].lev0 = (long long)lv;
         for (int first = 0; first < in[f]->n_pt; first += VBA_FU_NT) { tile[nt].prob = f; tile[nt].first = first; nt++; }
-        k += (size_t)in[f]->n_keys; p += (size_t)in[f]->n_pt; c += (size_t)nc + 1;
-        ft += (size_t)in[f]->cell_begin[nc]; lv += 2 * (size_t)in[f]->n_levels;
+        k += (size_t)in[f]->n_keys; p += (size_t)in[f]->n_pt; c += grid_cells(*in[f]) + 1;
+        ft += grid_feat(*in[f]); lv += 2 * (size_t)in[f]->n_levels;
     }
     return nt;
 }
@@ -115,13 +102,7 @@ inline void pack_fuse(const vba_fuse_problem* P, FuDesc& d, FuKey* hkey, FuPoint
     std::memcpy(d.c, P->Rcw, 72); std::memcpy(d.c + 9, P->tcw, 24); std::memcpy(d.c + 12, P->Ow, 24);
     std::memcpy(d.c + 15, P->K, 32); std::memcpy(d.c + 19, P->bounds, 32);
     d.c[23] = P->grid_inv_w; d.c[24] = P->grid_inv_h; d.c[25] = P->log_scale_factor; d.c[26] = P->th; d.c[27] = P->cos_view; d.c[28] = P->chi2_reproj;
-    FuKey* k = hkey + (size_t)d.key0;
-    for (size_t i = 0, e = (size_t)P->n_keys; i < e; i++) {
-        std::memcpy(k[i].d, P->desc + 32 * i, 32);
-        k[i].u = P->uv[2 * i]; k[i].v = P->uv[2 * i + 1];
-        k[i].oct = P->oct[i];
-        std::memset(k[i].pad, 0, sizeof k[i].pad);
-    }
+    pack_keys(*P, hkey + (size_t)d.key0);
     FuPoint* q = hpt + (size_t)d.pt0;
     for (size_t i = 0, e = (size_t)P->n_pt; i < e; i++) {
         std::memcpy(q[i].d, P->pt_desc + 32 * i, 32);
@@ -130,9 +111,8 @@ inline void pack_fuse(const vba_fuse_problem* P, FuDesc& d, FuKey* hkey, FuPoint
         q[i].skip = P->skip[i] ? 1 : 0;
         std::memset(q[i].pad, 0, sizeof q[i].pad);
     }
-    const size_t nc = (size_t)P->grid_cols * (size_t)P->grid_rows, nf = (size_t)P->cell_begin[nc], nl = (size_t)P->n_levels;
-    std::memcpy(hcell + (size_t)d.cell0, P->cell_begin, 4 * (nc + 1));
-    if (nf) std::memcpy(hfeat + (size_t)d.feat0, P->cell_feat, 4 * nf);
+    const size_t nl = (size_t)P->n_levels;
+    pack_grid(*P, hcell + (size_t)d.cell0, hfeat + (size_t)d.feat0);
     std::memcpy(hlev + (size_t)d.lev0, P->scale, 8 * nl);
     std::memcpy(hlev + (size_t)d.lev0 + nl, P->inv_level_sigma2, 8 * nl);
 }

@@ -6,6 +6,7 @@
 #pragma once
 #include "../../include/vislam_ba.h"
 #include "vba_host_arena.h"
+#include "vba_host_keygrid.h"
 #include "vba_layout.h"
 
 #include <cmath>
@@ -29,7 +30,6 @@ inline int check_search_proj(int n, const vba_search_proj_problem* const* in, co
         const vba_search_proj_problem* P = in[f];
         const vba_search_proj_result* R = out[f];
         auto fail = [&err, f](const std::string& m) { err = "problem " + std::to_string(f) + ": " + m; return 1; };
-        auto finite = [](const double* a, size_t k) { for (size_t i = 0; i < k; i++) if (!std::isfinite(a[i])) return false; return true; };
         if (!P || !R) return fail("NULL problem or result");
         if (P->mode != VBA_SEARCH_PROJ_LAST_FRAME && P->mode != VBA_SEARCH_PROJ_LOCAL_MAP) return fail("unknown mode");
         const bool local = P->mode == VBA_SEARCH_PROJ_LOCAL_MAP;
@@ -40,7 +40,7 @@ inline int check_search_proj(int n, const vba_search_proj_problem* const* in, co
         if (P->n_levels < 1 || P->n_levels > VBA_TRI_LEVELS) return fail("n_levels outside 1 .. 64");
         if (!P->scale) return fail("NULL level table");
         if (P->th_high < 0 || P->th_high > 256) return fail("th_high outside 0 .. 256");
-        if (P->grid_cols < 1 || P->grid_rows < 1 || (long long)P->grid_cols * P->grid_rows > 65536) return fail("grid size outside 1 .. 65536 cells");
+        if (!grid_size_ok(*P)) return fail("grid size outside 1 .. 65536 cells");
         if (P->n_keys > 0 && (!P->desc || !P->uv || !P->oct || !P->occupied || !R->key_match || (ori && !P->angle))) return fail("NULL array with n_keys > 0");
         if (P->n_q > 0 && (!P->q_pos || !P->q_desc || !P->q_skip || !P->q_blocks || !R->best_idx || !R->best_dist || !R->best_dist2 || !R->level ||
                            !R->view_cos || !R->uv || !R->bin || !R->state))
@@ -48,43 +48,31 @@ inline int check_search_proj(int n, const vba_search_proj_problem* const* in, co
         if (P->n_q > 0 && !local && (!P->q_oct || (ori && !P->q_angle))) return fail("NULL last-frame array with n_q > 0");
         if (P->n_q > 0 && local && (!P->q_normal || !P->q_dist_min || !P->q_dist_max || !P->q_pred_max)) return fail("NULL local-map array with n_q > 0");
         if (!P->cell_begin) return fail("NULL cell_begin");
-        if (!finite(P->Rcw, 9) || !finite(P->tcw, 3) || (local && !finite(P->Ow, 3))) return fail("the pose is not finite");
-        if (!finite(P->K, 4)) return fail("an intrinsic is not finite");
-        if (!finite(P->bounds, 4) || !finite(&P->grid_inv_w, 1) || !finite(&P->grid_inv_h, 1)) return fail("a bound or cell size is not finite");
-        if (!finite(&P->th, 1) || (local && (!finite(&P->cos_view, 1) || !std::isfinite(P->nn_ratio)))) return fail("a threshold is not finite");
-        if (!finite(P->scale, (size_t)P->n_levels) || (local && !finite(&P->log_scale_factor, 1))) return fail("a level table is not finite");
+        if (!all_finite(P->Rcw, 9) || !all_finite(P->tcw, 3) || (local && !all_finite(P->Ow, 3))) return fail("the pose is not finite");
+        if (!all_finite(P->K, 4)) return fail("an intrinsic is not finite");
+        if (!all_finite(P->bounds, 4) || !all_finite(&P->grid_inv_w, 1) || !all_finite(&P->grid_inv_h, 1)) return fail("a bound or cell size is not finite");
+        if (!all_finite(&P->th, 1) || (local && (!all_finite(&P->cos_view, 1) || !std::isfinite(P->nn_ratio)))) return fail("a threshold is not finite");
+        if (!all_finite(P->scale, (size_t)P->n_levels) || (local && !all_finite(&P->log_scale_factor, 1))) return fail("a level table is not finite");
         for (size_t i = 0, e = (size_t)P->n_keys; i < e; i++) {
-            if (!finite(P->uv + 2 * i, 2)) return fail("keypoint " + std::to_string(i) + ": a pixel is not finite");
-            if (P->oct[i] >= P->n_levels) return fail("keypoint " + std::to_string(i) + ": octave >= n_levels");
+            if (const char* why = keypoint_fault(*P, i)) return fail("keypoint " + std::to_string(i) + ": " + why);
             if (ori && !(P->angle[i] >= 0.0f && P->angle[i] < 360.0f)) return fail("keypoint " + std::to_string(i) + ": angle outside [0, 360)");
         }
         for (size_t i = 0, e = (size_t)P->n_q; i < e; i++) {
-            if (!finite(P->q_pos + 3 * i, 3)) return fail("query " + std::to_string(i) + ": the position is not finite");
+            if (!all_finite(P->q_pos + 3 * i, 3)) return fail("query " + std::to_string(i) + ": the position is not finite");
             if (!local) {
                 if (P->q_oct[i] >= P->n_levels) return fail("query " + std::to_string(i) + ": octave >= n_levels");
                 if (ori && !(P->q_angle[i] >= 0.0f && P->q_angle[i] < 360.0f)) return fail("query " + std::to_string(i) + ": angle outside [0, 360)");
             } else {
-                if (!finite(P->q_normal + 3 * i, 3)) return fail("query " + std::to_string(i) + ": the normal is not finite");
-                if (!finite(P->q_dist_min + i, 1) || !finite(P->q_dist_max + i, 1) || !finite(P->q_pred_max + i, 1))
+                if (!all_finite(P->q_normal + 3 * i, 3)) return fail("query " + std::to_string(i) + ": the normal is not finite");
+                if (!all_finite(P->q_dist_min + i, 1) || !all_finite(P->q_dist_max + i, 1) || !all_finite(P->q_pred_max + i, 1))
                     return fail("query " + std::to_string(i) + ": a distance is not finite");
             }
         }
-        const int nc = P->grid_cols * P->grid_rows;
-        if (P->cell_begin[0] != 0) return fail("cell_begin does not start at 0");
-        for (int c = 0; c < nc; c++)
-            if (P->cell_begin[c + 1] < P->cell_begin[c]) return fail("cell_begin decreases at cell " + std::to_string(c));
-        const int nf = P->cell_begin[nc];
-        if (nf > P->n_keys) return fail("cell_begin ends above n_keys");
-        if (nf > 0 && !P->cell_feat) return fail("NULL cell_feat");
-        seen.assign((size_t)P->n_keys, 0);
-        for (int i = 0; i < nf; i++) {
-            const int a = P->cell_feat[i];
-            if (a < 0 || a >= P->n_keys) return fail("cell_feat entry " + std::to_string(i) + ": keypoint index out of range");
-            if (seen[(size_t)a]) return fail("cell_feat entry " + std::to_string(i) + ": keypoint " + std::to_string(a) + " listed twice");
-            seen[(size_t)a] = 1;
-        }
+        int nf = 0;
+        const std::string why = check_cell_lists(P->grid_cols, P->grid_rows, P->n_keys, P->cell_begin, P->cell_feat, seen, nf);
+        if (!why.empty()) return fail(why);
         T.keys += (size_t)P->n_keys; T.qs += (size_t)P->n_q;
-        T.cells += (size_t)nc + 1; T.feat += (size_t)nf; T.lev += (size_t)P->n_levels;
+        T.cells += grid_cells(*P) + 1; T.feat += (size_t)nf; T.lev += (size_t)P->n_levels;
         if ((size_t)P->n_keys > T.max_keys) T.max_keys = (size_t)P->n_keys;
     }
     return 0;
@@ -110,10 +98,9 @@ struct SearchProjArena {
 inline void describe_search_proj(int n, const vba_search_proj_problem* const* in, SpDesc* desc) {
     size_t k = 0, q = 0, c = 0, ft = 0, lv = 0;
     for (int f = 0; f < n; f++) {
-        const int nc = in[f]->grid_cols * in[f]->grid_rows;
         desc[f].key0 = (long long)k; desc[f].q0 = (long long)q; desc[f].cell0 = (long long)c; desc[f].feat0 = (long long)ft; desc[f].lev0 = (long long)lv;
-        k += (size_t)in[f]->n_keys; q += (size_t)in[f]->n_q; c += (size_t)nc + 1;
-        ft += (size_t)in[f]->cell_begin[nc]; lv += (size_t)in[f]->n_levels;
+        k += (size_t)in[f]->n_keys; q += (size_t)in[f]->n_q; c += grid_cells(*in[f]) + 1;
+        ft += grid_feat(*in[f]); lv += (size_t)in[f]->n_levels;
     }
 }
 
@@ -129,15 +116,9 @@ inline void pack_search_proj(const vba_search_proj_problem* P, SpDesc& d, FuKey*
     for (int i = 0; i < 3; i++) d.c[12 + i] = local ? P->Ow[i] : 0.0;
     std::memcpy(d.c + 15, P->K, 32); std::memcpy(d.c + 19, P->bounds, 32);
     d.c[23] = P->grid_inv_w; d.c[24] = P->grid_inv_h; d.c[25] = local ? P->log_scale_factor : 0.0; d.c[26] = P->th; d.c[27] = local ? P->cos_view : 0.0;
-    FuKey* k = hkey + (size_t)d.key0;
+    pack_keys(*P, hkey + (size_t)d.key0);
     unsigned char* oc = hocc + (size_t)d.key0;
-    for (size_t i = 0, e = (size_t)P->n_keys; i < e; i++) {
-        std::memcpy(k[i].d, P->desc + 32 * i, 32);
-        k[i].u = P->uv[2 * i]; k[i].v = P->uv[2 * i + 1];
-        k[i].oct = P->oct[i];
-        std::memset(k[i].pad, 0, sizeof k[i].pad);
-        oc[i] = P->occupied[i] ? 1 : 0;
-    }
+    for (size_t i = 0, e = (size_t)P->n_keys; i < e; i++) oc[i] = P->occupied[i] ? 1 : 0;
     SpQuery* q = hq + (size_t)d.q0;
     for (size_t i = 0, e = (size_t)P->n_q; i < e; i++) {
         std::memset(&q[i], 0, sizeof q[i]);
@@ -151,10 +132,8 @@ inline void pack_search_proj(const vba_search_proj_problem* P, SpDesc& d, FuKey*
         q[i].skip = P->q_skip[i] ? 1 : 0;
         q[i].blocks = P->q_blocks[i] ? 1 : 0;
     }
-    const size_t nc = (size_t)P->grid_cols * (size_t)P->grid_rows, nf = (size_t)P->cell_begin[nc], nl = (size_t)P->n_levels;
-    std::memcpy(hcell + (size_t)d.cell0, P->cell_begin, 4 * (nc + 1));
-    if (nf) std::memcpy(hfeat + (size_t)d.feat0, P->cell_feat, 4 * nf);
-    std::memcpy(hlev + (size_t)d.lev0, P->scale, 8 * nl);
+    pack_grid(*P, hcell + (size_t)d.cell0, hfeat + (size_t)d.feat0);
+    std::memcpy(hlev + (size_t)d.lev0, P->scale, 8 * (size_t)P->n_levels);
 }
 
 // ComputeThreeMaxima (src/ORBmatcher.cpp:1800-1841) over bin counts, as k_search_tri has it

@@ -7,6 +7,7 @@
 #pragma once
 #include "../../include/vislam_ba.h"
 #include "vba_host_arena.h"
+#include "vba_host_keygrid.h"
 #include "vba_layout.h"
 
 #include <cmath>
@@ -24,12 +25,6 @@ struct SearchSim3Totals {
 
 inline size_t search_sim3_tiles(size_t n_q) { return (n_q + VBA_SS_NT - 1) / VBA_SS_NT; }
 
-inline bool ss_finite(const double* a, size_t k) {
-    for (size_t i = 0; i < k; i++)
-        if (!std::isfinite(a[i])) return false;
-    return true;
-}
-
 // one keyframe side of a pair with its result arrays: an empty string, or why it is refused.  n_q: its keypoints with has_pt && !matched
 inline std::string check_search_sim3_kf(const vba_search_sim3_kf& P, const int32_t* match, const uint16_t* best_dist, const int8_t* level,
                                         const uint8_t* state, bool match12_ok, std::vector<unsigned char>& seen, size_t& n_q) {
@@ -37,38 +32,24 @@ inline std::string check_search_sim3_kf(const vba_search_sim3_kf& P, const int32
     if (P.n_keys < 0) return "negative n_keys";
     if (P.n_levels < 1 || P.n_levels > VBA_TRI_LEVELS) return "n_levels outside 1 .. 64";
     if (!P.scale) return "NULL level table";
-    if (P.grid_cols < 1 || P.grid_rows < 1 || (long long)P.grid_cols * P.grid_rows > 65536) return "grid size outside 1 .. 65536 cells";
+    if (!grid_size_ok(P)) return "grid size outside 1 .. 65536 cells";
     if (P.n_keys > 0 && (!P.desc || !P.uv || !P.oct || !P.has_pt || !P.matched || !P.pos || !P.dist_min || !P.dist_max || !P.pred_max || !P.pt_desc ||
                          !match || !best_dist || !level || !state || !match12_ok))
         return "NULL array with n_keys > 0";
     if (!P.cell_begin) return "NULL cell_begin";
-    if (!ss_finite(P.Rcw, 9) || !ss_finite(P.tcw, 3)) return "the pose is not finite";
-    if (!ss_finite(P.bounds, 4) || !ss_finite(&P.grid_inv_w, 1) || !ss_finite(&P.grid_inv_h, 1)) return "a bound or cell size is not finite";
-    if (!ss_finite(P.scale, (size_t)P.n_levels) || !ss_finite(&P.log_scale_factor, 1)) return "a level table is not finite";
+    if (!all_finite(P.Rcw, 9) || !all_finite(P.tcw, 3)) return "the pose is not finite";
+    if (!all_finite(P.bounds, 4) || !all_finite(&P.grid_inv_w, 1) || !all_finite(&P.grid_inv_h, 1)) return "a bound or cell size is not finite";
+    if (!all_finite(P.scale, (size_t)P.n_levels) || !all_finite(&P.log_scale_factor, 1)) return "a level table is not finite";
     for (size_t i = 0, e = (size_t)P.n_keys; i < e; i++) {
-        if (!ss_finite(P.uv + 2 * i, 2)) return "keypoint " + std::to_string(i) + ": a pixel is not finite";
-        if (P.oct[i] >= P.n_levels) return "keypoint " + std::to_string(i) + ": octave >= n_levels";
+        if (const char* why = keypoint_fault(P, i)) return "keypoint " + std::to_string(i) + ": " + why;
         if (!P.has_pt[i]) continue;
-        if (!ss_finite(P.pos + 3 * i, 3)) return "keypoint " + std::to_string(i) + ": the position is not finite";
-        if (!ss_finite(P.dist_min + i, 1) || !ss_finite(P.dist_max + i, 1) || !ss_finite(P.pred_max + i, 1))
+        if (!all_finite(P.pos + 3 * i, 3)) return "keypoint " + std::to_string(i) + ": the position is not finite";
+        if (!all_finite(P.dist_min + i, 1) || !all_finite(P.dist_max + i, 1) || !all_finite(P.pred_max + i, 1))
             return "keypoint " + std::to_string(i) + ": a distance is not finite";
         n_q += !P.matched[i];
     }
-    const int nc = P.grid_cols * P.grid_rows;
-    if (P.cell_begin[0] != 0) return "cell_begin does not start at 0";
-    for (int c = 0; c < nc; c++)
-        if (P.cell_begin[c + 1] < P.cell_begin[c]) return "cell_begin decreases at cell " + std::to_string(c);
-    const int nf = P.cell_begin[nc];
-    if (nf > P.n_keys) return "cell_begin ends above n_keys";
-    if (nf > 0 && !P.cell_feat) return "NULL cell_feat";
-    seen.assign((size_t)P.n_keys, 0);
-    for (int i = 0; i < nf; i++) {
-        const int a = P.cell_feat[i];
-        if (a < 0 || a >= P.n_keys) return "cell_feat entry " + std::to_string(i) + ": keypoint index out of range";
-        if (seen[(size_t)a]) return "cell_feat entry " + std::to_string(i) + ": keypoint " + std::to_string(a) + " listed twice";
-        seen[(size_t)a] = 1;
-    }
-    return "";
+    int nf = 0;
+    return check_cell_lists(P.grid_cols, P.grid_rows, P.n_keys, P.cell_begin, P.cell_feat, seen, nf);
 }
 
 // 0: every pair is usable; otherwise err says which is not and why.  nq: the queries of every direction, [2 * pair + dir]
@@ -87,14 +68,13 @@ inline int check_search_sim3(int n, const vba_search_sim3_problem* const* in, co
         why = check_search_sim3_kf(P->kf2, R->match2, R->best_dist2, R->level2, R->state2, true, seen, nq[2 * (size_t)f + 1]);
         if (!why.empty()) return fail("keyframe 2: " + why);
         if (!std::isfinite(P->s12) || !(P->s12 > 0.0)) return fail("s12 is not finite or not positive");
-        if (!ss_finite(P->R12, 9) || !ss_finite(P->t12, 3)) return fail("the Sim3 is not finite");
-        if (!ss_finite(P->K, 4)) return fail("an intrinsic is not finite");
-        if (!ss_finite(&P->th, 1)) return fail("a threshold is not finite");
+        if (!all_finite(P->R12, 9) || !all_finite(P->t12, 3)) return fail("the Sim3 is not finite");
+        if (!all_finite(P->K, 4)) return fail("an intrinsic is not finite");
+        if (!all_finite(&P->th, 1)) return fail("a threshold is not finite");
         if (P->th_high < 0 || P->th_high > 256) return fail("th_high outside 0 .. 256");
         for (int s = 0; s < 2; s++) {
             const vba_search_sim3_kf& Kf = s ? P->kf2 : P->kf1;
-            const size_t nc = (size_t)Kf.grid_cols * (size_t)Kf.grid_rows;
-            T.keys += (size_t)Kf.n_keys; T.cells += nc + 1; T.feat += (size_t)Kf.cell_begin[nc]; T.lev += (size_t)Kf.n_levels;
+            T.keys += (size_t)Kf.n_keys; T.cells += grid_cells(Kf) + 1; T.feat += grid_feat(Kf); T.lev += (size_t)Kf.n_levels;
             T.queries += nq[2 * (size_t)f + s]; T.tiles += search_sim3_tiles(nq[2 * (size_t)f + s]);
         }
     }
@@ -124,7 +104,6 @@ inline size_t describe_search_sim3(int n, const vba_search_sim3_problem* const* 
     for (int f = 0; f < n; f++) {
         for (int s = 0; s < 2; s++) {   // side s is the SOURCE of direction s and the TARGET of direction 1 - s
             const vba_search_sim3_kf& Kf = s ? in[f]->kf2 : in[f]->kf1;
-            const size_t nc = (size_t)Kf.grid_cols * (size_t)Kf.grid_rows;
             SsDir& src = dir[2 * (size_t)f + s];
             SsDir& tgt = dir[2 * (size_t)f + 1 - s];
             src.q0 = (long long)q; src.n_q = (int)nq[2 * (size_t)f + s];
@@ -133,7 +112,7 @@ inline size_t describe_search_sim3(int n, const vba_search_sim3_problem* const* 
                 tile[nt].pair = f; tile[nt].dir = s; tile[nt].first = (int)first; tile[nt].pad = 0;
                 nt++;
             }
-            k += (size_t)Kf.n_keys; q += nq[2 * (size_t)f + s]; c += nc + 1; ft += (size_t)Kf.cell_begin[nc]; lv += (size_t)Kf.n_levels;
+            k += (size_t)Kf.n_keys; q += nq[2 * (size_t)f + s]; c += grid_cells(Kf) + 1; ft += grid_feat(Kf); lv += (size_t)Kf.n_levels;
         }
     }
     return nt;
@@ -167,16 +146,8 @@ inline void pack_search_sim3(const vba_search_sim3_problem* P, SsDir* d2, FuKey*
         std::memcpy(d.c + 24, P->K, 32); std::memcpy(d.c + 28, Tgt.bounds, 32);
         d.c[32] = Tgt.grid_inv_w; d.c[33] = Tgt.grid_inv_h; d.c[34] = Tgt.log_scale_factor; d.c[35] = P->th;
         // the records of the target of this direction sit where describe put them
-        FuKey* k = hkey + (size_t)d.key0;
-        for (size_t i = 0, e = (size_t)Tgt.n_keys; i < e; i++) {
-            std::memcpy(k[i].d, Tgt.desc + 32 * i, 32);
-            k[i].u = Tgt.uv[2 * i]; k[i].v = Tgt.uv[2 * i + 1];
-            k[i].oct = Tgt.oct[i];
-            std::memset(k[i].pad, 0, sizeof k[i].pad);
-        }
-        const size_t nc = (size_t)Tgt.grid_cols * (size_t)Tgt.grid_rows, nf = (size_t)Tgt.cell_begin[nc];
-        std::memcpy(hcell + (size_t)d.cell0, Tgt.cell_begin, 4 * (nc + 1));
-        if (nf) std::memcpy(hfeat + (size_t)d.feat0, Tgt.cell_feat, 4 * nf);
+        pack_keys(Tgt, hkey + (size_t)d.key0);
+        pack_grid(Tgt, hcell + (size_t)d.cell0, hfeat + (size_t)d.feat0);
         std::memcpy(hlev + (size_t)d.lev0, Tgt.scale, 8 * (size_t)Tgt.n_levels);
         SsQuery* q = hq + (size_t)d.q0;
         size_t m = 0;

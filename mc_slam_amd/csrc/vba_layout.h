@@ -276,7 +276,8 @@ struct StBatch {
 #define VBA_FU_NT 256          // lanes of a workgroup = most points of a tile
 #define VBA_FU_CONST 29        // doubles of a problem's constants: Rcw (9) tcw (3) Ow (3) K (4) bounds (4) grid_inv_w grid_inv_h
                                // log_scale_factor th cos_view chi2_reproj
-struct alignas(16) FuKey {     // one keypoint, 64 bytes: the descriptor in the first half, pixel and octave in the second
+struct alignas(16) FuKey {     // one keypoint, 64 bytes: the descriptor in the first half, pixel and octave in the second.  The record of
+                               // all three projection matchers: vba_search_area.h owns the walk over it (sa_walk), vba_host_keygrid.h packs it
     unsigned int d[8];         // the row of mDescriptors
     double u, v;               // mvKeysUn[idx].pt
     unsigned char oct;         // mvKeysUn[idx].octave

@@ -22,19 +22,9 @@
 #pragma once
 #include "vba_device.h"
 #include "vba_layout.h"
+#include "vba_search_area.h"
 
-#define SP_NT VBA_SP_NT
-// offsets in SpDesc::c (and in the LDS copy)
-#define SP_R 0
-#define SP_T 9
-#define SP_OW 12
-#define SP_K 15
-#define SP_B 19
-#define SP_GIW 23
-#define SP_GIH 24
-#define SP_LOGSF 25
-#define SP_TH 26
-#define SP_COS 27
+#define SP_NT VBA_SP_NT   // SpDesc::c is the camera block (SA_*, vba_search_area.h)
 
 __global__ void __launch_bounds__(SP_NT) k_search_proj(SpBatch B) {
 #pragma clang fp contract(off)
@@ -45,10 +35,9 @@ __global__ void __launch_bounds__(SP_NT) k_search_proj(SpBatch B) {
     const int nk = d.n_keys, nq = d.n_q, nl = d.n_levels;   // nk <= VBA_SP_MAX_KEYS, nl: 1 .. VBA_TRI_LEVELS (checked on the host)
     const bool local = d.mode != 0;
     if (tid < VBA_SP_CONST) sc[tid] = d.c[tid];
-    const FuKey* key = B.key + (size_t)d.key0;
+    const double* tb = sc + SA_TB;
+    const SaGrid grid = {B.key + (size_t)d.key0, B.cell_begin + (size_t)d.cell0, B.cell_feat + (size_t)d.feat0, d.cols, d.rows};
     const unsigned char* occupied = B.occupied + (size_t)d.key0;
-    const int* cell_begin = B.cell_begin + (size_t)d.cell0;
-    const int* cell_feat = B.cell_feat + (size_t)d.feat0;
     const double* scale = B.lev + (size_t)d.lev0;
     const SpQuery* query = B.query + (size_t)d.q0;
     const double qnan = __longlong_as_double(0x7ff8000000000000LL);
@@ -64,33 +53,26 @@ __global__ void __launch_bounds__(SP_NT) k_search_proj(SpBatch B) {
         do {
             if (Q.skip) { state = 1; break; }
             const double px = Q.pos[0], py = Q.pos[1], pz = Q.pos[2];
-            const double xc = ((sc[SP_R + 0] * px + sc[SP_R + 1] * py) + sc[SP_R + 2] * pz) + sc[SP_T + 0];
-            const double yc = ((sc[SP_R + 3] * px + sc[SP_R + 4] * py) + sc[SP_R + 5] * pz) + sc[SP_T + 1];
-            const double zc = ((sc[SP_R + 6] * px + sc[SP_R + 7] * py) + sc[SP_R + 8] * pz) + sc[SP_T + 2];
+            double xc, yc, zc;
+            sa_rigid(sc + SA_R, sc + SA_T, px, py, pz, xc, yc, zc);
             const double invz = 1.0 / zc;
             if (local ? (zc < 0.0) : (invz < 0.0)) { state = 2; break; }                 // Frame.cpp:506, ORBmatcher.cpp:1553
-            u = (sc[SP_K + 0] * xc) * invz + sc[SP_K + 2];
-            v = (sc[SP_K + 1] * yc) * invz + sc[SP_K + 3];
+            u = (sc[SA_K + 0] * xc) * invz + sc[SA_K + 2];
+            v = (sc[SA_K + 1] * yc) * invz + sc[SA_K + 3];
             // :513-516, :1559-1562; a NaN passes the reference's tests and leaves here (the one deviation)
-            if (!(isfinite(u) && isfinite(v)) || u < sc[SP_B + 0] || u > sc[SP_B + 1] || v < sc[SP_B + 2] || v > sc[SP_B + 3]) { state = 3; break; }
+            if (!(isfinite(u) && isfinite(v)) || u < tb[SA_B + 0] || u > tb[SA_B + 1] || v < tb[SA_B + 2] || v > tb[SA_B + 3]) { state = 3; break; }
             if (!local) {
-                r = sc[SP_TH] * scale[Q.oct];                                            // :1567
+                r = tb[SA_TH] * scale[Q.oct];                                            // :1567
                 break;
             }
-            const double ox = px - sc[SP_OW + 0], oy = py - sc[SP_OW + 1], oz = pz - sc[SP_OW + 2];
+            const double ox = px - sc[SA_OW + 0], oy = py - sc[SA_OW + 1], oz = pz - sc[SA_OW + 2];
             const double dist = sqrt((ox * ox + oy * oy) + oz * oz);
             if (dist < Q.dist_min || dist > Q.dist_max) { state = 4; break; }            // Frame.cpp:525
             vc = ((ox * Q.normal[0] + oy * Q.normal[1]) + oz * Q.normal[2]) / dist;
-            if (vc < sc[SP_COS]) { state = 5; break; }                                   // Frame.cpp:532
-            const double lv = ceil(log(Q.pred_max / dist) / sc[SP_LOGSF]);               // PredictScale
-            if (!(lv >= 0.0 && lv < (double)nl)) {                                       // Frame.cpp:537
-                state = 6;
-                level = (lv >= 127.0) ? 127 : ((lv > -128.0) ? (int)lv : -128);          // NaN gives -128
-                break;
-            }
-            level = (int)lv;
-            r = (vc > 0.998) ? 2.5 : 4.0;                                                // RadiusByViewingCos
-            if (sc[SP_TH] != 1.0) r = r * sc[SP_TH];                                     // :67, :88
+            if (vc < sc[SA_COS]) { state = 5; break; }                                   // Frame.cpp:532
+            if (!sa_predict_level(Q.pred_max, dist, tb[SA_LOGSF], nl, level)) { state = 6; break; }   // Frame.cpp:537
+            r =(vc > 0.998) ? 2.5 : 4.0;                                                // RadiusByViewingCos
+            if (tb[SA_TH] != 1.0) r = r * tb[SA_TH];                                     // :67, :88
             r = r * scale[level];                                                        // :93
         } while (false);
         B.best_idx[o] = -1;
@@ -106,7 +88,7 @@ __global__ void __launch_bounds__(SP_NT) k_search_proj(SpBatch B) {
     }
 
     // the conflict pass: at most n_q + 1 rounds
-    const int cols = d.cols, rows = d.rows, th_high = d.th_high;
+    const int th_high = d.th_high;
     const float nn_ratio = d.nn_ratio;
     int n_rounds = 0;
     for (int round = 0; round <= nq; ++round) {
@@ -120,50 +102,28 @@ __global__ void __launch_bounds__(SP_NT) k_search_proj(SpBatch B) {
             const int lo = local ? (int)B.level[o] - 1 : (int)Q.oct - 1, hi = local ? (int)B.level[o] : (int)Q.oct + 1;
             int bestDist = 256, bestDist2 = 256, bestLevel = -1, bestLevel2 = -1, bestIdx = -1;
             bool any = false;
-            do {
-                // Frame::GetFeaturesInArea(u, v, r, lo, hi): the cell range in double, clamped as max(0, .) and min(n - 1, .) do
-                const double fx0 = floor(((u - sc[SP_B + 0]) - r) * sc[SP_GIW]);
-                if (fx0 >= (double)cols) break;
-                const double fx1 = ceil(((u - sc[SP_B + 0]) + r) * sc[SP_GIW]);
-                if (fx1 < 0.0) break;
-                const double fy0 = floor(((v - sc[SP_B + 2]) - r) * sc[SP_GIH]);
-                if (fy0 >= (double)rows) break;
-                const double fy1 = ceil(((v - sc[SP_B + 2]) + r) * sc[SP_GIH]);
-                if (fy1 < 0.0) break;
-                const int x0 = (fx0 > 0.0) ? (int)fx0 : 0, x1 = (fx1 < (double)(cols - 1)) ? (int)fx1 : cols - 1;
-                const int y0 = (fy0 > 0.0) ? (int)fy0 : 0, y1 = (fy1 < (double)(rows - 1)) ? (int)fy1 : rows - 1;
-                if (y1 < y0) break;   // a negative radius: no cell
-                const bool check_levels = lo > 0 || hi >= 0;
-                unsigned int a[8];
-#pragma unroll
-                for (int w = 0; w < 8; w++) a[w] = Q.d[w];
-                for (int ix = x0; ix <= x1; ix++) {
-                    // the cells (ix, y0 .. y1) are neighbours in cell_begin: one range of cell_feat, in the order of the reference's loops
-                    const int jb = cell_begin[ix * rows + y0], je = cell_begin[ix * rows + y1 + 1];
-                    for (int j = jb; j < je; j++) {
-                        const int idx = cell_feat[j];
-                        const FuKey& k = key[idx];
-                        const int kl = k.oct;
-                        if (check_levels) {                                              // Frame.cpp:600-607
-                            if (kl < lo) continue;
-                            if (hi >= 0 && kl > hi) continue;
-                        }
-                        if (!(fabs(k.u - u) < r && fabs(k.v - v) < r)) continue;         // Frame.cpp:612
-                        any = true;
-                        if (sp_claim[idx] < q) continue;                                 // :113-115, :1596-1598
-                        int dist = 0;
-#pragma unroll
-                        for (int w = 0; w < 8; w++) dist += __popc(a[w] ^ k.d[w]);
-                        if (dist < bestDist) {                                           // :129-141, :1613
-                            bestDist2 = bestDist; bestDist = dist;
-                            bestLevel2 = bestLevel; bestLevel = kl;
-                            bestIdx = idx;
-                        } else if (dist < bestDist2) {
-                            bestLevel2 = kl; bestDist2 = dist;
-                        }
-                    }
+            const bool check_levels = lo > 0 || hi >= 0;
+            unsigned int a[8];
+            sa_load_desc(a, Q.d);
+            // Frame::GetFeaturesInArea(u, v, r, lo, hi)
+            sa_walk(grid, tb, u, v, r, [&](int idx, const FuKey& k) {
+                const int kl = k.oct;
+                if (check_levels) {                                                      // Frame.cpp:600-607
+                    if (kl < lo) return;
+                    if (hi >= 0 && kl > hi) return;
                 }
-            } while (false);
+                if (!(fabs(k.u - u) < r && fabs(k.v - v) < r)) return;                   // Frame.cpp:612
+                any = true;
+                if (sp_claim[idx] < q) return;                                           // :113-115, :1596-1598
+                const int dist = sa_hamming(a, k.d);
+                if (dist < bestDist) {                                                   // :129-141, :1613
+                    bestDist2 = bestDist; bestDist = dist;
+                    bestLevel2 = bestLevel; bestLevel = kl;
+                    bestIdx = idx;
+                } else if (dist < bestDist2) {
+                    bestLevel2 = kl; bestDist2 = dist;
+                }
+            });
             int state;
             if (!any) state = local ? 7 : 4;                                             // :96, :1582
             else if (!(bestDist <= th_high && bestIdx >= 0)) state = local ? 8 : 5;      // :145, :1621

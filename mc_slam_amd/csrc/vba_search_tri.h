@@ -17,6 +17,7 @@
 #pragma once
 #include "vba_device.h"
 #include "vba_layout.h"
+#include "vba_search_area.h"   // sa_load_desc, sa_hamming
 
 #define ST_NT VBA_ST_NT
 // offsets in StDesc::c (and in the LDS copy)
@@ -94,8 +95,7 @@ __global__ void __launch_bounds__(ST_NT) k_search_tri(StBatch B) {
         const StQuery qr = query[q];
         const StKey& k1 = key1[qr.idx1];
         unsigned int a[8];
-#pragma unroll
-        for (int w = 0; w < 8; w++) a[w] = k1.d[w];
+        sa_load_desc(a, k1.d);
         const double u1 = k1.u, v1 = k1.v;
         const float angle1 = k1.angle;
         // the epipolar line of kp1 in keyframe 2: l = x1' F12 = [a b c] (:172-174)
@@ -108,9 +108,7 @@ __global__ void __launch_bounds__(ST_NT) k_search_tri(StBatch B) {
         for (int c = qr.c_begin; c < qr.c_end; c++) {
             const int idx2 = feat[c];
             const StKey& k2 = key2[idx2];
-            int dist = 0;
-#pragma unroll
-            for (int w = 0; w < 8; w++) dist += __popc(a[w] ^ k2.d[w]);
+            const int dist = sa_hamming(a, k2.d);
             // the reference tests the map point (:848) in front of the distance (:863); both are plain `continue`s, so the order
             // is free, and this one reads the second half of the record only for a candidate whose distance passes
             if (dist > th_low || dist > bestDist) continue;                       // :863

@@ -20,6 +20,22 @@
 namespace ORB_SLAM2 {
 
 namespace {
+// mGrid of a KeyFrame or Frame (mnGridCols columns, checked by the caller) in CSR form: cell (ix, iy) at ix * mnGridRows + iy.
+// false: a column does not have mnGridRows cells
+template <class F>
+bool FlattenGrid(const F& f, std::vector<int32_t>& cell_begin, std::vector<int32_t>& cell_feat) {
+    cell_begin.assign(1, 0);
+    cell_feat.clear();
+    for (int ix = 0; ix < f.mnGridCols; ix++) {
+        if (f.mGrid[(size_t)ix].size() != (size_t)f.mnGridRows) return false;
+        for (int iy = 0; iy < f.mnGridRows; iy++) {
+            for (size_t idx : f.mGrid[(size_t)ix][(size_t)iy]) cell_feat.push_back((int32_t)idx);
+            cell_begin.push_back((int32_t)cell_feat.size());
+        }
+    }
+    return true;
+}
+
 // one keyframe's side of a vba_search_tri_problem
 struct MatchSide {
     std::vector<uint8_t> has_mp, oct;
@@ -158,16 +174,11 @@ struct FuseSearch {
             }
             uv[2 * i] = kp.pt.x; uv[2 * i + 1] = kp.pt.y; oct[i] = (uint8_t)kp.octave;
         }
-        std::vector<int32_t> cell_begin(1, 0), cell_feat;
-        for (int ix = 0; ix < pKF->mnGridCols; ix++)
-            for (int iy = 0; iy < pKF->mnGridRows; iy++) {
-                if (pKF->mGrid[(size_t)ix].size() != (size_t)pKF->mnGridRows) {
-                    std::cerr << who << ": the keyframe has no grid" << std::endl;
-                    return false;
-                }
-                for (size_t idx : pKF->mGrid[(size_t)ix][(size_t)iy]) cell_feat.push_back((int32_t)idx);
-                cell_begin.push_back((int32_t)cell_feat.size());
-            }
+        std::vector<int32_t> cell_begin, cell_feat;
+        if (!FlattenGrid(*pKF, cell_begin, cell_feat)) {
+            std::cerr << who << ": the keyframe has no grid" << std::endl;
+            return false;
+        }
         const std::vector<double> scale(pKF->mvScaleFactors.begin(), pKF->mvScaleFactors.end()), inv_sigma2(pKF->mvInvLevelSigma2.begin(), pKF->mvInvLevelSigma2.end());
         std::vector<double> pos(3 * np), normal(3 * np), dmin(np), dmax(np), pmax(np);
         std::vector<uint8_t> desc(32 * np);
@@ -330,16 +341,10 @@ struct Sim3Side {
             dmin[i] = pMP->GetMinDistanceInvariance(); dmax[i] = pMP->GetMaxDistanceInvariance(); pmax[i] = pMP->mfMaxDistance;
             std::memcpy(&pt_desc[32 * i], pMP->GetDescriptor(), 32);
         }
-        cell_begin.assign(1, 0);
-        for (int ix = 0; ix < pKF->mnGridCols; ix++)
-            for (int iy = 0; iy < pKF->mnGridRows; iy++) {
-                if (pKF->mGrid[(size_t)ix].size() != (size_t)pKF->mnGridRows) {
-                    std::cerr << who << ": a keyframe has no grid" << std::endl;
-                    return false;
-                }
-                for (size_t idx : pKF->mGrid[(size_t)ix][(size_t)iy]) cell_feat.push_back((int32_t)idx);
-                cell_begin.push_back((int32_t)cell_feat.size());
-            }
+        if (!FlattenGrid(*pKF, cell_begin, cell_feat)) {
+            std::cerr << who << ": a keyframe has no grid" << std::endl;
+            return false;
+        }
         scale.assign(pKF->mvScaleFactors.begin(), pKF->mvScaleFactors.end());
         pKF->GetRotation(S.Rcw); pKF->GetTranslation(S.tcw);
         S.bounds[0] = pKF->mnMinX; S.bounds[1] = pKF->mnMaxX; S.bounds[2] = pKF->mnMinY; S.bounds[3] = pKF->mnMaxY;
@@ -450,16 +455,10 @@ struct ProjSearch {
             uv[2 * i] = kp.pt.x; uv[2 * i + 1] = kp.pt.y; oct[i] = (uint8_t)kp.octave; angle[i] = kp.angle;
             occupied[i] = F.mvpMapPoints[i] && F.mvpMapPoints[i]->Observations() > 0;   // :113-115, :1596-1598 in front of the call
         }
-        cell_begin.assign(1, 0);
-        for (int ix = 0; ix < F.mnGridCols; ix++)
-            for (int iy = 0; iy < F.mnGridRows; iy++) {
-                if (F.mGrid[(size_t)ix].size() != (size_t)F.mnGridRows) {
-                    std::cerr << who << ": the frame has no grid" << std::endl;
-                    return false;
-                }
-                for (size_t idx : F.mGrid[(size_t)ix][(size_t)iy]) cell_feat.push_back((int32_t)idx);
-                cell_begin.push_back((int32_t)cell_feat.size());
-            }
+        if (!FlattenGrid(F, cell_begin, cell_feat)) {
+            std::cerr << who << ": the frame has no grid" << std::endl;
+            return false;
+        }
         scale.assign(F.mvScaleFactors.begin(), F.mvScaleFactors.end());
         P.K[0] = F.fx; P.K[1] = F.fy; P.K[2] = F.cx; P.K[3] = F.cy;
         P.bounds[0] = F.mnMinX; P.bounds[1] = F.mnMaxX; P.bounds[2] = F.mnMinY; P.bounds[3] = F.mnMaxY;

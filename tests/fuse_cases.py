@@ -47,20 +47,21 @@ def point(u, v, z, desc, level=0, skip=0, dmin=0.1, dmax=10.0, flip_normal=False
                 desc=desc, skip=skip)
 
 
-def craft(keys, pts, insert_order=None, **kw):
-    """a problem from lists of key() and point(); the grid is filled as AssignFeaturesToGrid does when it meets the keypoints in
-    insert_order (ascending by default), so a cell lists its keypoints in that order"""
+def craft(keys, pts, insert_order=None, grid=(COLS, ROWS), **kw):
+    """a problem from lists of key() and point(); the grid (columns, rows) is filled as AssignFeaturesToGrid does when it meets the
+    keypoints in insert_order (ascending by default), so a cell lists its keypoints in that order"""
     scale, sigma2 = synth.level_tables(NL)
     uv = np.array([[k["u"], k["v"]] for k in keys], dtype=float).reshape(-1, 2)
     order = list(range(len(keys))) if insert_order is None else list(insert_order)
-    inv_w, inv_h = COLS / W, ROWS / H
-    begin, feat = abi.grid_csr(uv[order], (0, W, 0, H), COLS, ROWS, inv_w, inv_h)
+    cols, rows = grid
+    inv_w, inv_h = cols / W, rows / H
+    begin, feat = abi.grid_csr(uv[order], (0, W, 0, H), cols, rows, inv_w, inv_h)
     feat = np.asarray(order, dtype=np.int32)[feat]
     a = lambda name, shape: np.array([q[name] for q in pts], dtype=float).reshape(shape)
     return abi.FuseProblem(Rcw=np.eye(3), tcw=np.zeros(3), Ow=np.zeros(3), K=K_HAND, bounds=(0, W, 0, H),
                            desc=np.array([k["desc"] for k in keys], dtype=np.uint8).reshape(-1, 32), uv=uv,
                            oct=np.array([k["oct"] for k in keys], dtype=np.uint8), scale=scale, inv_level_sigma2=1.0 / sigma2, log_scale_factor=LOG_SF,
-                           grid_cols=COLS, grid_rows=ROWS, grid_inv_w=inv_w, grid_inv_h=inv_h, cell_begin=begin, cell_feat=feat,
+                           grid_cols=cols, grid_rows=rows, grid_inv_w=inv_w, grid_inv_h=inv_h, cell_begin=begin, cell_feat=feat,
                            pos=a("pos", (-1, 3)), normal=a("normal", (-1, 3)), dist_min=a("dist_min", -1), dist_max=a("dist_max", -1),
                            pred_max=a("pred_max", -1), pt_desc=np.array([q["desc"] for q in pts], dtype=np.uint8).reshape(-1, 32),
                            skip=np.array([q["skip"] for q in pts], dtype=np.uint8), **kw)
@@ -145,6 +146,16 @@ def _border_returns():
     return craft([key(41, 30, 0, D[0])] + FILLER, pts, th=-20.0)
 
 
+def _one_axis_empty(grid):
+    """th = -20 over cells that are not square: every point passes the four early returns of GetFeaturesInArea, and the clamped cell
+    range is empty along ONE axis only.  grid = (1, 4), cells of 80 x 15 pixels: 40 pixels are less than a column and more than two
+    rows, so nMinCellX <= nMaxCellX and nMaxCellY < nMinCellY.  grid = (5, 1), cells of 16 x 60 pixels: the transpose.  A keypoint
+    with the exact descriptor sits under the first point (tests/test_fuse_ref.py prints and asserts the ranges)"""
+    pts = [point(41.5, 30.4, 4.0, D[0], level=0), point(33.3, 33.0, 4.0, D[0], level=0), point(47.8, 22.7, 4.0, D[0], level=0),
+           point(12.3, 30.4, 4.0, D[0], level=0)]
+    return craft([key(41, 30, 0, D[0])] + FILLER, pts, grid=grid, th=-20.0)
+
+
 def toggled(p, **kw):
     return p.copy(**kw)
 
@@ -159,6 +170,8 @@ def cases():
     c["border"] = _border()
     c["border_all"] = _border(th=1000.0, check_reproj=False)             # a radius larger than the image: every cell is walked
     c["border_returns"] = _border_returns()
+    c["rows_empty"] = _one_axis_empty((1, 4))
+    c["cols_empty"] = _one_axis_empty((5, 1))
     c["reproj_on"] = synth.fuse_scene(21, n_keys=150, n_pt=100, noise=1.6)
     c["reproj_off"] = c["reproj_on"].copy(check_reproj=False)
     c["empty_pt"] = synth.fuse_scene(22, n_keys=50, n_pt=0)

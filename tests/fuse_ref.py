@@ -66,29 +66,47 @@ def _to_int(x):
     return int(x)
 
 
-def features_in_area(p, fp, T, uvT, x, y, r):
-    """KeyFrame::GetFeaturesInArea: the keypoint indices in walk order"""
-    out = []
+def cell_range(p, fp, T, x, y, r):
+    """the clamped cell range (nMinCellX, nMaxCellX, nMinCellY, nMaxCellY) of GetFeaturesInArea; None after one of its four returns"""
     min_x, min_y = T(p.bounds[0]), T(p.bounds[2])
     iw, ih = T(p.grid_inv_w), T(p.grid_inv_h)
     cols, rows = int(p.grid_cols), int(p.grid_rows)
     n_min_x = max(0, _to_int(fp.floor((x - min_x - r) * iw)))
     if n_min_x >= cols:
-        return out
+        return None
     n_max_x = min(cols - 1, _to_int(fp.ceil((x - min_x + r) * iw)))
     if n_max_x < 0:
-        return out
+        return None
     n_min_y = max(0, _to_int(fp.floor((y - min_y - r) * ih)))
     if n_min_y >= rows:
-        return out
+        return None
     n_max_y = min(rows - 1, _to_int(fp.ceil((y - min_y + r) * ih)))
     if n_max_y < 0:
+        return None
+    return n_min_x, n_max_x, n_min_y, n_max_y
+
+
+def features_in_area(p, fp, T, uvT, x, y, r, min_level=-1, max_level=-1):
+    """KeyFrame::GetFeaturesInArea(x, y, r) and Frame::GetFeaturesInArea(x, y, r, minLevel, maxLevel) (src/Frame.cpp:562-620, the same
+    walk with a level filter in front of the pixel test; the defaults switch it off): the keypoint indices in walk order"""
+    out = []
+    cells = cell_range(p, fp, T, x, y, r)
+    if cells is None:
         return out
+    n_min_x, n_max_x, n_min_y, n_max_y = cells
+    rows = int(p.grid_rows)
+    check_levels = (min_level > 0) or (max_level >= 0)
     for ix in range(n_min_x, n_max_x + 1):
         for iy in range(n_min_y, n_max_y + 1):
             c = ix * rows + iy
             for j in range(p.cell_begin[c], p.cell_begin[c + 1]):
                 idx = int(p.cell_feat[j])
+                if check_levels:
+                    if int(p.oct[idx]) < min_level:
+                        continue
+                    if max_level >= 0:
+                        if int(p.oct[idx]) > max_level:
+                            continue
                 distx = uvT[idx, 0] - x
                 disty = uvT[idx, 1] - y
                 if fp.lt(abs(distx), r) and fp.lt(abs(disty), r):

@@ -13,46 +13,9 @@ counts): what an independent-query kernel would give.  The one deviation of the 
 projection leaves with state 3; and a match needs a keypoint (th_high = 256 with every candidate taken)."""
 import numpy as np
 
-from fuse_ref import _Fp, _to_int, descriptor_distance
+from fuse_ref import _Fp, descriptor_distance, features_in_area
 
 HISTO = 30
-
-
-def features_in_area(p, fp, T, uvT, x, y, r, min_level, max_level):
-    """Frame::GetFeaturesInArea(x, y, r, minLevel, maxLevel): the keypoint indices in walk order"""
-    out = []
-    min_x, min_y = T(p.bounds[0]), T(p.bounds[2])
-    iw, ih = T(p.grid_inv_w), T(p.grid_inv_h)
-    cols, rows = int(p.grid_cols), int(p.grid_rows)
-    n_min_x = max(0, _to_int(fp.floor((x - min_x - r) * iw)))
-    if n_min_x >= cols:
-        return out
-    n_max_x = min(cols - 1, _to_int(fp.ceil((x - min_x + r) * iw)))
-    if n_max_x < 0:
-        return out
-    n_min_y = max(0, _to_int(fp.floor((y - min_y - r) * ih)))
-    if n_min_y >= rows:
-        return out
-    n_max_y = min(rows - 1, _to_int(fp.ceil((y - min_y + r) * ih)))
-    if n_max_y < 0:
-        return out
-    check_levels = (min_level > 0) or (max_level >= 0)
-    for ix in range(n_min_x, n_max_x + 1):
-        for iy in range(n_min_y, n_max_y + 1):
-            c = ix * rows + iy
-            for j in range(p.cell_begin[c], p.cell_begin[c + 1]):
-                idx = int(p.cell_feat[j])
-                if check_levels:
-                    if int(p.oct[idx]) < min_level:
-                        continue
-                    if max_level >= 0:
-                        if int(p.oct[idx]) > max_level:
-                            continue
-                distx = uvT[idx, 0] - x
-                disty = uvT[idx, 1] - y
-                if fp.lt(abs(distx), r) and fp.lt(abs(disty), r):
-                    out.append(idx)
-    return out
 
 
 def three_maxima(hist):

@@ -27,6 +27,8 @@ import search_sim3_ref as ref_mod
 K_HAND = np.array([50.0, 50.0, 40.0, 30.0])
 LOG_SF = float(np.float32(np.log(np.float32(1.2))))
 GEOM = [dict(bounds=(0.0, 80.0, 0.0, 60.0), cols=8, rows=6, nl=4), dict(bounds=(4.0, 76.0, 6.0, 54.0), cols=6, rows=4, nl=5)]
+# the same images under cells that are not square: 80 x 15 pixels in keyframe 1, 18 x 48 pixels in keyframe 2 (one_axis_empty)
+GEOM_FLAT = [dict(GEOM[0], cols=1, rows=4), dict(GEOM[1], cols=4, rows=1)]
 
 
 def _rot(axis, a):
@@ -61,8 +63,8 @@ def _world(side, c, T):
     return T["R2"].T @ (T["R12"].T @ (c - T["t12"]) / T["s12"] - T["t2"])
 
 
-def _kf(side, keys, T, insert_order=None):
-    G = GEOM[side]
+def _kf(side, keys, T, insert_order=None, geom=GEOM):
+    G = geom[side]
     b = G["bounds"]
     inv_w, inv_h = G["cols"] / (b[1] - b[0]), G["rows"] / (b[3] - b[2])
     n = len(keys)
@@ -86,25 +88,25 @@ def _kf(side, keys, T, insert_order=None):
                             has_pt=has, matched=matched, pos=pos, dist_min=dist[:, 0], dist_max=dist[:, 1], pred_max=dist[:, 2], pt_desc=pdesc)
 
 
-def pair(keys1, keys2, T=GENERAL, order1=None, order2=None, th=3.0, th_high=100):
-    return abi.SearchSim3Problem(kf1=_kf(0, keys1, T, order1), kf2=_kf(1, keys2, T, order2), K=K_HAND, s12=T["s12"], R12=T["R12"], t12=T["t12"],
+def pair(keys1, keys2, T=GENERAL, order1=None, order2=None, th=3.0, th_high=100, geom=GEOM):
+    return abi.SearchSim3Problem(kf1=_kf(0, keys1, T, order1, geom), kf2=_kf(1, keys2, T, order2, geom), K=K_HAND, s12=T["s12"], R12=T["R12"], t12=T["t12"],
                                  th=th, th_high=th_high)
 
 
-def build(gen, T=GENERAL, descending=False, extra=(0, 0), **kw):
+def build(gen, T=GENERAL, descending=False, extra=(0, 0), geom=GEOM, **kw):
     """the pair of gen(G) -> (target keypoints, queries[, expected answers]) for both directions; extra[s] more keypoints without a
     point on side s.  Returns (pair, expect) with expect[d] = the answers of direction d as gen gave them (or None)"""
-    out = [gen(GEOM[1]), gen(GEOM[0])]                # direction 0 searches keyframe 2, direction 1 keyframe 1
+    out = [gen(geom[1]), gen(geom[0])]                # direction 0 searches keyframe 2, direction 1 keyframe 1
     keys, expect = [], []
     for s in range(2):
         targets, queries = out[1 - s][0], out[s][1]   # side s is the target of direction 1 - s and the source of direction s
-        b = GEOM[s]["bounds"]
+        b = geom[s]["bounds"]
         carriers = [key(b[0] + 2.5 + (3.1 * k) % (b[1] - b[0] - 5), b[3] - 1.5, 0, D[15], pt=q) for k, q in enumerate(queries)]
         spare = [key(b[0] + 3.5 + (2.7 * k) % (b[1] - b[0] - 5), b[3] - 1.2, 0, D[14]) for k in range(extra[s])]
         keys.append(list(targets) + carriers + spare)
         expect.append(out[s][2] if len(out[s]) > 2 else None)
     od = lambda s: range(len(keys[s]) - 1, -1, -1) if descending else None
-    return pair(keys[0], keys[1], T, od(0), od(1), **kw), expect
+    return pair(keys[0], keys[1], T, od(0), od(1), geom=geom, **kw), expect
 
 
 def fillers(G):
@@ -197,6 +199,24 @@ def _border_returns(G):
     return [key(xm - 0.5, ym - 0.4, 0, D[0])] + fillers(G), queries, [(7, -1, 256, 0)] * 5
 
 
+def _one_axis_empty(G):
+    """th = -20 over the cells of GEOM_FLAT: every query passes the four early returns of GetFeaturesInArea, and the clamped cell
+    range is empty along ONE axis only.  Into keyframe 1 (cells of 80 x 15 pixels) 40 pixels are less than a column and more than
+    two rows: nMinCellX <= nMaxCellX and nMaxCellY < nMinCellY.  Into keyframe 2 (18 x 48 pixels) the transpose.  A keypoint with
+    the exact descriptor sits under the first query (tests/test_search_sim3_ref.py prints and asserts the ranges)"""
+    x0, x1, y0, y1 = G["bounds"]
+    xm, ym = 0.5 * (x0 + x1) + 1.5, 0.5 * (y0 + y1) + 0.4
+    queries = [query(u, v, 4.0, D[0]) for u, v in one_axis_empty_uv(G)]
+    return [key(xm - 0.5, ym - 0.4, 0, D[0])] + fillers(G), queries, [(7, -1, 256, 0)] * len(queries)
+
+
+def one_axis_empty_uv(G):
+    """where the queries of one_axis_empty lie in the target's image"""
+    x0, x1, y0, y1 = G["bounds"]
+    xm, ym = 0.5 * (x0 + x1) + 1.5, 0.5 * (y0 + y1) + 0.4
+    return [(xm, ym), (xm - 8.2, ym + 2.6), (xm + 6.3, ym - 7.7), (x0 + 12.3, ym)]
+
+
 def _agree():
     """the agreement loop (:1480-1493) on keypoints that are source and target at once, all at level 0.  a / A: a mutual match.
     b -> B while B -> b2.  c -> C, which has no point.  d -> D', which is already matched: targets are never filtered, so match1
@@ -225,14 +245,16 @@ def agree_expect():
     return _agree()[1]
 
 
-HAND = dict(micro=_micro, tie_cells=_tie_cells, z_zero=_z_zero, level_edges=_level_edges, border=_border, border_all=_border, border_returns=_border_returns)
-HAND_KW = dict(micro=dict(extra=(2, 3)), tie_cells=dict(descending=True), z_zero=dict(T=IDENTITY), border_all=dict(th=1000.0), border_returns=dict(th=-20.0))
+HAND = dict(micro=_micro, tie_cells=_tie_cells, z_zero=_z_zero, level_edges=_level_edges, border=_border, border_all=_border, border_returns=_border_returns,
+            one_axis_empty=_one_axis_empty)
+HAND_KW = dict(micro=dict(extra=(2, 3)), tie_cells=dict(descending=True), z_zero=dict(T=IDENTITY), border_all=dict(th=1000.0), border_returns=dict(th=-20.0),
+               one_axis_empty=dict(th=-20.0, geom=GEOM_FLAT))
 
 
 def hand_expect(name):
     """expect[d][query] = (state, match, best_dist, level) of the hand-made case, and the index of query 0's carrier per direction"""
     p, e = build(HAND[name], **HAND_KW.get(name, {}))
-    first = [len(HAND[name](GEOM[s])[0]) for s in range(2)]      # side s holds the targets of direction 1 - s in front of its carriers
+    first = [len(HAND[name](HAND_KW.get(name, {}).get("geom", GEOM)[s])[0]) for s in range(2)]      # side s holds the targets of direction 1 - s in front of its carriers
     return e, first
 
 

@@ -95,6 +95,22 @@ def test_border_cases():
     assert list(cases.ref("border_returns")["state"]) == [7, 7, 7, 7, 7]
 
 
+@pytest.mark.parametrize("name, x_empty", [("rows_empty", False), ("cols_empty", True)])
+def test_negative_radius_empties_one_axis(name, x_empty):
+    """every point of the case passes the gates and the four returns of GetFeaturesInArea; its clamped cell range holds columns and
+    no row (rows_empty) or rows and no column (cols_empty); the yardstick leaves with state 7"""
+    p, r = cases.cases()[name], cases.ref(name)
+    assert list(r["state"]) == [7] * p.n_pt and list(r["level"]) == [0] * p.n_pt and p.n_pt >= 4
+    fp = ref_mod._Fp()
+    for i in range(p.n_pt):
+        cells = ref_mod.cell_range(p, fp, np.float64, r["uv"][i, 0], r["uv"][i, 1], np.float64(p.th) * np.float64(p.scale[0]))
+        print(name, "point", i, "uv", r["uv"][i], "cells x %s .. %s  y %s .. %s" % (cells or (None,) * 4))
+        assert cells is not None
+        nx0, nx1, ny0, ny1 = cells
+        assert (nx1 < nx0 and ny0 <= ny1) if x_empty else (nx0 <= nx1 and ny1 < ny0), (i, cells)
+    assert fp.n_round == 4 * p.n_pt and fp.margin_r >= MARGIN
+
+
 def test_reproj_and_empty_cases():
     on, off = cases.ref("reproj_on"), cases.ref("reproj_off")
     moved = (on["state"] != off["state"]) | (on["best_idx"] != off["best_idx"])

@@ -85,6 +85,26 @@ def test_hand_made_answers(name):
             assert f.index(5) + 1 == f.index(3) and f.index(7) < f.index(2)   # one cell lists 5 in front of 3; 7 sits in an earlier column
 
 
+def test_negative_radius_empties_one_axis():
+    """every query of one_axis_empty passes the four returns of GetFeaturesInArea; the clamped cell range holds columns and no row in
+    keyframe 1 and rows and no column in keyframe 2.  The ranges are taken at the pixels the queries were placed at; the yardstick
+    projects to within 1e-9 pixels of them (its own roundings are covered by test_every_comparison_and_rounding_has_a_margin), and
+    the floor and ceil arguments here keep 1e-6 from an integer"""
+    from fuse_ref import cell_range
+    p = cases.cases()["one_axis_empty"]
+    for d, (tgt, x_empty) in enumerate(((p.kf2, True), (p.kf1, False))):
+        fp = ref_mod._Fp()
+        G = cases.GEOM_FLAT[1 - d]
+        assert (tgt.grid_cols, tgt.grid_rows) == (G["cols"], G["rows"])
+        for i, (u, v) in enumerate(cases.one_axis_empty_uv(G)):
+            cells = cell_range(tgt, fp, np.float64, np.float64(u), np.float64(v), np.float64(p.th) * np.float64(tgt.scale[0]))
+            print("direction", d, "query", i, "uv", (u, v), "cells x %s .. %s  y %s .. %s" % (cells or (None,) * 4))
+            assert cells is not None
+            nx0, nx1, ny0, ny1 = cells
+            assert (nx1 < nx0 and ny0 <= ny1) if x_empty else (nx0 <= nx1 and ny1 < ny0), (d, i, cells)
+        assert fp.n_round == 16 and fp.margin_r >= 1e-6
+
+
 def test_agreement_cases():
     r, e = cases.ref("agree"), cases.agree_expect()
     for k, want in e.items():
