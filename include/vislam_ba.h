@@ -123,7 +123,7 @@ typedef struct vba_profile {
     double total_ms;             /* first launch -> last launch of the run */
     double factor_flops;         /* FP64 flop the factorisation class executed on MFMA: 2*32^3 per tile product of the
                                     symbolic tile lists, per solve (structurally zero tiles are never touched) */
-    int64_t kernel_launches;     /* kernel launches the last vba_batch_run / vba_solve / vba_sim3_optimize / vba_sim3_ransac / vba_triangulate / vba_two_view_init (at most 2) / vba_search_triangulation / vba_fuse / vba_search_by_sim3 / vba_search_by_projection / vba_posegraph_optimize enqueued (filled with or without profiling) */
+    int64_t kernel_launches;     /* kernel launches the last vba_batch_run / vba_solve / vba_sim3_optimize / vba_sim3_ransac / vba_triangulate / vba_two_view_init (at most 2) / vba_search_triangulation / vba_fuse / vba_search_by_sim3 / vba_search_by_projection / vba_search_by_bow / vba_posegraph_optimize enqueued (filled with or without profiling) */
 } vba_profile;
 
 /* One handle per host thread / GPU; owns device buffers and a stream.  Errors: nonzero return, message
@@ -178,7 +178,7 @@ int vba_batch_solve_b(void *handle, int32_t n_windows, vba_problem *const *inout
  *           every later one, those submitted afterwards included, with the same message: no GPU work starts for them (earlier
  *           tickets finish).  Waiting on an unknown or retired ticket returns -1.
  *   handle  while any ticket is submitted and not yet waited for, every synchronous entry point of the handle (vba_solve*,
- *           vba_batch_upload / run / download / solve*, vba_pose_optimize, vba_sim3_optimize, vba_sim3_ransac, vba_triangulate, vba_two_view_init, vba_search_triangulation, vba_fuse, vba_search_by_sim3, vba_search_by_projection, vba_posegraph_optimize, vba_preintegrate, vba_set_profile,
+ *           vba_batch_upload / run / download / solve*, vba_pose_optimize, vba_sim3_optimize, vba_sim3_ransac, vba_triangulate, vba_two_view_init, vba_search_triangulation, vba_fuse, vba_search_by_sim3, vba_search_by_projection, vba_search_by_bow, vba_posegraph_optimize, vba_preintegrate, vba_set_profile,
  *           vba_batch_set_depth) returns -1 with "asynchronous batches pending: wait for them first"; afterwards the handle
  *           works synchronously as before.  vba_destroy finishes pending tickets (their results land) before it frees.
  *           Profiling (vba_set_profile) covers synchronous calls only.  One caller thread at a time, as everywhere. */
@@ -811,6 +811,90 @@ typedef struct vba_search_proj_result {
  * bound, pixel, level table, position, normal, distance or threshold that the mode reads.  A problem's outputs do not depend on
  * where it stands in the batch. */
 int vba_search_by_projection(void *handle, int32_t n_problems, vba_search_proj_problem *const *in, vba_search_proj_result *const *out);
+
+/* ---- bag-of-words matching ----
+ * Both ORBmatcher::SearchByBoW overloads (src/ORBmatcher.cpp), selected by `mode`:
+ *   VBA_SEARCH_BOW_KF_FRAME  SearchByBoW(KeyFrame*, Frame&, vpMapPointMatches) (:207-350): Tracking::TrackReferenceKeyFrame
+ *                            (src/Tracking.cpp:1600, in front of vba_pose_optimize) and Tracking::Relocalization (:2429)
+ *   VBA_SEARCH_BOW_KF_KF     SearchByBoW(KeyFrame*, KeyFrame*, vpMatches12) (:609-748): LoopClosing::ComputeSim3
+ *                            (src/LoopClosing.cpp:317, in front of vba_sim3_ransac)
+ * One problem is one pair (side 1: the keyframe whose map points are carried over; side 2: the frame or the second keyframe); one
+ * call takes any number of pairs, ragged, both modes mixed, in one kernel launch (one 256-lane workgroup per pair).  The reference
+ * is restated as it stands:
+ *   node join   the two feature vectors are walked as the `while` of :229-322 / :639-725 does (equal ids: the node is shared; else
+ *               lower_bound on the side that is behind).  Every keypoint of side 1 in a shared node is visited in the order the
+ *               node lists it; it leaves when it has no map point or a bad one (:243-247, :649-652: good_mp1)
+ *   query       bestDist1 = 256, bestIdx = -1, bestDist2 = 256.  Every keypoint of side 2 in the same node, in list order: skipped
+ *               when it is TAKEN by an earlier match of this call (:260 vpMapPointMatches[realIdxF], :667 vbMatched2[idx2]) and, in
+ *               KF_KF mode only, when it has no map point or a bad one (:667-671: good_mp2); otherwise dist < bestDist1 (strict)
+ *               moves the best to the second and replaces the best, else dist < bestDist2 replaces the second.  Among equal
+ *               distances the FIRST in list order is the best and the equal one becomes bestDist2
+ *   threshold   bestDist1 <= th_low in KF_FRAME mode (:280), bestDist1 < th_low in KF_KF mode (:691)
+ *   ratio       (float)bestDist1 < nn_ratio * (float)bestDist2, the product in float32 (:284, :693)
+ *   match       the keypoint of side 2 is taken for every later query (:287, :696); nmatches++
+ *   orientation rot = angle1 - angle2; if (rot < 0) rot += 360.0f; bin = round(rot * (1.0f / 30)) in float32 with C round (:296-303,
+ *               :700-707), ComputeThreeMaxima (:1800-1841), every match of another bin cleared and nmatches-- (:325-347, :727-745).  The
+ *               drop clears outputs only: the walk is over, nothing is un-taken
+ * The queries of a pair are not independent: a query reads the taken flags earlier queries wrote.  It reads them only for keypoints
+ * of side 2 in its own node, and a keypoint is listed in at most one node, so queries of different shared nodes never interact.
+ * Taking a query's best candidate away changes bestDist1 AND bestDist2, so a query can move between matched, ratio test failed and
+ * threshold failed.  The kernel resolves that with an order-preserving conflict pass whose result is the sequential one (rounds of
+ * every open query against the claim table of the round before, the table rebuilt, until a round changes no claim); `rounds` counts
+ * them, the detecting round included, and is at most (the largest number of queries in one shared node) + 1 (DESIGN.md section 8,
+ * row f-14, has the proof).
+ * `state` says where a keypoint of side 1 left the function, numbered in the order of the reference's exits:
+ *   0  matched and kept
+ *   1  no good map point (:243-247, :649-652); this wins over 2
+ *   2  no node that both sides list holds it
+ *   3  threshold failed (:280, :691), "no candidate" and "every candidate taken" included
+ *   4  ratio test failed (:284, :693)
+ *   5  matched, then dropped by the orientation filter (:343, :741)
+ * Every output is an integer; float32 appears in the ratio product and in the bin only. */
+#define VBA_SEARCH_BOW_KF_FRAME 0      /* :207-350, threshold <=, every side-2 keypoint is a candidate */
+#define VBA_SEARCH_BOW_KF_KF    1      /* :609-748, threshold <,  side-2 keypoints without a good map point are no candidates */
+#define VBA_SEARCH_BOW_MAX_KEYS 16384  /* the claim table of side 2 lives in LDS */
+typedef struct vba_search_bow_problem {
+    int32_t mode;                    /* VBA_SEARCH_BOW_KF_FRAME or VBA_SEARCH_BOW_KF_KF */
+    int32_t check_orientation;       /* mbCheckOrientation (:291, :325, :698, :727) */
+    int32_t th_low;                  /* TH_LOW = 50 (:280, :691); 0 .. 255 */
+    float nn_ratio;                  /* mfNNratio: 0.75f at src/LoopClosing.cpp:285, 0.7f at src/Tracking.cpp:1597, 0.75f at :2405 */
+    int32_t n_keys1, n_keys2;        /* pKF->N / F.N; n_keys2 at most VBA_SEARCH_BOW_MAX_KEYS */
+    const uint8_t *desc1, *desc2;    /* [n_keys][32] the rows of mDescriptors (:249, :263) */
+    const uint8_t *good_mp1;         /* [n_keys1] non-zero: map point present and not bad (:243-247) */
+    const uint8_t *good_mp2;         /* [n_keys2] the same of side 2 (:665-671); read in KF_KF mode only, may be NULL in KF_FRAME mode */
+    const float *angle1, *angle2;    /* [n_keys] mvKeysUn[idx].angle / F.mvKeys[idx].angle in [0, 360) (:296, :700); read with check_orientation only */
+    int32_t n_nodes1, n_nodes2;      /* entries of mFeatVec */
+    const uint32_t *node_id1, *node_id2;      /* [n_nodes] strictly ascending: the order of the std::map */
+    const int32_t *node_begin1, *node_begin2; /* [n_nodes + 1] node k lists node_feat[node_begin[k] .. node_begin[k + 1]) */
+    const int32_t *node_feat1, *node_feat2;   /* keypoint indices in the order the node's vector holds them; each keypoint at most once */
+} vba_search_bow_problem;
+
+typedef struct vba_search_bow_result {
+    int32_t status;           /* VBA_OK */
+    int32_t n_matches;        /* the return value (:349, :747) */
+    int32_t n_before_filter;  /* nmatches in front of the orientation filter; n_matches without one */
+    int32_t hist[30];         /* rotHist[i].size() in front of the filter (zeros without check_orientation) */
+    int32_t ind[3];           /* ind1 .. ind3 of ComputeThreeMaxima, -1 as the reference leaves them (and without check_orientation) */
+    int32_t rounds;           /* rounds of the conflict pass, 1 .. (largest number of queries in one shared node) + 1 */
+    int32_t *match12;         /* [n_keys1] caller-allocated: the keypoint of side 2 behind the filter, -1 otherwise (vpMatches12 as an index) */
+    int32_t *best_idx;        /* [n_keys1] caller-allocated: bestIdx as the candidate loop left it, -1 if none (and in the states 1, 2) */
+    uint16_t *best_dist;      /* [n_keys1] caller-allocated: bestDist1; 256 = none */
+    uint16_t *best_dist2;     /* [n_keys1] caller-allocated: bestDist2; 256 = none */
+    uint8_t *bin;             /* [n_keys1] caller-allocated: the histogram bin of a match (states 0 and 5) with check_orientation; 255 = none */
+    uint8_t *state;           /* [n_keys1] caller-allocated: the codes above */
+    int32_t *match21;         /* [n_keys2] caller-allocated: the keypoint of side 1 whose match the function leaves there: -1 untouched, -2
+                                 set and then cleared by the orientation filter.  In KF_FRAME mode exactly vpMapPointMatches as an index */
+} vba_search_bow_result;
+
+/* Synchronous, like vba_search_triangulation; -1 while asynchronous tickets are pending.  n_pairs == 0 returns 0; a pair without
+ * keypoints or without a shared node is legal (n_matches = 0, every state 1 or 2, rounds = 1).  A bad pair fails the whole call
+ * before any GPU work, with nothing written, as "vba_search_by_bow: pair K: <why>" through vba_last_error: a NULL problem or
+ * result, an unknown mode, a negative count, n_keys2 above VBA_SEARCH_BOW_MAX_KEYS, th_low outside 0 .. 255, a non-finite nn_ratio, a
+ * NULL array with a non-zero count (match12, best_idx, best_dist, best_dist2, bin and state are required when n_keys1 > 0, match21
+ * when n_keys2 > 0, good_mp2 in KF_KF mode), node ids that are not strictly ascending, a node_begin that does not start at 0 or
+ * decreases, a keypoint index outside its side or listed twice in one feature vector, and with check_orientation a NULL angle array
+ * or an angle outside [0, 360).  A pair's outputs do not depend on where it stands in the batch. */
+int vba_search_by_bow(void *handle, int32_t n_pairs, vba_search_bow_problem *const *in, vba_search_bow_result *const *out);
 
 /* ---- essential-graph optimisation (Sim3 pose graph) ----
  * Optimizer::OptimizeEssentialGraph(Map*, KeyFrame* pLoopKF, KeyFrame* pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections,

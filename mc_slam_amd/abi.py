@@ -1433,6 +1433,141 @@ class SearchProjResultBuf:
                                 self.st[:n].copy(), self.km[:self.nk].copy())
 
 
+# ---- bag-of-words matching (include/vislam_ba.h: vba_search_bow_problem / vba_search_bow_result) ----
+SEARCH_BOW_KF_FRAME, SEARCH_BOW_KF_KF = 0, 1
+SEARCH_BOW_MAX_KEYS = 16384
+
+
+class vba_search_bow_problem(C.Structure):
+    _fields_ = [
+        ("mode", C.c_int32), ("check_orientation", C.c_int32), ("th_low", C.c_int32), ("nn_ratio", C.c_float), ("n_keys1", C.c_int32),
+        ("n_keys2", C.c_int32), ("desc1", _pu8), ("desc2", _pu8), ("good_mp1", _pu8), ("good_mp2", _pu8), ("angle1", _pf), ("angle2", _pf),
+        ("n_nodes1", C.c_int32), ("n_nodes2", C.c_int32), ("node_id1", _pu32), ("node_id2", _pu32), ("node_begin1", _pi), ("node_begin2", _pi),
+        ("node_feat1", _pi), ("node_feat2", _pi),
+    ]
+
+
+class vba_search_bow_result(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_matches", C.c_int32), ("n_before_filter", C.c_int32), ("hist", C.c_int32 * 30), ("ind", C.c_int32 * 3),
+                ("rounds", C.c_int32), ("match12", _pi), ("best_idx", _pi), ("best_dist", _pu16), ("best_dist2", _pu16), ("bin", _pu8), ("state", _pu8),
+                ("match21", _pi)]
+
+
+(SB_MATCHED, SB_NO_MAP_POINT, SB_NO_SHARED_NODE, SB_THRESHOLD, SB_RATIO, SB_ROTATION) = range(6)
+
+
+@dataclass
+class SearchBowProblem:
+    """One ORBmatcher::SearchByBoW call as flat arrays: side 1 is the keyframe whose map points are carried over, side 2 the frame
+    (mode SEARCH_BOW_KF_FRAME, src/ORBmatcher.cpp:207-350) or the second keyframe (SEARCH_BOW_KF_KF, :609-748); feature vectors in
+    CSR form.  good_mp2 and the angles may stay None where the mode does not read them."""
+    mode: int
+    desc1: np.ndarray              # [n1,32] uint8
+    desc2: np.ndarray              # [n2,32] uint8
+    good_mp1: np.ndarray           # [n1] uint8
+    node_id1: np.ndarray           # [nodes1] uint32, strictly ascending
+    node_begin1: np.ndarray        # [nodes1 + 1] int32
+    node_feat1: np.ndarray         # int32
+    node_id2: np.ndarray
+    node_begin2: np.ndarray
+    node_feat2: np.ndarray
+    good_mp2: np.ndarray = None    # [n2] uint8, KF_KF mode
+    angle1: np.ndarray = None      # [n1] float32, with check_orientation
+    angle2: np.ndarray = None      # [n2] float32
+    th_low: int = 50
+    nn_ratio: float = 0.75
+    check_orientation: bool = True
+    truth: dict = field(default_factory=dict)
+
+    def __post_init__(self):
+        u8 = lambda a, shape: np.ascontiguousarray(a, dtype=np.uint8).reshape(shape)
+        opt = lambda a, f, *s: None if a is None else f(a, *s)
+        f32 = lambda a, shape: np.ascontiguousarray(a, dtype=np.float32).reshape(shape)
+        self.desc1 = u8(self.desc1, (-1, 32)); self.desc2 = u8(self.desc2, (-1, 32))
+        self.good_mp1 = u8(self.good_mp1, (-1,)); self.good_mp2 = opt(self.good_mp2, u8, (-1,))
+        self.angle1 = opt(self.angle1, f32, (-1,)); self.angle2 = opt(self.angle2, f32, (-1,))
+        self.node_id1 = np.ascontiguousarray(self.node_id1, dtype=np.uint32).reshape(-1)
+        self.node_id2 = np.ascontiguousarray(self.node_id2, dtype=np.uint32).reshape(-1)
+        self.node_begin1 = _i32(self.node_begin1).reshape(-1); self.node_begin2 = _i32(self.node_begin2).reshape(-1)
+        self.node_feat1 = _i32(self.node_feat1).reshape(-1); self.node_feat2 = _i32(self.node_feat2).reshape(-1)
+        self.nn_ratio = float(np.float32(self.nn_ratio))
+
+    n_keys1 = property(lambda self: self.desc1.shape[0])
+    n_keys2 = property(lambda self: self.desc2.shape[0])
+    n_nodes1 = property(lambda self: self.node_id1.shape[0])
+    n_nodes2 = property(lambda self: self.node_id2.shape[0])
+    kf_kf = property(lambda self: self.mode == SEARCH_BOW_KF_KF)
+
+    def copy(self, **changes):
+        import copy as _c
+        q = _c.copy(self)
+        for k, v in changes.items():
+            setattr(q, k, v)
+        q.__post_init__()
+        return q
+
+    def as_struct(self) -> vba_search_bow_problem:
+        s = vba_search_bow_problem()
+        p = lambda a, t: None if a is None else a.ctypes.data_as(t)
+        s.mode, s.check_orientation, s.th_low, s.nn_ratio = int(self.mode), int(bool(self.check_orientation)), int(self.th_low), float(self.nn_ratio)
+        s.n_keys1, s.n_keys2, s.n_nodes1, s.n_nodes2 = self.n_keys1, self.n_keys2, self.n_nodes1, self.n_nodes2
+        s.desc1, s.desc2, s.good_mp1, s.good_mp2 = p(self.desc1, _pu8), p(self.desc2, _pu8), p(self.good_mp1, _pu8), p(self.good_mp2, _pu8)
+        s.angle1, s.angle2 = p(self.angle1, _pf), p(self.angle2, _pf)
+        s.node_id1, s.node_begin1, s.node_feat1 = p(self.node_id1, _pu32), p(self.node_begin1, _pi), p(self.node_feat1, _pi)
+        s.node_id2, s.node_begin2, s.node_feat2 = p(self.node_id2, _pu32), p(self.node_begin2, _pi), p(self.node_feat2, _pi)
+        return s
+
+
+@dataclass
+class SearchBowResult:
+    status: int
+    n_matches: int
+    n_before_filter: int
+    hist: np.ndarray                # [30]
+    ind: np.ndarray                 # [3]
+    rounds: int
+    match12: np.ndarray             # [n1] int32
+    best_idx: np.ndarray            # [n1] int32
+    best_dist: np.ndarray           # [n1] uint16
+    best_dist2: np.ndarray          # [n1] uint16
+    bin: np.ndarray                 # [n1] uint8
+    state: np.ndarray               # [n1] uint8
+    match21: np.ndarray             # [n2] int32
+
+
+class SearchBowResultBuf:
+    """Caller-allocated result storage of one pair."""
+
+    def __init__(self, p: SearchBowProblem):
+        self.n, self.n2 = p.n_keys1, p.n_keys2
+        m, m2 = max(self.n, 1), max(self.n2, 1)
+        self.m12 = np.full(m, -7, dtype=np.int32)
+        self.bi = np.full(m, -7, dtype=np.int32)
+        self.bd = np.full(m, 7, dtype=np.uint16)
+        self.bd2 = np.full(m, 7, dtype=np.uint16)
+        self.bn = np.full(m, 77, dtype=np.uint8)
+        self.st = np.full(m, 255, dtype=np.uint8)
+        self.m21 = np.full(m2, -7, dtype=np.int32)
+        s = self.s = vba_search_bow_result()
+        s.status, s.n_matches, s.n_before_filter, s.rounds = -7, -7, -7, -7
+        s.match12, s.best_idx, s.best_dist, s.best_dist2 = (self.m12.ctypes.data_as(_pi), self.bi.ctypes.data_as(_pi), self.bd.ctypes.data_as(_pu16),
+                                                            self.bd2.ctypes.data_as(_pu16))
+        s.bin, s.state, s.match21 = self.bn.ctypes.data_as(_pu8), self.st.ctypes.data_as(_pu8), self.m21.ctypes.data_as(_pi)
+
+    def untouched(self):
+        """nothing was written since construction"""
+        s = self.s
+        return ((s.status, s.n_matches, s.n_before_filter, s.rounds) == (-7, -7, -7, -7) and (self.m12 == -7).all() and (self.bi == -7).all() and
+                (self.bd == 7).all() and (self.bd2 == 7).all() and (self.bn == 77).all() and (self.st == 255).all() and (self.m21 == -7).all() and
+                not any(s.hist[:]) and not any(s.ind[:]))
+
+    def get(self) -> SearchBowResult:
+        s, n = self.s, self.n
+        return SearchBowResult(s.status, s.n_matches, s.n_before_filter, np.array(s.hist[:]), np.array(s.ind[:]), s.rounds, self.m12[:n].copy(),
+                               self.bi[:n].copy(), self.bd[:n].copy(), self.bd2[:n].copy(), self.bn[:n].copy(), self.st[:n].copy(),
+                               self.m21[:self.n2].copy())
+
+
 # ---- essential-graph optimisation (include/vislam_ba.h: vba_posegraph_problem / vba_posegraph_result) ----
 class vba_posegraph_problem(C.Structure):
     _fields_ = [

@@ -1,5 +1,5 @@
 // vba_host_small.h -- host side of the library, part 5: the small-problem entry points.  vba_preintegrate copies straight from and
-// to the caller's arrays.  The other ten are one driver, run_small, over the call object of their topic (PoseCall, Sim3Call, ...:
+// to the caller's arrays.  The other eleven are one driver, run_small, over the call object of their topic (PoseCall, Sim3Call, ...:
 // plain C++, vba_host_<topic>.h), which knows what is refused, the arena, the packing, the kernel's argument and the write-back;
 // what an entry point adds here is the launch of its kernel.  No entry point shares its arena (Handle::side) with another.
 #pragma once
@@ -12,6 +12,7 @@
 #include "vba_host_fuse.h"
 #include "vba_host_search_sim3.h"
 #include "vba_host_search_proj.h"
+#include "vba_host_search_bow.h"
 #include "vba_host_posegraph.h"
 
 namespace {
@@ -158,6 +159,16 @@ int search_by_projection(Handle* h, int32_t n_problems, vba_search_proj_problem*
     vba_host::SearchProjCall C;
     return run_small(h, SIDE_SEARCH_PROJ, "vba_search_by_projection", C, n_problems, in, out, [h, &C](const SpBatch& B, unsigned g) {
         VBA_LAUNCH(k_search_proj, dim3(g), dim3(SP_NT), C.lds_bytes(), h->stream, B);
+    });
+}
+
+// Both ORBmatcher::SearchByBoW overloads (src/ORBmatcher.cpp:207-350, :609-748) for a batch of pairs: the host does the node join
+// while it packs; the claim table of a workgroup is dynamic LDS sized to the call's largest side 2; histogram, maxima and drop run
+// in the write-back
+int search_by_bow(Handle* h, int32_t n_pairs, vba_search_bow_problem* const* in, vba_search_bow_result* const* out) {
+    vba_host::SearchBowCall C;
+    return run_small(h, SIDE_SEARCH_BOW, "vba_search_by_bow", C, n_pairs, in, out, [h, &C](const SbBatch& B, unsigned g) {
+        VBA_LAUNCH(k_search_bow, dim3(g), dim3(SB_NT), C.lds_bytes(), h->stream, B);
     });
 }
 

@@ -394,6 +394,41 @@ struct SpBatch {
     int* prev;                   // [total queries] device only: -2 the query never reaches the area, else the keypoint it claimed in
                                  // the round before (-1: none)
 };
+// vba_search_by_bow (vba_search_bow.h)
+#define VBA_SB_NT 256          // lanes of the one workgroup of a pair
+#define VBA_SB_MAX_KEYS 16384  // the claim table of a pair is n_keys2 int32 in LDS
+struct alignas(16) SbKey {     // one keypoint of either side, 32 bytes
+    unsigned int d[8];         // the row of mDescriptors
+};
+struct SbQuery {               // one keypoint of side 1 with a good map point in a shared node, in the order of the reference's walk
+    int idx1;                  // the keypoint
+    int c_begin, c_end;        // its candidates: feat[c_begin .. c_end) of the pair's copy of node_feat2
+    int rank;                  // its place among the queries of its node: final after round `rank` of the conflict pass
+};
+struct SbDesc {
+    long long key1_0, key2_0, feat0;   // offsets of the pair's keypoint records of side 1 (and query slots, roles and outputs), of side 2
+                                       // (and blocked flags) and of its node_feat2 copy in the concatenated arrays
+    int n_keys1, n_keys2, n_q, max_rank;   // max_rank: the largest number of queries in one shared node
+    int th_pass;                       // bestDist1 <= th_pass passes the threshold: th_low in KF_FRAME mode, th_low - 1 in KF_KF mode
+    float nn_ratio;
+};
+static_assert(sizeof(SbKey) == 32 && sizeof(SbQuery) == 16 && sizeof(SbDesc) == 48, "scripts/search_bow_bench.py derives the copied bytes from these sizes");
+struct SbBatch {
+    const SbDesc* desc;
+    const SbKey* key1;           // keypoint records of side 1 of all pairs
+    const SbKey* key2;           // ... of side 2
+    const unsigned char* role;   // [total keypoints of side 1] 0 a query, else the state the host found (1, 2)
+    const unsigned char* blocked;   // [total keypoints of side 2] 1: statically no candidate (KF_KF mode without a good map point)
+    const SbQuery* query;        // [total keypoints of side 1] the first n_q of a pair's region (at key1_0) are used
+    const int* feat;             // node_feat2 of all pairs
+    int* rounds;                 // [pairs]
+    int* best_idx;               // [total keypoints of side 1]
+    unsigned short* best_dist;   // ...
+    unsigned short* best_dist2;  // ...
+    unsigned char* state;        // ...
+    int* prev;                   // [total keypoints of side 1] device only, per query slot: the keypoint the query claimed in the round
+                                 // before (-1: none)
+};
 // vba_posegraph_optimize (vba_posegraph.h)
 struct PgDesc {
     int nv, ne, nf, npair;

@@ -5,8 +5,8 @@
 //                 vba_host_batch.h (lanes and tickets): vba_create / destroy / last_error, vba_solve*, vba_batch_upload / run /
 //                 download / solve*, vba_batch_set_depth / submit* / poll / wait
 //   small problems  vba_host_small.h: one driver over the plain-C++ call object of each topic (vba_host_<topic>.h).  Tracking:
-//                 vba_preintegrate, vba_search_by_projection (the matchers in front of) vba_pose_optimize.  Initialisation: vba_two_view_init.  Local mapping:
-//                 vba_search_triangulation (the matcher in front of) vba_triangulate, vba_fuse.  Loop closing: vba_sim3_ransac,
+//                 vba_preintegrate, vba_search_by_projection and vba_search_by_bow (the matchers in front of) vba_pose_optimize.  Initialisation: vba_two_view_init.  Local mapping:
+//                 vba_search_triangulation (the matcher in front of) vba_triangulate, vba_fuse.  Loop closing: vba_search_by_bow, vba_sim3_ransac,
 //                 vba_search_by_sim3, vba_sim3_optimize, vba_posegraph_optimize
 //   the rest      vba_host_hooks.h (vba_debug_*, hooks flavour), vba_host_threads, vba_set_profile / get_profile
 //
@@ -29,6 +29,7 @@
 #include "vba_fuse.h"
 #include "vba_search_sim3.h"
 #include "vba_search_proj.h"
+#include "vba_search_bow.h"
 #include "vba_posegraph.h"
 #include "vba_structure.h"
 #include "vba_pcg.h"
@@ -212,6 +213,10 @@ int vba_search_by_sim3(void* handle, int32_t n_pairs, vba_search_sim3_problem* c
 int vba_search_by_projection(void* handle, int32_t n_problems, vba_search_proj_problem* const* in, vba_search_proj_result* const* out) {
     Handle* h = idle_handle(handle);
     return h ? search_by_projection(h, n_problems, in, out) : -1;
+}
+int vba_search_by_bow(void* handle, int32_t n_pairs, vba_search_bow_problem* const* in, vba_search_bow_result* const* out) {
+    Handle* h = idle_handle(handle);
+    return h ? search_by_bow(h, n_pairs, in, out) : -1;
 }
 int vba_posegraph_optimize(void* handle, int32_t n_graphs, vba_posegraph_problem* const* inout, vba_posegraph_result* const* out) {
     Handle* h = idle_handle(handle);

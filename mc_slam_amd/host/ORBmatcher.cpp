@@ -7,7 +7,9 @@
 // :1291-1301, ONE call, vpMatches12 from the agreed matches.  And the two tracking matchers, SearchByProjection(F, vpMapPoints, th)
 // (:63-156, fused with Frame::isInFrustum) and SearchByProjection(CurrentFrame, LastFrame, th, bMono) (:1511-1665), over
 // vba_search_by_projection: the frame with its grid in CSR form and its occupied flags, the ordered queries, ONE call, then key_match
-// applied to mvpMapPoints.
+// applied to mvpMapPoints.  And both ORBmatcher::SearchByBoW overloads (:207-350, :609-748) and their batch forms over vba_search_by_bow:
+// every side as flat arrays (descriptors, good-map-point flags, angles, the feature vector in CSR form), ONE call for all pairs,
+// then match21 (keyframe -> frame) or match12 (keyframe -> keyframe) turned into map points.
 #include "ORBmatcher.h"
 
 #include <cstring>
@@ -596,6 +598,161 @@ int ORBmatcher::SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, 
     if (!s.run(who, n)) return -1;
     s.apply(CurrentFrame, LastFrame.mvpMapPoints);
     return s.R.n_matches;
+}
+
+// ---- SearchByBoW ----
+namespace {
+// one side of a vba_search_bow_problem: a KeyFrame (angles of mvKeysUn, :700) or a Frame (angles of mvKeys, :296)
+struct BowSide {
+    int n = 0;
+    const unsigned char* desc = nullptr;
+    const std::vector<MapPoint*>* points = nullptr;
+    std::vector<uint8_t> good;
+    std::vector<float> angle;
+    std::vector<uint32_t> node_id;
+    std::vector<int32_t> node_begin, node_feat;
+    bool ok = false;
+    template <class F>
+    void fill(const F& f, const std::vector<KeyPoint>& keys) {
+        n = f.N;
+        ok = f.N >= 0 && keys.size() == (size_t)f.N && f.mDescriptors.size() == 32 * (size_t)f.N && f.mvpMapPoints.size() == (size_t)f.N;
+        if (!ok) return;
+        desc = f.mDescriptors.data();
+        points = &f.mvpMapPoints;
+        good.resize((size_t)n); angle.resize((size_t)n);
+        for (size_t i = 0; i < (size_t)n; i++) {
+            MapPoint* pMP = f.mvpMapPoints[i];
+            good[i] = pMP && !pMP->isBad();                       // :243-247, :649-652, :665-671
+            angle[i] = keys[i].angle;
+        }
+        node_begin.push_back(0);
+        for (const auto& node : f.mFeatVec) {                     // a std::map: ascending node ids
+            node_id.push_back(node.first);
+            for (unsigned int idx : node.second) node_feat.push_back((int32_t)idx);
+            node_begin.push_back((int32_t)node_feat.size());
+        }
+    }
+    explicit BowSide(KeyFrame* kf) { fill(*kf, kf->mvKeysUn); }
+    explicit BowSide(const Frame& f) { fill(f, f.mvKeys); }
+};
+
+// the result arrays of one pair
+struct BowOut {
+    std::vector<int32_t> match12, best_idx, match21;
+    std::vector<uint16_t> best_dist, best_dist2;
+    std::vector<uint8_t> bin, state;
+    vba_search_bow_result R{};
+    BowOut(size_t n1, size_t n2) : match12(n1), best_idx(n1), match21(n2), best_dist(n1), best_dist2(n1), bin(n1), state(n1) {
+        R.match12 = match12.data(); R.best_idx = best_idx.data(); R.best_dist = best_dist.data(); R.best_dist2 = best_dist2.data();
+        R.bin = bin.data(); R.state = state.data(); R.match21 = match21.data();
+    }
+};
+
+// ONE vba_search_by_bow call over the pairs (side1[i], side2[i]) of `mode`
+bool RunBow(const char* who, int mode, const std::vector<const BowSide*>& side1, const std::vector<const BowSide*>& side2, float nnratio, bool check_ori,
+            std::vector<BowOut>& out) {
+    const size_t n = side1.size();
+    std::vector<vba_search_bow_problem> P(n);
+    std::vector<vba_search_bow_problem*> pp(n);
+    std::vector<vba_search_bow_result*> pr(n);
+    out.clear();
+    out.reserve(n);
+    for (size_t i = 0; i < n; i++) {
+        const BowSide &a = *side1[i], &b = *side2[i];
+        if (!a.ok || !b.ok) {
+            std::cerr << who << ": N, the keypoints, mvpMapPoints and mDescriptors of a keyframe or frame disagree" << std::endl;
+            return false;
+        }
+        vba_search_bow_problem& p = P[i];
+        p = vba_search_bow_problem{};
+        p.mode = mode; p.check_orientation = check_ori ? 1 : 0; p.th_low = ORBmatcher::TH_LOW; p.nn_ratio = nnratio;
+        p.n_keys1 = a.n; p.n_keys2 = b.n;
+        p.desc1 = a.desc; p.desc2 = b.desc;
+        p.good_mp1 = a.good.data(); p.good_mp2 = b.good.data();
+        p.angle1 = a.angle.data(); p.angle2 = b.angle.data();
+        p.n_nodes1 = (int32_t)a.node_id.size(); p.n_nodes2 = (int32_t)b.node_id.size();
+        p.node_id1 = a.node_id.data(); p.node_id2 = b.node_id.data();
+        p.node_begin1 = a.node_begin.data(); p.node_begin2 = b.node_begin.data();
+        p.node_feat1 = a.node_feat.data(); p.node_feat2 = b.node_feat.data();
+        out.emplace_back((size_t)a.n, (size_t)b.n);
+        pp[i] = &p;
+    }
+    for (size_t i = 0; i < n; i++) pr[i] = &out[i].R;            // out does not grow any more
+    void* h = Optimizer::BackendHandle();
+    if (!h || vba_search_by_bow(h, (int32_t)n, pp.data(), pr.data()) != 0) {
+        std::cerr << who << ": " << (h ? vba_last_error(h) : "no HIP device (the backend has no CPU path)") << std::endl;
+        return false;
+    }
+    return true;
+}
+
+// vpMapPointMatches of :211, :287, :343: the map point of pKF whose match the function leaves at each keypoint of F
+void FrameMatches(const BowSide& kf, const BowOut& o, std::vector<MapPoint*>& v) {
+    v.assign(o.match21.size(), static_cast<MapPoint*>(nullptr));
+    for (size_t k = 0; k < v.size(); k++)
+        if (o.match21[k] >= 0) v[k] = (*kf.points)[(size_t)o.match21[k]];
+}
+
+// vpMatches12 of :623, :695, :741: the map point of pKF2 matched to each keypoint of pKF1
+void KeyFrameMatches(const BowSide& kf2, const BowOut& o, std::vector<MapPoint*>& v) {
+    v.assign(o.match12.size(), static_cast<MapPoint*>(nullptr));
+    for (size_t i = 0; i < v.size(); i++)
+        if (o.match12[i] >= 0) v[i] = (*kf2.points)[(size_t)o.match12[i]];
+}
+}  // namespace
+
+int ORBmatcher::SearchByBoW(KeyFrame* pKF, Frame& F, std::vector<MapPoint*>& vpMapPointMatches) {
+    const BowSide s1(pKF), s2(F);
+    std::vector<BowOut> out;
+    if (!RunBow("ORBmatcher::SearchByBoW", VBA_SEARCH_BOW_KF_FRAME, {&s1}, {&s2}, mfNNratio, mbCheckOrientation, out)) return -1;
+    FrameMatches(s1, out[0], vpMapPointMatches);
+    return out[0].R.n_matches;
+}
+
+int ORBmatcher::SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoint*>& vpMatches12) {
+    const BowSide s1(pKF1), s2(pKF2);
+    std::vector<BowOut> out;
+    if (!RunBow("ORBmatcher::SearchByBoW", VBA_SEARCH_BOW_KF_KF, {&s1}, {&s2}, mfNNratio, mbCheckOrientation, out)) return -1;
+    KeyFrameMatches(s2, out[0], vpMatches12);
+    return out[0].R.n_matches;
+}
+
+int ORBmatcher::SearchByBoW(const std::vector<KeyFrame*>& vpKFs, Frame& F, std::vector<std::vector<MapPoint*>>& vvpMapPointMatches,
+                            std::vector<int>& vnMatches) {
+    const BowSide frame(F);
+    std::vector<BowSide> kfs;
+    kfs.reserve(vpKFs.size());
+    for (KeyFrame* kf : vpKFs) kfs.emplace_back(kf);
+    std::vector<const BowSide*> s1, s2(vpKFs.size(), &frame);
+    for (const BowSide& k : kfs) s1.push_back(&k);
+    std::vector<BowOut> out;
+    vvpMapPointMatches.assign(vpKFs.size(), std::vector<MapPoint*>());
+    vnMatches.assign(vpKFs.size(), 0);
+    if (!RunBow("ORBmatcher::SearchByBoW (keyframes against a frame)", VBA_SEARCH_BOW_KF_FRAME, s1, s2, mfNNratio, mbCheckOrientation, out)) return -1;
+    for (size_t i = 0; i < out.size(); i++) {
+        FrameMatches(kfs[i], out[i], vvpMapPointMatches[i]);
+        vnMatches[i] = out[i].R.n_matches;
+    }
+    return 0;
+}
+
+int ORBmatcher::SearchByBoW(KeyFrame* pKF1, const std::vector<KeyFrame*>& vpKFs2, std::vector<std::vector<MapPoint*>>& vvpMatches12,
+                            std::vector<int>& vnMatches) {
+    const BowSide first(pKF1);
+    std::vector<BowSide> kfs;
+    kfs.reserve(vpKFs2.size());
+    for (KeyFrame* kf : vpKFs2) kfs.emplace_back(kf);
+    std::vector<const BowSide*> s1(vpKFs2.size(), &first), s2;
+    for (const BowSide& k : kfs) s2.push_back(&k);
+    std::vector<BowOut> out;
+    vvpMatches12.assign(vpKFs2.size(), std::vector<MapPoint*>());
+    vnMatches.assign(vpKFs2.size(), 0);
+    if (!RunBow("ORBmatcher::SearchByBoW (a keyframe against keyframes)", VBA_SEARCH_BOW_KF_KF, s1, s2, mfNNratio, mbCheckOrientation, out)) return -1;
+    for (size_t i = 0; i < out.size(); i++) {
+        KeyFrameMatches(kfs[i], out[i], vvpMatches12[i]);
+        vnMatches[i] = out[i].R.n_matches;
+    }
+    return 0;
 }
 
 }  // namespace ORB_SLAM2

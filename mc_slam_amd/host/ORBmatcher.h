@@ -1,8 +1,10 @@
 // ORBmatcher.h -- the reference's ORBmatcher (include/ORBmatcher.h) as far as this backend carries it: SearchForTriangulation
 // (src/ORBmatcher.cpp:760-955, monocular) over vba_search_triangulation, both Fuse overloads (:958-1254, monocular) over vba_fuse and
 // SearchBySim3 (:1258-1496, monocular) over vba_search_by_sim3, and the two tracking matchers SearchByProjection(F, vpMapPoints, th)
-// (:63-156) and SearchByProjection(CurrentFrame, LastFrame, th, bMono) (:1511-1665) over vba_search_by_projection.  The other searches
-// stay matcher code of the caller.
+// (:63-156) and SearchByProjection(CurrentFrame, LastFrame, th, bMono) (:1511-1665) over vba_search_by_projection, and both SearchByBoW
+// overloads (:207-350 keyframe -> frame, :609-748 keyframe -> keyframe) over vba_search_by_bow, each also as a batch form that makes
+// one call for a vector of keyframes.  The other searches (SearchForInitialization, SearchByProjection(pKF, Scw, ...) and the
+// relocalisation overload) stay matcher code of the caller.
 #pragma once
 #include <array>
 #include <cstdint>
@@ -53,6 +55,18 @@ public:
     // case, then the orientation filter.  ONE vba_search_by_projection call in last-frame mode.  Returns nmatches, -1 when the backend
     // failed, bMono is false or CurrentFrame has a stereo keypoint
     int SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, const float th, const bool bMono);
+    // src/ORBmatcher.cpp:207-350: the map points of pKF matched to the keypoints of F inside shared vocabulary nodes, best against second
+    // best with mfNNratio, then the orientation filter; vpMapPointMatches gets one entry per keypoint of F.  ONE vba_search_by_bow call
+    // in KF_FRAME mode.  Returns nmatches, -1 when the backend failed or the arrays of pKF or F disagree, with a message on std::cerr
+    int SearchByBoW(KeyFrame* pKF, Frame& F, std::vector<MapPoint*>& vpMapPointMatches);
+    // src/ORBmatcher.cpp:609-748: the same between two keyframes, over the keypoints of pKF2 that have a good map point and with the
+    // strict threshold; vpMatches12 gets one entry per keypoint of pKF1, the map point of pKF2.  ONE call in KF_KF mode
+    int SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoint*>& vpMatches12);
+    // The loop of Tracking::Relocalization (src/Tracking.cpp:2429): every keyframe of vpKFs against F, ONE vba_search_by_bow call for
+    // all of them.  vvpMapPointMatches[i] and vnMatches[i] are what SearchByBoW(vpKFs[i], F, ...) gives.  Returns 0, -1 on failure
+    int SearchByBoW(const std::vector<KeyFrame*>& vpKFs, Frame& F, std::vector<std::vector<MapPoint*>>& vvpMapPointMatches, std::vector<int>& vnMatches);
+    // The loop of LoopClosing::ComputeSim3 (src/LoopClosing.cpp:317): pKF1 against every keyframe of vpKFs2, ONE call for all of them
+    int SearchByBoW(KeyFrame* pKF1, const std::vector<KeyFrame*>& vpKFs2, std::vector<std::vector<MapPoint*>>& vvpMatches12, std::vector<int>& vnMatches);
     // vbAlreadyMatched1 / vbAlreadyMatched2 of :1287-1301: a keypoint of pKF1 with a prior match, and the keypoint of pKF2 where
     // GetIndexInKeyFrame finds that match
     static void AlreadyMatched(KeyFrame* pKF1, KeyFrame* pKF2, const std::vector<MapPoint*>& vpMatches12, std::vector<uint8_t>& vb1,

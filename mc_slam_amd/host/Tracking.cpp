@@ -1,5 +1,6 @@
 // Tracking.cpp -- Tracking::SearchLocalPoints (src/Tracking.cpp:2111-2174) and the matching half of Tracking::TrackWithMotionModel
-// (:1749-1770) over vba_search_by_projection (ORBmatcher.cpp), monocular.
+// (:1749-1770) over vba_search_by_projection, and the matching half of Tracking::TrackReferenceKeyFrame (:1597-1607) over
+// vba_search_by_bow (ORBmatcher.cpp), monocular.
 #include "Tracking.h"
 
 #include <algorithm>
@@ -42,6 +43,16 @@ int Tracking::TrackWithMotionModelMatches() {
         std::fill(mCurrentFrame.mvpMapPoints.begin(), mCurrentFrame.mvpMapPoints.end(), static_cast<MapPoint*>(nullptr));
         nmatches = matcher.SearchByProjection(mCurrentFrame, mLastFrame, 2 * th, true);
     }
+    return nmatches;
+}
+
+int Tracking::TrackReferenceKeyFrameMatches() {
+    ORBmatcher matcher(0.7, true);                                // :1597
+    std::vector<MapPoint*> vpMapPointMatches;
+    const int nmatches = matcher.SearchByBoW(mpReferenceKF, mCurrentFrame, vpMapPointMatches);   // :1600
+    if (nmatches < 15) return nmatches;                           // :1602-1603
+    mCurrentFrame.mvpMapPoints = vpMapPointMatches;               // :1606
+    mCurrentFrame.SetPose(mLastFrame.mTcw);                       // :1607
     return nmatches;
 }
 

@@ -703,6 +703,75 @@ int fc_track_motion_model_matches(void* m, long cur, long last) {
     *M->frames.at(cur) = t.mCurrentFrame;
     return r;
 }
+// ---- bag-of-words matching (both ORBmatcher::SearchByBoW overloads, their batch forms, the Tracking slice) ----
+// what SearchByBoW reads of a frame beside the keypoints fc_frame_add_obs gave it: N x 32 descriptor bytes, one angle per keypoint
+// (mvKeys = mvKeysUn), the feature vector in CSR form (node ids ascending); N becomes the number of keypoints the frame holds
+int fc_frame_set_bow_data(void* m, long frame, const unsigned char* desc, const float* angle, int n_nodes, const unsigned int* node_id, const int* node_begin,
+                          const int* node_feat) {
+    Frame* f = reinterpret_cast<FcMap*>(m)->frames.at(frame).get();
+    f->N = (int)f->mvKeysUn.size();
+    f->mDescriptors.assign(desc, desc + 32 * (size_t)f->N);
+    for (int i = 0; i < f->N; i++) f->mvKeysUn[(size_t)i].angle = angle[i];
+    f->mvKeys = f->mvKeysUn;
+    f->mFeatVec.clear();
+    for (int j = 0; j < n_nodes; j++) {
+        std::vector<unsigned int>& v = f->mFeatVec[node_id[j]];
+        for (int i = node_begin[j]; i < node_begin[j + 1]; i++) v.push_back((unsigned int)node_feat[i]);
+    }
+    return f->N;
+}
+int fc_mp_set_bad(void* m, long mp, int bad) {
+    reinterpret_cast<FcMap*>(m)->mps.at(mp)->mbBad = bad != 0;
+    return 0;
+}
+static void ids_of(const std::vector<MapPoint*>& v, long* ids, int cap) {
+    for (size_t i = 0; i < v.size() && (int)i < cap; i++) ids[i] = v[i] ? (long)v[i]->mnId : -1;
+}
+// ORBmatcher(nnratio, check_ori).SearchByBoW(pKF, F, vpMapPointMatches): match_ids [cap] comes back with the ids (-1: NULL)
+int fc_search_by_bow_frame(void* m, long kf, long frame, float nnratio, int check_ori, long* match_ids, int cap) {
+    FcMap* M = reinterpret_cast<FcMap*>(m);
+    ORBmatcher matcher(nnratio, check_ori != 0);
+    std::vector<MapPoint*> v;
+    const int r = matcher.SearchByBoW(M->kfs.at(kf).get(), *M->frames.at(frame), v);
+    ids_of(v, match_ids, cap);
+    return r;
+}
+// ORBmatcher(nnratio, check_ori).SearchByBoW(pKF1, pKF2, vpMatches12)
+int fc_search_by_bow_kf(void* m, long kf1, long kf2, float nnratio, int check_ori, long* match_ids, int cap) {
+    FcMap* M = reinterpret_cast<FcMap*>(m);
+    ORBmatcher matcher(nnratio, check_ori != 0);
+    std::vector<MapPoint*> v;
+    const int r = matcher.SearchByBoW(M->kfs.at(kf1).get(), M->kfs.at(kf2).get(), v);
+    ids_of(v, match_ids, cap);
+    return r;
+}
+// the batch forms: n keyframes against one frame (frame >= 0) or keyframe kf1 against n keyframes; match_ids [n][stride], n_matches [n]
+int fc_search_by_bow_batch(void* m, long kf1, long frame, const long* kfs, int n, float nnratio, int check_ori, long* match_ids, int stride, int* n_matches) {
+    FcMap* M = reinterpret_cast<FcMap*>(m);
+    ORBmatcher matcher(nnratio, check_ori != 0);
+    std::vector<KeyFrame*> v;
+    for (int i = 0; i < n; i++) v.push_back(M->kfs.at(kfs[i]).get());
+    std::vector<std::vector<MapPoint*>> vv;
+    std::vector<int> vn;
+    const int r = frame >= 0 ? matcher.SearchByBoW(v, *M->frames.at(frame), vv, vn) : matcher.SearchByBoW(M->kfs.at(kf1).get(), v, vv, vn);
+    for (size_t i = 0; i < vv.size(); i++) {
+        ids_of(vv[i], match_ids + i * (size_t)stride, stride);
+        n_matches[i] = vn[i];
+    }
+    return r;
+}
+// the matching half of Tracking::TrackReferenceKeyFrame with mpReferenceKF = kf, mCurrentFrame = cur (copied in and back out) and
+// mLastFrame = last
+int fc_track_reference_kf_matches(void* m, long kf, long cur, long last) {
+    FcMap* M = reinterpret_cast<FcMap*>(m);
+    Tracking t;
+    t.mpReferenceKF = M->kfs.at(kf).get();
+    t.mCurrentFrame = *M->frames.at(cur);
+    t.mLastFrame = *M->frames.at(last);
+    const int r = t.TrackReferenceKeyFrameMatches();
+    *M->frames.at(cur) = t.mCurrentFrame;
+    return r;
+}
 // ---- Sim3 projection matching (ORBmatcher::SearchBySim3) ----
 // ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th): match_ids [n] holds the ids of vpMatches12 (-1: NULL) and
 // comes back with those after the call

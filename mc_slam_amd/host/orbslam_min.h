@@ -382,6 +382,7 @@ public:
     long unsigned int mnId = 0;
     std::vector<KeyPoint> mvKeys;
     std::vector<unsigned char> mDescriptors;              // N x 32
+    std::map<unsigned int, std::vector<unsigned int>> mFeatVec;   // what ComputeBoW leaves (SearchByBoW): node id -> keypoint indices
     std::vector<float> mvScaleFactors;
     int mnScaleLevels = 8;
     float mfLogScaleFactor = std::log(1.2f);

@@ -1197,3 +1197,65 @@ def search_proj_scene(seed, mode, n_keys=1000, n_q=600, twins=0.3, occupied=0.1,
     q_angle[q_angle >= 360.0] = 0.0
     return abi.SearchProjProblem(mode=mode, angle=angle, q_oct=q_oct, q_angle=q_angle, th=15.0 if th is None else th,
                                  check_orientation=check_orientation, **common)
+
+
+# ---------------------------------------------------------------- bag-of-words matching (vba_search_by_bow)
+def search_bow_scene(seed, mode, n_keys1=1500, n_keys2=1500, n_nodes=100, twins=0.6, flip_bits=12, near_dup=0.15, unshared=0.1, mp1=0.7, mp2=0.8,
+                     th_low=50, nn_ratio=0.75, check_orientation=True, rotation=25.0, angle_noise=3.0, angle_outliers=0.1):
+    """One ORBmatcher::SearchByBoW call (abi.SearchBowProblem of `mode`).
+      twins         the first share `twins` of min(n_keys1, n_keys2) keypoints exist on both sides: the descriptor of side 2 is the one
+                    of side 1 with up to flip_bits bits flipped, and both lie in the same vocabulary node (a share `unshared` of them
+                    is moved to another node on side 2).  The rest are strangers with random descriptors and random nodes
+      near_dup      a share of the keypoints of side 1 is overwritten with the descriptor of an EARLIER keypoint of its node, 0-4 bits
+                    off, so that several queries of a node want the same keypoint of side 2 (contention, ratio-test flips)
+      nodes         ids 10 k + 5 on both sides, 10 k + 1 on side 1 only, 10 k + 8 on side 2 only; the order inside a node is shuffled
+      mp1, mp2      shares of keypoints with a good map point (side 2: read in KF_KF mode only)
+      angles        uniform on side 1; a twin's angle on side 2 is that of side 1 minus `rotation` plus noise, random for outliers
+    Keypoint indices are shuffled on both sides.  truth: pair [n_twins, 2], the indices of every twin on both sides."""
+    r = np.random.default_rng(seed)
+    f32 = lambda a: np.asarray(a, dtype=np.float32)
+    nt = int(min(n_keys1, n_keys2) * twins)
+
+    def flipped(dsc, lo, hi):
+        out = np.unpackbits(dsc, axis=1)
+        for row in out:
+            row[r.permutation(256)[:int(r.integers(lo, hi + 1))]] ^= 1
+        return np.packbits(out, axis=1).reshape(-1, 32)
+
+    d1 = r.integers(0, 256, (n_keys1, 32), dtype=np.uint8)
+    node1 = 10 * r.integers(0, max(n_nodes, 1), n_keys1) + np.where(r.random(n_keys1) < 0.1, 1, 5)
+    node1[:nt] = node1[:nt] // 10 * 10 + 5
+    for i in range(n_keys1):
+        if r.random() < near_dup:
+            same = np.nonzero(node1[:i] == node1[i])[0]
+            if len(same):
+                d1[i] = flipped(d1[same[int(r.integers(len(same)))]][None], 0, 4)[0]
+    d2 = r.integers(0, 256, (n_keys2, 32), dtype=np.uint8)
+    node2 = 10 * r.integers(0, max(n_nodes, 1), n_keys2) + np.where(r.random(n_keys2) < 0.1, 8, 5)
+    if nt:
+        d2[:nt] = flipped(d1[:nt], 0, flip_bits)
+        moved = r.random(nt) < unshared
+        node2[:nt] = np.where(moved, 10 * ((node1[:nt] // 10 + 1) % max(n_nodes, 1)) + 5, node1[:nt])
+    ang1 = r.uniform(0, 360, n_keys1)
+    ang2 = r.uniform(0, 360, n_keys2)
+    keep = r.random(nt) >= angle_outliers
+    ang2[:nt] = np.where(keep, np.mod(ang1[:nt] - rotation + r.normal(size=nt) * angle_noise, 360.0), ang2[:nt])
+    ang1, ang2 = f32(ang1), f32(ang2)
+    ang1[ang1 >= 360] = 0; ang2[ang2 >= 360] = 0
+    good1 = (r.random(n_keys1) < mp1).astype(np.uint8)
+    good2 = (r.random(n_keys2) < mp2).astype(np.uint8)
+    p1, p2 = r.permutation(n_keys1), r.permutation(n_keys2)          # new index -> old index
+    inv1, inv2 = np.argsort(p1), np.argsort(p2)
+
+    def fv(node, perm):
+        m = {}
+        for new in r.permutation(len(perm)):                       # the order inside a node is not ascending
+            m.setdefault(int(node[perm[new]]), []).append(int(new))
+        return abi.feat_vec_csr(m)
+
+    id1, b1, ft1 = fv(node1, p1)
+    id2, b2, ft2 = fv(node2, p2)
+    return abi.SearchBowProblem(mode=mode, desc1=d1[p1], desc2=d2[p2], good_mp1=good1[p1], good_mp2=good2[p2] if mode == abi.SEARCH_BOW_KF_KF else None,
+                                node_id1=id1, node_begin1=b1, node_feat1=ft1, node_id2=id2, node_begin2=b2, node_feat2=ft2,
+                                angle1=ang1[p1] if check_orientation else None, angle2=ang2[p2] if check_orientation else None, th_low=th_low,
+                                nn_ratio=nn_ratio, check_orientation=check_orientation, truth=dict(pair=np.stack([inv1[:nt], inv2[:nt]], axis=1)))
