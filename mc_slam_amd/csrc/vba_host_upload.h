@@ -219,6 +219,7 @@ int upload_alloc_copy(Handle* h, Upload& U) {
     if (dalloc(h, BUF_LVL, obs0) || dalloc(h, BUF_CHI2E, obs0 * 8) || dalloc(h, BUF_DEPTH, idp ? 16 : obs0 * 8)) return -1;
     if (dalloc(h, BUF_EREC, obs0 * (idp ? VBA_EREC1 : VBA_EREC) * 8) || dalloc(h, BUF_PREC, pt0 * VBA_PREC * 8)) return -1;
     if (dalloc(h, BUF_SLOT, (obs0 + pt0) * (idp ? VBA_SLOT : VBA_SLOT3) * 8)) return -1;
+    if (dalloc(h, BUF_LMSD, idp ? pt0 * 16 : 16)) return -1;   // inverse depth: (sqrt(Dinv), beta) per landmark
     if (dalloc(h, BUF_CHI2F, obs0 * 8)) return -1;
     if (h2d(h, BUF_IMUI, G.imui) || h2d(h, BUF_IMUJ, G.imuj) || h2d(h, BUF_IMUMEAS, G.meas) || h2d(h, BUF_IMUINFO, G.info)) return -1;
     if (dalloc(h, BUF_IMUH, imu0 * VBA_IMUH * 8) || dalloc(h, BUF_IMUCHI, imu0 * 4 * 8) || dalloc(h, BUF_IMUJREC, imu0 * IMU_JREC * 8)) return -1;
@@ -299,7 +300,7 @@ int bind_batch(Handle* h, int n, bool idp) {
     B.obs_uv = dp<double>(h, BUF_OBSUV); B.obs_w = dp<double>(h, BUF_OBSW);
     B.lvl = dp<unsigned char>(h, BUF_LVL); B.chi2_e = dp<double>(h, BUF_CHI2E); B.depth_e = dp<double>(h, BUF_DEPTH);
     B.chi2_f = idp ? nullptr : dp<double>(h, BUF_CHI2F);
-    B.erec = dp<double>(h, BUF_EREC); B.prec = dp<double>(h, BUF_PREC); B.slot = dp<double>(h, BUF_SLOT); B.kf_fix = dp<unsigned char>(h, BUF_KFFIX);
+    B.erec = dp<double>(h, BUF_EREC); B.prec = dp<double>(h, BUF_PREC); B.slot = dp<double>(h, BUF_SLOT); B.lm_sd = dp<double2>(h, BUF_LMSD); B.kf_fix = dp<unsigned char>(h, BUF_KFFIX);
     B.imu_i = dp<int>(h, BUF_IMUI); B.imu_j = dp<int>(h, BUF_IMUJ);
     B.imu_meas = dp<double>(h, BUF_IMUMEAS); B.imu_info = dp<double>(h, BUF_IMUINFO);
     B.imuH = dp<double>(h, BUF_IMUH); B.imu_chi = dp<double>(h, BUF_IMUCHI); B.imu_jrec = dp<double>(h, BUF_IMUJREC);

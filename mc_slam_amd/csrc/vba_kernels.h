@@ -25,6 +25,7 @@ struct Batch {
     unsigned char* lvl;
     double *chi2_e, *depth_e, *chi2_f;  // chi2_f: chi2 recomputed at the final estimates (LM: chi2_e may be stale)
     double *erec, *prec, *slot;
+    double2* lm_sd;               // [n_pt] inverse depth: (sqrt(Dinv), beta) of every landmark, at the caller's landmark index
     const int* slot_perm;         // [n_obs] record position of every observation edge (keyframe-major for inverse-depth windows)
     const int* pt_perm;           // [n_pt] record position of every landmark (grouped by reference keyframe)
     const unsigned char* kf_fix;  // [n_kf] per-vertex setFixed() of listed-free keyframes: bit0 PR, bit1 V, bit2 Bias
@@ -471,7 +472,7 @@ DEVI void lin_imu_hess(const Batch& B, const WinDesc& d, int k, double* sm) {
 // 16-B chunks instead of 64 scattered records per store instruction.
 // ------------------------------------------------------------------------------------------------
 #define LIN2_ES 15   // LDS row stride (doubles) of one edge: phase B/C [0..5] A [6..7] a [8..9] r ; phase D/E [0..11] Bi [12..13] r
-#define LIN2_PS 19   // LDS row stride of one landmark: dd, y(3), Xw(3), N0(9), ref_free, sD, beta
+#define LIN2_PS 19   // LDS row stride of one landmark: dd, y(3), Xw(3), N0(9), ref_free, sD (+ one spare: the stride stays odd)
 #define LIN2_LDS ((256 * LIN2_ES + 64 * LIN2_PS + 4) * 8)   // 40 480 B: four workgroups per CU
 
 // The IMU factors: a launch of their own behind the vision linearisation (same stream) -- inlined into k_lin2 their ~60 live
@@ -737,15 +738,13 @@ DEVI void lin2_body(const Batch& B, int nblk_lin, int mode, double* lsm) {
         const int pp = c_pp;  // landmark records grouped by reference keyframe
         if (sub == 0) {
             q[17] = sD;
-            q[18] = beta;
             double* sr = B.slot + VBA_SLOT * (size_t)(d.obs0 + d.pt0 + d.n_obs + pp);
 #pragma unroll
             for (int k = 0; k < 3; k++) {
                 sr[k] = -wa[k] * rfm * sD;
                 sr[3 + k] = (N0[k] * wa[0] + N0[3 + k] * wa[1] + N0[6 + k] * wa[2]) * rfm * sD;
             }
-            sr[6] = beta;
-            sr[7] = sD;
+            B.lm_sd[d.pt0 + p0 + jl] = make_double2(sD, beta);   // once per landmark, not in every one of its slots
         }
         // (N0 = R0 hat(b0) had a 128-byte record of its own, 10 % of the bytes of a pass: its readers -- the reference items of the
         //  off-diagonal Schur pairs -- rebuild it from the landmark and the reference keyframe's rotation)
@@ -785,16 +784,14 @@ DEVI void lin2_body(const Batch& B, int nblk_lin, int mode, double* lsm) {
         if (t == 0) { RS[a_nruns] = npb; RS[65] = a_nruns; }
     }
     __syncthreads();
-    // D. one lane per edge: its slot record U = Bi^T a / sqrt(D) and its 64-B edge record (P_c, scale, weighted residual),
+    // D. one lane per edge: its 48-B slot record U = Bi^T a / sqrt(D) and its 48-B edge record (P_c, scale, weighted residual),
     //    from which the Schur kernels rebuild Bi, g = -Bi^T r and Br = [-A | A N0].  Records live keyframe-major (slot_perm).
     if (t < ne) {
-        const double sD = PT[pl * LIN2_PS + 17], beta = PT[pl * LIN2_PS + 18];
+        const double sD = PT[pl * LIN2_PS + 17];
         const int pe = e_pe;
         double* sl = B.slot + VBA_SLOT * (size_t)(d.obs0 + d.pt0 + pe);
 #pragma unroll
         for (int i = 0; i < 6; i++) sl[i] = ub[i] * sD;
-        sl[6] = beta;
-        sl[7] = sD;
         double2* dst = reinterpret_cast<double2*>(B.erec + VBA_EREC1 * (size_t)(d.obs0 + pe));
         dst[0] = make_double2(rpc[0], rpc[1]);
         dst[1] = make_double2(rpc[2], rsc);
@@ -1080,9 +1077,9 @@ DEVI void schur_write_block(const Batch& B, const WinDesc& d, const WinCtrl& c, 
 // off-diagonal keyframe pairs (a < b).  A pair has ~90 items on average, far too few for a whole wave: four
 // pairs share one wave, 16 lanes each (the 36-value reduction then costs 4 butterfly steps per FOUR pairs
 // instead of 6 per pair, and every lane sees ~6 items instead of ~1.4).
-// LD = landmark dimension (1: inverse depth, slot record 8 doubles; 3: XYZ, slot record 24 doubles)
+// LD = landmark dimension (1: inverse depth, slot record 6 doubles; 3: XYZ, slot record 24 doubles)
 // LP = lanes per pair: 64 (one pair per wave: small batches, latency) or 16 (four pairs per wave: throughput)
-// Bi = [A | B_rot] of an EdgePRIDP from its 64-B record (P_c, s = sqrt(rho' w), r) and the observer's rotation R_a:
+// Bi = [A | B_rot] of an EdgePRIDP from its 48-B record (P_c, s = sqrt(rho' w), r) and the observer's rotation R_a:
 // J_c = J_pi(P_c) R_cb, A = s J_c R_a^T, B_rot = -s J_c x t_a with t_a = R_cb^T (P_c - t_cb)   (k_lin2 phase B, g2otypes.cpp:139-145)
 DEVI void rebuild_edge(const WinDesc& d, const double* Ra, const double* rec, double* b0, double* b1, double& r0, double& r1) {
     const double Pc[3] = {rec[0], rec[1], rec[2]}, sc = rec[3];
@@ -1339,22 +1336,34 @@ DEVI void schur_diag_body(const Batch& B, int max_free, int hd_pass, double* blk
         for (int i = 0; i < 9; i++) Ra[i] = Ca[i];
     }
     // inverse depth: a third range of items -- the run records of this keyframe's reference terms (G0: 21, g0: 6 summed over runs of
-    // landmarks by k_lin2, phase E).  A lane's first run item has its index fetched now: inside the walk only the record itself is a
-    // dependent fetch, like a slot record.
-    int n_run = 0, run_first = -1;
+    // landmarks by k_lin2, phase E).
+    int n_run = 0;
     const int* run_list = nullptr;
     if (LD == 1) {
         const int* pfb = B.pref_begin + d.kf0 + d.win;
         const int m0 = pfb[a];
         n_run = pfb[a + 1] - m0;
         run_list = B.pref_list + d.pt0 + m0;
-        const int j0 = (t - (n_o + n_r)) & 63;   // the first run item this lane meets in the walk
-        if (j0 < n_run) run_first = run_list[j0];
     }
-    for (int it = t; it < n_o + n_r + n_run; it += 64) {
+    // inverse depth: every item of the walk reaches a record through one index -- a slot or reference record the (sqrt(Dinv), beta) of
+    // its landmark (lm_sd: beta lives with the landmark, not in the slot record), a run item its run record.  A lane holds the index of
+    // its NEXT item, fetched one trip ahead (all three index reads are contiguous across the wave): inside a trip beta and the run
+    // record are single dependent fetches, beside the slot and the edge record, and not two in sequence.
+    const int n_items = n_o + n_r + n_run;
+    // (the offsets of the three index ranges as scalars, the element indices unsigned: scalar base + 32-bit lane offset addressing.
+    // As 64-bit lane addresses they cost the fused kernels their register budget: k_schur_all 12 B of scratch, k_schur_all_w a wave)
+    const int o_s = __builtin_amdgcn_readfirstlane(d.obs0 + s0), o_r = __builtin_amdgcn_readfirstlane(d.pt0 + r0s - n_o);
+    const int o_n = __builtin_amdgcn_readfirstlane(n_o + n_r), o_p = __builtin_amdgcn_readfirstlane(d.pt0);
+    auto item_index = [&](int it) {
+        return (it < n_o) ? B.slot_lm[(unsigned)(o_s + it)] : (it < o_n) ? B.rec_lm[(unsigned)(o_r + it)] : run_list[(unsigned)(it - o_n)];
+    };
+    int nxt_idx = 0;
+    if (LD == 1 && t < n_items) nxt_idx = item_index(t);
+    for (int it = t; it < n_items; it += 64) {
+        const int idx = nxt_idx;
+        if (LD == 1 && it + 64 < n_items) nxt_idx = item_index(it + 64);
         if (LD == 1 && it >= n_o + n_r) {   // a run record: direct terms only
-            const int j = it - (n_o + n_r);
-            const double* pr_ = B.prec + VBA_PREC * (size_t)(d.pt0 + ((j < 64) ? run_first : run_list[j]));
+            const double* pr_ = B.prec + VBA_PREC * (size_t)(d.pt0 + idx);
 #pragma unroll
             for (int g = 0; g < 21; g++) acc[g] += pr_[g];
             // (no H_pp diagonal here: it feeds Levenberg-Marquardt's lambda init, and inverse-depth windows run Gauss-Newton)
@@ -1374,7 +1383,7 @@ DEVI void schur_diag_body(const Batch& B, int max_free, int hd_pass, double* blk
         if (LD == 1) {
 #pragma unroll
             for (int i = 0; i < 6 * LD; i++) UA[i] = UB[i];
-            beta[0] = qa[6];
+            beta[0] = B.lm_sd[(unsigned)(o_p + idx)].y;
         } else {
             // (the pass that opens an outer iteration reads no Sigma at all: the record may hold anything there -- after a failed
             // solve of the window that occupied this place before, a NaN, and 0 * NaN would poison the whole keyframe block)
@@ -2505,11 +2514,13 @@ __global__ void __launch_bounds__(64) k_update(Batch B, int nblk_pt) {
         const int p = blockIdx.x * 64 + threadIdx.x;
         if (p >= d.n_pt) return;
         const size_t gp = d.pt0 + p;
+        const double2 sb = B.lm_sd[gp];   // (sqrt(Dinv), beta): coalesced, and ahead of the pt_perm hop to the reference record
+        const int pp = B.pt_perm[gp];
+        const double sD = sb.x;
+        if (!(sD > 0.0)) return;  // landmark outside the active set: 16 bytes read, no slot line
         const double* slots = B.slot + VBA_SLOT * (size_t)(d.obs0 + d.pt0);
-        const double* sr = slots + VBA_SLOT * (size_t)(d.n_obs + B.pt_perm[gp]);
-        const double sD = sr[7];
-        if (!(sD > 0.0)) return;  // landmark outside the active set
-        double cl = sr[6];        // beta - sum U . x_p
+        const double* sr = slots + VBA_SLOT * (size_t)(d.n_obs + pp);
+        double cl = sb.y;         // beta - sum U . x_p
         const int rf = B.pt_ref[gp];
         if (rf < d.n_free)
 #pragma unroll

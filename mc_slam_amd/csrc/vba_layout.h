@@ -6,22 +6,27 @@
 
 #define VBA_NB 32          // block size of the dense reduced-system factorisation
 #define VBA_EREC 18        // doubles per edge record, XYZ variants (144 B): Bi (2x6), g = -Bi^T r
-#define VBA_EREC1 8        // doubles per edge record, inverse-depth variant (64 B): P_c (3), sqrt(rho' w) (1), r (2); the
+#define VBA_EREC1 6        // doubles per edge record, inverse-depth variant (48 B): P_c (3), sqrt(rho' w) (1), r (2); the
                            // readers rebuild Bi = [A | B_rot] from it and the observer's rotation (rebuild_edge)
 #define VBA_PREC 32        // doubles per point record  (256 B)
-#define VBA_SLOT 8         // doubles per slot record   (64 B = one line), inverse-depth landmarks
+#define VBA_SLOT 6         // doubles per slot record   (48 B), inverse-depth landmarks: U only
 #define VBA_SLOT3 18       // doubles per slot record, XYZ landmarks (144 B): W = Bi^T A (6x3), independent of the damping
 #define VBA_IMUH 960       // doubles per IMU edge pair: 30x30 local Hessian + 30 rhs (+ pad)
 #define VBA_TRACE 64
+// the inverse-depth records are written and read in 16-byte pieces (three per record): every piece stays aligned at any record index
+static_assert((VBA_SLOT * 8) % 16 == 0 && (VBA_EREC1 * 8) % 16 == 0, "inverse-depth slot and edge records: a multiple of 16 bytes");
 
 // Linearisation products kept in HBM between k_lin2 and its consumers (variant 2, EdgePRIDP).  A "slot" is one
-// (landmark, keyframe) incidence = one H_pl block: observation e -> slot e, reference keyframe of landmark p
-// -> slot n_obs + p.  Jacobians are pre-scaled by sqrt(rho' * invSigma2) and never stored unreduced.
-//   slot record  [0..5] U = W * sqrt(Dinv)  (W = H_pl block, 6x1)   [6] beta = sqrt(Dinv) * b_l   [7] sqrt(Dinv) (ref slot)
-//                -> Schur term of a keyframe pair is -U_a U_b^T, reduced rhs term -U_a beta, x_l = sD (beta - sum U.x_p)
-//   edge record  [0..11] Bi (2x6, d/d observing KF PR, g2otypes.cpp:139-145)  [12..23] Br (2x6, d/d reference KF PR,
-//                :128-134)  [24..29] g = -Bi^T r
-//   point record [0..20] G0 = sum Br^T Br (upper 6x6 packed)  [21..26] g0 = -sum Br^T r  [27] D
+// (landmark, keyframe) incidence = one H_pl block: observation e -> slot slot_perm[e] (keyframe-major), reference keyframe of
+// landmark p -> slot n_obs + pt_perm[p].  Jacobians are pre-scaled by sqrt(rho' * invSigma2) and never stored unreduced.
+//   slot record      [0..5] U = W * sqrt(Dinv)  (W = H_pl block, 6x1): edge slots and landmark reference records alike
+//   landmark scalars [0] sqrt(Dinv)  [1] beta = sqrt(Dinv) * b_l: one pair per landmark, at the CALLER's landmark index (lm_sd)
+//                    -> Schur term of a keyframe pair is -U_a U_b^T, reduced rhs term -U_a beta, x_l = sD (beta - sum U.x_p)
+//   edge record      [0..2] P_c  [3] s = sqrt(rho' w), 0 if the observer's pose is fixed  [4..5] s r: Bi (2x6, d/d observing
+//                    KF PR, g2otypes.cpp:139-145), g = -Bi^T r and Br = [-A | A N0] (d/d reference KF PR, :128-134) are
+//                    rebuilt from it by the readers (rebuild_edge)
+//   point record     one per RUN of consecutive landmarks with one reference keyframe:
+//                    [0..20] G0 = sum Br^T Br (upper 6x6 packed)  [21..26] g0 = -sum Br^T r
 struct WinDesc {
     int variant, algo;
     int n_kf, n_free, n_pt, n_obs, n_imu;
