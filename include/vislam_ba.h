@@ -123,7 +123,7 @@ typedef struct vba_profile {
     double total_ms;             /* first launch -> last launch of the run */
     double factor_flops;         /* FP64 flop the factorisation class executed on MFMA: 2*32^3 per tile product of the
                                     symbolic tile lists, per solve (structurally zero tiles are never touched) */
-    int64_t kernel_launches;     /* kernel launches the last vba_batch_run / vba_solve / vba_sim3_optimize / vba_sim3_ransac / vba_triangulate / vba_two_view_init (at most 2) / vba_search_triangulation / vba_fuse / vba_search_by_sim3 / vba_search_by_projection / vba_search_by_bow / vba_posegraph_optimize enqueued (filled with or without profiling) */
+    int64_t kernel_launches;     /* kernel launches the last vba_batch_run / vba_solve / vba_sim3_optimize / vba_sim3_ransac / vba_triangulate / vba_two_view_init (at most 2) / vba_search_triangulation / vba_fuse / vba_search_by_sim3 / vba_search_by_projection / vba_search_by_projection_kf / vba_search_by_bow / vba_posegraph_optimize enqueued (filled with or without profiling) */
 } vba_profile;
 
 /* One handle per host thread / GPU; owns device buffers and a stream.  Errors: nonzero return, message
@@ -178,7 +178,7 @@ int vba_batch_solve_b(void *handle, int32_t n_windows, vba_problem *const *inout
  *           every later one, those submitted afterwards included, with the same message: no GPU work starts for them (earlier
  *           tickets finish).  Waiting on an unknown or retired ticket returns -1.
  *   handle  while any ticket is submitted and not yet waited for, every synchronous entry point of the handle (vba_solve*,
- *           vba_batch_upload / run / download / solve*, vba_pose_optimize, vba_sim3_optimize, vba_sim3_ransac, vba_triangulate, vba_two_view_init, vba_search_triangulation, vba_fuse, vba_search_by_sim3, vba_search_by_projection, vba_search_by_bow, vba_posegraph_optimize, vba_preintegrate, vba_set_profile,
+ *           vba_batch_upload / run / download / solve*, vba_pose_optimize, vba_sim3_optimize, vba_sim3_ransac, vba_triangulate, vba_two_view_init, vba_search_triangulation, vba_fuse, vba_search_by_sim3, vba_search_by_projection, vba_search_by_projection_kf, vba_search_by_bow, vba_posegraph_optimize, vba_preintegrate, vba_set_profile,
  *           vba_batch_set_depth) returns -1 with "asynchronous batches pending: wait for them first"; afterwards the handle
  *           works synchronously as before.  vba_destroy finishes pending tickets (their results land) before it frees.
  *           Profiling (vba_set_profile) covers synchronous calls only.  One caller thread at a time, as everywhere. */
@@ -811,6 +811,121 @@ typedef struct vba_search_proj_result {
  * bound, pixel, level table, position, normal, distance or threshold that the mode reads.  A problem's outputs do not depend on
  * where it stands in the batch. */
 int vba_search_by_projection(void *handle, int32_t n_problems, vba_search_proj_problem *const *in, vba_search_proj_result *const *out);
+
+/* ---- projection matching for loop closure and relocalisation ----
+ * The two ORBmatcher::SearchByProjection overloads that project the map points of keyframes into one target, monocular, selected by
+ * `mode`:
+ *   VBA_SEARCH_PROJ_KF_LOOP   SearchByProjection(KeyFrame* pKF, cv::Mat Scw, vpPoints, vpMatched, th) (src/ORBmatcher.cpp:354-475), the
+ *                             last step of LoopClosing::ComputeSim3 (src/LoopClosing.cpp:470) behind vba_sim3_optimize; the target is
+ *                             the keyframe pKF, the queries are vpPoints in their order
+ *   VBA_SEARCH_PROJ_KF_RELOC  SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, sAlreadyFound, th, ORBdist) (:1667-1797), called
+ *                             twice per candidate by Tracking::Relocalization (src/Tracking.cpp:2513, :2527) between two
+ *                             PoseOptimization calls (vba_pose_optimize, VBA_FRAME_VISION); the target is the frame, the queries are
+ *                             the keypoints i of pKF in their order
+ * One problem is one target and one ORDERED list of queries; one call takes any number of problems, ragged, both modes mixed, in one
+ * kernel launch (one 256-lane workgroup per problem).  The queries of a problem are not independent: a match takes its keypoint away
+ * from every later query (:446 and :468; :1738 and :1754).  The kernel resolves that with the order-preserving conflict pass of
+ * vba_search_by_projection, with every query blocking: claim[k] is the smallest index of a query whose current result is keypoint k,
+ * query q treats k as taken iff occupied[k] || claim[k] < q, and rounds of (every open query walks against the table of the round
+ * before; the table is rebuilt) run until a round changes nothing.  `rounds` counts them, the detecting round included; it is at most
+ * n_q + 1.  The reference is restated as it stands:
+ *   loop    p3Dc = Rcw p + tcw; z < 0 leaves (:395; z == 0 passes and fails IsInImage); invz = 1 / z, u = fx * (xc * invz) + cx, v alike
+ *           (:399-404); IsInImage is the positive conjunction u >= minX && u < maxX && v >= minY && v < maxY (:407); dist = |p - Ow|
+ *           outside [q_dist_min, q_dist_max] leaves (:417); PO . Pn < cos_view * dist leaves (:423); nPredictedLevel =
+ *           ceil(log(q_pred_max / dist) / log_scale_factor) (:426); radius = th * scale[level] (:430); KeyFrame::GetFeaturesInArea(u, v,
+ *           radius) without level arguments, so the area counts as non-empty whatever the levels of its keypoints (:434); per
+ *           candidate: taken -> skip (:446), kpLevel < level - 1 || kpLevel > level -> skip (:451), dist < bestDist strict (:458);
+ *           bestDist <= th_dist matches (:466).  No ratio test, no orientation filter; n_matches counts the matches of this call only
+ *   reloc   x3Dc = Rcw p + tcw; NO depth test: invzc = 1.0 / z, u = (fx * xc) * invzc + cx, v alike (:1698-1701), so a point behind
+ *           the camera that lands inside the bounds goes on and can match; u < minX || u > maxX || v < minY || v > maxY leaves
+ *           (:1703-1706); dist3D = |p - Ow| outside [q_dist_min, q_dist_max] leaves (:1716); no viewing-angle test; the level as in
+ *           loop mode (:1719); radius = th * scale[level] (:1722); Frame::GetFeaturesInArea(u, v, radius, level - 1, level + 1) with the
+ *           level test INSIDE the cell loop: an area that holds only other levels is empty (:1727); per candidate: taken -> skip
+ *           (:1738), dist < bestDist strict (:1745); bestDist <= th_dist matches (:1752); with check_orientation the bin of
+ *           :1760-1766 in float32 with C round, rotHist[bin] holds bestIdx2, and ComputeThreeMaxima and the drop (:1775-1794) run in
+ *           the write-back: the drop clears the keypoint and decrements n_matches
+ *   area    GetFeaturesInArea literally (src/KeyFrame.cpp:1071-1115, src/Frame.cpp:562-620): floor for the first cell and CEIL for the
+ *           last one, the four early returns, the clamps, fabs(dx) < r && fabs(dy) < r; candidates in cell order (ix outer, iy inner)
+ *           and inside a cell in list order
+ * Deviations, those of the sibling entry points: the reference reads mvScaleFactors[nPredictedLevel] unchecked (:430, :1722), here a
+ * level outside 0 .. n_levels - 1 leaves with its own state; a non-finite u or v leaves as "outside the image" (the reference's
+ * reloc tests let a NaN through); with th_dist = 256 a query whose candidates all fail leaves as bestDist > th_dist does instead of
+ * indexing with -1.  `state` says where a query left, numbered in the order of the reference's exits.  Loop mode:
+ *   0  matched      1  skipped (q_skip)      2  z < 0 (:395)      3  not in the image (:407)      4  distance (:417)
+ *   5  viewing angle (:423)      6  level outside 0 .. n_levels - 1      7  area empty (:434)
+ *   8  bestDist > th_dist (:466), every candidate taken or of the wrong level included
+ * Reloc mode:
+ *   0  matched and kept      1  skipped (q_skip)      2  outside the image (:1703-1706)      3  distance (:1716)
+ *   4  level outside 0 .. n_levels - 1      5  area empty (:1727)      6  bestDist > th_dist (:1752), every candidate taken included
+ *   7  matched, then dropped by the orientation filter (:1783-1793)
+ * Everything but the bin is FP64 on the float32 inputs widened; the reference computes in float32. */
+#define VBA_SEARCH_PROJ_KF_LOOP  0   /* :354-475  */
+#define VBA_SEARCH_PROJ_KF_RELOC 1   /* :1667-1797 */
+#define VBA_SEARCH_PROJ_KF_MAX_KEYS 16384   /* the claim table of a target lives in LDS */
+typedef struct vba_search_proj_kf_problem {
+    int32_t mode;                    /* VBA_SEARCH_PROJ_KF_LOOP or VBA_SEARCH_PROJ_KF_RELOC */
+    int32_t check_orientation;       /* mbCheckOrientation (:1758, :1775); reloc mode only */
+    double Rcw[9], tcw[3];           /* row-major.  loop: Scw decomposed as :364-367 (Rcw = sRcw / scw, tcw = Scw.col(3) / scw), as for
+                                        vba_fuse; reloc: CurrentFrame.mTcw (:1672-1673) */
+    double Ow[3];                    /* -Rcw^T tcw, formed by the caller (:368, :1674) */
+    double K[4];                     /* fx fy cx cy of the target (:358-361, :1700-1701) */
+    double bounds[4];                /* mnMinX mnMaxX mnMinY mnMaxY of the target */
+    int32_t n_keys;                  /* pKF->N / CurrentFrame.N; at most VBA_SEARCH_PROJ_KF_MAX_KEYS */
+    int32_t n_levels;                /* mnScaleLevels of the target, 1 .. 64 */
+    const uint8_t *desc;             /* [n_keys][32] mDescriptors of the target (:454, :1741) */
+    const double *uv;                /* [n_keys][2] mvKeysUn[idx].pt */
+    const uint8_t *oct;              /* [n_keys] mvKeysUn[idx].octave (:449) */
+    const float *angle;              /* [n_keys] CurrentFrame.mvKeysUn[idx].angle in [0, 360) (:1760); reloc mode with check_orientation only */
+    const double *scale;             /* [n_levels] mvScaleFactors of the target (:430, :1722) */
+    double log_scale_factor;         /* mfLogScaleFactor of the target (:426, :1719) */
+    int32_t grid_cols, grid_rows;    /* the target's grid; >= 1, cols * rows <= 65536 */
+    double grid_inv_w, grid_inv_h;   /* mfGridElementWidthInv, mfGridElementHeightInv */
+    const int32_t *cell_begin;       /* [cols * rows + 1] as in vba_fuse_problem */
+    const int32_t *cell_feat;        /* keypoint indices in the order the grid's cells hold them; each keypoint at most once */
+    const uint8_t *occupied;         /* [n_keys] non-zero: loop, vpMatched[idx] != NULL (:446); reloc, mvpMapPoints[i2] != NULL (:1738).  No
+                                        Observations() test in either */
+    int32_t n_q;                     /* vpPoints.size() / vpMPs.size(): the queries in the reference's loop order */
+    int32_t th_dist;                 /* loop: TH_LOW = 50 (:466); reloc: ORBdist (:1752); 0 .. 256 */
+    double th;                       /* the radius factor: 10 in loop mode (LoopClosing.cpp:470); 10 or 3 in reloc mode (Tracking.cpp:2513, :2527) */
+    double cos_view;                 /* 0.5 (:423); loop mode only */
+    const double *q_pos;             /* [n_q][3] GetWorldPos() */
+    const uint8_t *q_desc;           /* [n_q][32] GetDescriptor() */
+    const uint8_t *q_skip;           /* [n_q] non-zero: loop, isBad() || spAlreadyFound.count(pMP) with the set as built at :372 and not updated
+                                        (:385); reloc, !pMP || isBad() || sAlreadyFound.count(pMP) (:1688-1690) */
+    const double *q_normal;          /* [n_q][3] GetNormal() (:421); loop mode only */
+    const double *q_dist_min, *q_dist_max; /* [n_q] GetMinDistanceInvariance(), GetMaxDistanceInvariance() as the reference returns them */
+    const double *q_pred_max;        /* [n_q] mfMaxDistance, which PredictScale reads */
+    const float *q_angle;            /* [n_q] pKF->mvKeysUn[i].angle in [0, 360) (:1760); reloc mode with check_orientation only */
+} vba_search_proj_kf_problem;
+
+typedef struct vba_search_proj_kf_result {
+    int32_t status;           /* VBA_OK */
+    int32_t n_matches;        /* the return value of the function */
+    int32_t n_before_filter;  /* nmatches in front of the orientation filter (:1775); n_matches without one */
+    int32_t hist[30];         /* rotHist[i].size() in front of the filter (zeros in loop mode and without check_orientation) */
+    int32_t ind[3];           /* ind1 .. ind3 of ComputeThreeMaxima, -1 as the reference leaves them (and without the filter) */
+    int32_t rounds;           /* rounds of the conflict pass, 1 .. n_q + 1 */
+    int32_t *best_idx;        /* [n_q] caller-allocated: bestIdx as the candidate loop left it, -1 for none */
+    uint16_t *best_dist;      /* [n_q] caller-allocated: bestDist; 256 = none */
+    int8_t *level;            /* [n_q] caller-allocated: nPredictedLevel where it was computed and in range, the out-of-range value
+                                 clamped to int8 for the level state (6 in loop mode, 4 in reloc mode); -128 where not computed */
+    double *uv;               /* [n_q][2] caller-allocated: the projection; NaN where not computed (loop: states 1 and 2; reloc: state 1) */
+    uint8_t *bin;             /* [n_q] caller-allocated: the histogram bin of a match (reloc states 0 and 7) with check_orientation; 255 = none */
+    uint8_t *state;           /* [n_q] caller-allocated: the codes above */
+    int32_t *key_match;       /* [n_keys] caller-allocated: what the function writes into vpMatched / mvpMapPoints, as a query index: -1
+                                 untouched, -2 cleared by the orientation filter (:1789), else the query that wrote the keypoint */
+} vba_search_proj_kf_result;
+
+/* Synchronous, like vba_search_by_projection; -1 while asynchronous tickets are pending.  n_problems == 0 returns 0; a problem with
+ * n_q == 0 or n_keys == 0 is legal.  A bad problem fails the whole call before any GPU work, with nothing written, as
+ * "vba_search_by_projection_kf: problem K: <why>" through vba_last_error: a NULL problem or result, an unknown mode, a negative count,
+ * n_keys above VBA_SEARCH_PROJ_KF_MAX_KEYS, a NULL array with a non-zero count (the per-query result arrays are required when
+ * n_q > 0, key_match when n_keys > 0; the arrays of the other mode may be NULL), n_levels outside 1 .. 64, an octave >= n_levels,
+ * th_dist outside 0 .. 256, grid sizes outside their range, a cell_begin that does not start at 0, decreases or ends above n_keys, a
+ * cell_feat entry out of range or listed twice, with check_orientation in reloc mode an angle outside [0, 360), any non-finite pose,
+ * intrinsic, bound, pixel, level table, position, normal, distance or threshold that the mode reads.  A problem's outputs do not
+ * depend on where it stands in the batch. */
+int vba_search_by_projection_kf(void *handle, int32_t n_problems, vba_search_proj_kf_problem *const *in, vba_search_proj_kf_result *const *out);
 
 /* ---- bag-of-words matching ----
  * Both ORBmatcher::SearchByBoW overloads (src/ORBmatcher.cpp), selected by `mode`:

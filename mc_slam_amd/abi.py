@@ -1433,6 +1433,166 @@ class SearchProjResultBuf:
                                 self.st[:n].copy(), self.km[:self.nk].copy())
 
 
+# ---- projection matching for loop closure and relocalisation (include/vislam_ba.h: vba_search_proj_kf_problem / _result) ----
+SEARCH_PROJ_KF_LOOP, SEARCH_PROJ_KF_RELOC = 0, 1
+SEARCH_PROJ_KF_MAX_KEYS = 16384
+
+
+class vba_search_proj_kf_problem(C.Structure):
+    _fields_ = [
+        ("mode", C.c_int32), ("check_orientation", C.c_int32), ("Rcw", C.c_double * 9), ("tcw", C.c_double * 3), ("Ow", C.c_double * 3),
+        ("K", C.c_double * 4), ("bounds", C.c_double * 4), ("n_keys", C.c_int32), ("n_levels", C.c_int32), ("desc", _pu8), ("uv", _pd),
+        ("oct", _pu8), ("angle", _pf), ("scale", _pd), ("log_scale_factor", C.c_double), ("grid_cols", C.c_int32), ("grid_rows", C.c_int32),
+        ("grid_inv_w", C.c_double), ("grid_inv_h", C.c_double), ("cell_begin", _pi), ("cell_feat", _pi), ("occupied", _pu8),
+        ("n_q", C.c_int32), ("th_dist", C.c_int32), ("th", C.c_double), ("cos_view", C.c_double), ("q_pos", _pd), ("q_desc", _pu8),
+        ("q_skip", _pu8), ("q_normal", _pd), ("q_dist_min", _pd), ("q_dist_max", _pd), ("q_pred_max", _pd), ("q_angle", _pf),
+    ]
+
+
+class vba_search_proj_kf_result(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_matches", C.c_int32), ("n_before_filter", C.c_int32), ("hist", C.c_int32 * 30), ("ind", C.c_int32 * 3),
+                ("rounds", C.c_int32), ("best_idx", _pi), ("best_dist", _pu16), ("level", _pi8), ("uv", _pd), ("bin", _pu8), ("state", _pu8),
+                ("key_match", _pi)]
+
+
+# the states of the two modes
+(SKL_MATCHED, SKL_SKIPPED, SKL_BEHIND, SKL_NOT_IN_IMAGE, SKL_DISTANCE, SKL_VIEW_ANGLE, SKL_LEVEL, SKL_EMPTY_AREA, SKL_NO_MATCH) = range(9)
+(SKR_MATCHED, SKR_SKIPPED, SKR_NOT_IN_IMAGE, SKR_DISTANCE, SKR_LEVEL, SKR_EMPTY_AREA, SKR_NO_MATCH, SKR_ROTATION) = range(8)
+
+
+@dataclass
+class SearchProjKfProblem:
+    """One call of the loop-closure or the relocalisation matcher as flat arrays: one target (a keyframe in mode SEARCH_PROJ_KF_LOOP,
+    ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th), src/ORBmatcher.cpp:354-475; a frame in mode SEARCH_PROJ_KF_RELOC,
+    SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist), :1667-1797) with its grid in CSR form and one ORDERED list of
+    queries.  The arrays of the other mode may stay None."""
+    mode: int
+    Rcw: np.ndarray                # [3,3]
+    tcw: np.ndarray                # [3]
+    Ow: np.ndarray                 # [3]
+    K: np.ndarray                  # [4] fx fy cx cy
+    bounds: np.ndarray             # [4] mnMinX mnMaxX mnMinY mnMaxY
+    desc: np.ndarray               # [n_keys,32] uint8
+    uv: np.ndarray                 # [n_keys,2]
+    oct: np.ndarray                # [n_keys] uint8
+    scale: np.ndarray              # [n_levels]
+    log_scale_factor: float
+    grid_cols: int
+    grid_rows: int
+    grid_inv_w: float
+    grid_inv_h: float
+    cell_begin: np.ndarray         # [cols * rows + 1] int32
+    cell_feat: np.ndarray          # int32
+    occupied: np.ndarray           # [n_keys] uint8
+    q_pos: np.ndarray              # [n_q,3]
+    q_desc: np.ndarray             # [n_q,32] uint8
+    q_skip: np.ndarray             # [n_q] uint8
+    q_dist_min: np.ndarray         # [n_q]
+    q_dist_max: np.ndarray         # [n_q]
+    q_pred_max: np.ndarray         # [n_q]
+    th: float = 10.0
+    th_dist: int = 50
+    cos_view: float = 0.5
+    q_normal: np.ndarray = None    # [n_q,3] loop mode
+    angle: np.ndarray = None       # [n_keys] float32, reloc mode with check_orientation
+    q_angle: np.ndarray = None     # [n_q] float32, reloc mode with check_orientation
+    check_orientation: bool = True
+    truth: dict = field(default_factory=dict)
+
+    def __post_init__(self):
+        u8 = lambda a, shape: np.ascontiguousarray(a, dtype=np.uint8).reshape(shape)
+        opt = lambda a, f, *s: None if a is None else f(a, *s)
+        f32 = lambda a, shape: np.ascontiguousarray(a, dtype=np.float32).reshape(shape)
+        self.Rcw = _f64(self.Rcw, (3, 3)); self.tcw = _f64(self.tcw, (3,)); self.Ow = _f64(self.Ow, (3,))
+        self.K = _f64(self.K, (4,)); self.bounds = _f64(self.bounds, (4,))
+        self.desc = u8(self.desc, (-1, 32)); self.oct = u8(self.oct, (-1,)); self.uv = _f64(self.uv, (-1, 2))
+        self.scale = _f64(self.scale, (-1,)); self.occupied = u8(self.occupied, (-1,))
+        self.cell_begin = _i32(self.cell_begin).reshape(-1); self.cell_feat = _i32(self.cell_feat).reshape(-1)
+        self.q_pos = _f64(self.q_pos, (-1, 3)); self.q_desc = u8(self.q_desc, (-1, 32)); self.q_skip = u8(self.q_skip, (-1,))
+        self.q_dist_min = _f64(self.q_dist_min, (-1,)); self.q_dist_max = _f64(self.q_dist_max, (-1,)); self.q_pred_max = _f64(self.q_pred_max, (-1,))
+        self.q_normal = opt(self.q_normal, _f64, (-1, 3))
+        self.angle = opt(self.angle, f32, (-1,)); self.q_angle = opt(self.q_angle, f32, (-1,))
+
+    n_keys = property(lambda self: self.desc.shape[0])
+    n_q = property(lambda self: self.q_pos.shape[0])
+    n_levels = property(lambda self: self.scale.shape[0])
+    reloc = property(lambda self: self.mode == SEARCH_PROJ_KF_RELOC)
+
+    def copy(self, **changes):
+        import copy as _c
+        q = _c.copy(self)
+        for k, v in changes.items():
+            setattr(q, k, v)
+        q.__post_init__()
+        return q
+
+    def as_struct(self) -> vba_search_proj_kf_problem:
+        s = vba_search_proj_kf_problem()
+        p = lambda a, t: None if a is None else a.ctypes.data_as(t)
+        s.mode, s.check_orientation = int(self.mode), int(bool(self.check_orientation))
+        s.Rcw[:] = self.Rcw.ravel().tolist(); s.tcw[:] = self.tcw.tolist(); s.Ow[:] = self.Ow.tolist()
+        s.K[:] = self.K.tolist(); s.bounds[:] = self.bounds.tolist()
+        s.n_keys, s.n_levels, s.n_q = self.n_keys, self.n_levels, self.n_q
+        s.desc, s.uv, s.oct, s.angle, s.scale = p(self.desc, _pu8), p(self.uv, _pd), p(self.oct, _pu8), p(self.angle, _pf), p(self.scale, _pd)
+        s.log_scale_factor = float(self.log_scale_factor)
+        s.grid_cols, s.grid_rows, s.grid_inv_w, s.grid_inv_h = int(self.grid_cols), int(self.grid_rows), float(self.grid_inv_w), float(self.grid_inv_h)
+        s.cell_begin, s.cell_feat, s.occupied = p(self.cell_begin, _pi), p(self.cell_feat, _pi), p(self.occupied, _pu8)
+        s.th_dist, s.th, s.cos_view = int(self.th_dist), float(self.th), float(self.cos_view)
+        s.q_pos, s.q_desc, s.q_skip, s.q_normal = p(self.q_pos, _pd), p(self.q_desc, _pu8), p(self.q_skip, _pu8), p(self.q_normal, _pd)
+        s.q_dist_min, s.q_dist_max, s.q_pred_max, s.q_angle = p(self.q_dist_min, _pd), p(self.q_dist_max, _pd), p(self.q_pred_max, _pd), p(self.q_angle, _pf)
+        return s
+
+
+@dataclass
+class SearchProjKfResult:
+    status: int
+    n_matches: int
+    n_before_filter: int
+    hist: np.ndarray                # [30]
+    ind: np.ndarray                 # [3]
+    rounds: int
+    best_idx: np.ndarray            # [n_q] int32
+    best_dist: np.ndarray           # [n_q] uint16
+    level: np.ndarray               # [n_q] int8
+    uv: np.ndarray                  # [n_q,2]
+    bin: np.ndarray                 # [n_q] uint8
+    state: np.ndarray               # [n_q] uint8
+    key_match: np.ndarray           # [n_keys] int32
+
+
+class SearchProjKfResultBuf:
+    """Caller-allocated result storage of one problem."""
+
+    def __init__(self, p: SearchProjKfProblem):
+        self.n, self.nk = p.n_q, p.n_keys
+        m, mk = max(self.n, 1), max(self.nk, 1)
+        self.bi = np.full(m, -7, dtype=np.int32)
+        self.bd = np.full(m, 7, dtype=np.uint16)
+        self.lv = np.full(m, 77, dtype=np.int8)
+        self.uv = np.full((m, 2), -7.0)
+        self.bn = np.full(m, 77, dtype=np.uint8)
+        self.st = np.full(m, 255, dtype=np.uint8)
+        self.km = np.full(mk, -7, dtype=np.int32)
+        s = self.s = vba_search_proj_kf_result()
+        s.status, s.n_matches, s.n_before_filter, s.rounds = -7, -7, -7, -7
+        s.best_idx, s.best_dist, s.level = self.bi.ctypes.data_as(_pi), self.bd.ctypes.data_as(_pu16), self.lv.ctypes.data_as(_pi8)
+        s.uv, s.bin, s.state, s.key_match = (self.uv.ctypes.data_as(_pd), self.bn.ctypes.data_as(_pu8), self.st.ctypes.data_as(_pu8),
+                                             self.km.ctypes.data_as(_pi))
+
+    def untouched(self):
+        """nothing was written since construction"""
+        s = self.s
+        return ((s.status, s.n_matches, s.n_before_filter, s.rounds) == (-7, -7, -7, -7) and (self.bi == -7).all() and (self.bd == 7).all() and
+                (self.lv == 77).all() and (self.uv == -7.0).all() and (self.bn == 77).all() and (self.st == 255).all() and (self.km == -7).all() and
+                not any(s.hist[:]) and not any(s.ind[:]))
+
+    def get(self) -> SearchProjKfResult:
+        s, n = self.s, self.n
+        return SearchProjKfResult(s.status, s.n_matches, s.n_before_filter, np.array(s.hist[:]), np.array(s.ind[:]), s.rounds, self.bi[:n].copy(),
+                                  self.bd[:n].copy(), self.lv[:n].copy(), self.uv[:n].copy(), self.bn[:n].copy(), self.st[:n].copy(),
+                                  self.km[:self.nk].copy())
+
+
 # ---- bag-of-words matching (include/vislam_ba.h: vba_search_bow_problem / vba_search_bow_result) ----
 SEARCH_BOW_KF_FRAME, SEARCH_BOW_KF_KF = 0, 1
 SEARCH_BOW_MAX_KEYS = 16384

@@ -20,7 +20,7 @@ EXPORTS = ["vba_create", "vba_destroy", "vba_last_error", "vba_solve", "vba_batc
            "vba_batch_download", "vba_batch_solve", "vba_solve_b", "vba_batch_run_b", "vba_batch_solve_b", "vba_preintegrate", "vba_pose_optimize", "vba_problem_save", "vba_problem_load", "vba_problem_free", "vba_set_profile", "vba_get_profile", "vba_host_threads",
            "vba_batch_set_depth", "vba_batch_submit", "vba_batch_submit_b", "vba_batch_poll", "vba_batch_wait", "vba_sim3_optimize",
            "vba_posegraph_optimize", "vba_sim3_ransac", "vba_triangulate", "vba_two_view_init", "vba_search_triangulation", "vba_fuse",
-           "vba_search_by_sim3", "vba_search_by_projection", "vba_search_by_bow"]
+           "vba_search_by_sim3", "vba_search_by_projection", "vba_search_by_bow", "vba_search_by_projection_kf"]
 
 # The small-problem entry points, all of the shape fn(handle, n, problems, results).  kind -> (library function, problem struct,
 # result struct, result buffer of one problem -- called with the problem and the extra arguments of its pack --, whether the call
@@ -35,6 +35,8 @@ _SMALL = {
     "fuse": ("vba_fuse", abi.vba_fuse_problem, abi.vba_fuse_result, abi.FuseResultBuf, False),
     "search_by_sim3": ("vba_search_by_sim3", abi.vba_search_sim3_problem, abi.vba_search_sim3_result, abi.SearchSim3ResultBuf, False),
     "search_by_projection": ("vba_search_by_projection", abi.vba_search_proj_problem, abi.vba_search_proj_result, abi.SearchProjResultBuf, False),
+    "search_by_projection_kf": ("vba_search_by_projection_kf", abi.vba_search_proj_kf_problem, abi.vba_search_proj_kf_result, abi.SearchProjKfResultBuf,
+                                False),
     "search_by_bow": ("vba_search_by_bow", abi.vba_search_bow_problem, abi.vba_search_bow_result, abi.SearchBowResultBuf, False),
     "posegraph": ("vba_posegraph_optimize", abi.vba_posegraph_problem, abi.vba_posegraph_result, lambda p: abi.vba_posegraph_result(), True),
 }
@@ -398,6 +400,20 @@ class LocalBA:
         """vba_search_by_projection on a list of abi.SearchProjProblem: list of abi.SearchProjResult"""
         packed = self.search_by_projection_pack(problems)
         self.search_by_projection_call(packed)
+        return [b.get() for b in packed[2]]
+
+    # projection matching for loop closure and relocalisation (vba_search_by_projection_kf): abi.SearchProjKfProblem, one target and
+    # one ordered query list each, both modes mixed
+    def search_by_projection_kf_pack(self, problems):
+        return self._small_pack("search_by_projection_kf", problems)
+
+    def search_by_projection_kf_call(self, packed):
+        self._small_call("search_by_projection_kf", packed)
+
+    def search_by_projection_kf(self, problems):
+        """vba_search_by_projection_kf on a list of abi.SearchProjKfProblem: list of abi.SearchProjKfResult"""
+        packed = self.search_by_projection_kf_pack(problems)
+        self.search_by_projection_kf_call(packed)
         return [b.get() for b in packed[2]]
 
     # bag-of-words matching (vba_search_by_bow): abi.SearchBowProblem, one pair each, both modes mixed

@@ -3,8 +3,8 @@
 // grid_cols * grid_rows + 1 entries, cell_feat of cell_begin[last] keypoint indices).  vba_fuse_problem, vba_search_sim3_kf and
 // vba_search_proj_problem name these fields alike (n_keys, desc, uv, oct, n_levels, grid_cols, grid_rows, cell_begin, cell_feat),
 // so the helpers are templates over the struct.  What check_cell_lists accepts is what bounds the loops of sa_walk
-// (vba_search_area.h).  Included by vba_host_fuse.h, vba_host_search_sim3.h and vba_host_search_proj.h, and through them by the
-// sanitizer harnesses of the three.
+// (vba_search_area.h).  Included by vba_host_fuse.h, vba_host_search_sim3.h, vba_host_search_proj.h and vba_host_search_proj_kf.h, and
+// through them by their sanitizer harnesses.
 #pragma once
 #include "vba_layout.h"
 

@@ -1,5 +1,5 @@
 // vba_host_small.h -- host side of the library, part 5: the small-problem entry points.  vba_preintegrate copies straight from and
-// to the caller's arrays.  The other eleven are one driver, run_small, over the call object of their topic (PoseCall, Sim3Call, ...:
+// to the caller's arrays.  The other twelve are one driver, run_small, over the call object of their topic (PoseCall, Sim3Call, ...:
 // plain C++, vba_host_<topic>.h), which knows what is refused, the arena, the packing, the kernel's argument and the write-back;
 // what an entry point adds here is the launch of its kernel.  No entry point shares its arena (Handle::side) with another.
 #pragma once
@@ -12,6 +12,7 @@
 #include "vba_host_fuse.h"
 #include "vba_host_search_sim3.h"
 #include "vba_host_search_proj.h"
+#include "vba_host_search_proj_kf.h"
 #include "vba_host_search_bow.h"
 #include "vba_host_posegraph.h"
 
@@ -159,6 +160,17 @@ int search_by_projection(Handle* h, int32_t n_problems, vba_search_proj_problem*
     vba_host::SearchProjCall C;
     return run_small(h, SIDE_SEARCH_PROJ, "vba_search_by_projection", C, n_problems, in, out, [h, &C](const SpBatch& B, unsigned g) {
         VBA_LAUNCH(k_search_proj, dim3(g), dim3(SP_NT), C.lds_bytes(), h->stream, B);
+    });
+}
+
+// The loop-closure and the relocalisation matcher, ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th)
+// (src/ORBmatcher.cpp:354-475) and SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (:1667-1797), monocular, for a
+// batch of (target, ordered query list) problems, both modes mixed: the conflict pass of k_search_proj with every query blocking;
+// histogram, maxima and drop of the relocalisation mode run in the write-back
+int search_by_projection_kf(Handle* h, int32_t n_problems, vba_search_proj_kf_problem* const* in, vba_search_proj_kf_result* const* out) {
+    vba_host::SearchProjKfCall C;
+    return run_small(h, SIDE_SEARCH_PROJ_KF, "vba_search_by_projection_kf", C, n_problems, in, out, [h, &C](const SkBatch& B, unsigned g) {
+        VBA_LAUNCH(k_search_proj_kf, dim3(g), dim3(SK_NT), C.lds_bytes(), h->stream, B);
     });
 }
 

@@ -399,6 +399,28 @@ struct SpBatch {
     int* prev;                   // [total queries] device only: -2 the query never reaches the area, else the keypoint it claimed in
                                  // the round before (-1: none)
 };
+// vba_search_by_projection_kf (vba_search_proj_kf.h); keypoints are FuKey, queries SpQuery (blocks = 1, oct unused), the descriptor
+// SpDesc (mode: 0 loop, 1 reloc; th_high holds th_dist; nn_ratio = 0)
+#define VBA_SK_NT 256          // lanes of the one workgroup of a problem
+#define VBA_SK_MAX_KEYS 16384  // the claim table of a problem is n_keys int32 in LDS
+struct SkBatch {
+    const SpDesc* desc;
+    const FuKey* key;            // keypoint records of all problems
+    const unsigned char* occupied;   // [total keypoints]
+    const SpQuery* query;        // query records of all problems
+    const int* cell_begin;       // cell_begin of all problems
+    const int* cell_feat;        // cell_feat of all problems
+    const double* lev;           // scale tables of all problems
+    int* rounds;                 // [problems]
+    int* best_idx;               // [total queries]
+    unsigned short* best_dist;   // ...
+    signed char* level;          // ...
+    double* uv;                  // [total queries][2]
+    unsigned char* state;        // [total queries]
+    double* rad;                 // [total queries] device only: the radius of the area
+    int* prev;                   // [total queries] device only: -2 the query never reaches the area, else the keypoint it claimed in
+                                 // the round before (-1: none)
+};
 // vba_search_by_bow (vba_search_bow.h)
 #define VBA_SB_NT 256          // lanes of the one workgroup of a pair
 #define VBA_SB_MAX_KEYS 16384  // the claim table of a pair is n_keys2 int32 in LDS

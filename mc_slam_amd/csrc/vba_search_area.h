@@ -1,4 +1,4 @@
-// vba_search_area.h -- what the projection matchers share on the device (k_fuse, k_search_sim3, k_search_proj; the descriptor
+// vba_search_area.h -- what the projection matchers share on the device (k_fuse, k_search_sim3, k_search_proj, k_search_proj_kf; the descriptor
 // helpers also k_search_tri): the rigid transform, MapPoint::PredictScale (src/MapPoint.cpp:529-540), the descriptor load and the
 // Hamming distance, and the cell walk of GetFeaturesInArea (src/KeyFrame.cpp:1071-1115, src/Frame.cpp:562-620) over a keyframe grid
 // in CSR form.  A kernel keeps its gates, its candidate tests and its outputs; the next matcher is written against sa_walk.
@@ -14,7 +14,8 @@
 // Contraction: `#pragma clang fp contract(off)` holds for the compound statement it stands in and a callee does not inherit it, so
 // every helper with FP64 arithmetic opens with its own; at file scope it would reach the kernels included afterwards.
 // The pinhole projection is NOT here: k_fuse and k_search_sim3 compute K0 * (xc * invz) + K2, k_search_proj (K0 * xc) * invz + K2,
-// each as the reference lines it cites, and the two round differently.
+// k_search_proj_kf the first in loop mode and the second in reloc mode, each as the reference lines it cites, and the two round
+// differently.
 #pragma once
 #include "vba_device.h"
 #include "vba_layout.h"

@@ -7,7 +7,8 @@
 //   small problems  vba_host_small.h: one driver over the plain-C++ call object of each topic (vba_host_<topic>.h).  Tracking:
 //                 vba_preintegrate, vba_search_by_projection and vba_search_by_bow (the matchers in front of) vba_pose_optimize.  Initialisation: vba_two_view_init.  Local mapping:
 //                 vba_search_triangulation (the matcher in front of) vba_triangulate, vba_fuse.  Loop closing: vba_search_by_bow, vba_sim3_ransac,
-//                 vba_search_by_sim3, vba_sim3_optimize, vba_posegraph_optimize
+//                 vba_search_by_sim3, vba_sim3_optimize, vba_search_by_projection_kf (the matcher behind it), vba_posegraph_optimize.
+//                 Relocalisation: vba_search_by_bow, vba_search_by_projection_kf between two vba_pose_optimize calls
 //   the rest      vba_host_hooks.h (vba_debug_*, hooks flavour), vba_host_threads, vba_set_profile / get_profile
 //
 // Host-side control flow restated from src/Optimizer.cpp:453-517 (two-stage protocol) and
@@ -29,6 +30,7 @@
 #include "vba_fuse.h"
 #include "vba_search_sim3.h"
 #include "vba_search_proj.h"
+#include "vba_search_proj_kf.h"
 #include "vba_search_bow.h"
 #include "vba_posegraph.h"
 #include "vba_structure.h"
@@ -213,6 +215,10 @@ int vba_search_by_sim3(void* handle, int32_t n_pairs, vba_search_sim3_problem* c
 int vba_search_by_projection(void* handle, int32_t n_problems, vba_search_proj_problem* const* in, vba_search_proj_result* const* out) {
     Handle* h = idle_handle(handle);
     return h ? search_by_projection(h, n_problems, in, out) : -1;
+}
+int vba_search_by_projection_kf(void* handle, int32_t n_problems, vba_search_proj_kf_problem* const* in, vba_search_proj_kf_result* const* out) {
+    Handle* h = idle_handle(handle);
+    return h ? search_by_projection_kf(h, n_problems, in, out) : -1;
 }
 int vba_search_by_bow(void* handle, int32_t n_pairs, vba_search_bow_problem* const* in, vba_search_bow_result* const* out) {
     Handle* h = idle_handle(handle);

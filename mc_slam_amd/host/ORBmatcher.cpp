@@ -9,7 +9,9 @@
 // vba_search_by_projection: the frame with its grid in CSR form and its occupied flags, the ordered queries, ONE call, then key_match
 // applied to mvpMapPoints.  And both ORBmatcher::SearchByBoW overloads (:207-350, :609-748) and their batch forms over vba_search_by_bow:
 // every side as flat arrays (descriptors, good-map-point flags, angles, the feature vector in CSR form), ONE call for all pairs,
-// then match21 (keyframe -> frame) or match12 (keyframe -> keyframe) turned into map points.
+// then match21 (keyframe -> frame) or match12 (keyframe -> keyframe) turned into map points.  And the loop-closure and the
+// relocalisation overload of SearchByProjection (:354-475, :1667-1797) over vba_search_by_projection_kf: the target with its grid in CSR
+// form and its occupied flags, the ordered queries, ONE call, then key_match applied to vpMatched / mvpMapPoints.
 #include "ORBmatcher.h"
 
 #include <cstring>
@@ -224,6 +226,26 @@ struct FuseSearch {
 };
 }  // namespace
 
+namespace {
+// src/ORBmatcher.cpp:364-368 and :1134-1138 in float32 like cv::Mat: scw = |row 0 of sRcw|, Rcw = sRcw / scw, tcw = Scw[0:3, 3] / scw,
+// Ow = -Rcw^T tcw
+void DecomposeScw(const Mat4f& Scw, double Rcw[9], double tcw[3], double Ow[3]) {
+    const float scw = std::sqrt(Scw[0] * Scw[0] + Scw[1] * Scw[1] + Scw[2] * Scw[2]);
+    float Rf[9], tf[3];
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) Rf[3 * i + j] = Scw[4 * i + j] / scw;
+        tf[i] = Scw[4 * i + 3] / scw;
+    }
+    for (int i = 0; i < 9; i++) Rcw[i] = Rf[i];
+    for (int i = 0; i < 3; i++) {
+        tcw[i] = tf[i];
+        float a = 0;
+        for (int k = 0; k < 3; k++) a += -Rf[3 * k + i] * tf[k];
+        Ow[i] = a;
+    }
+}
+}  // namespace
+
 int ORBmatcher::Fuse(KeyFrame* pKF, const std::vector<MapPoint*>& vpMapPoints, const float th) {
     double Rcw[9], tcw[3], Ow[3];
     pKF->GetRotation(Rcw); pKF->GetTranslation(tcw); pKF->GetCameraCenter(Ow);
@@ -260,21 +282,8 @@ int ORBmatcher::Fuse(KeyFrame* pKF, const std::vector<MapPoint*>& vpMapPoints, c
 }
 
 int ORBmatcher::Fuse(KeyFrame* pKF, const Mat4f& Scw, const std::vector<MapPoint*>& vpPoints, float th, std::vector<MapPoint*>& vpReplacePoint) {
-    // :1134-1138 in float32 like cv::Mat: scw = |row 0 of sRcw|, Rcw = sRcw / scw, tcw = Scw[0:3, 3] / scw, Ow = -Rcw^T tcw
-    const float scw = std::sqrt(Scw[0] * Scw[0] + Scw[1] * Scw[1] + Scw[2] * Scw[2]);
-    float Rf[9], tf[3];
-    for (int i = 0; i < 3; i++) {
-        for (int j = 0; j < 3; j++) Rf[3 * i + j] = Scw[4 * i + j] / scw;
-        tf[i] = Scw[4 * i + 3] / scw;
-    }
     double Rcw[9], tcw[3], Ow[3];
-    for (int i = 0; i < 9; i++) Rcw[i] = Rf[i];
-    for (int i = 0; i < 3; i++) {
-        tcw[i] = tf[i];
-        float a = 0;
-        for (int k = 0; k < 3; k++) a += -Rf[3 * k + i] * tf[k];
-        Ow[i] = a;
-    }
+    DecomposeScw(Scw, Rcw, tcw, Ow);                                  // :1134-1138
     const std::set<MapPoint*> spAlreadyFound = pKF->GetMapPoints();   // :1141
     const size_t nPoints = vpPoints.size();
     std::vector<uint8_t> skip(nPoints);
@@ -597,6 +606,158 @@ int ORBmatcher::SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, 
     s.P.th = th;
     if (!s.run(who, n)) return -1;
     s.apply(CurrentFrame, LastFrame.mvpMapPoints);
+    return s.R.n_matches;
+}
+
+// ---- SearchByProjection for loop closure and relocalisation ----
+namespace {
+// One vba_search_by_projection_kf problem over a target T (a KeyFrame in loop mode, a Frame in reloc mode): its keypoints and grid,
+// the ordered queries, and the call.  The caller fills mode, pose, thresholds and `occupied` in front of run(); key_match comes back
+struct KfProjSearch {
+    vba_search_proj_kf_problem P{};
+    vba_search_proj_kf_result R{};
+    std::vector<double> uv, scale, pos, normal, dmin, dmax, pmax, puv;
+    std::vector<uint8_t> oct, occupied, desc, skip, bin, state;
+    std::vector<float> angle, q_angle;
+    std::vector<int32_t> cell_begin, cell_feat, key_match, best_idx;
+    std::vector<uint16_t> best_dist;
+    std::vector<int8_t> level;
+    template <class T>
+    bool target(const char* who, const char* what, T& F) {
+        const size_t nk = (size_t)F.N;
+        if (F.N < 0 || nk != F.mvKeysUn.size() || F.mDescriptors.size() != 32 * nk || F.mvpMapPoints.size() != nk || F.mvuRight.size() != nk) {
+            std::cerr << who << ": N, mvKeysUn, mvuRight, mvpMapPoints and mDescriptors of the " << what << " disagree" << std::endl;
+            return false;
+        }
+        if (F.mnScaleLevels < 1 || F.mvScaleFactors.size() != (size_t)F.mnScaleLevels) {
+            std::cerr << who << ": mnScaleLevels and mvScaleFactors of the " << what << " disagree" << std::endl;
+            return false;
+        }
+        if (F.mnGridCols < 1 || F.mnGridRows < 1 || F.mGrid.size() != (size_t)F.mnGridCols || !FlattenGrid(F, cell_begin, cell_feat)) {
+            std::cerr << who << ": the " << what << " has no grid" << std::endl;
+            return false;
+        }
+        uv.resize(2 * nk); oct.resize(nk); angle.resize(nk); occupied.assign(nk, 0);
+        for (size_t i = 0; i < nk; i++) {
+            const KeyPoint& kp = F.mvKeysUn[i];
+            if (F.mvuRight[i] >= 0) {
+                std::cerr << who << ": the " << what << " has a stereo keypoint (the backend is monocular)" << std::endl;
+                return false;
+            }
+            if (kp.octave < 0 || kp.octave > 255) {
+                std::cerr << who << ": a keypoint's octave is outside 0 .. 255" << std::endl;
+                return false;
+            }
+            uv[2 * i] = kp.pt.x; uv[2 * i + 1] = kp.pt.y; oct[i] = (uint8_t)kp.octave; angle[i] = kp.angle;
+        }
+        scale.assign(F.mvScaleFactors.begin(), F.mvScaleFactors.end());
+        P.K[0] = F.fx; P.K[1] = F.fy; P.K[2] = F.cx; P.K[3] = F.cy;
+        P.bounds[0] = F.mnMinX; P.bounds[1] = F.mnMaxX; P.bounds[2] = F.mnMinY; P.bounds[3] = F.mnMaxY;
+        P.n_keys = F.N; P.n_levels = F.mnScaleLevels;
+        P.desc = F.mDescriptors.data(); P.uv = uv.data(); P.oct = oct.data(); P.angle = angle.data(); P.scale = scale.data();
+        P.log_scale_factor = F.mfLogScaleFactor;
+        P.grid_cols = F.mnGridCols; P.grid_rows = F.mnGridRows; P.grid_inv_w = F.mfGridElementWidthInv; P.grid_inv_h = F.mfGridElementHeightInv;
+        P.cell_begin = cell_begin.data(); P.cell_feat = cell_feat.data();
+        key_match.assign(nk, -1);
+        return true;
+    }
+    void queries(size_t n) {
+        pos.assign(3 * n, 0.0); normal.assign(3 * n, 0.0); dmin.assign(n, 0.0); dmax.assign(n, 0.0); pmax.assign(n, 0.0); desc.assign(32 * n, 0);
+        skip.assign(n, 1); q_angle.assign(n, 0.0f);
+    }
+    void point(size_t i, MapPoint* pMP) {
+        skip[i] = 0;
+        pMP->GetWorldPos(&pos[3 * i]);
+        pMP->GetNormal(&normal[3 * i]);
+        dmin[i] = pMP->GetMinDistanceInvariance(); dmax[i] = pMP->GetMaxDistanceInvariance(); pmax[i] = pMP->mfMaxDistance;
+        std::memcpy(&desc[32 * i], pMP->GetDescriptor(), 32);
+    }
+    bool run(const char* who) {
+        const size_t nq = skip.size();
+        P.occupied = occupied.data();
+        P.n_q = (int32_t)nq;
+        P.q_pos = pos.data(); P.q_desc = desc.data(); P.q_skip = skip.data(); P.q_normal = normal.data(); P.q_dist_min = dmin.data();
+        P.q_dist_max = dmax.data(); P.q_pred_max = pmax.data(); P.q_angle = q_angle.data();
+        best_idx.assign(nq, -1); best_dist.assign(nq, 256); level.assign(nq, -128); puv.assign(2 * nq, 0.0); bin.assign(nq, 255); state.assign(nq, 1);
+        R.best_idx = best_idx.data(); R.best_dist = best_dist.data(); R.level = level.data(); R.uv = puv.data(); R.bin = bin.data();
+        R.state = state.data(); R.key_match = key_match.data();
+        vba_search_proj_kf_problem* pp = &P;
+        vba_search_proj_kf_result* pr = &R;
+        void* h = Optimizer::BackendHandle();
+        if (!h || vba_search_by_projection_kf(h, 1, &pp, &pr) != 0) {
+            std::cerr << who << ": " << (h ? vba_last_error(h) : "no HIP device (the backend has no CPU path)") << std::endl;
+            return false;
+        }
+        return true;
+    }
+};
+}  // namespace
+
+int ORBmatcher::SearchByProjection(KeyFrame* pKF, const Mat4f& Scw, const std::vector<MapPoint*>& vpPoints, std::vector<MapPoint*>& vpMatched, int th) {
+    const char* who = "ORBmatcher::SearchByProjection (loop)";
+    KfProjSearch s;
+    if (!s.target(who, "keyframe", *pKF)) return -1;
+    if (vpMatched.size() != (size_t)pKF->N) {
+        std::cerr << who << ": vpMatched does not have one entry per keypoint of the keyframe" << std::endl;
+        return -1;
+    }
+    s.P.mode = VBA_SEARCH_PROJ_KF_LOOP;
+    DecomposeScw(Scw, s.P.Rcw, s.P.tcw, s.P.Ow);                                  // :364-368
+    std::set<MapPoint*> spAlreadyFound(vpMatched.begin(), vpMatched.end());        // :372-373, not updated by the matches of the call
+    spAlreadyFound.erase(static_cast<MapPoint*>(nullptr));
+    for (size_t k = 0; k < vpMatched.size(); k++) s.occupied[k] = vpMatched[k] != nullptr;   // :446
+    const size_t n = vpPoints.size();
+    s.queries(n);
+    for (size_t i = 0; i < n; i++) {
+        MapPoint* pMP = vpPoints[i];
+        if (!pMP || pMP->isBad() || spAlreadyFound.count(pMP)) continue;           // :385; a NULL entry is skipped
+        s.point(i, pMP);
+    }
+    s.P.th = th; s.P.th_dist = TH_LOW; s.P.cos_view = 0.5;
+    if (!s.run(who)) return -1;
+    for (size_t k = 0; k < s.key_match.size(); k++)
+        if (s.key_match[k] >= 0) vpMatched[k] = vpPoints[(size_t)s.key_match[k]];  // :468
+    return s.R.n_matches;
+}
+
+int ORBmatcher::SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, const std::set<MapPoint*>& sAlreadyFound, const float th, const int ORBdist) {
+    const char* who = "ORBmatcher::SearchByProjection (relocalisation)";
+    KfProjSearch s;
+    if (!s.target(who, "frame", CurrentFrame)) return -1;
+    const std::vector<MapPoint*> vpMPs = pKF->GetMapPointMatches();               // :1682
+    const size_t n = vpMPs.size();
+    if (pKF->mvKeysUn.size() != n) {
+        std::cerr << who << ": mvKeysUn and mvpMapPoints of the keyframe disagree" << std::endl;
+        return -1;
+    }
+    s.P.mode = VBA_SEARCH_PROJ_KF_RELOC;
+    s.P.check_orientation = mbCheckOrientation ? 1 : 0;
+    float Rf[9], tf[3];
+    for (int i = 0; i < 3; i++) {                                                 // :1672-1674 in float32 like cv::Mat
+        for (int j = 0; j < 3; j++) Rf[3 * i + j] = CurrentFrame.mTcw[4 * i + j];
+        tf[i] = CurrentFrame.mTcw[4 * i + 3];
+    }
+    for (int i = 0; i < 9; i++) s.P.Rcw[i] = Rf[i];
+    for (int i = 0; i < 3; i++) {
+        s.P.tcw[i] = tf[i];
+        float a = 0;
+        for (int k = 0; k < 3; k++) a += -Rf[3 * k + i] * tf[k];
+        s.P.Ow[i] = a;
+    }
+    for (size_t k = 0; k < s.occupied.size(); k++) s.occupied[k] = CurrentFrame.mvpMapPoints[k] != nullptr;   // :1738
+    s.queries(n);
+    for (size_t i = 0; i < n; i++) {
+        MapPoint* pMP = vpMPs[i];
+        if (!pMP || pMP->isBad() || sAlreadyFound.count(pMP)) continue;            // :1688-1690
+        s.point(i, pMP);
+        s.q_angle[i] = pKF->mvKeysUn[i].angle;                                    // :1760
+    }
+    s.P.th = th; s.P.th_dist = ORBdist;
+    if (!s.run(who)) return -1;
+    for (size_t k = 0; k < s.key_match.size(); k++) {
+        if (s.key_match[k] >= 0) CurrentFrame.mvpMapPoints[k] = vpMPs[(size_t)s.key_match[k]];   // :1754
+        else if (s.key_match[k] == -2) CurrentFrame.mvpMapPoints[k] = nullptr;                   // :1789
+    }
     return s.R.n_matches;
 }
 

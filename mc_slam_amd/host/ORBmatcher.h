@@ -3,11 +3,13 @@
 // SearchBySim3 (:1258-1496, monocular) over vba_search_by_sim3, and the two tracking matchers SearchByProjection(F, vpMapPoints, th)
 // (:63-156) and SearchByProjection(CurrentFrame, LastFrame, th, bMono) (:1511-1665) over vba_search_by_projection, and both SearchByBoW
 // overloads (:207-350 keyframe -> frame, :609-748 keyframe -> keyframe) over vba_search_by_bow, each also as a batch form that makes
-// one call for a vector of keyframes.  The other searches (SearchForInitialization, SearchByProjection(pKF, Scw, ...) and the
-// relocalisation overload) stay matcher code of the caller.
+// one call for a vector of keyframes, and the loop-closure overload SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) (:354-475)
+// and the relocalisation overload SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (:1667-1797) over
+// vba_search_by_projection_kf.  SearchForInitialization stays matcher code of the caller.
 #pragma once
 #include <array>
 #include <cstdint>
+#include <set>
 #include <utility>
 #include <vector>
 
@@ -55,6 +57,18 @@ public:
     // case, then the orientation filter.  ONE vba_search_by_projection call in last-frame mode.  Returns nmatches, -1 when the backend
     // failed, bMono is false or CurrentFrame has a stereo keypoint
     int SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, const float th, const bool bMono);
+    // src/ORBmatcher.cpp:354-475, the last step of LoopClosing::ComputeSim3: vpPoints projected into pKF under the Sim3 pose Scw (decomposed
+    // in float32 as :364-368); a point takes the best free keypoint of its area at its predicted level or the one below, and a
+    // match is written into vpMatched, which has one entry per keypoint of pKF and whose non-NULL entries are taken from the start.
+    // ONE vba_search_by_projection_kf call in loop mode.  A NULL entry of vpPoints is skipped.  Returns nmatches, the matches of this
+    // call only, -1 when the backend failed, vpMatched has the wrong size or pKF has a stereo keypoint (this backend is monocular),
+    // with a message on std::cerr
+    int SearchByProjection(KeyFrame* pKF, const Mat4f& Scw, const std::vector<MapPoint*>& vpPoints, std::vector<MapPoint*>& vpMatched, int th);
+    // src/ORBmatcher.cpp:1667-1797, the calls of Tracking::Relocalization (src/Tracking.cpp:2513, :2527): the map points of pKF that are not
+    // in sAlreadyFound projected into CurrentFrame with its pose mTcw (no depth test, as the reference has none), matched to the keypoints
+    // that hold no point, then the orientation filter.  ONE vba_search_by_projection_kf call in reloc mode.  Returns nmatches, -1
+    // when the backend failed or CurrentFrame has a stereo keypoint
+    int SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, const std::set<MapPoint*>& sAlreadyFound, const float th, const int ORBdist);
     // src/ORBmatcher.cpp:207-350: the map points of pKF matched to the keypoints of F inside shared vocabulary nodes, best against second
     // best with mfNNratio, then the orientation filter; vpMapPointMatches gets one entry per keypoint of F.  ONE vba_search_by_bow call
     // in KF_FRAME mode.  Returns nmatches, -1 when the backend failed or the arrays of pKF or F disagree, with a message on std::cerr

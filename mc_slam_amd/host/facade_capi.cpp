@@ -11,6 +11,7 @@
 #include "Initializer.h"
 #include "ORBmatcher.h"
 #include "Tracking.h"
+#include "LoopClosing.h"
 
 using namespace ORB_SLAM2;
 
@@ -850,6 +851,48 @@ int fc_last_posegraph_ids(long* kf_ids, int cap_kf, long* mp_ids, int cap_mp) { 
     for (size_t i = 0; i < G.vKF.size() && (int)i < cap_kf; i++) kf_ids[i] = (long)G.vKF[i]->mnId;
     for (size_t i = 0; i < G.vMP.size() && (int)i < cap_mp; i++) mp_ids[i] = (long)G.vMP[i]->mnId;
     return (int)G.vMP.size();
+}
+// ---- projection matching for loop closure and relocalisation (the two other ORBmatcher::SearchByProjection overloads, LoopClosing) ----
+// ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th): matched_ids [n_matched] holds the ids of vpMatched going in and
+// coming back (-1: NULL)
+int fc_search_by_projection_loop(void* m, long kf, const float* Scw16, const long* mp_ids, int n, long* matched_ids, int n_matched, int th) {
+    FcMap* M = reinterpret_cast<FcMap*>(m);
+    Mat4f S; std::memcpy(S.data(), Scw16, 64);
+    std::vector<MapPoint*> matched = point_list(M, matched_ids, n_matched);
+    ORBmatcher matcher(0.75, true);
+    const int r = matcher.SearchByProjection(M->kfs.at(kf).get(), S, point_list(M, mp_ids, n), matched, th);
+    ids_of(matched, matched_ids, n_matched);
+    return r;
+}
+// ORBmatcher(0.9, check_ori).SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist); the frame's points: fc_frame_points
+int fc_search_by_projection_reloc(void* m, long frame, long kf, const long* found_ids, int n_found, float th, int orb_dist, int check_ori) {
+    FcMap* M = reinterpret_cast<FcMap*>(m);
+    const std::vector<MapPoint*> found = point_list(M, found_ids, n_found);
+    ORBmatcher matcher(0.9, check_ori != 0);
+    return matcher.SearchByProjection(*M->frames.at(frame), M->kfs.at(kf).get(), std::set<MapPoint*>(found.begin(), found.end()), th, orb_dist);
+}
+// the keypoint angles of a keyframe (what the relocalisation overload reads of pKF beside its map points)
+int fc_kf_set_angles(void* m, long kf, const float* angle, int n) {
+    KeyFrame* k = reinterpret_cast<FcMap*>(m)->kfs.at(kf).get();
+    for (int i = 0; i < n && i < (int)k->mvKeysUn.size(); i++) k->mvKeysUn[(size_t)i].angle = angle[i];
+    return (int)k->mvKeysUn.size();
+}
+// LoopClosing::MatchLoopMapPoints with mpCurrentKF, mpMatchedKF, mScw and mvpCurrentMatchedPoints (ids, -1: NULL) as given; matched_ids
+// comes back as the call left mvpCurrentMatchedPoints, loop_ids [cap] with the ids of mvpLoopMapPoints.  out3: the decision,
+// nTotalMatches, the size of mvpLoopMapPoints
+int fc_match_loop_map_points(void* m, long cur, long matched_kf, const float* Scw16, long* matched_ids, int n_matched, long* loop_ids, int cap, int* out3) {
+    FcMap* M = reinterpret_cast<FcMap*>(m);
+    LoopClosing& lc = M->lc;
+    lc.mpCurrentKF = M->kfs.at(cur).get();
+    lc.mpMatchedKF = M->kfs.at(matched_kf).get();
+    std::memcpy(lc.mScw.data(), Scw16, 64);
+    lc.mvpCurrentMatchedPoints = point_list(M, matched_ids, n_matched);
+    out3[0] = lc.MatchLoopMapPoints() ? 1 : 0;
+    out3[1] = lc.mnLoopTotalMatches;
+    out3[2] = (int)lc.mvpLoopMapPoints.size();
+    ids_of(lc.mvpCurrentMatchedPoints, matched_ids, n_matched);
+    ids_of(lc.mvpLoopMapPoints, loop_ids, cap);
+    return 0;
 }
 int fc_loop_map_updated(void* m) { return reinterpret_cast<FcMap*>(m)->lc.mbMapUpdateFlagForTracking ? 1 : 0; }
 int fc_map_updated(void* m) { return reinterpret_cast<FcMap*>(m)->lm.mbMapUpdateFlagForTracking ? 1 : 0; }

@@ -351,6 +351,7 @@ public:
     Map* mpMap = nullptr;
     float mPosGBA[3] = {0, 0, 0};          // include/MapPoint.h:90-91
     long unsigned int mnBAGlobalForKF = 0;
+    long unsigned int mnLoopPointForKF = 0;   // include/MapPoint.h:85: the mark of LoopClosing::ComputeSim3 (src/LoopClosing.cpp:455-459)
 };
 
 // include/Frame.h: the slice PoseOptimization reads and writes (:48-67, :104, :214, :230)
@@ -564,5 +565,12 @@ public:
     typedef std::map<KeyFrame*, g2o::Sim3, std::less<KeyFrame*>> KeyFrameAndPose;
     void SetMapUpdateFlagInTracking(bool b) { mbMapUpdateFlagForTracking = b; }
     bool mbMapUpdateFlagForTracking = false;
+    // what steps 6-9 of ComputeSim3 read and write (include/LoopClosing.h:117-126; LoopClosing.h has the function)
+    KeyFrame* mpCurrentKF = nullptr;
+    KeyFrame* mpMatchedKF = nullptr;
+    Mat4f mScw{};
+    std::vector<MapPoint*> mvpCurrentMatchedPoints, mvpLoopMapPoints;
+    int mnLoopTotalMatches = 0;            // nTotalMatches of the last MatchLoopMapPoints (src/LoopClosing.cpp:473-478), -1 when it failed
+    bool MatchLoopMapPoints();             // LoopClosing.cpp
 };
 }  // namespace ORB_SLAM2

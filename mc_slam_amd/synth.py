@@ -1199,6 +1199,47 @@ def search_proj_scene(seed, mode, n_keys=1000, n_q=600, twins=0.3, occupied=0.1,
                                  check_orientation=check_orientation, **common)
 
 
+# ---------------------------------------------------------------- loop-closure / relocalisation projection matching (vba_search_by_projection_kf)
+def search_proj_kf_scene(seed, mode, n_keys=1000, n_q=600, twins=0.3, occupied=0.1, th=10.0, th_dist=None, behind=0.1, check_orientation=True,
+                         rotation=20.0, angle_noise=3.0, angle_outliers=0.1, **kw):
+    """One call of the loop-closure or the relocalisation matcher (abi.SearchProjKfProblem of `mode`), every input rounded through
+    float32 as the reference holds it.  The target, the queries, the twins (contention) and the occupied share are those of
+    search_proj_scene(seed, SEARCH_PROJ_LOCAL_MAP, ...), which is built on fuse_scene; every query blocks.  th_dist defaults to TH_LOW = 50
+    in loop mode and to ORBdist = 100 in reloc mode.  Reloc mode adds
+      behind        a share of the queries of kind match is mirrored through the camera centre: the point lies behind the camera at
+                    the same distance and projects to the same pixel, so it passes every gate of the mode and can match
+      angles        keypoint angles are uniform in [0, 360), a match's q_angle is its keypoint's plus `rotation` plus angle_noise
+                    degrees of noise, a share angle_outliers of them and every other query has a random one
+    truth: that of fuse_scene, and behind [n_q] in reloc mode."""
+    reloc = mode == abi.SEARCH_PROJ_KF_RELOC
+    g = search_proj_scene(seed, abi.SEARCH_PROJ_LOCAL_MAP, n_keys=n_keys, n_q=n_q, twins=twins, occupied=occupied, non_blocking=0.0, **kw)
+    r = np.random.default_rng(seed + 104729)
+    f32 = lambda a: np.asarray(a, dtype=np.float32)
+    common = dict(mode=mode, Rcw=g.Rcw, tcw=g.tcw, Ow=g.Ow, K=g.K, bounds=g.bounds, desc=g.desc, uv=g.uv, oct=g.oct, scale=g.scale,
+                  log_scale_factor=g.log_scale_factor, grid_cols=g.grid_cols, grid_rows=g.grid_rows, grid_inv_w=g.grid_inv_w, grid_inv_h=g.grid_inv_h,
+                  cell_begin=g.cell_begin, cell_feat=g.cell_feat, occupied=g.occupied, q_desc=g.q_desc, q_skip=g.q_skip, q_dist_min=g.q_dist_min,
+                  q_dist_max=g.q_dist_max, q_pred_max=g.q_pred_max, th=th)
+    if not reloc:
+        return abi.SearchProjKfProblem(q_pos=g.q_pos, q_normal=g.q_normal, th_dist=50 if th_dist is None else th_dist, cos_view=0.5, truth=g.truth, **common)
+    key, kind = g.truth["key"], g.truth["kind"]
+    pos = g.q_pos.copy()
+    is_behind = np.zeros(n_q, dtype=bool)
+    for i in range(n_q):
+        if FUSE_KINDS[kind[i]] == "match" and r.random() < behind:
+            xc = g.Rcw @ pos[i] + g.tcw
+            pos[i] = f32(g.Rcw.T @ (-xc - g.tcw)).astype(np.float64)
+            is_behind[i] = True
+    angle = f32(r.uniform(0.0, 360.0, n_keys))
+    angle[angle >= 360.0] = 0.0
+    q_angle = f32(r.uniform(0.0, 360.0, n_q))
+    for i in range(n_q):
+        if key[i] >= 0 and r.random() >= angle_outliers:
+            q_angle[i] = np.float32(np.mod(float(angle[key[i]]) + rotation + r.normal() * angle_noise, 360.0))
+    q_angle[q_angle >= 360.0] = 0.0
+    return abi.SearchProjKfProblem(q_pos=pos, angle=angle, q_angle=q_angle, th_dist=100 if th_dist is None else th_dist,
+                                   check_orientation=check_orientation, truth=dict(g.truth, behind=is_behind), **common)
+
+
 # ---------------------------------------------------------------- bag-of-words matching (vba_search_by_bow)
 def search_bow_scene(seed, mode, n_keys1=1500, n_keys2=1500, n_nodes=100, twins=0.6, flip_bits=12, near_dup=0.15, unshared=0.1, mp1=0.7, mp2=0.8,
                      th_low=50, nn_ratio=0.75, check_orientation=True, rotation=25.0, angle_noise=3.0, angle_outliers=0.1):
