@@ -4,7 +4,9 @@
 // vba_search_proj_problem name these fields alike (n_keys, desc, uv, oct, n_levels, grid_cols, grid_rows, cell_begin, cell_feat),
 // so the helpers are templates over the struct.  What check_cell_lists accepts is what bounds the loops of sa_walk
 // (vba_search_area.h).  Included by vba_host_fuse.h, vba_host_search_sim3.h, vba_host_search_proj.h and vba_host_search_proj_kf.h, and
-// through them by their sanitizer harnesses.
+// through them by their sanitizer harnesses.  What only the two SearchByProjection halves share (SpDesc and SpQuery: common checks,
+// the upload half of the arena, describe_sp, pack_sp_common) is at the head of vba_host_search_proj.h; the ordered replay of the
+// write-backs is vba_host_orient.h.
 #pragma once
 #include "vba_layout.h"
 

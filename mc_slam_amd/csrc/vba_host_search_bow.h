@@ -2,13 +2,13 @@
 // descriptor of a pair, the node join of src/ORBmatcher.cpp:229-322 / :639-725 with the ordered query list it yields (every query
 // with its rank among the queries of its node), the packing of the descriptor records into the staging block, and the write-back:
 // match12 and match21, the rotation histogram, ComputeThreeMaxima and the drop (:325-347, :727-745).  The feature-vector check is
-// check_feat_vec of vba_host_search_tri.h; the bin and the three maxima are rot_bin and three_maxima of vba_host_search_proj.h.
+// check_feat_vec of vba_host_search_tri.h; the replay with the bin and the three maxima is replay_matches of vba_host_orient.h.
 // Included by vislam_ba.hip (vba_host_small.h) and by the sanitizer harness tests/host_search_bow_check.cpp
 // (g++ -fsanitize=address,undefined, tests/test_host_search_bow.py).
 #pragma once
 #include "../../include/vislam_ba.h"
 #include "vba_host_arena.h"
-#include "vba_host_search_proj.h"
+#include "vba_host_orient.h"
 #include "vba_host_search_tri.h"
 #include "vba_layout.h"
 
@@ -133,51 +133,23 @@ inline void pack_search_bow(const vba_search_bow_problem* P, SbDesc& d, SbKey* h
 
 // The call's back regions as they came back, then what the reference does with a match (:287-305, :695-709) and the orientation
 // filter (:325-347, :727-745): a keypoint of side 2 is taken by at most one query, so match21 does not depend on the order; a
-// dropped bin clears match12 and marks match21 with -2, and its queries leave with state 5.  Histogram, maxima and drop run here and
-// not in the kernel: they need the angles, which the device then never sees, and the drop touches outputs only
+// dropped bin clears match12 and marks match21 with -2, and its queries leave with state 5
 inline void unpack_search_bow(const vba_search_bow_problem* P, vba_search_bow_result* R, const SbDesc& d, int rounds, const int32_t* best_idx,
                               const uint16_t* best_dist, const uint16_t* best_dist2, const unsigned char* state) {
     const size_t o = (size_t)d.key1_0, n = (size_t)d.n_keys1, n2 = (size_t)d.n_keys2;
-    const bool ori = P->check_orientation != 0;
     R->status = VBA_OK;
     R->rounds = rounds;
-    for (int i = 0; i < VBA_ST_HISTO; i++) R->hist[i] = 0;
-    R->ind[0] = R->ind[1] = R->ind[2] = -1;
+    for (size_t i = 0; i < n; i++) R->match12[i] = -1;
     for (size_t k = 0; k < n2; k++) R->match21[k] = -1;
-    int nmatches = 0;
     if (n) {
         std::memcpy(R->best_idx, best_idx + o, 4 * n);
         std::memcpy(R->best_dist, best_dist + o, 2 * n);
         std::memcpy(R->best_dist2, best_dist2 + o, 2 * n);
         std::memcpy(R->state, state + o, n);
     }
-    for (size_t i = 0; i < n; i++) {
-        R->bin[i] = 255;
-        R->match12[i] = -1;
-        const int32_t b = R->best_idx[i];
-        if (R->state[i] != 0 || b < 0 || (size_t)b >= n2) continue;   // a state 0 always brings a keypoint of side 2
-        R->match12[i] = b;
-        R->match21[b] = (int32_t)i;
-        nmatches++;
-        if (ori) {
-            const int bin = rot_bin(P->angle1[i], P->angle2[b]);
-            R->bin[i] = (uint8_t)bin;
-            R->hist[bin]++;
-        }
-    }
-    R->n_before_filter = nmatches;
-    if (ori) {
-        three_maxima(R->hist, R->ind);
-        for (size_t i = 0; i < n; i++) {
-            const int bin = R->bin[i];
-            if (bin == 255 || bin == R->ind[0] || bin == R->ind[1] || bin == R->ind[2]) continue;
-            R->match21[R->match12[i]] = -2;   // :343
-            R->match12[i] = -1;               // :741
-            R->state[i] = 5;
-            nmatches--;
-        }
-    }
-    R->n_matches = nmatches;
+    replay_matches(R, n, n2, P->check_orientation != 0, P->angle1, P->angle2, 5,
+                   [R](size_t i, int32_t b) { R->match12[i] = b; R->match21[b] = (int32_t)i; },
+                   [R](size_t i) { R->match21[R->match12[i]] = -2; R->match12[i] = -1; });   // :343, :741
 }
 
 // One call (a fresh object each): what the driver (run_small, vba_host_small.h) and the sanitizer harness (run_call,

@@ -165,11 +165,11 @@ int search_by_projection(Handle* h, int32_t n_problems, vba_search_proj_problem*
 
 // The loop-closure and the relocalisation matcher, ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th)
 // (src/ORBmatcher.cpp:354-475) and SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (:1667-1797), monocular, for a
-// batch of (target, ordered query list) problems, both modes mixed: the conflict pass of k_search_proj with every query blocking;
-// histogram, maxima and drop of the relocalisation mode run in the write-back
+// batch of (target, ordered query list) problems, both modes mixed: the conflict pass of k_search_proj (vba_search_claim.h) with
+// every query blocking, over k_search_proj's argument; histogram, maxima and drop of the relocalisation mode run in the write-back
 int search_by_projection_kf(Handle* h, int32_t n_problems, vba_search_proj_kf_problem* const* in, vba_search_proj_kf_result* const* out) {
     vba_host::SearchProjKfCall C;
-    return run_small(h, SIDE_SEARCH_PROJ_KF, "vba_search_by_projection_kf", C, n_problems, in, out, [h, &C](const SkBatch& B, unsigned g) {
+    return run_small(h, SIDE_SEARCH_PROJ_KF, "vba_search_by_projection_kf", C, n_problems, in, out, [h, &C](const SpBatch& B, unsigned g) {
         VBA_LAUNCH(k_search_proj_kf, dim3(g), dim3(SK_NT), C.lds_bytes(), h->stream, B);
     });
 }

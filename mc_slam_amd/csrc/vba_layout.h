@@ -358,7 +358,7 @@ struct SsBatch {
     unsigned char* state;        // ...
 };
 // vba_search_by_projection (vba_search_proj.h); the frame's keypoints reuse FuKey
-#define VBA_SP_NT 256          // lanes of the one workgroup of a problem
+#define VBA_SP_NT 256          // lanes of the one workgroup of a problem (k_search_proj and k_search_proj_kf)
 #define VBA_SP_MAX_KEYS 16384  // the claim table of a problem is n_keys int32 in LDS
 #define VBA_SP_CONST 28        // doubles of a problem's constants: Rcw (9) tcw (3) Ow (3) K (4) bounds (4) grid_inv_w grid_inv_h
                                // log_scale_factor th cos_view
@@ -390,37 +390,20 @@ struct SpBatch {
     int* rounds;                 // [problems]
     int* best_idx;               // [total queries]
     unsigned short* best_dist;   // ...
-    unsigned short* best_dist2;  // ...
+    unsigned short* best_dist2;  // ... (k_search_proj only)
     signed char* level;          // ...
-    double* view_cos;            // ...
+    double* view_cos;            // ... (k_search_proj only)
     double* uv;                  // [total queries][2]
     unsigned char* state;        // [total queries]
     double* rad;                 // [total queries] device only: the radius of the area
     int* prev;                   // [total queries] device only: -2 the query never reaches the area, else the keypoint it claimed in
                                  // the round before (-1: none)
 };
-// vba_search_by_projection_kf (vba_search_proj_kf.h); keypoints are FuKey, queries SpQuery (blocks = 1, oct unused), the descriptor
-// SpDesc (mode: 0 loop, 1 reloc; th_high holds th_dist; nn_ratio = 0)
-#define VBA_SK_NT 256          // lanes of the one workgroup of a problem
-#define VBA_SK_MAX_KEYS 16384  // the claim table of a problem is n_keys int32 in LDS
-struct SkBatch {
-    const SpDesc* desc;
-    const FuKey* key;            // keypoint records of all problems
-    const unsigned char* occupied;   // [total keypoints]
-    const SpQuery* query;        // query records of all problems
-    const int* cell_begin;       // cell_begin of all problems
-    const int* cell_feat;        // cell_feat of all problems
-    const double* lev;           // scale tables of all problems
-    int* rounds;                 // [problems]
-    int* best_idx;               // [total queries]
-    unsigned short* best_dist;   // ...
-    signed char* level;          // ...
-    double* uv;                  // [total queries][2]
-    unsigned char* state;        // [total queries]
-    double* rad;                 // [total queries] device only: the radius of the area
-    int* prev;                   // [total queries] device only: -2 the query never reaches the area, else the keypoint it claimed in
-                                 // the round before (-1: none)
-};
+// vba_search_by_projection_kf (vba_search_proj_kf.h) shares all of it: keypoints are FuKey, queries SpQuery (blocks = 1, oct unused),
+// the descriptor SpDesc (mode: 0 loop, 1 reloc; th_high holds th_dist; nn_ratio = 0), the argument SpBatch with best_dist2 and
+// view_cos null (k_search_proj_kf never touches them, and its arena has no region for them).  The former name of its argument stays
+// as an alias: the sanitizer harness tests/host_search_proj_kf_check.cpp spells it
+using SkBatch = SpBatch;
 // vba_search_by_bow (vba_search_bow.h)
 #define VBA_SB_NT 256          // lanes of the one workgroup of a pair
 #define VBA_SB_MAX_KEYS 16384  // the claim table of a pair is n_keys2 int32 in LDS

@@ -9,13 +9,9 @@
 // candidate is one 32-byte SbKey record, two 16-byte loads.
 //
 // The queries of a pair are NOT independent: a query skips the keypoints of side 2 an earlier query has taken (:260, :667) and then
-// takes its own (:287, :696).  The conflict pass is the one of k_search_proj (vba_search_proj.h): claim[k] is the smallest walk index
-// of a query whose current result is a MATCH (threshold and ratio test passed) on keypoint k, -1 for a keypoint that is statically
-// no candidate (KF_KF mode without a good map point), INT_MAX otherwise, and query q treats k as taken iff claim[k] < q.  In a round
-// every open query walks its node's candidates against the table of the round before; then the table is reset and rebuilt from
-// the new results with an LDS atomic min between barriers.  The pass stops after the first round in which no query changed its claim:
-// the table the next round would read equals the one this round read, so every result stands.  Any fixed point is the sequential
-// answer (induction on q: query 0 reads no claim, query q reads claims of queries < q only).
+// takes its own (:287, :696).  The conflict pass is the one of vba_search_claim.h (the protocol and its proof are there) over the
+// walk indices: a query claims keypoint k when its current result is a MATCH on k (threshold and ratio test passed), and a keypoint
+// is statically taken when it is no candidate at all (KF_KF mode without a good map point).
 //
 // The node-local bound.  A keypoint of side 2 is listed in at most one node (checked on the host), and a query walks the candidates
 // of its own node only.  So claim[k] < q can hold, for a k that q reads, only through a query of q's node with a smaller walk index,
@@ -27,13 +23,13 @@
 //
 // The claim table is n_keys2 int32 of dynamic LDS (n_keys2 <= VBA_SB_MAX_KEYS, checked on the host); the kernel declares no static
 // LDS (the code object reports the 256 bytes of the workgroup reduction behind __syncthreads_or), and the table is read and
-// written in 32-bit words only.  Nothing waits on another workgroup, every loop is bounded by the pair's sizes, no atomic touches
-// memory, every output address is written by one lane only, and a lane reads back only the prev slots it wrote itself.  The ratio
-// test is one float32 product, as the reference computes it.
+// written in 32-bit words only.  No atomic touches memory, and every output address is written by one lane only.  The ratio test is
+// one float32 product, as the reference computes it.
 #pragma once
 #include "vba_device.h"
 #include "vba_layout.h"
 #include "vba_search_area.h"   // sa_load_desc, sa_hamming
+#include "vba_search_claim.h"
 
 #define SB_NT VBA_SB_NT
 
@@ -62,52 +58,39 @@ __global__ void __launch_bounds__(SB_NT) k_search_bow(SbBatch B) {
         if (r != 0) { best_idx[i] = -1; best_dist[i] = 256; best_dist2[i] = 256; state[i] = r; }
     }
     for (int q = tid; q < nq; q += SB_NT) prev[q] = -1;
-    for (int k = tid; k < n2; k += SB_NT) sb_claim[k] = blocked[k] ? -1 : 0x7fffffff;
-    __syncthreads();
+    const auto taken = [&](int k) { return blocked[k] != 0; };
+    claim_reset<SB_NT>(sb_claim, n2, taken);
 
-    // the conflict pass: at most max_rank + 1 rounds
-    int n_rounds = 0;
-    for (int round = 0; round <= max_rank; ++round) {
-        int changed = 0;
-        for (int q = tid; q < nq; q += SB_NT) {
-            const SbQuery Q = query[q];
-            if (Q.rank < round) continue;   // final since round rank
-            unsigned int a[8];
-            sa_load_desc(a, key1[Q.idx1].d);
-            int bestDist1 = 256, bestDist2 = 256, bestIdx = -1;
-            for (int c = Q.c_begin; c < Q.c_end; c++) {
-                const int idx2 = feat[c];
-                if (sb_claim[idx2] < q) continue;                                        // :260, :667-671
-                const int dist = sa_hamming(a, key2[idx2].d);
-                if (dist < bestDist1) {                                                  // :267-276, :677-686
-                    bestDist2 = bestDist1; bestDist1 = dist;
-                    bestIdx = idx2;
-                } else if (dist < bestDist2) {
-                    bestDist2 = dist;
-                }
+    // the conflict pass: at most max_rank + 1 rounds.  The visitor walks one query against the table of the round before
+    const int n_rounds = claim_rounds<SB_NT>(sb_claim, n2, nq, max_rank, taken, [&](int q) { return prev[q]; }, [&](int q, int round) {
+        const SbQuery Q = query[q];
+        if (Q.rank < round) return false;   // final since round rank
+        unsigned int a[8];
+        sa_load_desc(a, key1[Q.idx1].d);
+        int bestDist1 = 256, bestDist2 = 256, bestIdx = -1;
+        for (int c = Q.c_begin; c < Q.c_end; c++) {
+            const int idx2 = feat[c];
+            if (sb_claim[idx2] < q) continue;                                        // :260, :667-671
+            const int dist = sa_hamming(a, key2[idx2].d);
+            if (dist < bestDist1) {                                                  // :267-276, :677-686
+                bestDist2 = bestDist1; bestDist1 = dist;
+                bestIdx = idx2;
+            } else if (dist < bestDist2) {
+                bestDist2 = dist;
             }
-            int st;
-            if (!(bestDist1 <= th_pass)) st = 3;                                         // :280, :691
-            else if (!((float)bestDist1 < nn_ratio * (float)bestDist2)) st = 4;          // :284, :693
-            else st = 0;
-            const int now = (st == 0) ? bestIdx : -1;
-            changed |= now != prev[q];
-            prev[q] = now;
-            best_idx[Q.idx1] = bestIdx;
-            best_dist[Q.idx1] = (unsigned short)bestDist1;
-            best_dist2[Q.idx1] = (unsigned short)bestDist2;
-            state[Q.idx1] = (unsigned char)st;
         }
-        changed = __syncthreads_or(changed);   // every walk of the round has read the table
-        n_rounds = round + 1;
-        if (!changed) break;
-        for (int k = tid; k < n2; k += SB_NT) sb_claim[k] = blocked[k] ? -1 : 0x7fffffff;
-        __syncthreads();
-        for (int q = tid; q < nq; q += SB_NT) {
-            const int c = prev[q];
-            if (c >= 0) atomicMin(&sb_claim[c], q);
-        }
-        __syncthreads();
-    }
+        int st;
+        if (!(bestDist1 <= th_pass)) st = 3;                                         // :280, :691
+        else if (!((float)bestDist1 < nn_ratio * (float)bestDist2)) st = 4;          // :284, :693
+        else st = 0;
+        const int now = (st == 0) ? bestIdx : -1;
+        const bool changed = now != prev[q];
+        prev[q] = now;
+        best_idx[Q.idx1] = bestIdx;
+        best_dist[Q.idx1] = (unsigned short)bestDist1;
+        best_dist2[Q.idx1] = (unsigned short)bestDist2;
+        state[Q.idx1] = (unsigned char)st;
+        return changed;
+    });
     if (tid == 0) B.rounds[blockIdx.x] = n_rounds;
 }

@@ -7,22 +7,18 @@
 //
 // The queries of a problem are NOT independent: a query skips the keypoints an earlier query of the call has claimed (:113-115,
 // :1596-1598) and then claims its own (:150, :1623).  One 256-lane workgroup owns a problem; its lanes stride over the queries.
-// Phase 1 evaluates the gates and the projection once per query.  Then rounds of a fixed-point iteration run: in a round every
-// query still open walks its area against the claim table of the round before -- claim[k] is the smallest index of a blocking
-// query (Observations() > 0) whose result is keypoint k, -1 for a keypoint occupied before the call, and query q treats k as taken
-// iff claim[k] < q --, then the table is cleared and rebuilt from the new results with an LDS atomic min between barriers.  The
-// iteration stops after the first round in which no blocking query changed its keypoint.  Any fixed point is the sequential answer
-// (induction on q: query 0 reads no claim, query q reads claims of queries < q only), and after round t (counted from 0) the queries
-// 0 .. t are final, so a round only walks the queries q >= t and the loop `round <= n_q` always ends by itself: at round n_q no
-// query is left to change.  The walk is repeated each round, not cached: a query's candidates are few, and a cache per query would
-// have to live in global memory.  The claim table is n_keys int32 of dynamic LDS (n_keys <= VBA_SP_MAX_KEYS, checked on the host).
-// Nothing waits on another workgroup, every loop is bounded by the problem's sizes, every output address is written by one lane
-// only.  Plain log, floor, ceil and sqrt in FP64, contraction off so that the operations are the ones the header names; the ratio
-// test is one float32 product, as the reference computes it.
+// Phase 1 evaluates the gates and the projection once per query.  Then the conflict pass of vba_search_claim.h runs (the protocol,
+// its proof and the bound of n_q + 1 rounds are there): only a blocking query (Observations() > 0) claims its keypoint, a keypoint
+// occupied before the call is statically taken, and the visitor skips a query that never reaches the area.  The walk is repeated each
+// round, not cached: a query's candidates are few, and a cache per query would have to live in global memory.  The claim table is
+// n_keys int32 of dynamic LDS (n_keys <= VBA_SP_MAX_KEYS, checked on the host).  Every output address is written by one lane only.
+// Plain log, floor, ceil and sqrt in FP64, contraction off so that the operations are the ones the header names; the ratio test is
+// one float32 product, as the reference computes it.
 #pragma once
 #include "vba_device.h"
 #include "vba_layout.h"
 #include "vba_search_area.h"
+#include "vba_search_claim.h"
 
 #define SP_NT VBA_SP_NT   // SpDesc::c is the camera block (SA_*, vba_search_area.h)
 
@@ -41,8 +37,8 @@ __global__ void __launch_bounds__(SP_NT) k_search_proj(SpBatch B) {
     const double* scale = B.lev + (size_t)d.lev0;
     const SpQuery* query = B.query + (size_t)d.q0;
     const double qnan = __longlong_as_double(0x7ff8000000000000LL);
-    for (int k = tid; k < nk; k += SP_NT) sp_claim[k] = occupied[k] ? -1 : 0x7fffffff;
-    __syncthreads();
+    const auto taken = [&](int k) { return occupied[k] != 0; };
+    claim_reset<SP_NT>(sp_claim, nk, taken);
 
     // phase 1: the gates and the projection, once per query
     for (int q = tid; q < nq; q += SP_NT) {
@@ -87,66 +83,53 @@ __global__ void __launch_bounds__(SP_NT) k_search_proj(SpBatch B) {
         B.prev[o] = (state == 255) ? -1 : -2;
     }
 
-    // the conflict pass: at most n_q + 1 rounds
+    // the conflict pass: at most n_q + 1 rounds.  The visitor walks one query against the table of the round before
     const int th_high = d.th_high;
     const float nn_ratio = d.nn_ratio;
-    int n_rounds = 0;
-    for (int round = 0; round <= nq; ++round) {
-        int changed = 0;
-        for (int q = tid; q < nq; q += SP_NT) {
-            const size_t o = (size_t)d.q0 + (size_t)q;
-            const int before = B.prev[o];
-            if (q < round || before == -2) continue;   // final since round q; never reaches the area
-            const SpQuery& Q = query[q];
-            const double u = B.uv[2 * o], v = B.uv[2 * o + 1], r = B.rad[o];
-            const int lo = local ? (int)B.level[o] - 1 : (int)Q.oct - 1, hi = local ? (int)B.level[o] : (int)Q.oct + 1;
-            int bestDist = 256, bestDist2 = 256, bestLevel = -1, bestLevel2 = -1, bestIdx = -1;
-            bool any = false;
-            const bool check_levels = lo > 0 || hi >= 0;
-            unsigned int a[8];
-            sa_load_desc(a, Q.d);
-            // Frame::GetFeaturesInArea(u, v, r, lo, hi)
-            sa_walk(grid, tb, u, v, r, [&](int idx, const FuKey& k) {
-                const int kl = k.oct;
-                if (check_levels) {                                                      // Frame.cpp:600-607
-                    if (kl < lo) return;
-                    if (hi >= 0 && kl > hi) return;
-                }
-                if (!(fabs(k.u - u) < r && fabs(k.v - v) < r)) return;                   // Frame.cpp:612
-                any = true;
-                if (sp_claim[idx] < q) return;                                           // :113-115, :1596-1598
-                const int dist = sa_hamming(a, k.d);
-                if (dist < bestDist) {                                                   // :129-141, :1613
-                    bestDist2 = bestDist; bestDist = dist;
-                    bestLevel2 = bestLevel; bestLevel = kl;
-                    bestIdx = idx;
-                } else if (dist < bestDist2) {
-                    bestLevel2 = kl; bestDist2 = dist;
-                }
-            });
-            int state;
-            if (!any) state = local ? 7 : 4;                                             // :96, :1582
-            else if (!(bestDist <= th_high && bestIdx >= 0)) state = local ? 8 : 5;      // :145, :1621
-            else if (local && bestLevel == bestLevel2 && (float)bestDist > nn_ratio * (float)bestDist2) state = 9;   // :147
-            else state = 0;
-            const int now = (state == 0 && Q.blocks) ? bestIdx : -1;
-            changed |= now != before;
-            B.prev[o] = now;
-            B.best_idx[o] = bestIdx;
-            B.best_dist[o] = (unsigned short)bestDist;
-            B.best_dist2[o] = (unsigned short)(local ? bestDist2 : 256);
-            B.state[o] = (unsigned char)state;
-        }
-        changed = __syncthreads_or(changed);   // every walk of the round has read the table
-        n_rounds = round + 1;
-        if (!changed) break;
-        for (int k = tid; k < nk; k += SP_NT) sp_claim[k] = occupied[k] ? -1 : 0x7fffffff;
-        __syncthreads();
-        for (int q = tid; q < nq; q += SP_NT) {
-            const int c = B.prev[(size_t)d.q0 + (size_t)q];
-            if (c >= 0) atomicMin(&sp_claim[c], q);
-        }
-        __syncthreads();
-    }
+    const auto claim_of = [&](int q) { return B.prev[(size_t)d.q0 + (size_t)q]; };
+    const int n_rounds = claim_rounds<SP_NT>(sp_claim, nk, nq, nq, taken, claim_of, [&](int q, int round) {
+        const size_t o = (size_t)d.q0 + (size_t)q;
+        const int before = B.prev[o];
+        if (q < round || before == -2) return false;   // final since round q; never reaches the area
+        const SpQuery& Q = query[q];
+        const double u = B.uv[2 * o], v = B.uv[2 * o + 1], r = B.rad[o];
+        const int lo = local ? (int)B.level[o] - 1 : (int)Q.oct - 1, hi = local ? (int)B.level[o] : (int)Q.oct + 1;
+        int bestDist = 256, bestDist2 = 256, bestLevel = -1, bestLevel2 = -1, bestIdx = -1;
+        bool any = false;
+        const bool check_levels = lo > 0 || hi >= 0;
+        unsigned int a[8];
+        sa_load_desc(a, Q.d);
+        // Frame::GetFeaturesInArea(u, v, r, lo, hi)
+        sa_walk(grid, tb, u, v, r, [&](int idx, const FuKey& k) {
+            const int kl = k.oct;
+            if (check_levels) {                                                      // Frame.cpp:600-607
+                if (kl < lo) return;
+                if (hi >= 0 && kl > hi) return;
+            }
+            if (!(fabs(k.u - u) < r && fabs(k.v - v) < r)) return;                   // Frame.cpp:612
+            any = true;
+            if (sp_claim[idx] < q) return;                                           // :113-115, :1596-1598
+            const int dist = sa_hamming(a, k.d);
+            if (dist < bestDist) {                                                   // :129-141, :1613
+                bestDist2 = bestDist; bestDist = dist;
+                bestLevel2 = bestLevel; bestLevel = kl;
+                bestIdx = idx;
+            } else if (dist < bestDist2) {
+                bestLevel2 = kl; bestDist2 = dist;
+            }
+        });
+        int state;
+        if (!any) state = local ? 7 : 4;                                             // :96, :1582
+        else if (!(bestDist <= th_high && bestIdx >= 0)) state = local ? 8 : 5;      // :145, :1621
+        else if (local && bestLevel == bestLevel2 && (float)bestDist > nn_ratio * (float)bestDist2) state = 9;   // :147
+        else state = 0;
+        const int now = (state == 0 && Q.blocks) ? bestIdx : -1;
+        B.prev[o] = now;
+        B.best_idx[o] = bestIdx;
+        B.best_dist[o] = (unsigned short)bestDist;
+        B.best_dist2[o] = (unsigned short)(local ? bestDist2 : 256);
+        B.state[o] = (unsigned char)state;
+        return now != before;
+    });
     if (tid == 0) B.rounds[blockIdx.x] = n_rounds;
 }

@@ -8,30 +8,27 @@
 //
 // The queries of a problem are NOT independent: a match takes its keypoint away from every later query (:446 and :468; :1738 and
 // :1754).  The layout is that of k_search_proj (vba_search_proj.h), with every query blocking: one 256-lane workgroup owns a problem
-// and its lanes stride over the queries.  Phase 1 evaluates the mode's gates and the projection once per query.  Then rounds of a
-// fixed-point iteration run: in a round every query still open walks its area against the claim table of the round before --
-// claim[k] is the smallest index of a query whose result is keypoint k, -1 for a keypoint occupied before the call, and query q treats
-// k as taken iff claim[k] < q --, then the table is rebuilt from the new results with an LDS atomic min between barriers.  The
-// iteration stops after the first round in which no query changed its keypoint.  Any fixed point is the sequential answer (induction
-// on q: query 0 reads no claim, query q reads claims of queries < q only), and after round t (counted from 0) the queries 0 .. t are
-// final, so a round only walks the queries q >= t and the loop `round <= n_q` always ends by itself: at most n_q + 1 rounds.  The
-// claim table is n_keys int32 of dynamic LDS (n_keys <= VBA_SK_MAX_KEYS, checked on the host).  Nothing waits on another workgroup,
-// every loop is bounded by the problem's sizes, every output address is written by one lane only.  Plain log, floor, ceil and sqrt in
-// FP64, contraction off so that the operations are the ones the header names.
+// and its lanes stride over the queries.  Phase 1 evaluates the mode's gates and the projection once per query.  Then the conflict
+// pass of vba_search_claim.h runs (the protocol, its proof and the bound of n_q + 1 rounds are there): every match claims its
+// keypoint, a keypoint occupied before the call is statically taken, and the visitor skips a query that never reaches the area.  The
+// claim table is n_keys int32 of dynamic LDS (n_keys <= VBA_SP_MAX_KEYS, checked on the host).  The kernel takes k_search_proj's
+// argument and leaves best_dist2 and view_cos alone (the host binds them as null).  Every output address is written by one lane
+// only.  Plain log, floor, ceil and sqrt in FP64, contraction off so that the operations are the ones the header names.
 #pragma once
 #include "vba_device.h"
 #include "vba_layout.h"
 #include "vba_search_area.h"
+#include "vba_search_claim.h"
 
-#define SK_NT VBA_SK_NT   // SpDesc::c is the camera block (SA_*, vba_search_area.h)
+#define SK_NT VBA_SP_NT   // SpDesc::c is the camera block (SA_*, vba_search_area.h)
 
-__global__ void __launch_bounds__(SK_NT) k_search_proj_kf(SkBatch B) {
+__global__ void __launch_bounds__(SK_NT) k_search_proj_kf(SpBatch B) {
 #pragma clang fp contract(off)
     extern __shared__ int sk_claim[];   // [n_keys of the call's largest target]
     __shared__ double sc[VBA_SP_CONST];
     const SpDesc& d = B.desc[blockIdx.x];
     const int tid = threadIdx.x;
-    const int nk = d.n_keys, nq = d.n_q, nl = d.n_levels;   // nk <= VBA_SK_MAX_KEYS, nl: 1 .. VBA_TRI_LEVELS (checked on the host)
+    const int nk = d.n_keys, nq = d.n_q, nl = d.n_levels;   // nk <= VBA_SP_MAX_KEYS, nl: 1 .. VBA_TRI_LEVELS (checked on the host)
     const bool reloc = d.mode != 0;
     if (tid < VBA_SP_CONST) sc[tid] = d.c[tid];
     const double* tb = sc + SA_TB;
@@ -40,8 +37,8 @@ __global__ void __launch_bounds__(SK_NT) k_search_proj_kf(SkBatch B) {
     const double* scale = B.lev + (size_t)d.lev0;
     const SpQuery* query = B.query + (size_t)d.q0;
     const double qnan = __longlong_as_double(0x7ff8000000000000LL);
-    for (int k = tid; k < nk; k += SK_NT) sk_claim[k] = occupied[k] ? -1 : 0x7fffffff;
-    __syncthreads();
+    const auto taken = [&](int k) { return occupied[k] != 0; };
+    claim_reset<SK_NT>(sk_claim, nk, taken);
 
     // phase 1: the gates and the projection, once per query.  255: the query reaches the area
     const int st_level = reloc ? 4 : 6;
@@ -89,53 +86,40 @@ __global__ void __launch_bounds__(SK_NT) k_search_proj_kf(SkBatch B) {
         B.prev[o] = (state == 255) ? -1 : -2;
     }
 
-    // the conflict pass: at most n_q + 1 rounds
+    // the conflict pass: at most n_q + 1 rounds.  The visitor walks one query against the table of the round before
     const int th_dist = d.th_high;
-    int n_rounds = 0;
-    for (int round = 0; round <= nq; ++round) {
-        int changed = 0;
-        for (int q = tid; q < nq; q += SK_NT) {
-            const size_t o = (size_t)d.q0 + (size_t)q;
-            const int before = B.prev[o];
-            if (q < round || before == -2) continue;   // final since round q; never reaches the area
-            const SpQuery& Q = query[q];
-            const double u = B.uv[2 * o], v = B.uv[2 * o + 1], r = B.rad[o];
-            const int L = (int)B.level[o];
-            int bestDist = 256, bestIdx = -1;
-            bool any = false;
-            unsigned int a[8];
-            sa_load_desc(a, Q.d);
-            sa_walk(grid, tb, u, v, r, [&](int idx, const FuKey& k) {
-                const int kl = k.oct;
-                if (reloc && (kl < L - 1 || kl > L + 1)) return;                         // Frame.cpp:600-607 with (L - 1, L + 1): maxLevel >= 0
-                if (!(fabs(k.u - u) < r && fabs(k.v - v) < r)) return;                   // KeyFrame.cpp:1107, Frame.cpp:612
-                any = true;                                                              // :434, :1727
-                if (sk_claim[idx] < q) return;                                           // :446, :1738
-                if (!reloc && (kl < L - 1 || kl > L)) return;                            // :451
-                const int dist = sa_hamming(a, k.d);
-                if (dist < bestDist) { bestDist = dist; bestIdx = idx; }                 // :458, :1745
-            });
-            int state;
-            if (!any) state = reloc ? 5 : 7;
-            else if (!(bestDist <= th_dist && bestIdx >= 0)) state = reloc ? 6 : 8;      // :466, :1752
-            else state = 0;
-            const int now = (state == 0) ? bestIdx : -1;
-            changed |= now != before;
-            B.prev[o] = now;
-            B.best_idx[o] = bestIdx;
-            B.best_dist[o] = (unsigned short)bestDist;
-            B.state[o] = (unsigned char)state;
-        }
-        changed = __syncthreads_or(changed);   // every walk of the round has read the table
-        n_rounds = round + 1;
-        if (!changed) break;
-        for (int k = tid; k < nk; k += SK_NT) sk_claim[k] = occupied[k] ? -1 : 0x7fffffff;
-        __syncthreads();
-        for (int q = tid; q < nq; q += SK_NT) {
-            const int c = B.prev[(size_t)d.q0 + (size_t)q];
-            if (c >= 0) atomicMin(&sk_claim[c], q);
-        }
-        __syncthreads();
-    }
+    const auto claim_of = [&](int q) { return B.prev[(size_t)d.q0 + (size_t)q]; };
+    const int n_rounds = claim_rounds<SK_NT>(sk_claim, nk, nq, nq, taken, claim_of, [&](int q, int round) {
+        const size_t o = (size_t)d.q0 + (size_t)q;
+        const int before = B.prev[o];
+        if (q < round || before == -2) return false;   // final since round q; never reaches the area
+        const SpQuery& Q = query[q];
+        const double u = B.uv[2 * o], v = B.uv[2 * o + 1], r = B.rad[o];
+        const int L = (int)B.level[o];
+        int bestDist = 256, bestIdx = -1;
+        bool any = false;
+        unsigned int a[8];
+        sa_load_desc(a, Q.d);
+        sa_walk(grid, tb, u, v, r, [&](int idx, const FuKey& k) {
+            const int kl = k.oct;
+            if (reloc && (kl < L - 1 || kl > L + 1)) return;                         // Frame.cpp:600-607 with (L - 1, L + 1): maxLevel >= 0
+            if (!(fabs(k.u - u) < r && fabs(k.v - v) < r)) return;                   // KeyFrame.cpp:1107, Frame.cpp:612
+            any = true;                                                              // :434, :1727
+            if (sk_claim[idx] < q) return;                                           // :446, :1738
+            if (!reloc && (kl < L - 1 || kl > L)) return;                            // :451
+            const int dist = sa_hamming(a, k.d);
+            if (dist < bestDist) { bestDist = dist; bestIdx = idx; }                 // :458, :1745
+        });
+        int state;
+        if (!any) state = reloc ? 5 : 7;
+        else if (!(bestDist <= th_dist && bestIdx >= 0)) state = reloc ? 6 : 8;      // :466, :1752
+        else state = 0;
+        const int now = (state == 0) ? bestIdx : -1;
+        B.prev[o] = now;
+        B.best_idx[o] = bestIdx;
+        B.best_dist[o] = (unsigned short)bestDist;
+        B.state[o] = (unsigned char)state;
+        return now != before;
+    });
     if (tid == 0) B.rounds[blockIdx.x] = n_rounds;
 }
