@@ -3,9 +3,8 @@
 
 #include <cstdlib>
 #include <cstring>
-#include <iostream>
 
-#include "Optimizer.h"
+#include "BackendCall.h"
 #include "Sim3Solver.h"
 
 namespace ORB_SLAM2 {
@@ -84,13 +83,7 @@ bool Initializer::Initialize(const Frame& CurrentFrame, const std::vector<int>& 
     P.min_parallax = 1.0;                                                                           // :124-126
     P.min_triangulated = 50;
     R.inlier_h = ih.data(); R.inlier_f = jf.data(); R.x3d = x3d.data(); R.triangulated = tri.data();
-    void* h = Optimizer::BackendHandle();
-    vba_two_view_problem* pp = &P;
-    vba_two_view_result* pr = &R;
-    if (!h || vba_two_view_init(h, 1, &pp, &pr) != 0) {
-        std::cerr << "Initializer::Initialize: " << (h ? vba_last_error(h) : "no HIP device (the backend has no CPU path)") << std::endl;
-        return false;
-    }
+    if (!BackendCall("Initializer::Initialize", vba_two_view_init, P, R)) return false;
     mLast = R;
     mLast.inlier_h = mLast.inlier_f = mLast.triangulated = nullptr;
     mLast.x3d = mLast.hyp_score_h = mLast.hyp_score_f = nullptr;

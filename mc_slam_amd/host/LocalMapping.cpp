@@ -8,11 +8,10 @@
 // descriptor that the call of target i changed (and points it made bad or put into keyframes): the targets cannot share a call
 // without changing an answer.
 #include <cmath>
-#include <iostream>
 
 #include "../../include/vislam_ba.h"
+#include "BackendCall.h"
 #include "ORBmatcher.h"
-#include "Optimizer.h"
 
 namespace ORB_SLAM2 {
 
@@ -74,13 +73,7 @@ int create_new_map_points(KeyFrame* pKF, const std::vector<KeyFrame*>& vpNeighKF
         P.uv1 = uv1.data(); P.uv2 = uv2.data(); P.oct1 = oct1.data(); P.oct2 = oct2.data();
         vba_triangulate_result R{};
         R.x3d = x3d.data(); R.reason = reason.data();
-        vba_triangulate_problem* pp = &P;
-        vba_triangulate_result* pr = &R;
-        void* h = Optimizer::BackendHandle();
-        if (!h || vba_triangulate(h, 1, &pp, &pr) != 0) {
-            std::cerr << "CreateNewMapPoints: " << (h ? vba_last_error(h) : "no HIP device (the backend has no CPU path)") << std::endl;
-            return -1;
-        }
+        if (!BackendCall("CreateNewMapPoints", vba_triangulate, P, R)) return -1;
         // :1520-1542 for every accepted match, in match order
         for (int ikp = 0; ikp < nmatches; ikp++) {
             if (reason[ikp] != 0) continue;

@@ -16,35 +16,33 @@
 
 #include <cstring>
 #include <iostream>
+#include <map>
 #include <set>
+#include <string>
 
 #include "../../include/vislam_ba.h"
-#include "Optimizer.h"
+#include "BackendCall.h"
 
 namespace ORB_SLAM2 {
 
 namespace {
-// mGrid of a KeyFrame or Frame (mnGridCols columns, checked by the caller) in CSR form: cell (ix, iy) at ix * mnGridRows + iy.
-// false: a column does not have mnGridRows cells
-template <class F>
-bool FlattenGrid(const F& f, std::vector<int32_t>& cell_begin, std::vector<int32_t>& cell_feat) {
-    cell_begin.assign(1, 0);
-    cell_feat.clear();
-    for (int ix = 0; ix < f.mnGridCols; ix++) {
-        if (f.mGrid[(size_t)ix].size() != (size_t)f.mnGridRows) return false;
-        for (int iy = 0; iy < f.mnGridRows; iy++) {
-            for (size_t idx : f.mGrid[(size_t)ix][(size_t)iy]) cell_feat.push_back((int32_t)idx);
-            cell_begin.push_back((int32_t)cell_feat.size());
-        }
-    }
-    return true;
-}
-
-// one keyframe's side of a vba_search_tri_problem
-struct MatchSide {
-    std::vector<uint8_t> has_mp, oct;
+// mFeatVec of a KeyFrame or Frame in CSR form: node k lists node_feat[node_begin[k] .. node_begin[k + 1])
+struct FeatVecCsr {
     std::vector<uint32_t> node_id;
     std::vector<int32_t> node_begin, node_feat;
+    void fill(const std::map<unsigned int, std::vector<unsigned int>>& fv) {
+        node_begin.push_back(0);
+        for (const auto& node : fv) {   // a std::map: ascending node ids
+            node_id.push_back(node.first);
+            for (unsigned int idx : node.second) node_feat.push_back((int32_t)idx);
+            node_begin.push_back((int32_t)node_feat.size());
+        }
+    }
+};
+
+// one keyframe's side of a vba_search_tri_problem
+struct MatchSide : FeatVecCsr {
+    std::vector<uint8_t> has_mp, oct;
     std::vector<double> uv;
     std::vector<float> angle;
     explicit MatchSide(KeyFrame* kf) {
@@ -57,14 +55,115 @@ struct MatchSide {
             uv[2 * i] = kp.pt.x; uv[2 * i + 1] = kp.pt.y;
             angle[i] = kp.angle;
         }
-        node_begin.push_back(0);
-        for (const auto& node : kf->mFeatVec) {   // a std::map: ascending node ids
-            node_id.push_back(node.first);
-            for (unsigned int idx : node.second) node_feat.push_back((int32_t)idx);
-            node_begin.push_back((int32_t)node_feat.size());
-        }
+        fill(kf->mFeatVec);
     }
 };
+
+// A KeyFrame or Frame as the target of a projection search: the checks every entry point makes, the keypoints and the level table
+// as flat arrays, mGrid in CSR form (cell (ix, iy) at ix * mnGridRows + iy), and the fields the four problem structs share
+template <class T>
+struct SearchTarget {
+    const T* f = nullptr;
+    std::vector<double> uv, scale;
+    std::vector<uint8_t> oct;
+    std::vector<float> angle;
+    std::vector<int32_t> cell_begin, cell_feat;
+    // noun: "the keyframe", "a keyframe", "the frame".  n_points: the length of the map-point list that goes with the keypoints.
+    // more_levels: a further per-level table, which level_tables then names.  false: refused, with the message on std::cerr
+    bool fill(const char* who, const std::string& noun, const T& F, size_t n_points, const char* level_tables = "mnScaleLevels and mvScaleFactors",
+              const std::vector<float>* more_levels = nullptr) {
+        const auto refuse = [&](const std::string& why) { std::cerr << who << ": " << why << std::endl; return false; };
+        const size_t nk = (size_t)F.N, nl = (size_t)F.mnScaleLevels;
+        if (nk != F.mvKeysUn.size() || F.mDescriptors.size() != 32 * nk || n_points != nk || F.mvuRight.size() != nk)
+            return refuse("N, mvKeysUn, mvuRight, mvpMapPoints and mDescriptors of " + noun + " disagree");
+        if (F.mnScaleLevels < 1 || F.mvScaleFactors.size() != nl || (more_levels && more_levels->size() != nl))
+            return refuse(level_tables + (" of " + noun) + " disagree");
+        if (F.mnGridCols < 1 || F.mnGridRows < 1 || F.mGrid.size() != (size_t)F.mnGridCols) return refuse(noun + " has no grid");
+        uv.resize(2 * nk); oct.resize(nk);
+        for (size_t i = 0; i < nk; i++) {
+            const KeyPoint& kp = F.mvKeysUn[i];
+            if (F.mvuRight[i] >= 0) return refuse(noun + " has a stereo keypoint (the backend is monocular)");
+            if (kp.octave < 0 || kp.octave > 255)   // the ABI carries octaves as uint8; the library checks them against n_levels
+                return refuse("a keypoint's octave is outside 0 .. 255");
+            uv[2 * i] = kp.pt.x; uv[2 * i + 1] = kp.pt.y; oct[i] = (uint8_t)kp.octave;
+        }
+        cell_begin.reserve((size_t)F.mnGridCols * (size_t)F.mnGridRows + 1); cell_feat.reserve(nk);
+        cell_begin.assign(1, 0);
+        for (int ix = 0; ix < F.mnGridCols; ix++) {
+            if (F.mGrid[(size_t)ix].size() != (size_t)F.mnGridRows) return refuse(noun + " has no grid");   // a ragged column
+            for (int iy = 0; iy < F.mnGridRows; iy++) {
+                for (size_t idx : F.mGrid[(size_t)ix][(size_t)iy]) cell_feat.push_back((int32_t)idx);
+                cell_begin.push_back((int32_t)cell_feat.size());
+            }
+        }
+        scale.assign(F.mvScaleFactors.begin(), F.mvScaleFactors.end());
+        f = &F;
+        return true;
+    }
+    // vba_fuse_problem, vba_search_sim3_kf, vba_search_proj_problem, vba_search_proj_kf_problem: K and the keypoints' angles where the
+    // struct has them
+    template <class P>
+    void bind(P& p) {
+        BindK(p, 0); BindAngle(p, 0);
+        p.bounds[0] = f->mnMinX; p.bounds[1] = f->mnMaxX; p.bounds[2] = f->mnMinY; p.bounds[3] = f->mnMaxY;
+        p.n_keys = f->N; p.n_levels = f->mnScaleLevels;
+        p.desc = f->mDescriptors.data(); p.uv = uv.data(); p.oct = oct.data(); p.scale = scale.data();
+        p.log_scale_factor = f->mfLogScaleFactor;
+        p.grid_cols = f->mnGridCols; p.grid_rows = f->mnGridRows; p.grid_inv_w = f->mfGridElementWidthInv; p.grid_inv_h = f->mfGridElementHeightInv;
+        p.cell_begin = cell_begin.data(); p.cell_feat = cell_feat.data();
+    }
+    template <class P> auto BindK(P& p, int) const -> decltype((void)p.K) { p.K[0] = f->fx; p.K[1] = f->fy; p.K[2] = f->cx; p.K[3] = f->cy; }
+    template <class P> void BindK(P&, long) const {}
+    template <class P> auto BindAngle(P& p, int) -> decltype((void)p.angle) {
+        angle.resize(f->mvKeysUn.size());
+        for (size_t i = 0; i < angle.size(); i++) angle[i] = f->mvKeysUn[i].angle;
+        p.angle = angle.data();
+    }
+    template <class P> void BindAngle(P&, long) {}
+};
+
+// the arrays of a list of map points; zeros where point() was not called.  normals: false for vba_search_sim3_kf, which has none
+struct PointBlock {
+    std::vector<double> pos, normal, dmin, dmax, pmax;
+    std::vector<uint8_t> desc;
+    explicit PointBlock(size_t n = 0, bool normals = true) : pos(3 * n), normal(normals ? 3 * n : 0), dmin(n), dmax(n), pmax(n), desc(32 * n) {}
+    void point(size_t i, MapPoint* pMP) {
+        pMP->GetWorldPos(&pos[3 * i]);
+        if (!normal.empty()) pMP->GetNormal(&normal[3 * i]);
+        dmin[i] = pMP->GetMinDistanceInvariance(); dmax[i] = pMP->GetMaxDistanceInvariance(); pmax[i] = pMP->mfMaxDistance;
+        std::memcpy(&desc[32 * i], pMP->GetDescriptor(), 32);
+    }
+    template <class P>   // vba_fuse_problem (which also takes `normal`), vba_search_sim3_kf
+    void bind_points(P& p) const {
+        p.pos = pos.data(); p.dist_min = dmin.data(); p.dist_max = dmax.data(); p.pred_max = pmax.data(); p.pt_desc = desc.data();
+    }
+    template <class P>   // the queries of vba_search_proj_problem, vba_search_proj_kf_problem
+    void bind_queries(P& p) const {
+        p.q_pos = pos.data(); p.q_desc = desc.data(); p.q_normal = normal.data(); p.q_dist_min = dmin.data(); p.q_dist_max = dmax.data();
+        p.q_pred_max = pmax.data();
+    }
+};
+
+// R, t and Ow = -R^T t of the float32 4x4 T with its upper three rows divided by `div`, in float32 like cv::Mat
+void PoseParts(const Mat4f& T, float div, double Rcw[9], double tcw[3], double Ow[3]) {
+    float Rf[9], tf[3];
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) Rf[3 * i + j] = T[4 * i + j] / div;
+        tf[i] = T[4 * i + 3] / div;
+    }
+    for (int i = 0; i < 9; i++) Rcw[i] = Rf[i];
+    for (int i = 0; i < 3; i++) {
+        tcw[i] = tf[i];
+        float a = 0;
+        for (int k = 0; k < 3; k++) a += -Rf[3 * k + i] * tf[k];
+        Ow[i] = a;
+    }
+}
+
+// src/ORBmatcher.cpp:364-368 and :1134-1138: scw = |row 0 of sRcw|, Rcw = sRcw / scw, tcw = Scw[0:3, 3] / scw, Ow = -Rcw^T tcw
+void DecomposeScw(const Mat4f& Scw, double Rcw[9], double tcw[3], double Ow[3]) {
+    PoseParts(Scw, std::sqrt(Scw[0] * Scw[0] + Scw[1] * Scw[1] + Scw[2] * Scw[2]), Rcw, tcw, Ow);
+}
 }  // namespace
 
 void ORBmatcher::Epipole(KeyFrame* pKF1, KeyFrame* pKF2, float& ex, float& ey) {
@@ -132,13 +231,7 @@ int ORBmatcher::SearchForTriangulation(KeyFrame* pKF1, KeyFrame* pKF2, const Mat
     std::vector<uint8_t> best_dist(n1), state(n1);
     vba_search_tri_result R{};
     R.match12 = match12.data(); R.best_dist = best_dist.data(); R.state = state.data(); R.pairs = pairs.data();
-    vba_search_tri_problem* pp = &P;
-    vba_search_tri_result* pr = &R;
-    void* h = Optimizer::BackendHandle();
-    if (!h || vba_search_triangulation(h, 1, &pp, &pr) != 0) {
-        std::cerr << "ORBmatcher::SearchForTriangulation: " << (h ? vba_last_error(h) : "no HIP device (the backend has no CPU path)") << std::endl;
-        return -1;
-    }
+    if (!BackendCall("ORBmatcher::SearchForTriangulation", vba_search_triangulation, P, R)) return -1;
     vMatchedPairs.reserve((size_t)R.n_matches);
     for (int k = 0; k < R.n_matches; k++) vMatchedPairs.emplace_back((size_t)pairs[2 * k], (size_t)pairs[2 * k + 1]);
     return R.n_matches;
@@ -151,62 +244,20 @@ struct FuseSearch {
     std::vector<uint8_t> state;
     bool run(const char* who, KeyFrame* pKF, const double Rcw[9], const double tcw[3], const double Ow[3], const std::vector<MapPoint*>& pts,
              const std::vector<uint8_t>& skip, double th, bool check_reproj) {
-        const size_t nk = (size_t)pKF->N, np = pts.size();
-        if (nk != pKF->mvKeysUn.size() || pKF->mDescriptors.size() != 32 * nk || pKF->mvpMapPoints.size() != nk || pKF->mvuRight.size() != nk) {
-            std::cerr << who << ": N, mvKeysUn, mvuRight, mvpMapPoints and mDescriptors of the keyframe disagree" << std::endl;
+        SearchTarget<KeyFrame> t;
+        if (!t.fill(who, "the keyframe", *pKF, pKF->mvpMapPoints.size(), "mnScaleLevels, mvScaleFactors and mvInvLevelSigma2", &pKF->mvInvLevelSigma2))
             return false;
-        }
-        if (pKF->mnScaleLevels < 1 || pKF->mvScaleFactors.size() != (size_t)pKF->mnScaleLevels || pKF->mvInvLevelSigma2.size() != (size_t)pKF->mnScaleLevels) {
-            std::cerr << who << ": mnScaleLevels, mvScaleFactors and mvInvLevelSigma2 of the keyframe disagree" << std::endl;
-            return false;
-        }
-        if (pKF->mnGridCols < 1 || pKF->mnGridRows < 1 || pKF->mGrid.size() != (size_t)pKF->mnGridCols) {
-            std::cerr << who << ": the keyframe has no grid" << std::endl;
-            return false;
-        }
-        std::vector<double> uv(2 * nk);
-        std::vector<uint8_t> oct(nk);
-        for (size_t i = 0; i < nk; i++) {
-            const KeyPoint& kp = pKF->mvKeysUn[i];
-            if (pKF->mvuRight[i] >= 0) {
-                std::cerr << who << ": the keyframe has a stereo keypoint (the backend is monocular)" << std::endl;
-                return false;
-            }
-            if (kp.octave < 0 || kp.octave > 255) {   // the ABI carries octaves as uint8; the library checks them against n_levels
-                std::cerr << who << ": a keypoint's octave is outside 0 .. 255" << std::endl;
-                return false;
-            }
-            uv[2 * i] = kp.pt.x; uv[2 * i + 1] = kp.pt.y; oct[i] = (uint8_t)kp.octave;
-        }
-        std::vector<int32_t> cell_begin, cell_feat;
-        if (!FlattenGrid(*pKF, cell_begin, cell_feat)) {
-            std::cerr << who << ": the keyframe has no grid" << std::endl;
-            return false;
-        }
-        const std::vector<double> scale(pKF->mvScaleFactors.begin(), pKF->mvScaleFactors.end()), inv_sigma2(pKF->mvInvLevelSigma2.begin(), pKF->mvInvLevelSigma2.end());
-        std::vector<double> pos(3 * np), normal(3 * np), dmin(np), dmax(np), pmax(np);
-        std::vector<uint8_t> desc(32 * np);
-        for (size_t i = 0; i < np; i++) {
-            MapPoint* pMP = pts[i];
-            if (!pMP) continue;   // skipped: zeros
-            pMP->GetWorldPos(&pos[3 * i]);
-            pMP->GetNormal(&normal[3 * i]);
-            dmin[i] = pMP->GetMinDistanceInvariance(); dmax[i] = pMP->GetMaxDistanceInvariance(); pmax[i] = pMP->mfMaxDistance;
-            std::memcpy(&desc[32 * i], pMP->GetDescriptor(), 32);
-        }
+        const std::vector<double> inv_sigma2(pKF->mvInvLevelSigma2.begin(), pKF->mvInvLevelSigma2.end());
+        const size_t np = pts.size();
+        PointBlock q(np);
+        for (size_t i = 0; i < np; i++)
+            if (pts[i]) q.point(i, pts[i]);   // every point of the list, the skipped ones included; NULL: zeros
         vba_fuse_problem P{};
         std::memcpy(P.Rcw, Rcw, 72); std::memcpy(P.tcw, tcw, 24); std::memcpy(P.Ow, Ow, 24);
-        P.K[0] = pKF->fx; P.K[1] = pKF->fy; P.K[2] = pKF->cx; P.K[3] = pKF->cy;
-        P.bounds[0] = pKF->mnMinX; P.bounds[1] = pKF->mnMaxX; P.bounds[2] = pKF->mnMinY; P.bounds[3] = pKF->mnMaxY;
-        P.n_keys = pKF->N; P.n_levels = pKF->mnScaleLevels;
-        P.desc = pKF->mDescriptors.data(); P.uv = uv.data(); P.oct = oct.data();
-        P.scale = scale.data(); P.inv_level_sigma2 = inv_sigma2.data(); P.log_scale_factor = pKF->mfLogScaleFactor;
-        P.grid_cols = pKF->mnGridCols; P.grid_rows = pKF->mnGridRows;
-        P.grid_inv_w = pKF->mfGridElementWidthInv; P.grid_inv_h = pKF->mfGridElementHeightInv;
-        P.cell_begin = cell_begin.data(); P.cell_feat = cell_feat.data();
-        P.n_pt = (int32_t)np; P.th_low = ORBmatcher::TH_LOW;
-        P.pos = pos.data(); P.normal = normal.data(); P.dist_min = dmin.data(); P.dist_max = dmax.data(); P.pred_max = pmax.data();
-        P.pt_desc = desc.data(); P.skip = skip.data();
+        t.bind(P);
+        q.bind_points(P);
+        P.normal = q.normal.data(); P.inv_level_sigma2 = inv_sigma2.data();
+        P.n_pt = (int32_t)np; P.th_low = ORBmatcher::TH_LOW; P.skip = skip.data();
         P.th = th; P.cos_view = 0.5; P.check_reproj = check_reproj ? 1 : 0; P.chi2_reproj = 5.99;
         best_idx.assign(np, -1); state.assign(np, 1);
         std::vector<uint16_t> best_dist(np);
@@ -214,36 +265,9 @@ struct FuseSearch {
         std::vector<double> puv(2 * np);
         vba_fuse_result R{};
         R.best_idx = best_idx.data(); R.best_dist = best_dist.data(); R.level = level.data(); R.uv = puv.data(); R.state = state.data();
-        vba_fuse_problem* pp = &P;
-        vba_fuse_result* pr = &R;
-        void* h = Optimizer::BackendHandle();
-        if (!h || vba_fuse(h, 1, &pp, &pr) != 0) {
-            std::cerr << who << ": " << (h ? vba_last_error(h) : "no HIP device (the backend has no CPU path)") << std::endl;
-            return false;
-        }
-        return true;
+        return BackendCall(who, vba_fuse, P, R);
     }
 };
-}  // namespace
-
-namespace {
-// src/ORBmatcher.cpp:364-368 and :1134-1138 in float32 like cv::Mat: scw = |row 0 of sRcw|, Rcw = sRcw / scw, tcw = Scw[0:3, 3] / scw,
-// Ow = -Rcw^T tcw
-void DecomposeScw(const Mat4f& Scw, double Rcw[9], double tcw[3], double Ow[3]) {
-    const float scw = std::sqrt(Scw[0] * Scw[0] + Scw[1] * Scw[1] + Scw[2] * Scw[2]);
-    float Rf[9], tf[3];
-    for (int i = 0; i < 3; i++) {
-        for (int j = 0; j < 3; j++) Rf[3 * i + j] = Scw[4 * i + j] / scw;
-        tf[i] = Scw[4 * i + 3] / scw;
-    }
-    for (int i = 0; i < 9; i++) Rcw[i] = Rf[i];
-    for (int i = 0; i < 3; i++) {
-        tcw[i] = tf[i];
-        float a = 0;
-        for (int k = 0; k < 3; k++) a += -Rf[3 * k + i] * tf[k];
-        Ow[i] = a;
-    }
-}
 }  // namespace
 
 int ORBmatcher::Fuse(KeyFrame* pKF, const std::vector<MapPoint*>& vpMapPoints, const float th) {
@@ -315,58 +339,22 @@ int ORBmatcher::Fuse(KeyFrame* pKF, const Mat4f& Scw, const std::vector<MapPoint
 namespace {
 // one keyframe's side of a vba_search_sim3_problem: the keyframe as a search target and its own map points per keypoint
 struct Sim3Side {
-    std::vector<double> uv, scale, pos, dmin, dmax, pmax;
-    std::vector<uint8_t> oct, has_pt, pt_desc;
-    std::vector<int32_t> cell_begin, cell_feat;
+    SearchTarget<KeyFrame> t;
+    PointBlock q;
+    std::vector<uint8_t> has_pt;
     bool fill(const char* who, KeyFrame* pKF, const std::vector<MapPoint*>& pts, const std::vector<uint8_t>& matched, vba_search_sim3_kf& S) {
-        const size_t nk = (size_t)pKF->N;
-        if (nk != pKF->mvKeysUn.size() || pKF->mDescriptors.size() != 32 * nk || pts.size() != nk || pKF->mvuRight.size() != nk) {
-            std::cerr << who << ": N, mvKeysUn, mvuRight, mvpMapPoints and mDescriptors of a keyframe disagree" << std::endl;
-            return false;
-        }
-        if (pKF->mnScaleLevels < 1 || pKF->mvScaleFactors.size() != (size_t)pKF->mnScaleLevels) {
-            std::cerr << who << ": mnScaleLevels and mvScaleFactors of a keyframe disagree" << std::endl;
-            return false;
-        }
-        if (pKF->mnGridCols < 1 || pKF->mnGridRows < 1 || pKF->mGrid.size() != (size_t)pKF->mnGridCols) {
-            std::cerr << who << ": a keyframe has no grid" << std::endl;
-            return false;
-        }
-        uv.resize(2 * nk); oct.resize(nk); has_pt.assign(nk, 0); pos.assign(3 * nk, 0.0); dmin.assign(nk, 0.0); dmax.assign(nk, 0.0); pmax.assign(nk, 0.0);
-        pt_desc.assign(32 * nk, 0);
-        for (size_t i = 0; i < nk; i++) {
-            const KeyPoint& kp = pKF->mvKeysUn[i];
-            if (pKF->mvuRight[i] >= 0) {
-                std::cerr << who << ": a keyframe has a stereo keypoint (the backend is monocular)" << std::endl;
-                return false;
-            }
-            if (kp.octave < 0 || kp.octave > 255) {   // the ABI carries octaves as uint8; the library checks them against n_levels
-                std::cerr << who << ": a keypoint's octave is outside 0 .. 255" << std::endl;
-                return false;
-            }
-            uv[2 * i] = kp.pt.x; uv[2 * i + 1] = kp.pt.y; oct[i] = (uint8_t)kp.octave;
+        if (!t.fill(who, "a keyframe", *pKF, pts.size())) return false;
+        q = PointBlock(pts.size(), false); has_pt.assign(pts.size(), 0);
+        for (size_t i = 0; i < pts.size(); i++) {
             MapPoint* pMP = pts[i];
             if (!pMP || pMP->isBad()) continue;       // :1314-1318
             has_pt[i] = 1;
-            pMP->GetWorldPos(&pos[3 * i]);
-            dmin[i] = pMP->GetMinDistanceInvariance(); dmax[i] = pMP->GetMaxDistanceInvariance(); pmax[i] = pMP->mfMaxDistance;
-            std::memcpy(&pt_desc[32 * i], pMP->GetDescriptor(), 32);
+            q.point(i, pMP);
         }
-        if (!FlattenGrid(*pKF, cell_begin, cell_feat)) {
-            std::cerr << who << ": a keyframe has no grid" << std::endl;
-            return false;
-        }
-        scale.assign(pKF->mvScaleFactors.begin(), pKF->mvScaleFactors.end());
         pKF->GetRotation(S.Rcw); pKF->GetTranslation(S.tcw);
-        S.bounds[0] = pKF->mnMinX; S.bounds[1] = pKF->mnMaxX; S.bounds[2] = pKF->mnMinY; S.bounds[3] = pKF->mnMaxY;
-        S.n_keys = pKF->N; S.n_levels = pKF->mnScaleLevels;
-        S.desc = pKF->mDescriptors.data(); S.uv = uv.data(); S.oct = oct.data(); S.scale = scale.data();
-        S.log_scale_factor = pKF->mfLogScaleFactor;
-        S.grid_cols = pKF->mnGridCols; S.grid_rows = pKF->mnGridRows;
-        S.grid_inv_w = pKF->mfGridElementWidthInv; S.grid_inv_h = pKF->mfGridElementHeightInv;
-        S.cell_begin = cell_begin.data(); S.cell_feat = cell_feat.data();
-        S.has_pt = has_pt.data(); S.matched = matched.data(); S.pos = pos.data();
-        S.dist_min = dmin.data(); S.dist_max = dmax.data(); S.pred_max = pmax.data(); S.pt_desc = pt_desc.data();
+        t.bind(S);
+        q.bind_points(S);
+        S.has_pt = has_pt.data(); S.matched = matched.data();
         return true;
     }
 };
@@ -412,13 +400,7 @@ int ORBmatcher::SearchBySim3(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoin
     vba_search_sim3_result R{};
     R.match1 = match1.data(); R.match2 = match2.data(); R.best_dist1 = dist1.data(); R.best_dist2 = dist2.data();
     R.level1 = level1.data(); R.level2 = level2.data(); R.state1 = state1.data(); R.state2 = state2.data(); R.match12 = match12.data();
-    vba_search_sim3_problem* pp = &P;
-    vba_search_sim3_result* pr = &R;
-    void* h = Optimizer::BackendHandle();
-    if (!h || vba_search_by_sim3(h, 1, &pp, &pr) != 0) {
-        std::cerr << who << ": " << (h ? vba_last_error(h) : "no HIP device (the backend has no CPU path)") << std::endl;
-        return -1;
-    }
+    if (!BackendCall(who, vba_search_by_sim3, P, R)) return -1;
     for (size_t i1 = 0; i1 < N1; i1++)
         if (match12[i1] >= 0) vpMatches12[i1] = vpMapPoints2[(size_t)match12[i1]];   // :1489
     return R.n_found;
@@ -430,54 +412,20 @@ namespace {
 struct ProjSearch {
     vba_search_proj_problem P{};
     vba_search_proj_result R{};
-    std::vector<double> uv, scale;
-    std::vector<uint8_t> oct, occupied;
-    std::vector<float> angle;
-    std::vector<int32_t> cell_begin, cell_feat, key_match, best_idx;
+    SearchTarget<Frame> t;
+    std::vector<uint8_t> occupied;
+    std::vector<int32_t> key_match, best_idx;
     std::vector<uint16_t> best_dist, best_dist2;
     std::vector<int8_t> level;
     std::vector<double> view_cos, puv;
     std::vector<uint8_t> bin, state;
     bool frame(const char* who, Frame& F) {
+        if (!t.fill(who, "the frame", F, F.mvpMapPoints.size())) return false;
         const size_t nk = (size_t)F.N;
-        if (nk != F.mvKeysUn.size() || F.mDescriptors.size() != 32 * nk || F.mvpMapPoints.size() != nk || F.mvuRight.size() != nk) {
-            std::cerr << who << ": N, mvKeysUn, mvuRight, mvpMapPoints and mDescriptors of the frame disagree" << std::endl;
-            return false;
-        }
-        if (F.mnScaleLevels < 1 || F.mvScaleFactors.size() != (size_t)F.mnScaleLevels) {
-            std::cerr << who << ": mnScaleLevels and mvScaleFactors of the frame disagree" << std::endl;
-            return false;
-        }
-        if (F.mnGridCols < 1 || F.mnGridRows < 1 || F.mGrid.size() != (size_t)F.mnGridCols) {
-            std::cerr << who << ": the frame has no grid" << std::endl;
-            return false;
-        }
-        uv.resize(2 * nk); oct.resize(nk); occupied.resize(nk); angle.resize(nk);
-        for (size_t i = 0; i < nk; i++) {
-            const KeyPoint& kp = F.mvKeysUn[i];
-            if (F.mvuRight[i] >= 0) {
-                std::cerr << who << ": the frame has a stereo keypoint (the backend is monocular)" << std::endl;
-                return false;
-            }
-            if (kp.octave < 0 || kp.octave > 255) {
-                std::cerr << who << ": a keypoint's octave is outside 0 .. 255" << std::endl;
-                return false;
-            }
-            uv[2 * i] = kp.pt.x; uv[2 * i + 1] = kp.pt.y; oct[i] = (uint8_t)kp.octave; angle[i] = kp.angle;
-            occupied[i] = F.mvpMapPoints[i] && F.mvpMapPoints[i]->Observations() > 0;   // :113-115, :1596-1598 in front of the call
-        }
-        if (!FlattenGrid(F, cell_begin, cell_feat)) {
-            std::cerr << who << ": the frame has no grid" << std::endl;
-            return false;
-        }
-        scale.assign(F.mvScaleFactors.begin(), F.mvScaleFactors.end());
-        P.K[0] = F.fx; P.K[1] = F.fy; P.K[2] = F.cx; P.K[3] = F.cy;
-        P.bounds[0] = F.mnMinX; P.bounds[1] = F.mnMaxX; P.bounds[2] = F.mnMinY; P.bounds[3] = F.mnMaxY;
-        P.n_keys = F.N; P.n_levels = F.mnScaleLevels;
-        P.desc = F.mDescriptors.data(); P.uv = uv.data(); P.oct = oct.data(); P.angle = angle.data(); P.scale = scale.data();
-        P.log_scale_factor = F.mfLogScaleFactor;
-        P.grid_cols = F.mnGridCols; P.grid_rows = F.mnGridRows; P.grid_inv_w = F.mfGridElementWidthInv; P.grid_inv_h = F.mfGridElementHeightInv;
-        P.cell_begin = cell_begin.data(); P.cell_feat = cell_feat.data(); P.occupied = occupied.data();
+        occupied.resize(nk);
+        for (size_t i = 0; i < nk; i++) occupied[i] = F.mvpMapPoints[i] && F.mvpMapPoints[i]->Observations() > 0;   // :113-115, :1596-1598 in front of the call
+        t.bind(P);
+        P.occupied = occupied.data();
         P.th_high = ORBmatcher::TH_HIGH;
         key_match.assign(nk, -1);
         R.key_match = key_match.data();
@@ -489,14 +437,7 @@ struct ProjSearch {
         bin.assign(nq, 255); state.assign(nq, 1);
         R.best_idx = best_idx.data(); R.best_dist = best_dist.data(); R.best_dist2 = best_dist2.data(); R.level = level.data(); R.view_cos = view_cos.data();
         R.uv = puv.data(); R.bin = bin.data(); R.state = state.data();
-        vba_search_proj_problem* pp = &P;
-        vba_search_proj_result* pr = &R;
-        void* h = Optimizer::BackendHandle();
-        if (!h || vba_search_by_projection(h, 1, &pp, &pr) != 0) {
-            std::cerr << who << ": " << (h ? vba_last_error(h) : "no HIP device (the backend has no CPU path)") << std::endl;
-            return false;
-        }
-        return true;
+        return BackendCall(who, vba_search_by_projection, P, R);
     }
     // what the function leaves in mvpMapPoints: the last query that wrote a keypoint, NULL where the orientation filter cleared it
     void apply(Frame& F, const std::vector<MapPoint*>& queries) const {
@@ -508,20 +449,16 @@ struct ProjSearch {
 };
 
 // the per-point arrays both modes read
-struct ProjQueries {
-    std::vector<double> pos, normal, dmin, dmax, pmax;
-    std::vector<uint8_t> desc, skip, blocks;
-    explicit ProjQueries(size_t n) : pos(3 * n), normal(3 * n), dmin(n), dmax(n), pmax(n), desc(32 * n), skip(n, 1), blocks(n) {}
+struct ProjQueries : PointBlock {
+    std::vector<uint8_t> skip, blocks;
+    explicit ProjQueries(size_t n) : PointBlock(n), skip(n, 1), blocks(n) {}
     void point(size_t i, MapPoint* pMP) {
-        pMP->GetWorldPos(&pos[3 * i]);
-        pMP->GetNormal(&normal[3 * i]);
-        dmin[i] = pMP->GetMinDistanceInvariance(); dmax[i] = pMP->GetMaxDistanceInvariance(); pmax[i] = pMP->mfMaxDistance;
-        std::memcpy(&desc[32 * i], pMP->GetDescriptor(), 32);
+        PointBlock::point(i, pMP);
         blocks[i] = pMP->Observations() > 0;
     }
     void bind(vba_search_proj_problem& P) const {
-        P.q_pos = pos.data(); P.q_desc = desc.data(); P.q_skip = skip.data(); P.q_blocks = blocks.data();
-        P.q_normal = normal.data(); P.q_dist_min = dmin.data(); P.q_dist_max = dmax.data(); P.q_pred_max = pmax.data();
+        bind_queries(P);
+        P.q_skip = skip.data(); P.q_blocks = blocks.data();
     }
 };
 }  // namespace
@@ -613,90 +550,51 @@ int ORBmatcher::SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, 
 namespace {
 // One vba_search_by_projection_kf problem over a target T (a KeyFrame in loop mode, a Frame in reloc mode): its keypoints and grid,
 // the ordered queries, and the call.  The caller fills mode, pose, thresholds and `occupied` in front of run(); key_match comes back
+template <class T>
 struct KfProjSearch {
     vba_search_proj_kf_problem P{};
     vba_search_proj_kf_result R{};
-    std::vector<double> uv, scale, pos, normal, dmin, dmax, pmax, puv;
-    std::vector<uint8_t> oct, occupied, desc, skip, bin, state;
-    std::vector<float> angle, q_angle;
-    std::vector<int32_t> cell_begin, cell_feat, key_match, best_idx;
+    SearchTarget<T> t;
+    PointBlock q;
+    std::vector<double> puv;
+    std::vector<uint8_t> occupied, skip, bin, state;
+    std::vector<float> q_angle;
+    std::vector<int32_t> key_match, best_idx;
     std::vector<uint16_t> best_dist;
     std::vector<int8_t> level;
-    template <class T>
-    bool target(const char* who, const char* what, T& F) {
-        const size_t nk = (size_t)F.N;
-        if (F.N < 0 || nk != F.mvKeysUn.size() || F.mDescriptors.size() != 32 * nk || F.mvpMapPoints.size() != nk || F.mvuRight.size() != nk) {
-            std::cerr << who << ": N, mvKeysUn, mvuRight, mvpMapPoints and mDescriptors of the " << what << " disagree" << std::endl;
-            return false;
-        }
-        if (F.mnScaleLevels < 1 || F.mvScaleFactors.size() != (size_t)F.mnScaleLevels) {
-            std::cerr << who << ": mnScaleLevels and mvScaleFactors of the " << what << " disagree" << std::endl;
-            return false;
-        }
-        if (F.mnGridCols < 1 || F.mnGridRows < 1 || F.mGrid.size() != (size_t)F.mnGridCols || !FlattenGrid(F, cell_begin, cell_feat)) {
-            std::cerr << who << ": the " << what << " has no grid" << std::endl;
-            return false;
-        }
-        uv.resize(2 * nk); oct.resize(nk); angle.resize(nk); occupied.assign(nk, 0);
-        for (size_t i = 0; i < nk; i++) {
-            const KeyPoint& kp = F.mvKeysUn[i];
-            if (F.mvuRight[i] >= 0) {
-                std::cerr << who << ": the " << what << " has a stereo keypoint (the backend is monocular)" << std::endl;
-                return false;
-            }
-            if (kp.octave < 0 || kp.octave > 255) {
-                std::cerr << who << ": a keypoint's octave is outside 0 .. 255" << std::endl;
-                return false;
-            }
-            uv[2 * i] = kp.pt.x; uv[2 * i + 1] = kp.pt.y; oct[i] = (uint8_t)kp.octave; angle[i] = kp.angle;
-        }
-        scale.assign(F.mvScaleFactors.begin(), F.mvScaleFactors.end());
-        P.K[0] = F.fx; P.K[1] = F.fy; P.K[2] = F.cx; P.K[3] = F.cy;
-        P.bounds[0] = F.mnMinX; P.bounds[1] = F.mnMaxX; P.bounds[2] = F.mnMinY; P.bounds[3] = F.mnMaxY;
-        P.n_keys = F.N; P.n_levels = F.mnScaleLevels;
-        P.desc = F.mDescriptors.data(); P.uv = uv.data(); P.oct = oct.data(); P.angle = angle.data(); P.scale = scale.data();
-        P.log_scale_factor = F.mfLogScaleFactor;
-        P.grid_cols = F.mnGridCols; P.grid_rows = F.mnGridRows; P.grid_inv_w = F.mfGridElementWidthInv; P.grid_inv_h = F.mfGridElementHeightInv;
-        P.cell_begin = cell_begin.data(); P.cell_feat = cell_feat.data();
-        key_match.assign(nk, -1);
+    bool target(const char* who, const char* noun, T& F) {
+        if (!t.fill(who, noun, F, F.mvpMapPoints.size())) return false;
+        t.bind(P);
+        occupied.assign((size_t)F.N, 0);
+        key_match.assign((size_t)F.N, -1);
         return true;
     }
     void queries(size_t n) {
-        pos.assign(3 * n, 0.0); normal.assign(3 * n, 0.0); dmin.assign(n, 0.0); dmax.assign(n, 0.0); pmax.assign(n, 0.0); desc.assign(32 * n, 0);
+        q = PointBlock(n);
         skip.assign(n, 1); q_angle.assign(n, 0.0f);
     }
     void point(size_t i, MapPoint* pMP) {
         skip[i] = 0;
-        pMP->GetWorldPos(&pos[3 * i]);
-        pMP->GetNormal(&normal[3 * i]);
-        dmin[i] = pMP->GetMinDistanceInvariance(); dmax[i] = pMP->GetMaxDistanceInvariance(); pmax[i] = pMP->mfMaxDistance;
-        std::memcpy(&desc[32 * i], pMP->GetDescriptor(), 32);
+        q.point(i, pMP);
     }
     bool run(const char* who) {
         const size_t nq = skip.size();
         P.occupied = occupied.data();
         P.n_q = (int32_t)nq;
-        P.q_pos = pos.data(); P.q_desc = desc.data(); P.q_skip = skip.data(); P.q_normal = normal.data(); P.q_dist_min = dmin.data();
-        P.q_dist_max = dmax.data(); P.q_pred_max = pmax.data(); P.q_angle = q_angle.data();
+        q.bind_queries(P);
+        P.q_skip = skip.data(); P.q_angle = q_angle.data();
         best_idx.assign(nq, -1); best_dist.assign(nq, 256); level.assign(nq, -128); puv.assign(2 * nq, 0.0); bin.assign(nq, 255); state.assign(nq, 1);
         R.best_idx = best_idx.data(); R.best_dist = best_dist.data(); R.level = level.data(); R.uv = puv.data(); R.bin = bin.data();
         R.state = state.data(); R.key_match = key_match.data();
-        vba_search_proj_kf_problem* pp = &P;
-        vba_search_proj_kf_result* pr = &R;
-        void* h = Optimizer::BackendHandle();
-        if (!h || vba_search_by_projection_kf(h, 1, &pp, &pr) != 0) {
-            std::cerr << who << ": " << (h ? vba_last_error(h) : "no HIP device (the backend has no CPU path)") << std::endl;
-            return false;
-        }
-        return true;
+        return BackendCall(who, vba_search_by_projection_kf, P, R);
     }
 };
 }  // namespace
 
 int ORBmatcher::SearchByProjection(KeyFrame* pKF, const Mat4f& Scw, const std::vector<MapPoint*>& vpPoints, std::vector<MapPoint*>& vpMatched, int th) {
     const char* who = "ORBmatcher::SearchByProjection (loop)";
-    KfProjSearch s;
-    if (!s.target(who, "keyframe", *pKF)) return -1;
+    KfProjSearch<KeyFrame> s;
+    if (!s.target(who, "the keyframe", *pKF)) return -1;
     if (vpMatched.size() != (size_t)pKF->N) {
         std::cerr << who << ": vpMatched does not have one entry per keypoint of the keyframe" << std::endl;
         return -1;
@@ -722,8 +620,8 @@ int ORBmatcher::SearchByProjection(KeyFrame* pKF, const Mat4f& Scw, const std::v
 
 int ORBmatcher::SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, const std::set<MapPoint*>& sAlreadyFound, const float th, const int ORBdist) {
     const char* who = "ORBmatcher::SearchByProjection (relocalisation)";
-    KfProjSearch s;
-    if (!s.target(who, "frame", CurrentFrame)) return -1;
+    KfProjSearch<Frame> s;
+    if (!s.target(who, "the frame", CurrentFrame)) return -1;
     const std::vector<MapPoint*> vpMPs = pKF->GetMapPointMatches();               // :1682
     const size_t n = vpMPs.size();
     if (pKF->mvKeysUn.size() != n) {
@@ -732,18 +630,7 @@ int ORBmatcher::SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, const std
     }
     s.P.mode = VBA_SEARCH_PROJ_KF_RELOC;
     s.P.check_orientation = mbCheckOrientation ? 1 : 0;
-    float Rf[9], tf[3];
-    for (int i = 0; i < 3; i++) {                                                 // :1672-1674 in float32 like cv::Mat
-        for (int j = 0; j < 3; j++) Rf[3 * i + j] = CurrentFrame.mTcw[4 * i + j];
-        tf[i] = CurrentFrame.mTcw[4 * i + 3];
-    }
-    for (int i = 0; i < 9; i++) s.P.Rcw[i] = Rf[i];
-    for (int i = 0; i < 3; i++) {
-        s.P.tcw[i] = tf[i];
-        float a = 0;
-        for (int k = 0; k < 3; k++) a += -Rf[3 * k + i] * tf[k];
-        s.P.Ow[i] = a;
-    }
+    PoseParts(CurrentFrame.mTcw, 1.0f, s.P.Rcw, s.P.tcw, s.P.Ow);                 // :1672-1674 in float32 like cv::Mat
     for (size_t k = 0; k < s.occupied.size(); k++) s.occupied[k] = CurrentFrame.mvpMapPoints[k] != nullptr;   // :1738
     s.queries(n);
     for (size_t i = 0; i < n; i++) {
@@ -764,19 +651,17 @@ int ORBmatcher::SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, const std
 // ---- SearchByBoW ----
 namespace {
 // one side of a vba_search_bow_problem: a KeyFrame (angles of mvKeysUn, :700) or a Frame (angles of mvKeys, :296)
-struct BowSide {
+struct BowSide : FeatVecCsr {
     int n = 0;
     const unsigned char* desc = nullptr;
     const std::vector<MapPoint*>* points = nullptr;
     std::vector<uint8_t> good;
     std::vector<float> angle;
-    std::vector<uint32_t> node_id;
-    std::vector<int32_t> node_begin, node_feat;
     bool ok = false;
     template <class F>
     void fill(const F& f, const std::vector<KeyPoint>& keys) {
         n = f.N;
-        ok = f.N >= 0 && keys.size() == (size_t)f.N && f.mDescriptors.size() == 32 * (size_t)f.N && f.mvpMapPoints.size() == (size_t)f.N;
+        ok = keys.size() == (size_t)f.N && f.mDescriptors.size() == 32 * (size_t)f.N && f.mvpMapPoints.size() == (size_t)f.N;
         if (!ok) return;
         desc = f.mDescriptors.data();
         points = &f.mvpMapPoints;
@@ -786,12 +671,7 @@ struct BowSide {
             good[i] = pMP && !pMP->isBad();                       // :243-247, :649-652, :665-671
             angle[i] = keys[i].angle;
         }
-        node_begin.push_back(0);
-        for (const auto& node : f.mFeatVec) {                     // a std::map: ascending node ids
-            node_id.push_back(node.first);
-            for (unsigned int idx : node.second) node_feat.push_back((int32_t)idx);
-            node_begin.push_back((int32_t)node_feat.size());
-        }
+        FeatVecCsr::fill(f.mFeatVec);
     }
     explicit BowSide(KeyFrame* kf) { fill(*kf, kf->mvKeysUn); }
     explicit BowSide(const Frame& f) { fill(f, f.mvKeys); }
@@ -839,12 +719,7 @@ bool RunBow(const char* who, int mode, const std::vector<const BowSide*>& side1,
         pp[i] = &p;
     }
     for (size_t i = 0; i < n; i++) pr[i] = &out[i].R;            // out does not grow any more
-    void* h = Optimizer::BackendHandle();
-    if (!h || vba_search_by_bow(h, (int32_t)n, pp.data(), pr.data()) != 0) {
-        std::cerr << who << ": " << (h ? vba_last_error(h) : "no HIP device (the backend has no CPU path)") << std::endl;
-        return false;
-    }
-    return true;
+    return BackendCall(who, vba_search_by_bow, (int32_t)n, pp.data(), pr.data());
 }
 
 // vpMapPointMatches of :211, :287, :343: the map point of pKF whose match the function leaves at each keypoint of F

@@ -6,9 +6,8 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <iostream>
 
-#include "Optimizer.h"
+#include "BackendCall.h"
 
 namespace ORB_SLAM2 {
 
@@ -130,11 +129,7 @@ bool Sim3Solver::iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbIn
         P.best_inliers = mnBestInliers;
         std::memcpy(P.best_S12, mBestS12, sizeof mBestS12);
         R.inlier = inl.data();
-        void* h = Optimizer::BackendHandle();
-        vba_sim3_ransac_problem* pp = &P;
-        vba_sim3_ransac_result* pr = &R;
-        if (!h || vba_sim3_ransac(h, 1, &pp, &pr) != 0) {
-            std::cerr << "Sim3Solver::iterate: " << (h ? vba_last_error(h) : "no HIP device (the backend has no CPU path)") << std::endl;
+        if (!BackendCall("Sim3Solver::iterate", vba_sim3_ransac, P, R)) {
             bNoMore = true;
             return false;
         }
