@@ -166,6 +166,7 @@ enum { VBA_BUFFERS(VBA_BUF_ENUM) BUF_N };
 struct ProfEvt {
     int cls;
     hipEvent_t a, b;
+    int counts = 1;   // 0: the time goes to the class, but the scope is no pass of its own (the redo launches of a linearisation pass)
 };
 
 // Host threads that the stages of asynchronous batches (vba_batch_submit) share: the packing of one ticket may run while another

@@ -78,9 +78,13 @@ int vba_debug_buf_id(const char* name) {
 // chain columns of the factorisation (vba_chain.h): 0 = one launch per block column everywhere, 1 = the default policy
 int vba_debug_set_chain(void* handle, int32_t on) { return set_path_opt(handle, &PathOverrides::no_chain, on ? 0 : 1); }
 
-// the A/B paths read from the environment, per handle: "schur_split", "trsv_old", "pcg_jacobi" (value 0 / 1)
+// the A/B paths read from the environment, per handle: "schur_split", "trsv_old", "pcg_jacobi" (value 0 / 1); and "lin_probe", which
+// no variable sets: 0 off, 1 on at any batch size, 2 a chi2-only probe wherever one may run, -1 back to the default (plan_lin_probe).
+// A window's counters are the last two ints of its WinCtrl (vba_debug_copy of buffer "CTRL"; size: vba_debug_window_layout [13]):
+// n_probe at sizeof(WinCtrl) - 8, n_redo at - 4
 int vba_debug_set_path(void* handle, const char* name, int32_t value) {
     if (!name) return -1;
+    if (!strcmp(name, "lin_probe")) return (value < -1 || value > 2) ? -1 : set_path_opt(handle, &PathOverrides::lin_probe, value);
     int PathOverrides::*f = !strcmp(name, "schur_split") ? &PathOverrides::schur_split : !strcmp(name, "trsv_old") ? &PathOverrides::trsv_old
                           : !strcmp(name, "pcg_jacobi") ? &PathOverrides::pcg_jacobi : nullptr;
     return f ? set_path_opt(handle, f, value ? 1 : 0) : -1;

@@ -97,6 +97,7 @@ struct PathOverrides {
     int lin_fallback = 0;  // 1: XYZ windows without the edge-parallel work split (vba_debug_set_lin_fallback)
     int chol_step = 0;     // > 0: form of the fused factorisation step (vba_debug_set_chol_step)
     int schur_split = -1, trsv_old = -1, pcg_jacobi = -1;   // 0 / 1: vba_debug_set_path; -1: the environment's
+    int lin_probe = -1;    // vba_debug_set_path "lin_probe": 0 off, 1 on at any batch size, 2 probe every pass that may be one; -1: plan_lin_probe's default
 };
 struct Overrides {
     PathOverrides path;
@@ -173,7 +174,18 @@ struct RunPlan {
     int dbg_stop_after = -1; // Batch::dbg_stop_after
     int ngroups = 1;         // window groups, each with its own stream
     int word_report = 0;     // one Gauss-Newton window: k_ctrl_gn reports through the pinned word, no event per iteration
+    int lin_probe = 0;       // plan_lin_probe (Batch::lin_probe; not one of the plan_ints)
 };
+// The chi2-only probe of a linearisation pass that is expected to stop its window (vba_kernels.h, LIN_AUTO / LIN_REDO): 0 off,
+// 1 on, 2 on for every pass that may be one (the hook only: the tests' way to reach every path).  Gauss-Newton over inverse-depth
+// windows only -- the Levenberg-Marquardt schedule and the XYZ kernels have no such pass.  By default from 64 windows on, where
+// the IMU factors have launches of their own (plan_run: imu_lin): below that a pass is launch latency, and the redo launches
+// behind the control kernel would only add to it.  The hook (0 / 1 / 2) overrides the size rule, never the variant or the algorithm.
+inline int plan_lin_probe(int n, int variant, int algo, const PathOverrides& path) {
+    if (variant != VBA_VARIANT_PRV_IDP || algo != VBA_ALGO_GN) return 0;
+    if (path.lin_probe >= 0) return std::min(path.lin_probe, 2);
+    return n >= 64 ? 1 : 0;
+}
 inline RunPlan plan_run(const UploadPlan& u, int n, int variant, int algo, const Overrides& ov, const Knobs& k, bool profile, bool is_lane,
                         int streams_available) {
     RunPlan r;
@@ -211,6 +223,7 @@ inline RunPlan plan_run(const UploadPlan& u, int n, int variant, int algo, const
     if (!profile && max_streams > 1 && n >= 8)
         r.ngroups = std::max(1, std::min(max_streams, n / 8));   // a group never falls below the 8 windows of the XCD-aware mapping
     r.word_report = algo == VBA_ALGO_GN && n == 1 && !profile;   // see k_ctrl_gn
+    r.lin_probe = plan_lin_probe(n, variant, algo, ov.path);
     return r;
 }
 

@@ -218,6 +218,7 @@ void enqueue_lin(Handle* h, const Group& g, int mode) {
     const LaunchGeom& L = h->geom;
     const int imu_lin = L.max_imu > 0 ? h->rp.imu_lin : -1;
     ProfScope ps(h, g.stream, VBA_PROF_LINEARIZE);
+    if (mode == LIN_REDO) ps.e.counts = 0;   // the second half of the pass LIN_AUTO opened
     if (h->variant == VBA_VARIANT_PRV_IDP) {
         const size_t shm = LIN2_LDS;
         if (imu_lin == vba_host::LIN_IMU_FUSED) {   // edges and IMU factors in one launch
@@ -233,7 +234,7 @@ void enqueue_lin(Handle* h, const Group& g, int mode) {
         VBA_LAUNCH(k_lin_imu_pair, dim3(L.max_imu, g.n_win), dim3(64), 0, g.stream, g.B, mode);
     } else if (imu_lin == vba_host::LIN_IMU_RES_HESS) {   // a lane per keyframe pair for the Lie-group part, then a wave per pair for J^T Omega J
         VBA_LAUNCH(k_lin_imu_res, dim3((L.max_imu + 63) / 64, g.n_win), dim3(64), 0, g.stream, g.B, mode);
-        if (mode == LIN_FULL) VBA_LAUNCH(k_lin_imu_hess, dim3(L.max_imu, g.n_win), dim3(64), 0, g.stream, g.B);
+        if (mode != LIN_ERR && mode != LIN_ERR_TRIAL) VBA_LAUNCH(k_lin_imu_hess, dim3(L.max_imu, g.n_win), dim3(64), 0, g.stream, g.B, mode);
     }
 }
 
@@ -366,6 +367,7 @@ int enqueue_schedule(Handle* h, std::vector<Group>& groups, StopRef stop_flag) {
             const bool word_report = h->rp.word_report && nit <= 32;   // see k_ctrl_gn
             const bool pace = nit <= 32;  // also when profiling: the launch counts (and hence the per-launch averages) then equal those of a normal run
             const int depth = h->rp.pace_depth;   // how far ahead
+            const bool probe = h->rp.lin_probe != 0;
             for (auto& g : groups) g.dead = false;
             for (int it = 0; it < nit; it++) {
                 bool any = false;
@@ -389,7 +391,10 @@ int enqueue_schedule(Handle* h, std::vector<Group>& groups, StopRef stop_flag) {
                     }
                     any = true;
                     forward_stop(h, stop_flag);   // InterruptBA raised while the host paces itself: the device sees it at its next poll
-                    enqueue_lin(h, g, LIN_FULL);
+                    // probing (plan_lin_probe): windows whose last chi2 decrease predicts a stop evaluate chi2 only, and the ones
+                    // that go on all the same get their full pass behind the control launch.  k_ctrl_gn sets no probe before its
+                    // call of iteration 1, so the first pass that can be one -- and the first redo -- is that of iteration 2.
+                    enqueue_lin(h, g, probe ? LIN_AUTO : LIN_FULL);
                     {
                         ProfScope ps(h, g.stream, VBA_PROF_CONTROL);
                         if (h->rp.poll) VBA_LAUNCH(k_poll_stop, dim3(1), dim3(1), 0, g.stream, g.B);
@@ -399,6 +404,7 @@ int enqueue_schedule(Handle* h, std::vector<Group>& groups, StopRef stop_flag) {
                         ev[gi][it] = get_evt(h);
                         (void)hipEventRecord(ev[gi][it], g.stream);
                     }
+                    if (probe && it >= 2) enqueue_lin(h, g, LIN_REDO);
                     enqueue_solve_iteration(h, g, stop_flag);
                 }
                 if (!any) break;
@@ -426,6 +432,7 @@ int do_run(Handle* h, StopRef stop_flag) {
                                (int)h->xstreams.size() + (h->owns_streams ? 11 : 1));
     h->B.dbg_stop_after = h->rp.dbg_stop_after;
     h->B.pcg_tri = h->rp.pcg_tri;
+    h->B.lin_probe = h->rp.lin_probe;
     const Batch B = h->B;
     *h->stop_host = stop_flag.set() ? 1 : 0;
     for (int i = 64; i < 1024; i++) h->stop_host[i] = 0;
@@ -527,7 +534,7 @@ int do_run(Handle* h, StopRef stop_flag) {
             float ms = 0;
             (void)hipEventElapsedTime(&ms, e.a, e.b);
             pf.ms[e.cls] += ms;
-            pf.launches[e.cls] += 1;
+            pf.launches[e.cls] += e.counts;
         }
         float tot = 0;
         (void)hipEventElapsedTime(&tot, ev_begin, ev_end);

@@ -77,10 +77,23 @@ struct Batch {
     double* out_chi2;
     double* dbg;  // 4 KiB scratch for diagnostic builds (in-kernel stamps); never read by the product path
     int dbg_stop_after;  // test hook (vba_debug_set_stop_after): >= 0 -- the stop flag reads 1 from that poll of a window on; -1: off
+    int lin_probe;       // the run's RunPlan::lin_probe (k_ctrl_gn): 0 no window ever probes, 1 by the last chi2 decrease, 2 every pass it may
 };
 
 #define LIN_FULL 0
 #define LIN_ERR 1
+// (2: LIN_ERR_TRIAL of the Levenberg-Marquardt schedule, vba_kernels_lm.h)
+// Gauss-Newton, inverse-depth variant, probing on (vba_host::plan_lin_probe).  The pass in which a window stops by |dchi2| < 1e-3
+// is read for its chi2 alone: its Jacobians, its 96 B of records per edge and its IMU Hessians are never used.  So after an
+// iteration whose chi2 decrease was below LIN_PROBE_DCHI2 the window's next pass is a PROBE -- the LIN_ERR path, the same chi2
+// from the same instructions, no stores -- and only if the window then goes on is the full pass run, before the solve:
+//   LIN_AUTO  a window with WinCtrl::lin_probe takes LIN_ERR, every other one LIN_FULL
+//   LIN_REDO  behind the control launch: the windows with WinCtrl::lin_redo take LIN_FULL, the others exit at once
+// Both resolve per window, hence uniformly over a workgroup (lin_mode_of).
+#define LIN_AUTO 3
+#define LIN_REDO 4
+#define LIN_SKIP (-1)
+#define LIN_PROBE_DCHI2 10.0
 
 // One read of the caller's stop flag by one window: g2o's terminate() before an iteration (sparse_optimizer.cpp:376), inside the
 // Levenberg-Marquardt trial loop (levenberg.cpp:149), and the bDoMore check between the stages (src/Optimizer.cpp:462-466).  The
@@ -165,6 +178,7 @@ __global__ void __launch_bounds__(256) k_reset(Batch B) {
         c.lm_trial = 0; c.lm_need_trial = 0; c.nbad = 0; c.lin_its = 0; c.polls = 0;
         c.lambda = 0; c.ni = 2; c.chi_prev = 0; c.chi_ini = 0;
         c.chi2_vis = c.chi2_prv = c.chi2_bias = 0;
+        c.lin_probe = c.lin_redo = 0; c.n_probe = c.n_redo = 0;
     }
 }
 
@@ -199,6 +213,7 @@ __global__ void __launch_bounds__(64) k_stage_clear(Batch B, int stage) {
         if (d.its[stage] <= 0) c.active = 0;  // optimize(0) runs nothing
         c.stage = stage; c.it = 0; c.chol_fail = 0;
         c.lm_trial = 0; c.lm_need_trial = 0; c.nbad = 0; c.ni = 2;
+        c.lin_probe = c.lin_redo = 0;   // a stage starts with no chi2 decrease behind it
     }
 }
 
@@ -475,11 +490,22 @@ DEVI void lin_imu_hess(const Batch& B, const WinDesc& d, int k, double* sm) {
 #define LIN2_PS 19   // LDS row stride of one landmark: dd, y(3), Xw(3), N0(9), ref_free, sD (+ one spare: the stride stays odd)
 #define LIN2_LDS ((256 * LIN2_ES + 64 * LIN2_PS + 4) * 8)   // 40 480 B: four workgroups per CU
 
+// what a launch in `mode` is for window c: LIN_FULL, LIN_ERR, or LIN_SKIP (nothing to do).  Modes other than LIN_AUTO / LIN_REDO
+// pass through.
+DEVI int lin_mode_of(const WinCtrl& c, int mode) {
+    if (mode == LIN_AUTO) return c.lin_probe ? LIN_ERR : LIN_FULL;
+    if (mode == LIN_REDO) return c.lin_redo ? LIN_FULL : LIN_SKIP;
+    return mode;
+}
+
 // The IMU factors: a launch of their own behind the vision linearisation (same stream) -- inlined into k_lin2 their ~60 live
 // doubles of Lie algebra set the register budget of the 130x more numerous edge workgroups.  k_lin_imu_res: a lane per keyframe
 // pair; k_lin_imu_hess (LIN_FULL only): a wave per pair.  `gate_lm`: the XYZ / Levenberg-Marquardt gating of k_lin_xyz.
-DEVI bool lin_imu_gate(const WinDesc& d, const WinCtrl& c, int mode) {
+// `mode` comes in as launched and leaves resolved for the window (lin_mode_of).
+DEVI bool lin_imu_gate(const WinDesc& d, const WinCtrl& c, int& mode) {
     if (!c.active) return false;
+    mode = lin_mode_of(c, mode);
+    if (mode == LIN_SKIP) return false;
     if (d.variant == 2) return true;
     if (mode == 2 /* LIN_ERR_TRIAL */ && !win_on(d, c)) return false;
     if (mode == LIN_FULL && d.algo == 1 && c.lm_need_trial) return false;
@@ -488,7 +514,7 @@ DEVI bool lin_imu_gate(const WinDesc& d, const WinCtrl& c, int mode) {
 __global__ void __launch_bounds__(64) k_lin_imu_res(Batch B, int mode) {
     const int w = blockIdx.y;
     const WinDesc& d = B.desc[w];
-    if (!lin_imu_gate(d, B.ctrl[w], mode)) return;
+    if (!lin_imu_gate(d, B.ctrl[w], mode)) return;   // (mode: resolved for the window from here on)
     const int k = blockIdx.x * 64 + threadIdx.x;
     if (k >= d.n_imu) return;
     lin_imu_res(B, d, k, (mode == LIN_FULL) ? LIN_FULL : LIN_ERR);
@@ -507,11 +533,12 @@ __global__ void __launch_bounds__(64) k_lin_imu_pair(Batch B, int mode) {
     __syncthreads();
     lin_imu_hess(B, d, k, sm);
 }
-__global__ void __launch_bounds__(64) k_lin_imu_hess(Batch B) {
+// mode: LIN_FULL, or LIN_AUTO / LIN_REDO -- a probing window has no record to read and owes no Hessian
+__global__ void __launch_bounds__(64) k_lin_imu_hess(Batch B, int mode) {
     __shared__ double sm[672];
     const int w = blockIdx.y;
     const WinDesc& d = B.desc[w];
-    if (!lin_imu_gate(d, B.ctrl[w], LIN_FULL)) return;
+    if (!lin_imu_gate(d, B.ctrl[w], mode) || mode != LIN_FULL) return;
     const int k = blockIdx.x;
     if (k >= d.n_imu) return;
     lin_imu_hess(B, d, k, sm);
@@ -565,6 +592,9 @@ DEVI void lin2_body(const Batch& B, int nblk_lin, int mode, double* lsm) {
     const WinDesc& d = B.desc[w];
     const WinCtrl& c = B.ctrl[w];
     if (!c.active) return;
+    const bool probe = mode == LIN_AUTO && c.lin_probe;   // (uniform over the workgroup: one window, one flag)
+    mode = lin_mode_of(c, mode);
+    if (mode == LIN_SKIP) return;
     const int t = threadIdx.x;
     const int lb = blockIdx.x;
     if (lb >= d.n_part_lin) return;
@@ -689,7 +719,12 @@ DEVI void lin2_body(const Batch& B, int nblk_lin, int mode, double* lsm) {
     }
     if (mode != LIN_FULL) {
         const double tot = block_sum256(chi, red);
-        if (t == 0) B.part[d.part0 + lb] = tot;
+        if (t == 0) {
+            B.part[d.part0 + lb] = tot;
+            // a probe is counted once per pass, by the window's first workgroup (here, behind the last load of the pass: a store to the
+            // control block ahead of them costs k_lin2 three registers)
+            if (probe && lb == 0) B.ctrl[w].n_probe++;
+        }
         return;
     }
     __syncthreads();
@@ -884,6 +919,15 @@ __global__ void __launch_bounds__(64) k_ctrl_gn(Batch B, int final_eval, int hos
     // the trace holds preChi2 of iteration 0 and afterChi2 of every iteration run: an optimize() stopped before its first
     // iteration has evaluated nothing
     if ((it >= 1 || active) && c.n_trace < VBA_TRACE) c.trace[c.n_trace++] = cur;
+    // the probe (LIN_AUTO / LIN_REDO): a window that goes on behind a chi2-only pass owes the full one; its next pass is a probe when
+    // this stage has a decrease to judge by (it >= 1) and that decrease was small.  The final evaluation is LIN_ERR for every window.
+    if (final_eval) c.lin_probe = c.lin_redo = 0;
+    else {
+        const int redo = c.lin_probe && active;
+        c.lin_redo = redo;
+        c.n_redo += redo;
+        c.lin_probe = B.lin_probe && active && it >= 1 && (B.lin_probe == 2 || fabs(c.chi_prev - cur) < LIN_PROBE_DCHI2);
+    }
     c.chi_prev = cur;
     c.active = active;
     c.chol_fail = 0;

@@ -2,6 +2,7 @@
 // record-size constants and the item records of the small-problem entry points.  Plain C / C++ (no HIP): included by vba_device.h for the kernels, and by the host code that lays a batch
 // out (vba_host_layout.h), which the tests compile with plain g++ under sanitizers.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #define VBA_NB 32          // block size of the dense reduced-system factorisation
@@ -93,7 +94,15 @@ struct WinCtrl {
     double chi_ini;   // LM: iniChi
     double chi2_vis, chi2_prv, chi2_bias;
     double trace[VBA_TRACE];
+    // Gauss-Newton, inverse-depth variant: the chi2-only probe of a pass that is expected to stop the window (k_ctrl_gn, LIN_AUTO /
+    // LIN_REDO).  The last four ints of the block: a reader finds them at sizeof(WinCtrl) - 16 .. - 4 (vba_debug_window_layout [13])
+    int lin_probe;    // 1: the window's next linearisation pass evaluates chi2 only
+    int lin_redo;     // 1: the probe did not stop the window, the full pass is owed before the solve
+    int n_probe;      // chi2-only passes of this run
+    int n_redo;       // full passes redone behind a probe
 };
+static_assert(offsetof(WinCtrl, n_redo) + 4 == sizeof(WinCtrl) && offsetof(WinCtrl, lin_probe) + 16 == sizeof(WinCtrl),
+              "the probe state is the tail of WinCtrl: tests read it from sizeof(WinCtrl) backwards");
 
 // ---- the small-problem entry points: per-item descriptor (host -> device), result record (device -> host) and the *Batch of
 // device pointers a kernel takes as its argument (filled by bind() of the topic's call object, vba_host_<topic>.h)

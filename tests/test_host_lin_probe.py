@@ -1,0 +1,45 @@
+"""vba_host::plan_lin_probe (mc_slam_amd/csrc/vba_host_plan.h): whether a run probes linearisation passes with a chi2-only pass
+(LIN_AUTO / LIN_REDO, vba_kernels.h), under AddressSanitizer + UBSan (CPU only; harness: tests/host_lin_probe_check.cpp).  Every
+expected value is restated from the rule: on for Gauss-Newton over inverse-depth windows, by default from 64 windows on (where the
+IMU factors have launches of their own); the hook vba_debug_set_path(h, "lin_probe", v) -- 0 off, 1 on, 2 every pass -- overrides
+the size rule and never the variant or the algorithm."""
+import pytest
+
+import plan_cases as pc
+import host_check_lib as hc
+
+SIZES = [1, 5, 9, 63, 64, 65, 66, 255, 256, 4096]
+
+
+@pytest.fixture(scope="module")
+def checker(tmp_path_factory):
+    return hc.build(tmp_path_factory, "host_lin_probe_check")
+
+
+def _run(checker, tmp_path, cases):
+    path = str(tmp_path / "cases.txt")
+    open(path, "w").write("".join("n=%d variant=%d algo=%d hook=%d\n" % c for c in cases))
+    out = [tuple(map(int, l.split())) for l in hc.run(checker, [path], n_lines=len(cases))]
+    for fn, planned, n_ints in out:
+        assert fn == planned                      # plan_run carries the function's value
+        assert n_ints == len(pc.FIELDS) == 23     # and the integers of vba_debug_plan stay what they were
+    return [fn for fn, _, _ in out]
+
+
+def test_default_by_batch_size_variant_and_algorithm(checker, tmp_path):
+    cases = [(n, v, a, -1) for n in SIZES for v in (pc.SE3_XYZ, pc.PRV_XYZ, pc.PRV_IDP) for a in (pc.GN, pc.LM)]
+    got = _run(checker, tmp_path, cases)
+    for (n, v, a, _), g in zip(cases, got):
+        assert g == int(v == pc.PRV_IDP and a == pc.GN and n >= 64), (n, v, a, g)
+    on = {n for (n, v, a, _), g in zip(cases, got) if g}
+    assert on == {64, 65, 66, 255, 256, 4096}     # the threshold is the one of the IMU launches (plan_cases: imu_lin)
+    assert all((pc.expected(n)[pc.FIELDS.index("imu_lin")] == pc.IMU_RES_HESS) == (n in on) for n in SIZES)
+
+
+def test_the_hook_overrides_the_size_rule_only(checker, tmp_path):
+    cases = [(n, v, a, h) for n in (1, 9, 63, 64, 300) for v in (pc.SE3_XYZ, pc.PRV_XYZ, pc.PRV_IDP) for a in (pc.GN, pc.LM) for h in (0, 1, 2)]
+    got = _run(checker, tmp_path, cases)
+    for (n, v, a, h), g in zip(cases, got):
+        assert g == (h if v == pc.PRV_IDP and a == pc.GN else 0), (n, v, a, h, g)
+    # -1 hands the decision back to the default
+    assert _run(checker, tmp_path, [(8, pc.PRV_IDP, pc.GN, -1), (64, pc.PRV_IDP, pc.GN, -1)]) == [0, 1]
