@@ -7,7 +7,9 @@
 //   pt_perm / ref_seg   record position of every landmark: by reference keyframe, lm_order inside (inverse-depth windows)
 //   item lists          per off-diagonal keyframe pair (a < b) the (record_a, record_b) of every landmark both see:
 //                       [item_begin, item_mid) pairs of two observation records, [item_mid, item_end) pairs that involve
-//                       the landmark's reference keyframe (these also carry a direct H_pp term)
+//                       the landmark's reference keyframe (these also carry a direct H_pp term).  A reference keyframe whose
+//                       PR vertex is fixed through kf_fix has no Hessian block: its reference items are left out of the lists
+//                       (the readers rebuild Br from the OBSERVER's edge record, which knows nothing of the reference's flag)
 // All of it is a stable counting sort or a ranked compaction, done with wave ballots: a wave walks a sequence 64
 // entries at a time, `ballot(predicate)` gives the members of the bucket among them, the popcount below a lane its rank
 // -- no atomics decide an order, so the structure (and with it every summation order of the solve) is reproducible.
@@ -337,6 +339,7 @@ DEVI void st_row_body(const Batch& B, const StBuild& T, int* c0, int* c1) {
         const bool valid = slot < kseg[a + 1];
         const int p = (FILL && valid) ? T.slot_obs[d.obs0 + slot] : 0;
         const int r = (valid && idp) ? T.slot_ref[d.obs0 + slot] : -1;
+        const bool r_free = r > a && r < nf && (kf_free(B, d, r) & 1);   // (a reference keyframe with its PR vertex fixed has no block: no reference item)
         int4 sr_lo = make_int4(0, 0, 0, 0), sr_hi = make_int4(0, 0, 0, 0);
         if (FILL) slot_row_load(T, d, valid ? T.slot_q[d.obs0 + slot] : 0, valid, sr_lo, sr_hi);
         const u64_t lmw0 = valid ? T.slot_mask[(size_t)(d.obs0 + slot) * T.smw] : 0ull;   // word 0 of the landmark's mask
@@ -344,7 +347,7 @@ DEVI void st_row_body(const Batch& B, const StBuild& T, int* c0, int* c1) {
             const u64_t rg = range(wd);
             if (!rg) continue;
             const u64_t Mr = valid ? (T.slot_mask[(size_t)(d.obs0 + slot) * T.smw + wd] & rg) : 0ull;
-            const u64_t rb = (r > a && r < nf && (r >> 6) == wd) ? (1ull << (r & 63)) : 0ull;
+            const u64_t rb = (r_free && (r >> 6) == wd) ? (1ull << (r & 63)) : 0ull;
             u64_t U = wave_or64(Mr | rb);
             while (U) {
                 const int bb = __builtin_ctzll(U);
@@ -362,8 +365,8 @@ DEVI void st_row_body(const Batch& B, const StBuild& T, int* c0, int* c1) {
             }
         }
     }
-    // 2. landmark records a is the reference keyframe of: reference items only
-    if (idp)
+    // 2. landmark records a is the reference keyframe of: reference items only (none when a's PR vertex is fixed through kf_fix)
+    if (idp && (kf_free(B, d, a) & 1))
         for (int c = rseg[a]; c < rseg[a + 1]; c += 64) {
             const int rec = c + lane;
             const bool valid = rec < rseg[a + 1];
@@ -431,11 +434,12 @@ DEVI void st_row_body1(const Batch& B, const StBuild& T) {
         const bool valid = slot < kseg[a + 1];
         const int p = (FILL && valid) ? T.slot_obs[d.obs0 + slot] : 0;
         const int r = (valid && idp) ? T.slot_ref[d.obs0 + slot] : -1;
+        const bool r_free = r > a && r < nf && (kf_free(B, d, r) & 1);   // (a reference keyframe with its PR vertex fixed has no block: no reference item)
         int4 sr_lo = make_int4(0, 0, 0, 0), sr_hi = make_int4(0, 0, 0, 0);
         if (FILL) slot_row_load(T, d, valid ? T.slot_q[d.obs0 + slot] : 0, valid, sr_lo, sr_hi);
         const u64_t lmw0 = valid ? T.slot_mask[(size_t)(d.obs0 + slot) * T.smw] : 0ull;
         const u64_t Mr = lmw0 & rg;
-        const u64_t rb = (r > a && r < nf) ? (1ull << r) : 0ull;
+        const u64_t rb = r_free ? (1ull << r) : 0ull;
         u64_t U = wave_or64(Mr | rb);
         U = ((u64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(U >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)U);   // (uniform: scalar loop)
         while (U) {
@@ -451,8 +455,8 @@ DEVI void st_row_body1(const Batch& B, const StBuild& T) {
             if (lane == b) { r0 += __popcll(m0); r1 += __popcll(m1); }
         }
     }
-    // 2. landmark records a is the reference keyframe of: reference items only
-    if (idp)
+    // 2. landmark records a is the reference keyframe of: reference items only (none when a's PR vertex is fixed through kf_fix)
+    if (idp && (kf_free(B, d, a) & 1))
         for (int c = rseg[a]; c < rseg[a + 1]; c += 64) {
             const int rec = c + lane;
             const bool valid = rec < rseg[a + 1];

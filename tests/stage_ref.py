@@ -11,6 +11,9 @@ Bounds (eps = 2^-53, c a small constant):
   factor |L D L^T - S| <= c nS eps |L| |D| |L^T|                   (componentwise backward error of LDL^T)
   solve  |r - L y| <= c nS eps |L| |y|,  |y - D L^T x| <= c nS eps (|D| |L^T| |x| + |y|)
   x_c    |Ds (x - x_ref)|_2 <= (|E|_F |Ds x|_2 + |f|_2) / lambda_min(S^)   with S^ = Ds^-1 S Ds^-1 and E, f the scaled bounds above
+  dl     accumulation c eps (k + kappa) |Dinv| (|b_l| + |W|^T |x_c|), plus, for inverse depth, the forward error of J_rho and of the
+         residuals carried through Dinv (landmark_step_tol: J_rho cancels at low parallax)
+`worst_blocks` says where an S is wrong: the keyframe pairs and PR / V / Bias sub-blocks beyond their bound, in the oracle's order.
 """
 import numpy as np
 
@@ -139,7 +142,7 @@ def reduced(p, H, b, chi2, lvl, lam=0.0, dtype=LD):
     aW = np.abs(W.astype(np.float64))
     rabs = np.sqrt(h * max(chi2, 0.0)) + np.einsum("cpa,pab,pb->c", aW, np.abs(Dinv.astype(np.float64)), np.abs(bl.astype(np.float64)))
     return dict(S=S, r=r, H=H, b=b, var_act=var_act, pt_act=pt_act, lam=lam, k=k, kappa=kappa, h=h, rabs=rabs,
-                Dinv=Dinv, W=W, bl=bl, np=np_, pdim=pdim, ldim=L)
+                Dinv=Dinv, W=W, bl=bl, np=np_, pdim=pdim, ldim=L, p=p, lvl=np.asarray(lvl))
 
 
 def tol_S(red, c=8.0):
@@ -168,11 +171,83 @@ def landmark_step(red, xc, dtype=LD):
     return np.einsum("pab,pb->pa", Dinv, cl)
 
 
-def landmark_step_tol(red, xc, c=8.0):
-    """bound of the float64 back-substitution: c eps (k + kappa) |Dinv| (|b_l| + |W|^T |x_c|)"""
+def idp_edge_terms(p, lvl, robust_vis=True):
+    """per active inverse-depth edge (the landmark's position among the ACTIVE landmarks first): weight Wt = rho' w, residual e,
+    its forward bound ebar, J_rho, its forward bound Jbar, and the two pose Jacobians with their columns (-1: no column).
+
+    e = z - K pi(P_i) and J_rho = de/drho = (1 / rho) (J_pi R_cb R_i^T) (R_0 R_cb^T P_0), P_0 = (xbar, ybar, 1) / rho: a chain of four
+    nested three-term products that ends in a dot product A . y which cancels at low parallax (moving a landmark along its ray does not
+    move its pixel in a camera that looks along that ray).  Jbar is the same chain with every factor replaced by its absolute value,
+    i.e. the sum the rounding errors of the chain are relative to; ebar = |z| + |K pi| likewise for the residual's subtraction."""
+    fix = np.zeros(p.n_kf, np.uint8) if p.kf_fix is None else np.asarray(p.kf_fix, np.uint8)
+    pdim, nf = 15, p.n_kf_free
+    col = lambda kf: -1 if (kf >= nf or fix[kf] & 1) else pdim * int(kf)
+    R = [np.asarray(oracle_lib.quat_to_R(p.kf_pose[k, 3:7])).reshape(3, 3) for k in range(p.n_kf)]
+    Rcb = np.asarray(oracle_lib.quat_to_R(np.asarray(p.T_cb)[3:7])).reshape(3, 3)
+    K = np.asarray(p.K, np.float64)
+    beg = np.asarray(p.pt_obs_begin)
+    _, pt_act = active_sets(p, lvl)
+    pos = np.cumsum(pt_act) - 1
+    out = dict(lm=[], Wt=[], e=[], ebar=[], J=[], Jbar=[], Jref=[], Jobs=[], cref=[], cobs=[])
+    for q in np.flatnonzero(pt_act):
+        rf = int(p.pt_ref_kf[q])
+        rho = max(p.pt[q, 0], 1e-6)
+        P0 = np.array([p.pt[q, 1], p.pt[q, 2], 1.0]) / rho
+        ybar = np.abs(R[rf]) @ (np.abs(Rcb.T) @ np.abs(P0))
+        for o in range(beg[q], beg[q + 1]):
+            if lvl[o]:
+                continue
+            kf = int(p.obs_kf[o])
+            e, Pc, Jr, Jref, Jobs = oracle_lib.edge_idp(p.pt[q], p.kf_pose[rf], p.kf_pose[kf], p.T_cb, K, p.obs_uv[o])
+            iz = 1.0 / Pc[2]
+            Jpi = np.abs(np.array([[K[0] * iz, 0.0, K[0] * Pc[0] * iz * iz], [0.0, K[1] * iz, K[1] * Pc[1] * iz * iz]]))
+            w = float(p.obs_w[o])
+            if robust_vis:
+                w *= oracle_lib.huber(w * (e @ e), p.huber_vis)[1]
+            out["lm"].append(pos[q]); out["Wt"].append(w); out["e"].append(e); out["J"].append(Jr)
+            out["ebar"].append(np.abs(p.obs_uv[o]) + np.abs(p.obs_uv[o] - e))
+            out["Jbar"].append((Jpi @ np.abs(Rcb) @ np.abs(R[kf].T)) @ ybar / rho)
+            out["Jref"].append(Jref); out["Jobs"].append(Jobs); out["cref"].append(col(rf)); out["cobs"].append(col(kf))
+    n = len(out["lm"])
+    shapes = dict(lm=(n,), Wt=(n,), cref=(n,), cobs=(n,), Jref=(n, 2, 6), Jobs=(n, 2, 6))
+    return {k: np.asarray(v, np.int64 if k in ("lm", "cref", "cobs") else np.float64).reshape(shapes.get(k, (n, 2))) for k, v in out.items()}
+
+
+N_CHAIN = 12   # three-term products on the chain from the inputs to J_rho: R_cb^T P_0, R_0 ., R_cb R_i^T ., J_pi . (4 x 3 terms)
+
+
+def landmark_step_tol(red, xc, c=8.0, robust_vis=True):
+    """bound of the float64 back-substitution dl = Dinv (b_l - W^T x_c).
+
+    Accumulation, given exact W, Dinv and b_l:  c eps (k + kappa) |Dinv| (|b_l| + |W|^T |x_c|).
+
+    Inverse depth (one parameter per landmark) adds the forward error of what W, Dinv and b_l are made of.  With the landmark's active
+    edges i, weights w_i, residuals e_i and Jacobians a_i = J_rho,i (2-vectors), D = sum w a.a and
+        dl = -(1 / D) sum_i w_i a_i . (e_i + J_i x),      J_i x = J_ref,i x_ref + J_obs,i x_obs  (what the pose step does to e_i),
+    so  d(dl)/d(a_i) = -(w_i / D) ((e_i + J_i x) + 2 a_i dl)   and   d(dl)/d(e_i) = -(w_i / D) a_i.
+    a_i is known to |da_i| <= c eps N_CHAIN abar_i and e_i to |de_i| <= c eps ebar_i (idp_edge_terms: abar = (1 / rho) sum |A_k| |y_k|
+    with the absolute values carried through the chain).  First order, componentwise:
+        |d dl| <= (c eps / D) sum_i w_i [ N_CHAIN abar_i . (|e_i + J_i x| + 2 |a_i| |dl|) + |a_i| . ebar_i ].
+    At low parallax |a_i| << abar_i: with one or two edges per landmark nothing averages that out, and this term is the larger one
+    (tests/test_stage_ref.py::test_perturbed_reference_stays_inside_the_landmark_bound: inputs perturbed by one unit roundoff move
+    the float64 reference by up to 16 times the accumulation bound alone).  The constants are those of the other bounds (c, terms
+    per sum); nothing here is fitted to a kernel's error."""
     aW, aD = np.abs(red["W"].astype(np.float64)), np.abs(red["Dinv"].astype(np.float64))
-    t = np.abs(red["bl"].astype(np.float64)) + np.einsum("cpa,c->pa", aW, np.abs(np.asarray(xc, np.float64)))
-    return c * EPS * (red["k"] + red["kappa"]) * np.einsum("pab,pb->pa", aD, t)
+    x = np.asarray(xc, np.float64)
+    t = np.abs(red["bl"].astype(np.float64)) + np.einsum("cpa,c->pa", aW, np.abs(x))
+    tol = c * EPS * (red["k"] + red["kappa"]) * np.einsum("pab,pb->pa", aD, t)
+    if red["ldim"] == 1 and tol.size:
+        E = idp_edge_terms(red["p"], red["lvl"], robust_vis)
+        xz = np.concatenate([x, np.zeros(6)])   # a vertex without a column (-1) reads the zeros behind the step
+        at = lambda cols: xz[np.where(cols < 0, x.size, cols)[:, None] + np.arange(6)]
+        Jx = np.einsum("eij,ej->ei", E["Jref"], at(E["cref"])) + np.einsum("eij,ej->ei", E["Jobs"], at(E["cobs"]))
+        dl = np.abs(landmark_step(red, x, dtype=np.float64)[:, 0])
+        per_edge = E["Wt"] * ((N_CHAIN * E["Jbar"] * (np.abs(E["e"] + Jx) + 2 * np.abs(E["J"]) * dl[E["lm"], None])
+                               + np.abs(E["J"]) * E["ebar"]).sum(axis=1))
+        add = np.zeros(tol.shape[0])
+        np.add.at(add, E["lm"], per_edge)
+        tol[:, 0] += c * EPS * aD[:, 0, 0] * add
+    return tol
 
 
 def full_step(red, xc=None):
@@ -249,6 +324,43 @@ def ratio(err, tol):
         return 0.0
     q = np.divide(err, tol, out=np.where(err == 0, 0.0, np.inf), where=tol > 0)
     return float(q.max())
+
+
+PARTS = (("PR", 0, 6), ("V", 6, 9), ("Bias", 9, 15))
+
+
+def worst_blocks(dS, tS, layout, var_act=None, n=5):
+    """where S is wrong: the n worst (keyframe a, keyframe b, PR/V/Bias x PR/V/Bias) sub-blocks of dS = S - Sref (window order, as
+    compared: entries that were not compared are zero) in units of the bound tS, in the oracle's order (a >= b, one triangle: an
+    entry counts wherever the window's order put it).  Returns [(ratio, a, b, part_a, part_b, a_in, b_in)], worst first, blocks
+    within their bound left out; a_in / b_in tell whether that vertex is inside the index mapping (var_act; None: not known)."""
+    rows, _ = window_rows(layout)
+    pdim, nf = layout["pdim"], layout["n_free"]
+    E = np.abs(np.asarray(dS, np.float64))[np.ix_(rows, rows)]
+    T = np.asarray(tS, np.float64)[np.ix_(rows, rows)]
+    E, T = np.maximum(E, E.T), np.maximum(T, T.T)
+    parts = [pt for pt in PARTS if pt[2] <= pdim]
+    inside = lambda kf, lo: None if var_act is None else bool(var_act[pdim * kf + lo])
+    out = []
+    for a in range(nf):
+        for b in range(a + 1):
+            for na, la, ha in parts:
+                for nb_, lb, hb in parts:
+                    if a == b and lb > la:
+                        continue
+                    sl = (slice(pdim * a + la, pdim * a + ha), slice(pdim * b + lb, pdim * b + hb))
+                    q = ratio(E[sl], T[sl])
+                    if q > 1.0:
+                        out.append((q, a, b, na, nb_, inside(a, la), inside(b, lb)))
+    out.sort(key=lambda v: -v[0])
+    return out[:n]
+
+
+def format_blocks(blocks):
+    """one line per block of worst_blocks, for an assertion message"""
+    tag = {None: "", True: " (in)", False: " (outside the index mapping)"}
+    return "; ".join("kf %d %s%s x kf %d %s%s: %.3g x bound" % (a, pa, tag[ia], b, pb, tag[ib], q) for q, a, b, pa, pb, ia, ib in blocks) \
+        or "every block within its bound"
 
 
 def solve_tols(L, d, y, x, c=8.0):
