@@ -155,7 +155,7 @@ struct Staging {
     X(PAIRMASK) X(DBG) X(CU) X(KFFIX) X(TLKB) X(TLK) X(DVEC) X(WINV) X(SLOTPERM) X(PTPERM) X(LMASK) X(KFSEG) X(REFSEG) \
     X(ITEMMID) X(STKEY) X(LMORDER) X(SLOTOBS) X(PTINV) X(KEYSEG) X(TSLOT) X(ADJBEG) X(ADJ) X(PCGV) X(PCGM) X(KFDIR) X(MASKQ) \
     X(SLOTMASK) X(REFQ) X(PCGS) X(IMUJREC) X(ALIVE) X(SLOTO) X(SLOTREF) X(SLOTQ) X(RECQ) X(TSQ) X(RECCNT) X(RESULTS) X(PRUN0) \
-    X(PREFBEG) X(PREFLIST) X(CHAINTAB) X(LMSD)
+    X(PREFBEG) X(PREFLIST) X(CHAINTAB) X(LMSD) X(OBSUVK)
 #define VBA_BUF_ENUM(id) BUF_##id,
 enum { VBA_BUFFERS(VBA_BUF_ENUM) BUF_N };
 #undef VBA_BUF_ENUM

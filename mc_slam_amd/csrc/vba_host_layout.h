@@ -46,6 +46,9 @@ inline const char* check_window(const vba_problem* P, const vba_problem* first) 
     if (P->solver != VBA_SOLVER_LDLT && P->solver != VBA_SOLVER_PCG) return "unknown solver";
     if (P->its_stage1 > 30 || P->its_stage2 > 30 || P->its_stage1 < 0 || P->its_stage2 < 0) return "its out of range";
     if (P->protocol != VBA_PROTO_LOCAL && P->protocol != VBA_PROTO_SINGLE) return "unknown protocol";
+    // the diagonal Schur walk reaches a window's slot records through a 32-bit byte offset from the window's first one
+    if (P->variant == VBA_VARIANT_PRV_IDP && ((long long)P->n_obs + P->n_pt) * (VBA_SLOT * 8) >= (1ll << 32))
+        return "inverse-depth window with more than 2^32 bytes of slot records";
     return nullptr;
 }
 

@@ -220,6 +220,7 @@ int upload_alloc_copy(Handle* h, Upload& U) {
     if (dalloc(h, BUF_EREC, obs0 * (idp ? VBA_EREC1 : VBA_EREC) * 8) || dalloc(h, BUF_PREC, pt0 * VBA_PREC * 8)) return -1;
     if (dalloc(h, BUF_SLOT, (obs0 + pt0) * (idp ? VBA_SLOT : VBA_SLOT3) * 8)) return -1;
     if (dalloc(h, BUF_LMSD, idp ? pt0 * 16 : 16)) return -1;   // inverse depth: (sqrt(Dinv), beta) per landmark
+    if (dalloc(h, BUF_OBSUVK, idp ? obs0 * 16 : 16)) return -1;   // inverse depth: the pixels in record order, beside the edge records (k_st_rec_fill)
     if (dalloc(h, BUF_CHI2F, obs0 * 8)) return -1;
     if (h2d(h, BUF_IMUI, G.imui) || h2d(h, BUF_IMUJ, G.imuj) || h2d(h, BUF_IMUMEAS, G.meas) || h2d(h, BUF_IMUINFO, G.info)) return -1;
     if (dalloc(h, BUF_IMUH, imu0 * VBA_IMUH * 8) || dalloc(h, BUF_IMUCHI, imu0 * 4 * 8) || dalloc(h, BUF_IMUJREC, imu0 * IMU_JREC * 8)) return -1;
@@ -298,6 +299,7 @@ int bind_batch(Handle* h, int n, bool idp) {
     B.pt_ref = dp<int>(h, BUF_PTREF); B.pt_obs_begin = dp<int>(h, BUF_PTOBS);
     B.obs_kf = dp<int>(h, BUF_OBSKF); B.obs_pt = dp<int>(h, BUF_OBSPT);
     B.obs_uv = dp<double>(h, BUF_OBSUV); B.obs_w = dp<double>(h, BUF_OBSW);
+    B.obs_uvk = idp ? dp<double>(h, BUF_OBSUVK) : nullptr;
     B.lvl = dp<unsigned char>(h, BUF_LVL); B.chi2_e = dp<double>(h, BUF_CHI2E); B.depth_e = dp<double>(h, BUF_DEPTH);
     B.chi2_f = idp ? nullptr : dp<double>(h, BUF_CHI2F);
     B.erec = dp<double>(h, BUF_EREC); B.prec = dp<double>(h, BUF_PREC); B.slot = dp<double>(h, BUF_SLOT); B.lm_sd = dp<double2>(h, BUF_LMSD); B.kf_fix = dp<unsigned char>(h, BUF_KFFIX);
@@ -351,6 +353,7 @@ int enqueue_structure_build(Handle* h, const Upload& U) {
     T.smw = g.max_mwords;
     T.row_lds = h->up.row_lds;
     T.slot_o = dp<int>(h, BUF_SLOTO);
+    T.obs_uvk = const_cast<double*>(B.obs_uvk);
     T.slot_ref = dp<int>(h, BUF_SLOTREF); T.slot_q = dp<int>(h, BUF_SLOTQ); T.rec_q = dp<int>(h, BUF_RECQ); T.tsq = dp<int>(h, BUF_TSQ);
     VBA_LAUNCH(k_st_hist, dim3(n), dim3(h->up.hist_block), sh_order, h->up_stream, B, T);
     {

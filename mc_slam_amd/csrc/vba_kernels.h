@@ -22,6 +22,7 @@ struct Batch {
     // observations (CSR by point)
     const int *obs_kf, *obs_pt;
     const double *obs_uv, *obs_w;
+    const double* obs_uvk;        // [n_obs][2] inverse depth: obs_uv in RECORD order (slot_perm), beside the edge records (k_st_rec_fill)
     unsigned char* lvl;
     double *chi2_e, *depth_e, *chi2_f;  // chi2_f: chi2 recomputed at the final estimates (LM: chi2_e may be stale)
     double *erec, *prec, *slot;
@@ -84,7 +85,7 @@ struct Batch {
 #define LIN_ERR 1
 // (2: LIN_ERR_TRIAL of the Levenberg-Marquardt schedule, vba_kernels_lm.h)
 // Gauss-Newton, inverse-depth variant, probing on (vba_host::plan_lin_probe).  The pass in which a window stops by |dchi2| < 1e-3
-// is read for its chi2 alone: its Jacobians, its 96 B of records per edge and its IMU Hessians are never used.  So after an
+// is read for its chi2 alone: its Jacobians, its 80 B of records per edge and its IMU Hessians are never used.  So after an
 // iteration whose chi2 decrease was below LIN_PROBE_DCHI2 the window's next pass is a PROBE -- the LIN_ERR path, the same chi2
 // from the same instructions, no stores -- and only if the window then goes on is the full pass run, before the solve:
 //   LIN_AUTO  a window with WinCtrl::lin_probe takes LIN_ERR, every other one LIN_FULL
@@ -566,11 +567,22 @@ DEVI void idp_edge_pc(const WinDesc& d, const double* Xw, const double* Ri, cons
     mv3(d.Rcb, ta, Pc);
     Pc[0] += d.tcb[0]; Pc[1] += d.tcb[1]; Pc[2] += d.tcb[2];
 }
-DEVI double idp_edge_chi2(const WinDesc& d, const double (&Pc)[3], double u, double v, double wgt, double& iz, double& ex, double& ey) {
+DEVI void idp_edge_err(const WinDesc& d, const double (&Pc)[3], double u, double v, double& iz, double& ex, double& ey) {
     iz = 1.0 / Pc[2];
     ex = u - (Pc[0] * iz * d.K[0] + d.K[2]);
     ey = v - (Pc[1] * iz * d.K[1] + d.K[3]);
+}
+DEVI double idp_edge_chi2(const WinDesc& d, const double (&Pc)[3], double u, double v, double wgt, double& iz, double& ex, double& ey) {
+    idp_edge_err(d, Pc, u, v, iz, ex, ey);
     return ex * (wgt * ex) + ey * (wgt * ey);
+}
+// The weighted residual sc r of an edge, sc = sqrt(rho' w).  The linearisation (lin2_body, phase B) sums it into b_l and the reference
+// keyframe's g0; the diagonal Schur walk forms it AGAIN from the edge record (P_c, sc) and the pixel for b_p = -sum Bi^T r, instead of
+// reading a copy the linearisation used to store per edge and pass.  Both call this one function: the same expression, the same bits.
+DEVI void idp_edge_wres(const WinDesc& d, const double (&Pc)[3], double u, double v, double sc, double& r0, double& r1) {
+    double iz, ex, ey;
+    idp_edge_err(d, Pc, u, v, iz, ex, ey);
+    r0 = sc * ex; r1 = sc * ey;
 }
 // chi2 and depth of edge go at the current estimates (the classification passes)
 DEVI void idp_edge_eval(const Batch& B, const WinDesc& d, size_t go, double& s, double& depth) {
@@ -707,7 +719,7 @@ DEVI void lin2_body(const Batch& B, int nblk_lin, int mode, double* lsm) {
                 }
 #pragma unroll
                 for (int i = 0; i < 6; i++) ub[i] = Bi[i] * a[0] + Bi[6 + i] * a[1];
-                r2[0] = sc * ex; r2[1] = sc * ey;
+                idp_edge_wres(d, Pc, e_u, e_v, sc, r2[0], r2[1]);
             }
         }
         if (mode == LIN_FULL) {
@@ -819,8 +831,9 @@ DEVI void lin2_body(const Batch& B, int nblk_lin, int mode, double* lsm) {
         if (t == 0) { RS[a_nruns] = npb; RS[65] = a_nruns; }
     }
     __syncthreads();
-    // D. one lane per edge: its 48-B slot record U = Bi^T a / sqrt(D) and its 48-B edge record (P_c, scale, weighted residual),
-    //    from which the Schur kernels rebuild Bi, g = -Bi^T r and Br = [-A | A N0].  Records live keyframe-major (slot_perm).
+    // D. one lane per edge: its 48-B slot record U = Bi^T a / sqrt(D) and its 32-B edge record (P_c, scale), from which the Schur
+    //    kernels rebuild Bi and Br = [-A | A N0], and with the pixel (obs_uvk) the weighted residual of g = -Bi^T r (idp_edge_wres:
+    //    r2 stays here, it went into b_l and g0 through LDS).  Records live keyframe-major (slot_perm).
     if (t < ne) {
         const double sD = PT[pl * LIN2_PS + 17];
         const int pe = e_pe;
@@ -830,7 +843,6 @@ DEVI void lin2_body(const Batch& B, int nblk_lin, int mode, double* lsm) {
         double2* dst = reinterpret_cast<double2*>(B.erec + VBA_EREC1 * (size_t)(d.obs0 + pe));
         dst[0] = make_double2(rpc[0], rpc[1]);
         dst[1] = make_double2(rpc[2], rsc);
-        dst[2] = make_double2(r2[0], r2[1]);
     }
     // E. the reference-keyframe terms, one record per run: value v of run r is the sum over the run's landmarks, in order
     {
@@ -1123,11 +1135,11 @@ DEVI void schur_write_block(const Batch& B, const WinDesc& d, const WinCtrl& c, 
 // instead of 6 per pair, and every lane sees ~6 items instead of ~1.4).
 // LD = landmark dimension (1: inverse depth, slot record 6 doubles; 3: XYZ, slot record 24 doubles)
 // LP = lanes per pair: 64 (one pair per wave: small batches, latency) or 16 (four pairs per wave: throughput)
-// Bi = [A | B_rot] of an EdgePRIDP from its 48-B record (P_c, s = sqrt(rho' w), r) and the observer's rotation R_a:
-// J_c = J_pi(P_c) R_cb, A = s J_c R_a^T, B_rot = -s J_c x t_a with t_a = R_cb^T (P_c - t_cb)   (k_lin2 phase B, g2otypes.cpp:139-145)
-DEVI void rebuild_edge(const WinDesc& d, const double* Ra, const double* rec, double* b0, double* b1, double& r0, double& r1) {
+// Bi = [A | B_rot] of an EdgePRIDP from its 32-B record (P_c, s = sqrt(rho' w)) and the observer's rotation R_a:
+// J_c = J_pi(P_c) R_cb, A = s J_c R_a^T, B_rot = -s J_c x t_a with t_a = R_cb^T (P_c - t_cb)   (k_lin2 phase B, g2otypes.cpp:139-145).
+// All the reference items of the off-diagonal pairs need; the diagonal walk adds the weighted residual (rebuild_edge_res).
+DEVI void rebuild_edge(const WinDesc& d, const double* Ra, const double (&rec)[VBA_EREC1], double* b0, double* b1) {
     const double Pc[3] = {rec[0], rec[1], rec[2]}, sc = rec[3];
-    r0 = rec[4]; r1 = rec[5];
     const double fx = d.K[0], fy = d.K[1];
     const double iz = 1.0 / Pc[2];
     const double Jp[6] = {fx * iz, 0.0, -Pc[0] * iz * fx * iz, 0.0, fy * iz, -Pc[1] * iz * fy * iz};
@@ -1151,6 +1163,20 @@ DEVI void rebuild_edge(const WinDesc& d, const double* Ra, const double* rec, do
         bb[4] = -sc * (j2 * ta[0] - j0 * ta[2]);
         bb[5] = -sc * (j0 * ta[1] - j1 * ta[0]);
     }
+}
+// The weighted residual s r the linearisation formed for this record (idp_edge_wres, the same function), from the record and the
+// pixel of its observation.  The record used to carry it; what it held where s = 0 was
+//   an outlier edge (level != 0):  r = 0.  The select gives 0 again.
+//   a fixed observer:              s r of the edge, not 0.  But there Bi = s (...) is +-0 in every entry, so its term of
+//                                  b_p = -(b0 r0 + b1 r1) was +-0 with that r and is +-0 with r = 0, and a sum that starts at +0
+//                                  is left unchanged, bit for bit, by adding either zero.
+// A select, not a product with s: where s = 0 nothing vouches for P_c (an outlier behind the camera, z = 0), and 0 * inf is a NaN.
+DEVI void rebuild_edge_res(const WinDesc& d, const double (&rec)[VBA_EREC1], double u, double v, double& r0, double& r1) {
+    const double Pc[3] = {rec[0], rec[1], rec[2]}, sc = rec[3];
+    double w0, w1;
+    idp_edge_wres(d, Pc, u, v, sc, w0, w1);
+    r0 = (sc != 0.0) ? w0 : 0.0;
+    r1 = (sc != 0.0) ? w1 : 0.0;
 }
 
 #ifndef VBA_SCHUR_UNR
@@ -1279,11 +1305,10 @@ DEVI void schur_off_body(const Batch& B, int max_quads, double* blk4, int w_in =
             const double* re = B.erec + VBA_EREC1 * (size_t)(d.obs0 + (a_ref ? sb : sa));
             const double rho = B.pt[3 * gp], xb = B.pt[3 * gp + 1], yb = B.pt[3 * gp + 2];
             const double* Ro = B.kfR + 12 * (size_t)(d.kf0 + (a_ref ? b : a));  // the observer's rotation
-            double rec[6], bi0[6], bi1[6], br0[6], br1[6], rr0, rr1;
+            double rec[VBA_EREC1], bi0[6], bi1[6], br0[6], br1[6];
 #pragma unroll
-            for (int i = 0; i < 4; i++) rec[i] = re[i];
-            rec[4] = rec[5] = 0.0;
-            rebuild_edge(d, Ro, rec, bi0, bi1, rr0, rr1);   // (the rotation is read where it is used: nine registers fewer in flight)
+            for (int i = 0; i < VBA_EREC1; i++) rec[i] = re[i];   // (one aligned 32-byte record)
+            rebuild_edge(d, Ro, rec, bi0, bi1);   // (the rotation is read where it is used: nine registers fewer in flight)
             {   // N0 = R0 hat(b0) of the landmark in its reference keyframe, as the linearisation forms it (lin2_body, phase A): the
                 // landmark has not moved since (the update comes after the solve).  Br = [-A | A N0], both rows, then N0 is dead.
                 const double* C0 = B.kfR + 12 * (size_t)(d.kf0 + (a_ref ? a : b));
@@ -1401,6 +1426,12 @@ DEVI void schur_diag_body(const Batch& B, int max_free, int hd_pass, double* blk
     auto item_index = [&](int it) {
         return (it < n_o) ? B.slot_lm[(unsigned)(o_s + it)] : (it < o_n) ? B.rec_lm[(unsigned)(o_r + it)] : run_list[(unsigned)(it - o_n)];
     };
+    // likewise the records (inverse depth): the slot records from the window's first one, the keyframe's edge records and the pixels
+    // beside them (item `it` < n_o sits at record o_s + it) from the start of the keyframe's segment -- a scalar base + the lane's BYTE
+    // offset, formed in 32 bits (check_window refuses a window whose slot records pass 2^32 bytes; the other two are smaller).  With
+    // 64-bit lane addresses for the three the walk does not fit the register budget of the fused kernels
+    const char* e_base = (LD == 1) ? reinterpret_cast<const char*>(B.erec + VBA_EREC1 * (size_t)o_s) : nullptr;
+    const char* u_base = (LD == 1) ? reinterpret_cast<const char*>(B.obs_uvk + 2 * (size_t)o_s) : nullptr;
     int nxt_idx = 0;
     if (LD == 1 && t < n_items) nxt_idx = item_index(t);
     for (int it = t; it < n_items; it += 64) {
@@ -1420,7 +1451,8 @@ DEVI void schur_diag_body(const Batch& B, int max_free, int hd_pass, double* blk
         // that opens an outer iteration (hd_pass) takes them from the edge records ONCE and parks them per keyframe (kf_dir);
         // the trials then read the slot records U(lambda) only -- 192 B instead of 384 B per record and trial
         const bool want_u = (LD == 1) || !hd_pass, want_dir = (LD == 1) || hd_pass;
-        const double* qa = slots + SS * (size_t)sa;
+        const double* qa = (LD == 1) ? reinterpret_cast<const double*>(reinterpret_cast<const char*>(slots) + (unsigned)sa * (unsigned)(SS * 8))
+                                     : slots + SS * (size_t)sa;
         double UA[6 * LD], UB[6 * LD], beta[LD];   // XYZ: UA = W_a Sigma, UB = W_a, beta = t = Sigma b_l; inverse depth: UA = UB = U, beta
 #pragma unroll
         for (int i = 0; i < 6 * LD; i++) UB[i] = want_u ? qa[i] : 0.0;
@@ -1448,14 +1480,18 @@ DEVI void schur_diag_body(const Batch& B, int max_free, int hd_pass, double* blk
         } else if (LD == 1 && sa >= d.n_obs) {
             // (a landmark record of this keyframe: its direct terms come summed over runs of landmarks, below)
         } else {
-            const double* ra = B.erec + ((LD == 1) ? VBA_EREC1 : VBA_EREC) * (size_t)(d.obs0 + sa);
+            const double* ra = (LD == 1) ? reinterpret_cast<const double*>(e_base + (unsigned)it * (unsigned)(VBA_EREC1 * 8))
+                                         : B.erec + VBA_EREC * (size_t)(d.obs0 + sa);
             double r0 = 0.0, r1 = 0.0;
             double b0[6], b1[6];
             if (LD == 1) {
-                double rec[6];
+                // slot record, 32-B edge record and pixel all sit at record position sa = s0 + it: three contiguous reads across the wave
+                double rec[VBA_EREC1];
 #pragma unroll
-                for (int i = 0; i < 6; i++) rec[i] = ra[i];
-                rebuild_edge(d, Ra, rec, b0, b1, r0, r1);
+                for (int i = 0; i < VBA_EREC1; i++) rec[i] = ra[i];
+                const double2 uv = *reinterpret_cast<const double2*>(u_base + (unsigned)it * 16u);
+                rebuild_edge_res(d, rec, uv.x, uv.y, r0, r1);
+                rebuild_edge(d, Ra, rec, b0, b1);
             } else {
 #pragma unroll
                 for (int i = 0; i < 6; i++) { b0[i] = ra[i]; b1[i] = ra[6 + i]; }   // XYZ edge record: Bi (12), g (6)

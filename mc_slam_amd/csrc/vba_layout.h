@@ -7,14 +7,16 @@
 
 #define VBA_NB 32          // block size of the dense reduced-system factorisation
 #define VBA_EREC 18        // doubles per edge record, XYZ variants (144 B): Bi (2x6), g = -Bi^T r
-#define VBA_EREC1 6        // doubles per edge record, inverse-depth variant (48 B): P_c (3), sqrt(rho' w) (1), r (2); the
-                           // readers rebuild Bi = [A | B_rot] from it and the observer's rotation (rebuild_edge)
+#define VBA_EREC1 4        // doubles per edge record, inverse-depth variant (32 B): P_c (3), sqrt(rho' w) (1); the readers
+                           // rebuild Bi = [A | B_rot] from it and the observer's rotation (rebuild_edge), the diagonal walk also
+                           // the weighted residual from the observation's pixel (obs_uvk, idp_edge_wres)
 #define VBA_PREC 32        // doubles per point record  (256 B)
 #define VBA_SLOT 6         // doubles per slot record   (48 B), inverse-depth landmarks: U only
 #define VBA_SLOT3 18       // doubles per slot record, XYZ landmarks (144 B): W = Bi^T A (6x3), independent of the damping
 #define VBA_IMUH 960       // doubles per IMU edge pair: 30x30 local Hessian + 30 rhs (+ pad)
 #define VBA_TRACE 64
-// the inverse-depth records are written and read in 16-byte pieces (three per record): every piece stays aligned at any record index
+// the inverse-depth records are written and read in 16-byte pieces (three per slot record, two per edge record): every piece stays
+// aligned at any record index
 static_assert((VBA_SLOT * 8) % 16 == 0 && (VBA_EREC1 * 8) % 16 == 0, "inverse-depth slot and edge records: a multiple of 16 bytes");
 
 // Linearisation products kept in HBM between k_lin2 and its consumers (variant 2, EdgePRIDP).  A "slot" is one
@@ -23,9 +25,12 @@ static_assert((VBA_SLOT * 8) % 16 == 0 && (VBA_EREC1 * 8) % 16 == 0, "inverse-de
 //   slot record      [0..5] U = W * sqrt(Dinv)  (W = H_pl block, 6x1): edge slots and landmark reference records alike
 //   landmark scalars [0] sqrt(Dinv)  [1] beta = sqrt(Dinv) * b_l: one pair per landmark, at the CALLER's landmark index (lm_sd)
 //                    -> Schur term of a keyframe pair is -U_a U_b^T, reduced rhs term -U_a beta, x_l = sD (beta - sum U.x_p)
-//   edge record      [0..2] P_c  [3] s = sqrt(rho' w), 0 if the observer's pose is fixed  [4..5] s r: Bi (2x6, d/d observing
-//                    KF PR, g2otypes.cpp:139-145), g = -Bi^T r and Br = [-A | A N0] (d/d reference KF PR, :128-134) are
-//                    rebuilt from it by the readers (rebuild_edge)
+//   edge record      [0..2] P_c  [3] s = sqrt(rho' w), 0 if the observer's pose is fixed: Bi (2x6, d/d observing KF PR,
+//                    g2otypes.cpp:139-145) and Br = [-A | A N0] (d/d reference KF PR, :128-134) are rebuilt from it by the
+//                    readers (rebuild_edge).  The weighted residual s r of g = -Bi^T r is not stored: its one reader, the
+//                    diagonal walk, forms it from P_c, s and the pixel (u, v) of the record's observation
+//   pixel copy       [0..1] (u, v) of the observation behind every edge record, at the record's position (obs_uvk): written
+//                    once per upload by the structure build, so the diagonal walk reads it in sequence beside the two records
 //   point record     one per RUN of consecutive landmarks with one reference keyframe:
 //                    [0..20] G0 = sum Br^T Br (upper 6x6 packed)  [21..26] g0 = -sum Br^T r
 struct WinDesc {

@@ -27,6 +27,7 @@ struct StBuild {   // what the build writes (the solve reads the same arrays thr
                                                   // walks read them in sequence instead of gathering them through an index
     int *ref_q;                                   // scratch: reference keyframe of the landmark at rank q
     int *slot_o;                                  // observation of the record in slot s (k_stage_mark walks a keyframe's edges through it)
+    double *obs_uvk;                              // inverse depth: the pixel of that observation, [slot][2] (null: XYZ windows keep none)
     int *rec_cnt;                                 // scratch: per chunk of 64 landmarks (lm_order) and keyframe the observed / referenced counts, then their prefix
     int *slot_ref, *slot_q, *rec_q, *tsq;         // scratch, so that the pair-row walk gathers nothing through a landmark index: reference
                                                   // keyframe and lm_order rank of the landmark in slot s, rank of the landmark in record r,
@@ -282,6 +283,10 @@ __global__ void __launch_bounds__(64) k_st_rec_fill(Batch B, StBuild T, int max_
                 T.slot_perm[d.obs0 + o] = slot;
                 T.slot_obs[d.obs0 + slot] = L.p;   // the landmark of the record in this slot
                 T.slot_o[d.obs0 + slot] = o;
+                // the pixel beside the edge record the linearisation will write at this position (the diagonal Schur walk rebuilds the
+                // weighted residual from the two).  obs_uv is resident here: every upload path copies it on this stream, ahead of the build
+                if (T.obs_uvk)
+                    reinterpret_cast<double2*>(T.obs_uvk)[d.obs0 + slot] = reinterpret_cast<const double2*>(B.obs_uv)[d.obs0 + o];
                 T.slot_q[d.obs0 + slot] = L.q;
                 T.slot_ref[d.obs0 + slot] = L.ref;
                 for (int v = 0; v < mw; v++) T.slot_mask[(size_t)(d.obs0 + slot) * T.smw + v] = M[v];
