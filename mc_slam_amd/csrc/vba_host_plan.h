@@ -113,7 +113,7 @@ enum { CAP_FACTOR_STEP1 = 1, CAP_FACTOR_STEP4 = 4, CAP_FACTOR_STEP4_ONE = 5, CAP
 enum { CAP_TRSV_P, CAP_TRSV };
 enum { LIN_IMU_FUSED, LIN_IMU_PAIR, LIN_IMU_RES_HESS };   // k_lin2_imu / k_lin_imu_pair / k_lin_imu_res + k_lin_imu_hess
 
-// Grids whose workgroups schur_map() (vba_kernels.h) deals to the 8 XCDs by window: the windows of a group, rounded up to 8.
+// Grids whose workgroups schur_map() (vba_schur.h) deals to the 8 XCDs by window: the windows of a group, rounded up to 8.
 // Three places must agree on the 8: this function, schur_map's `B.n_win >= 8` test on the GROUP's window count, and plan_run's
 // rule that a group never holds fewer than 8 windows unless it is the whole batch.
 inline int xcd_windows(int n) { return (n >= 8) ? 8 * ((n + 7) / 8) : n; }
@@ -176,7 +176,7 @@ struct RunPlan {
     int word_report = 0;     // one Gauss-Newton window: k_ctrl_gn reports through the pinned word, no event per iteration
     int lin_probe = 0;       // plan_lin_probe (Batch::lin_probe; not one of the plan_ints)
 };
-// The chi2-only probe of a linearisation pass that is expected to stop its window (vba_kernels.h, LIN_AUTO / LIN_REDO): 0 off,
+// The chi2-only probe of a linearisation pass that is expected to stop its window (vba_batch.h, LIN_AUTO / LIN_REDO): 0 off,
 // 1 on, 2 on for every pass that may be one (the hook only: the tests' way to reach every path).  Gauss-Newton over inverse-depth
 // windows only -- the Levenberg-Marquardt schedule and the XYZ kernels have no such pass.  By default from 64 windows on, where
 // the IMU factors have launches of their own (plan_run: imu_lin): below that a pass is launch latency, and the redo launches

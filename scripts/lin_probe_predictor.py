@@ -1,4 +1,4 @@
-"""How often the chi2-only probe of a linearisation pass (LIN_AUTO / LIN_REDO, mc_slam_amd/csrc/vba_kernels.h) is right, on the 256
+"""How often the chi2-only probe of a linearisation pass (LIN_AUTO / LIN_REDO, mc_slam_amd/csrc/vba_batch.h) is right, on the 256
 distinct windows of bench.py's C3 workload (synth.config_c3_ragged, seeds 100..355, caller landmark order, three kinds).
 
 CPU only by default: every window is solved by the oracle, and the rule of k_ctrl_gn -- pass p of a stage is a probe when p >= 2, it

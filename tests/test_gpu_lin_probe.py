@@ -1,4 +1,4 @@
-"""The chi2-only probe of a linearisation pass (LIN_AUTO / LIN_REDO, mc_slam_amd/csrc/vba_kernels.h; plan_lin_probe): a Gauss-Newton
+"""The chi2-only probe of a linearisation pass (LIN_AUTO / LIN_REDO, mc_slam_amd/csrc/vba_batch.h; plan_lin_probe): a Gauss-Newton
 window whose last chi2 decrease was below 10 evaluates chi2 only in its next pass, and gets the full pass behind the control launch
 if it goes on all the same.  The chi2 of a probe comes from the instructions of the full pass and the redone pass rewrites the same
 partial sums, so every output is BIT FOR BIT what it is without the probe: that is what these tests assert, for the three settings

@@ -1,5 +1,5 @@
 """vba_host::plan_lin_probe (mc_slam_amd/csrc/vba_host_plan.h): whether a run probes linearisation passes with a chi2-only pass
-(LIN_AUTO / LIN_REDO, vba_kernels.h), under AddressSanitizer + UBSan (CPU only; harness: tests/host_lin_probe_check.cpp).  Every
+(LIN_AUTO / LIN_REDO, vba_batch.h), under AddressSanitizer + UBSan (CPU only; harness: tests/host_lin_probe_check.cpp).  Every
 expected value is restated from the rule: on for Gauss-Newton over inverse-depth windows, by default from 64 windows on (where the
 IMU factors have launches of their own); the hook vba_debug_set_path(h, "lin_probe", v) -- 0 off, 1 on, 2 every pass -- overrides
 the size rule and never the variant or the algorithm."""
