@@ -1011,6 +1011,97 @@ typedef struct vba_search_bow_result {
  * or an angle outside [0, 360).  A pair's outputs do not depend on where it stands in the batch. */
 int vba_search_by_bow(void *handle, int32_t n_pairs, vba_search_bow_problem *const *in, vba_search_bow_result *const *out);
 
+/* ---- matching for the monocular initialisation ----
+ * ORBmatcher::SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize) (src/ORBmatcher.cpp:477-595), which
+ * Tracking::MonocularInitialization calls on every frame until a map exists (src/Tracking.cpp:1371-1373), directly in front of
+ * Initializer::Initialize (vba_two_view_init).  One problem is one frame pair; one call takes any number of pairs, ragged, in one
+ * kernel launch (one 256-lane workgroup per pair).  The reference is restated as it stands:
+ *   level gate  every keypoint i1 of frame 1, in index order, leaves when its octave is > 0 (:495)
+ *   area        F2.GetFeaturesInArea(vbPrevMatched[i1].x, .y, windowSize, 0, 0) (src/Frame.cpp:562-620): both level arguments are 0, so
+ *               bCheckLevels is true and the level test runs INSIDE the cell loop, in front of the pixel test: a candidate has octave
+ *               0, and an area that holds only other levels is empty (:501).  Floor for the first cell and CEIL for the last one, the
+ *               four early returns, the clamps, fabs(dx) < r && fabs(dy) < r; candidates in cell order (ix outer, iy inner) and inside
+ *               a cell in list order
+ *   candidates  `if (vMatchedDistance[i2] <= dist) continue;` comes first (:518): a skipped candidate counts for neither distance.
+ *               Then dist < bestDist (strict) moves the best to the second and replaces the best, else dist < bestDist2 replaces the
+ *               second (:521-530).  bestDist, bestDist2 and vMatchedDistance start at INT_MAX, not at 256
+ *   threshold   bestDist <= th_low (:534)
+ *   ratio       bestDist < (float)bestDist2 * nn_ratio in float32 (:536); with one surviving candidate the right-hand side is
+ *               (float)INT_MAX * nn_ratio, and it is evaluated so although best_dist2 REPORTS "none" as 256
+ *   match       if vnMatches21[bestIdx2] >= 0 that earlier query loses its match (vnMatches12[..] = -1, nmatches--); then
+ *               vnMatches12[i1], vnMatches21[bestIdx2] and vMatchedDistance[bestIdx2] = bestDist are set and nmatches++ (:538-546)
+ *   orientation rot = angle1 - angle2; if (rot < 0) rot += 360.0f; bin = round(rot * (1.0f / 30)) in float32 with C round (:550-555);
+ *               rotHist[bin] receives i1 and KEEPS it when the match is stolen later, so stolen matches count in ComputeThreeMaxima
+ *               (:570); the drop clears and decrements only where vnMatches12[idx1] >= 0 (:579-582) and leaves vnMatches21 alone
+ *   positions   vbPrevMatched[i1] = F2.mvKeysUn[vnMatches12[i1]].pt for every match kept (:590-592)
+ * The queries of a pair are not independent: query q reads vMatchedDistance[k] as the queries before it left it, which is
+ * min { bestDist_p : p < q, p accepted, bestIdx_p = k } (INT_MAX for the empty set), and a later query can take a keypoint away from an
+ * earlier one.  The kernel keeps per keypoint of frame 2 the list of its current claimers and runs the order-preserving conflict
+ * pass of the other ordered matchers over it: rounds of (every open query walks against the lists of the round before; the lists
+ * are rebuilt) until a round changes no claim.  Any fixed point is the sequential answer, and `rounds`, the detecting round
+ * included, is at most (level-0 keypoints of frame 1) + 1 (has the proof).
+ * `state` says where a keypoint of frame 1 left the function, numbered in the order of the reference's exits:
+ *   0  matched and kept
+ *   1  octave > 0 (:495)
+ *   2  area empty (:501)
+ *   3  bestDist > th_low (:534), every candidate skipped included
+ *   4  ratio test failed (:536)
+ *   5  matched, then replaced by a later query (:538-541); this wins over 6
+ *   6  matched, then dropped by the orientation filter (:579-582)
+ * Every decision is an integer one but the area: it is FP64 on the float32 inputs widened, the reference computes it in float32.
+ * float32 appears in the ratio product and in the bin only.  Stereo is out of scope. */
+#define VBA_SEARCH_INIT_MAX_KEYS 16384  /* the claimer lists of frame 2 live in LDS */
+typedef struct vba_search_init_problem {
+    int32_t check_orientation;       /* mbCheckOrientation (:548, :564) */
+    int32_t th_low;                  /* TH_LOW = 50 (:534); 0 .. 255 */
+    float nn_ratio;                  /* mfNNratio: 0.9f at src/Tracking.cpp:1371 */
+    double window_size;              /* windowSize: 100 at src/Tracking.cpp:1372; finite, a negative value is legal and matches nothing */
+    int32_t n_keys1;                 /* F1.mvKeysUn.size() */
+    const uint8_t *desc1;            /* [n_keys1][32] the rows of F1.mDescriptors (:504) */
+    const uint8_t *oct1;             /* [n_keys1] F1.mvKeysUn[i1].octave (:494) */
+    const float *angle1;             /* [n_keys1] F1.mvKeysUn[i1].angle in [0, 360) (:550); read with check_orientation only */
+    const float *prev_matched;       /* [n_keys1][2] vbPrevMatched as the caller holds it (:498); finite */
+    int32_t n_keys2;                 /* F2.mvKeysUn.size(); at most VBA_SEARCH_INIT_MAX_KEYS */
+    const uint8_t *desc2;            /* [n_keys2][32] the rows of F2.mDescriptors (:514) */
+    const double *uv2;               /* [n_keys2][2] F2.mvKeysUn[i2].pt */
+    const uint8_t *oct2;             /* [n_keys2] F2.mvKeysUn[i2].octave (src/Frame.cpp:602) */
+    const float *angle2;             /* [n_keys2] F2.mvKeysUn[i2].angle in [0, 360) (:550); read with check_orientation only */
+    double bounds[4];                /* mnMinX mnMaxX mnMinY mnMaxY of frame 2 */
+    int32_t grid_cols, grid_rows;    /* frame 2's grid; >= 1, cols * rows <= 65536 */
+    double grid_inv_w, grid_inv_h;   /* mfGridElementWidthInv, mfGridElementHeightInv */
+    const int32_t *cell_begin;       /* [cols * rows + 1] as in vba_fuse_problem */
+    const int32_t *cell_feat;        /* keypoint indices in the order the grid's cells hold them; each keypoint at most once */
+} vba_search_init_problem;
+
+typedef struct vba_search_init_result {
+    int32_t status;           /* VBA_OK */
+    int32_t n_matches;        /* the return value (:594) */
+    int32_t n_before_filter;  /* nmatches in front of the orientation filter (:564), net of steals; n_matches without one */
+    int32_t n_stolen;         /* how often :538-541 took a match back */
+    int32_t hist[30];         /* rotHist[i].size() in front of the filter, stolen entries counted (zeros without check_orientation) */
+    int32_t ind[3];           /* ind1 .. ind3 of ComputeThreeMaxima, -1 as the reference leaves them (and without check_orientation) */
+    int32_t rounds;           /* rounds of the conflict pass, 1 .. (level-0 keypoints of frame 1) + 1 */
+    int32_t *match12;         /* [n_keys1] caller-allocated: vnMatches12 as the function leaves it */
+    int32_t *best_idx;        /* [n_keys1] caller-allocated: bestIdx2 as the candidate loop left it, -1 if none (and in the states 1, 2) */
+    uint16_t *best_dist;      /* [n_keys1] caller-allocated: bestDist; 256 = none */
+    uint16_t *best_dist2;     /* [n_keys1] caller-allocated: bestDist2; 256 = none */
+    uint8_t *bin;             /* [n_keys1] caller-allocated: the histogram bin of a match (states 0, 5 and 6) with check_orientation; 255 = none */
+    uint8_t *state;           /* [n_keys1] caller-allocated: the codes above */
+    float *prev_matched;      /* [n_keys1][2] caller-allocated: a copy of the problem's prev_matched with :590-592 applied */
+    int32_t *match21;         /* [n_keys2] caller-allocated: vnMatches21 as the function leaves it; the filter does not clear it */
+    uint16_t *matched_dist;   /* [n_keys2] caller-allocated: vMatchedDistance as the function leaves it; 256 = none */
+} vba_search_init_result;
+
+/* Synchronous, like vba_search_by_bow; -1 while asynchronous tickets are pending.  n_pairs == 0 returns 0; a pair with n_keys1 == 0
+ * or n_keys2 == 0 is legal (n_matches = 0, rounds = 1).  A bad pair fails the whole call before any GPU work, with nothing written,
+ * as "vba_search_for_initialization: pair K: <why>" through vba_last_error: a NULL problem or result, a negative count, n_keys2 above
+ * VBA_SEARCH_INIT_MAX_KEYS, th_low outside 0 .. 255, a non-finite nn_ratio or window_size, grid sizes outside their range, a NULL
+ * array with a non-zero count (every per-keypoint result array of a side is required when the side has keypoints; the angles only
+ * with check_orientation), a non-finite bound, cell size, pixel or prev_matched entry, with check_orientation an angle outside
+ * [0, 360), a cell_begin that does not start at 0, decreases or ends above n_keys2, a cell_feat entry out of range or listed twice.
+ * A pair's outputs do not depend on where it stands in the batch. */
+int vba_search_for_initialization(void *handle, int32_t n_pairs, vba_search_init_problem *const *in, vba_search_init_result *const *out);
+
 /* ---- essential-graph optimisation (Sim3 pose graph) ----
  * Optimizer::OptimizeEssentialGraph(Map*, KeyFrame* pLoopKF, KeyFrame* pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections,
  * bFixScale, LoopClosing*)   src/Optimizer.cpp:4243-4552

@@ -1728,6 +1728,146 @@ class SearchBowResultBuf:
                                self.m21[:self.n2].copy())
 
 
+# ---- matching for the monocular initialisation (include/vislam_ba.h: vba_search_init_problem / vba_search_init_result) ----
+SEARCH_INIT_MAX_KEYS = 16384
+
+
+class vba_search_init_problem(C.Structure):
+    _fields_ = [
+        ("check_orientation", C.c_int32), ("th_low", C.c_int32), ("nn_ratio", C.c_float), ("window_size", C.c_double), ("n_keys1", C.c_int32),
+        ("desc1", _pu8), ("oct1", _pu8), ("angle1", _pf), ("prev_matched", _pf), ("n_keys2", C.c_int32), ("desc2", _pu8), ("uv2", _pd),
+        ("oct2", _pu8), ("angle2", _pf), ("bounds", C.c_double * 4), ("grid_cols", C.c_int32), ("grid_rows", C.c_int32),
+        ("grid_inv_w", C.c_double), ("grid_inv_h", C.c_double), ("cell_begin", _pi), ("cell_feat", _pi),
+    ]
+
+
+class vba_search_init_result(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_matches", C.c_int32), ("n_before_filter", C.c_int32), ("n_stolen", C.c_int32), ("hist", C.c_int32 * 30),
+                ("ind", C.c_int32 * 3), ("rounds", C.c_int32), ("match12", _pi), ("best_idx", _pi), ("best_dist", _pu16), ("best_dist2", _pu16),
+                ("bin", _pu8), ("state", _pu8), ("prev_matched", _pf), ("match21", _pi), ("matched_dist", _pu16)]
+
+
+(SI_MATCHED, SI_UPPER_LEVEL, SI_EMPTY_AREA, SI_THRESHOLD, SI_RATIO, SI_STOLEN, SI_ROTATION) = range(7)
+
+
+@dataclass
+class SearchInitProblem:
+    """One ORBmatcher::SearchForInitialization call (src/ORBmatcher.cpp:477-595) as flat arrays: frame 1 with vbPrevMatched, frame 2
+    with its grid in CSR form.  The angles may stay None without check_orientation."""
+    desc1: np.ndarray              # [n1,32] uint8
+    oct1: np.ndarray               # [n1] uint8
+    prev_matched: np.ndarray       # [n1,2] float32
+    desc2: np.ndarray              # [n2,32] uint8
+    uv2: np.ndarray                # [n2,2]
+    oct2: np.ndarray               # [n2] uint8
+    bounds: np.ndarray             # [4] mnMinX mnMaxX mnMinY mnMaxY
+    grid_cols: int
+    grid_rows: int
+    grid_inv_w: float
+    grid_inv_h: float
+    cell_begin: np.ndarray         # [cols * rows + 1] int32
+    cell_feat: np.ndarray          # int32
+    angle1: np.ndarray = None      # [n1] float32, with check_orientation
+    angle2: np.ndarray = None      # [n2] float32
+    window_size: float = 100.0
+    th_low: int = 50
+    nn_ratio: float = 0.9
+    check_orientation: bool = True
+    truth: dict = field(default_factory=dict)
+
+    def __post_init__(self):
+        u8 = lambda a, shape: np.ascontiguousarray(a, dtype=np.uint8).reshape(shape)
+        opt = lambda a, f, *s: None if a is None else f(a, *s)
+        f32 = lambda a, shape: np.ascontiguousarray(a, dtype=np.float32).reshape(shape)
+        self.desc1 = u8(self.desc1, (-1, 32)); self.desc2 = u8(self.desc2, (-1, 32))
+        self.oct1 = u8(self.oct1, (-1,)); self.oct2 = u8(self.oct2, (-1,))
+        self.prev_matched = f32(self.prev_matched, (-1, 2)); self.uv2 = _f64(self.uv2, (-1, 2))
+        self.angle1 = opt(self.angle1, f32, (-1,)); self.angle2 = opt(self.angle2, f32, (-1,))
+        self.bounds = _f64(self.bounds, (4,))
+        self.cell_begin = _i32(self.cell_begin).reshape(-1); self.cell_feat = _i32(self.cell_feat).reshape(-1)
+        self.nn_ratio = float(np.float32(self.nn_ratio))
+
+    n_keys1 = property(lambda self: self.desc1.shape[0])
+    n_keys2 = property(lambda self: self.desc2.shape[0])
+    n_q = property(lambda self: int((self.oct1 == 0).sum()))
+
+    def copy(self, **changes):
+        import copy as _c
+        q = _c.copy(self)
+        for k, v in changes.items():
+            setattr(q, k, v)
+        q.__post_init__()
+        return q
+
+    def as_struct(self) -> vba_search_init_problem:
+        s = vba_search_init_problem()
+        p = lambda a, t: None if a is None else a.ctypes.data_as(t)
+        s.check_orientation, s.th_low, s.nn_ratio, s.window_size = int(bool(self.check_orientation)), int(self.th_low), float(self.nn_ratio), float(self.window_size)
+        s.n_keys1, s.n_keys2 = self.n_keys1, self.n_keys2
+        s.desc1, s.oct1, s.angle1, s.prev_matched = p(self.desc1, _pu8), p(self.oct1, _pu8), p(self.angle1, _pf), p(self.prev_matched, _pf)
+        s.desc2, s.uv2, s.oct2, s.angle2 = p(self.desc2, _pu8), p(self.uv2, _pd), p(self.oct2, _pu8), p(self.angle2, _pf)
+        s.bounds[:] = self.bounds.tolist()
+        s.grid_cols, s.grid_rows, s.grid_inv_w, s.grid_inv_h = int(self.grid_cols), int(self.grid_rows), float(self.grid_inv_w), float(self.grid_inv_h)
+        s.cell_begin, s.cell_feat = p(self.cell_begin, _pi), p(self.cell_feat, _pi)
+        return s
+
+
+@dataclass
+class SearchInitResult:
+    status: int
+    n_matches: int
+    n_before_filter: int
+    n_stolen: int
+    hist: np.ndarray                # [30]
+    ind: np.ndarray                 # [3]
+    rounds: int
+    match12: np.ndarray             # [n1] int32
+    best_idx: np.ndarray            # [n1] int32
+    best_dist: np.ndarray           # [n1] uint16
+    best_dist2: np.ndarray          # [n1] uint16
+    bin: np.ndarray                 # [n1] uint8
+    state: np.ndarray               # [n1] uint8
+    prev_matched: np.ndarray        # [n1,2] float32
+    match21: np.ndarray             # [n2] int32
+    matched_dist: np.ndarray        # [n2] uint16
+
+
+class SearchInitResultBuf:
+    """Caller-allocated result storage of one pair."""
+
+    def __init__(self, p: SearchInitProblem):
+        self.n, self.n2 = p.n_keys1, p.n_keys2
+        m, m2 = max(self.n, 1), max(self.n2, 1)
+        self.m12 = np.full(m, -7, dtype=np.int32)
+        self.bi = np.full(m, -7, dtype=np.int32)
+        self.bd = np.full(m, 7, dtype=np.uint16)
+        self.bd2 = np.full(m, 7, dtype=np.uint16)
+        self.bn = np.full(m, 77, dtype=np.uint8)
+        self.st = np.full(m, 255, dtype=np.uint8)
+        self.pm = np.full((m, 2), -7.0, dtype=np.float32)
+        self.m21 = np.full(m2, -7, dtype=np.int32)
+        self.md = np.full(m2, 7, dtype=np.uint16)
+        s = self.s = vba_search_init_result()
+        s.status, s.n_matches, s.n_before_filter, s.n_stolen, s.rounds = -7, -7, -7, -7, -7
+        s.match12, s.best_idx, s.best_dist, s.best_dist2 = (self.m12.ctypes.data_as(_pi), self.bi.ctypes.data_as(_pi), self.bd.ctypes.data_as(_pu16),
+                                                            self.bd2.ctypes.data_as(_pu16))
+        s.bin, s.state, s.prev_matched = self.bn.ctypes.data_as(_pu8), self.st.ctypes.data_as(_pu8), self.pm.ctypes.data_as(_pf)
+        s.match21, s.matched_dist = self.m21.ctypes.data_as(_pi), self.md.ctypes.data_as(_pu16)
+
+    def untouched(self):
+        """nothing was written since construction"""
+        s = self.s
+        return ((s.status, s.n_matches, s.n_before_filter, s.n_stolen, s.rounds) == (-7, -7, -7, -7, -7) and (self.m12 == -7).all() and
+                (self.bi == -7).all() and (self.bd == 7).all() and (self.bd2 == 7).all() and (self.bn == 77).all() and (self.st == 255).all() and
+                (self.pm == -7.0).all() and (self.m21 == -7).all() and (self.md == 7).all() and not any(s.hist[:]) and not any(s.ind[:]))
+
+    def get(self) -> SearchInitResult:
+        s, n = self.s, self.n
+        return SearchInitResult(s.status, s.n_matches, s.n_before_filter, s.n_stolen, np.array(s.hist[:]), np.array(s.ind[:]), s.rounds,
+                                self.m12[:n].copy(), self.bi[:n].copy(), self.bd[:n].copy(), self.bd2[:n].copy(), self.bn[:n].copy(),
+                                self.st[:n].copy(), self.pm[:n].copy(), self.m21[:self.n2].copy(), self.md[:self.n2].copy())
+
+
 # ---- essential-graph optimisation (include/vislam_ba.h: vba_posegraph_problem / vba_posegraph_result) ----
 class vba_posegraph_problem(C.Structure):
     _fields_ = [

@@ -20,7 +20,8 @@ EXPORTS = ["vba_create", "vba_destroy", "vba_last_error", "vba_solve", "vba_batc
            "vba_batch_download", "vba_batch_solve", "vba_solve_b", "vba_batch_run_b", "vba_batch_solve_b", "vba_preintegrate", "vba_pose_optimize", "vba_problem_save", "vba_problem_load", "vba_problem_free", "vba_set_profile", "vba_get_profile", "vba_host_threads",
            "vba_batch_set_depth", "vba_batch_submit", "vba_batch_submit_b", "vba_batch_poll", "vba_batch_wait", "vba_sim3_optimize",
            "vba_posegraph_optimize", "vba_sim3_ransac", "vba_triangulate", "vba_two_view_init", "vba_search_triangulation", "vba_fuse",
-           "vba_search_by_sim3", "vba_search_by_projection", "vba_search_by_bow", "vba_search_by_projection_kf"]
+           "vba_search_by_sim3", "vba_search_by_projection", "vba_search_by_bow", "vba_search_by_projection_kf",
+           "vba_search_for_initialization"]
 
 # The small-problem entry points, all of the shape fn(handle, n, problems, results).  kind -> (library function, problem struct,
 # result struct, result buffer of one problem -- called with the problem and the extra arguments of its pack --, whether the call
@@ -38,6 +39,8 @@ _SMALL = {
     "search_by_projection_kf": ("vba_search_by_projection_kf", abi.vba_search_proj_kf_problem, abi.vba_search_proj_kf_result, abi.SearchProjKfResultBuf,
                                 False),
     "search_by_bow": ("vba_search_by_bow", abi.vba_search_bow_problem, abi.vba_search_bow_result, abi.SearchBowResultBuf, False),
+    "search_for_initialization": ("vba_search_for_initialization", abi.vba_search_init_problem, abi.vba_search_init_result, abi.SearchInitResultBuf,
+                                  False),
     "posegraph": ("vba_posegraph_optimize", abi.vba_posegraph_problem, abi.vba_posegraph_result, lambda p: abi.vba_posegraph_result(), True),
 }
 
@@ -427,6 +430,19 @@ class LocalBA:
         """vba_search_by_bow on a list of abi.SearchBowProblem: list of abi.SearchBowResult"""
         packed = self.search_by_bow_pack(problems)
         self.search_by_bow_call(packed)
+        return [b.get() for b in packed[2]]
+
+    # matching for the monocular initialisation (vba_search_for_initialization): abi.SearchInitProblem, one frame pair each
+    def search_for_initialization_pack(self, problems):
+        return self._small_pack("search_for_initialization", problems)
+
+    def search_for_initialization_call(self, packed):
+        self._small_call("search_for_initialization", packed)
+
+    def search_for_initialization(self, problems):
+        """vba_search_for_initialization on a list of abi.SearchInitProblem: list of abi.SearchInitResult"""
+        packed = self.search_for_initialization_pack(problems)
+        self.search_for_initialization_call(packed)
         return [b.get() for b in packed[2]]
 
     # essential-graph optimisation (vba_posegraph_optimize): abi.PoseGraphProblem, independent Sim3 pose graphs.  The call updates

@@ -60,6 +60,8 @@ int make_handle(int device, Handle* parent, Handle** out) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_search_proj), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (VBA_SP_MAX_KEYS + 1));
     // the claim table of k_search_bow (VBA_SB_MAX_KEYS int32): its only LDS
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_search_bow), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (VBA_SB_MAX_KEYS + 1));
+    // the list heads of k_search_init (VBA_SI_MAX_KEYS int32) beside its static LDS
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_search_init), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (VBA_SI_MAX_KEYS + 1));
     (void)hipEventCreateWithFlags(&h->up_done, hipEventDisableTiming);
     memset(&h->prof, 0, sizeof h->prof);
     *out = h;

@@ -1,7 +1,8 @@
 // vba_host_orient.h -- what the write-backs of the ordered matchers share (plain C++17, no HIP): the rotation bin, ComputeThreeMaxima
 // and the replay of the reference's apply loop with its orientation filter, in query order.  Used by unpack_search_proj,
 // unpack_search_proj_kf and unpack_search_bow (vba_host_search_proj.h, vba_host_search_proj_kf.h, vba_host_search_bow.h) and through
-// them by their sanitizer harnesses.  The replay runs on the host and not in the kernels: it needs the angles, which the device then
+// them by their sanitizer harnesses; unpack_search_init (vba_host_search_init.h) uses rot_bin and three_maxima with an apply loop of its
+// own, because a match there can be stolen.  The replay runs on the host and not in the kernels: it needs the angles, which the device then
 // never sees, and it touches outputs only.
 #pragma once
 #include "vba_layout.h"

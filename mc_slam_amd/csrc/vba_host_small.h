@@ -1,5 +1,5 @@
 // vba_host_small.h -- host side of the library, part 5: the small-problem entry points.  vba_preintegrate copies straight from and
-// to the caller's arrays.  The other twelve are one driver, run_small, over the call object of their topic (PoseCall, Sim3Call, ...:
+// to the caller's arrays.  The other thirteen are one driver, run_small, over the call object of their topic (PoseCall, Sim3Call, ...:
 // plain C++, vba_host_<topic>.h), which knows what is refused, the arena, the packing, the kernel's argument and the write-back;
 // what an entry point adds here is the launch of its kernel.  No entry point shares its arena (Handle::side) with another.
 #pragma once
@@ -14,6 +14,7 @@
 #include "vba_host_search_proj.h"
 #include "vba_host_search_proj_kf.h"
 #include "vba_host_search_bow.h"
+#include "vba_host_search_init.h"
 #include "vba_host_posegraph.h"
 
 namespace {
@@ -181,6 +182,16 @@ int search_by_bow(Handle* h, int32_t n_pairs, vba_search_bow_problem* const* in,
     vba_host::SearchBowCall C;
     return run_small(h, SIDE_SEARCH_BOW, "vba_search_by_bow", C, n_pairs, in, out, [h, &C](const SbBatch& B, unsigned g) {
         VBA_LAUNCH(k_search_bow, dim3(g), dim3(SB_NT), C.lds_bytes(), h->stream, B);
+    });
+}
+
+// ORBmatcher::SearchForInitialization (src/ORBmatcher.cpp:477-595) for a batch of frame pairs: the host compacts the level-0
+// keypoints of frame 1 into the query list while it packs; the claimer lists of a workgroup have their heads in dynamic LDS sized
+// to the call's largest frame 2; steals, histogram, maxima, drop and the vbPrevMatched update run in the write-back
+int search_for_initialization(Handle* h, int32_t n_pairs, vba_search_init_problem* const* in, vba_search_init_result* const* out) {
+    vba_host::SearchInitCall C;
+    return run_small(h, SIDE_SEARCH_INIT, "vba_search_for_initialization", C, n_pairs, in, out, [h, &C](const SiBatch& B, unsigned g) {
+        VBA_LAUNCH(k_search_init, dim3(g), dim3(SI_NT), C.lds_bytes(), h->stream, B);
     });
 }
 

@@ -453,6 +453,41 @@ struct SbBatch {
     int* prev;                   // [total keypoints of side 1] device only, per query slot: the keypoint the query claimed in the round
                                  // before (-1: none)
 };
+// vba_search_for_initialization (vba_search_init.h); the keypoints of frame 2 reuse FuKey
+#define VBA_SI_NT 256          // lanes of the one workgroup of a pair
+#define VBA_SI_MAX_KEYS 16384  // the list heads of a pair are n_keys2 int32 in LDS
+#define VBA_SI_CONST 8         // doubles of a pair's constants: the target block of sa_walk (bounds (4) grid_inv_w grid_inv_h, then the
+                               // window at SA_LOGSF and 0 at SA_TH)
+struct alignas(16) SiQuery {   // one level-0 keypoint of frame 1, in index order, 64 bytes
+    unsigned int d[8];         // the row of F1.mDescriptors
+    double u, v;               // vbPrevMatched[idx1], widened
+    int idx1;                  // the keypoint
+    int pad[3];
+};
+struct SiDesc {
+    long long key0, q0, cell0, feat0;   // offsets of the pair's keypoint records of frame 2, query records (and outputs), cell_begin copy and
+                                        // cell_feat copy in the concatenated arrays
+    int n_keys, n_q, cols, rows;        // n_keys: of frame 2
+    int th_low;
+    float nn_ratio;
+    int pad[2];
+    double c[VBA_SI_CONST];
+};
+static_assert(sizeof(SiQuery) == 64 && sizeof(SiDesc) == 128, "scripts/search_init_bench.py derives the copied bytes from these sizes");
+struct SiBatch {
+    const SiDesc* desc;
+    const FuKey* key;            // keypoint records of frame 2 of all pairs
+    const SiQuery* query;        // query records of all pairs
+    const int* cell_begin;       // cell_begin of all pairs
+    const int* cell_feat;        // cell_feat of all pairs
+    int* rounds;                 // [pairs]
+    int* best_idx;               // [total queries]
+    unsigned short* best_dist;   // ...
+    unsigned short* best_dist2;  // ...
+    unsigned char* state;        // ... 0 accepted, 2 area empty, 3 threshold, 4 ratio (the states 1, 5 and 6 are the host's)
+    int* next;                   // [total queries] device only: the next claimer of the same keypoint, -1 at the end of a list
+    int* cdist;                  // [total queries] device only: the distance of the query's claim as the last rebuild saw it
+};
 // vba_posegraph_optimize (vba_posegraph.h)
 struct PgDesc {
     int nv, ne, nf, npair;

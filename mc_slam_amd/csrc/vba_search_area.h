@@ -1,9 +1,9 @@
-// vba_search_area.h -- what the projection matchers share on the device (k_fuse, k_search_sim3, k_search_proj, k_search_proj_kf; the descriptor
+// vba_search_area.h -- what the projection matchers share on the device (k_fuse, k_search_sim3, k_search_proj, k_search_proj_kf, k_search_init; the descriptor
 // helpers also k_search_tri): the rigid transform, MapPoint::PredictScale (src/MapPoint.cpp:529-540), the descriptor load and the
 // Hamming distance, and the cell walk of GetFeaturesInArea (src/KeyFrame.cpp:1071-1115, src/Frame.cpp:562-620) over a keyframe grid
 // in CSR form.  A kernel keeps its gates, its candidate tests and its outputs; the next matcher is written against sa_walk.  What the
 // ORDERED matchers share beyond this (k_search_proj, k_search_proj_kf, k_search_bow), the conflict pass over a claim table in LDS, is
-// vba_search_claim.h.
+// vba_search_claim.h; k_search_init is ordered too, over claimer lists of its own (vba_search_init.h).
 //
 // The walk: the cell range in double, clamped as max(0, .) and min(n - 1, .) do, with the reference's four early returns.  The
 // cells (ix, y0 .. y1) are neighbours in cell_begin, so a column of the range is ONE range of cell_feat, in the order of the

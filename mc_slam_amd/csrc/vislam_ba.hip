@@ -5,7 +5,7 @@
 //                 vba_host_batch.h (lanes and tickets): vba_create / destroy / last_error, vba_solve*, vba_batch_upload / run /
 //                 download / solve*, vba_batch_set_depth / submit* / poll / wait
 //   small problems  vba_host_small.h: one driver over the plain-C++ call object of each topic (vba_host_<topic>.h).  Tracking:
-//                 vba_preintegrate, vba_search_by_projection and vba_search_by_bow (the matchers in front of) vba_pose_optimize.  Initialisation: vba_two_view_init.  Local mapping:
+//                 vba_preintegrate, vba_search_by_projection and vba_search_by_bow (the matchers in front of) vba_pose_optimize.  Initialisation: vba_search_for_initialization (the matcher in front of) vba_two_view_init.  Local mapping:
 //                 vba_search_triangulation (the matcher in front of) vba_triangulate, vba_fuse.  Loop closing: vba_search_by_bow, vba_sim3_ransac,
 //                 vba_search_by_sim3, vba_sim3_optimize, vba_search_by_projection_kf (the matcher behind it), vba_posegraph_optimize.
 //                 Relocalisation: vba_search_by_bow, vba_search_by_projection_kf between two vba_pose_optimize calls
@@ -32,6 +32,7 @@
 #include "vba_search_proj.h"
 #include "vba_search_proj_kf.h"
 #include "vba_search_bow.h"
+#include "vba_search_init.h"
 #include "vba_posegraph.h"
 #include "vba_structure.h"
 #include "vba_pcg.h"
@@ -223,6 +224,10 @@ int vba_search_by_projection_kf(void* handle, int32_t n_problems, vba_search_pro
 int vba_search_by_bow(void* handle, int32_t n_pairs, vba_search_bow_problem* const* in, vba_search_bow_result* const* out) {
     Handle* h = idle_handle(handle);
     return h ? search_by_bow(h, n_pairs, in, out) : -1;
+}
+int vba_search_for_initialization(void* handle, int32_t n_pairs, vba_search_init_problem* const* in, vba_search_init_result* const* out) {
+    Handle* h = idle_handle(handle);
+    return h ? search_for_initialization(h, n_pairs, in, out) : -1;
 }
 int vba_posegraph_optimize(void* handle, int32_t n_graphs, vba_posegraph_problem* const* inout, vba_posegraph_result* const* out) {
     Handle* h = idle_handle(handle);

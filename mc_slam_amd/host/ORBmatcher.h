@@ -5,7 +5,7 @@
 // overloads (:207-350 keyframe -> frame, :609-748 keyframe -> keyframe) over vba_search_by_bow, each also as a batch form that makes
 // one call for a vector of keyframes, and the loop-closure overload SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) (:354-475)
 // and the relocalisation overload SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (:1667-1797) over
-// vba_search_by_projection_kf.  SearchForInitialization stays matcher code of the caller.
+// vba_search_by_projection_kf, and SearchForInitialization (:477-595) over vba_search_for_initialization.
 #pragma once
 #include <array>
 #include <cstdint>
@@ -16,6 +16,8 @@
 #include "orbslam_min.h"
 
 namespace ORB_SLAM2 {
+
+struct Point2f { float x = 0, y = 0; };   // cv::Point2f
 
 class ORBmatcher {
 public:
@@ -81,6 +83,14 @@ public:
     int SearchByBoW(const std::vector<KeyFrame*>& vpKFs, Frame& F, std::vector<std::vector<MapPoint*>>& vvpMapPointMatches, std::vector<int>& vnMatches);
     // The loop of LoopClosing::ComputeSim3 (src/LoopClosing.cpp:317): pKF1 against every keyframe of vpKFs2, ONE call for all of them
     int SearchByBoW(KeyFrame* pKF1, const std::vector<KeyFrame*>& vpKFs2, std::vector<std::vector<MapPoint*>>& vvpMatches12, std::vector<int>& vnMatches);
+    // src/ORBmatcher.cpp:477-595, the matcher of Tracking::MonocularInitialization: every level-0 keypoint of F1 searches the window of
+    // windowSize pixels around vbPrevMatched[i1] in F2 among the level-0 keypoints, best against second best with mfNNratio, a later
+    // keypoint steals a keypoint of F2 from an earlier one when it is strictly nearer, then the orientation filter; vnMatches12 gets
+    // one entry per keypoint of F1 and vbPrevMatched the pixel of every match kept.  ONE vba_search_for_initialization call.  Returns
+    // nmatches, -1 when the backend failed, vbPrevMatched has not one entry per keypoint of F1, the arrays of a frame disagree or a
+    // frame has a stereo keypoint (this backend is monocular), with a message on std::cerr; vnMatches12 and vbPrevMatched are then
+    // left as they were
+    int SearchForInitialization(Frame& F1, Frame& F2, std::vector<Point2f>& vbPrevMatched, std::vector<int>& vnMatches12, int windowSize = 10);
     // vbAlreadyMatched1 / vbAlreadyMatched2 of :1287-1301: a keypoint of pKF1 with a prior match, and the keypoint of pKF2 where
     // GetIndexInKeyFrame finds that match
     static void AlreadyMatched(KeyFrame* pKF1, KeyFrame* pKF2, const std::vector<MapPoint*>& vpMatches12, std::vector<uint8_t>& vb1,

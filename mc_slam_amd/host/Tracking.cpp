@@ -1,6 +1,7 @@
 // Tracking.cpp -- Tracking::SearchLocalPoints (src/Tracking.cpp:2111-2174) and the matching half of Tracking::TrackWithMotionModel
 // (:1749-1770) over vba_search_by_projection, and the matching half of Tracking::TrackReferenceKeyFrame (:1597-1607) over
-// vba_search_by_bow (ORBmatcher.cpp), monocular.
+// vba_search_by_bow, and the matching part of Tracking::MonocularInitialization (:1360-1381) over vba_search_for_initialization
+// (ORBmatcher.cpp), monocular.
 #include "Tracking.h"
 
 #include <algorithm>
@@ -53,6 +54,18 @@ int Tracking::TrackReferenceKeyFrameMatches() {
     if (nmatches < 15) return nmatches;                           // :1602-1603
     mCurrentFrame.mvpMapPoints = vpMapPointMatches;               // :1606
     mCurrentFrame.SetPose(mLastFrame.mTcw);                       // :1607
+    return nmatches;
+}
+
+int Tracking::MonocularInitializationMatches() {
+    if ((int)mCurrentFrame.mvKeys.size() <= 100) {                // :1360-1366
+        mpInitializer.reset();
+        std::fill(mvIniMatches.begin(), mvIniMatches.end(), -1);
+        return -2;
+    }
+    ORBmatcher matcher(0.9, true);                                // :1371
+    const int nmatches = matcher.SearchForInitialization(mInitialFrame, mCurrentFrame, mvbPrevMatched, mvIniMatches, 100);
+    if (nmatches < 100) mpInitializer.reset();                    // :1376-1381
     return nmatches;
 }
 

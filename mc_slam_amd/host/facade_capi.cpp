@@ -452,6 +452,85 @@ int fc_initializer_initialize(void* s, const float* uv2, int n2, const int* vMat
     std::memcpy(info, v, sizeof v);
     return ok ? 1 : 0;
 }
+// ---- the matcher of the monocular initialisation (ORBmatcher::SearchForInitialization, the Tracking slice) ----
+// a Frame of n keypoints as the matcher reads it: uv [n][2], octaves, angles, N x 32 descriptor bytes, K (fx fy cx cy), the image
+// bounds (min_x max_x min_y max_y) and the grid, which is assigned here; mvKeys = mvKeysUn, every keypoint monocular
+void* fc_init_frame_create(int n, const float* uv, const int* octave, const float* angle, const unsigned char* desc, const float* K, const float* bounds,
+                           int cols, int rows) {
+    Frame* F = new Frame();
+    F->fx = K[0]; F->fy = K[1]; F->cx = K[2]; F->cy = K[3];
+    F->N = n;
+    F->mvKeysUn.resize((size_t)n);
+    for (int i = 0; i < n; i++) {
+        KeyPoint& kp = F->mvKeysUn[(size_t)i];
+        kp.pt.x = uv[2 * i]; kp.pt.y = uv[2 * i + 1]; kp.octave = octave[i]; kp.angle = angle[i];
+    }
+    F->mvKeys = F->mvKeysUn;
+    F->mvuRight.assign((size_t)n, -1.0f);
+    F->mvpMapPoints.assign((size_t)n, nullptr);
+    F->mDescriptors.assign(desc, desc + 32 * (size_t)n);
+    F->mnScaleLevels = 8;
+    F->mvScaleFactors.resize(8);
+    for (int l = 0; l < 8; l++) F->mvScaleFactors[(size_t)l] = (float)std::pow(1.2, l);
+    F->mnMinX = bounds[0]; F->mnMaxX = bounds[1]; F->mnMinY = bounds[2]; F->mnMaxY = bounds[3];
+    F->mnGridCols = cols; F->mnGridRows = rows;
+    F->AssignFeaturesToGrid();
+    return F;
+}
+void fc_init_frame_destroy(void* f) { delete reinterpret_cast<Frame*>(f); }
+void fc_init_frame_set_uright(void* f, int idx, float ur) { reinterpret_cast<Frame*>(f)->mvuRight.at((size_t)idx) = ur; }
+// ORBmatcher(nnratio, check_ori).SearchForInitialization(F1, F2, vbPrevMatched [n_prev][2] in and out, vnMatches12, windowSize); matches
+// [cap] receives vnMatches12 as the call leaves it (n_out: its size).  Returns the return value
+int fc_search_for_initialization(void* f1, void* f2, float* prev, int n_prev, int* matches, int cap, int* n_out, float nnratio, int check_ori, int window) {
+    std::vector<Point2f> vbPrevMatched((size_t)n_prev);
+    for (int i = 0; i < n_prev; i++) { vbPrevMatched[(size_t)i].x = prev[2 * i]; vbPrevMatched[(size_t)i].y = prev[2 * i + 1]; }
+    std::vector<int> vnMatches12;
+    ORBmatcher matcher(nnratio, check_ori != 0);
+    const int r = matcher.SearchForInitialization(*reinterpret_cast<Frame*>(f1), *reinterpret_cast<Frame*>(f2), vbPrevMatched, vnMatches12, window);
+    for (int i = 0; i < n_prev; i++) { prev[2 * i] = vbPrevMatched[(size_t)i].x; prev[2 * i + 1] = vbPrevMatched[(size_t)i].y; }
+    *n_out = (int)vnMatches12.size();
+    for (size_t i = 0; i < vnMatches12.size() && (int)i < cap; i++) matches[i] = vnMatches12[i];
+    return r;
+}
+// Tracking::MonocularInitializationMatches with mInitialFrame = f_init, mCurrentFrame = f_cur, mvbPrevMatched = prev [n1][2] (in and
+// out), mvIniMatches = matches [n1] (in and out) and an Initializer(mInitialFrame, 1.0, 200).  alive: whether the initializer
+// survived.  With do_initialize and a live initializer the slice's matches go on into Initialize (src/Tracking.cpp:1388), whose
+// outputs are those of fc_initializer_initialize and whose return value lands in init_ret (-1: not called).  Returns the slice's
+// return value
+int fc_monocular_initialization(void* f_init, void* f_cur, float* prev, int* matches, int n1, int do_initialize, int* alive, int* init_ret, float* R21,
+                                float* t21, float* vP3D, uint8_t* vbTriangulated, int32_t* sets, int32_t* info) {
+    Tracking t;
+    t.mInitialFrame = *reinterpret_cast<Frame*>(f_init);
+    t.mCurrentFrame = *reinterpret_cast<Frame*>(f_cur);
+    t.mvbPrevMatched.resize((size_t)n1);
+    for (int i = 0; i < n1; i++) { t.mvbPrevMatched[(size_t)i].x = prev[2 * i]; t.mvbPrevMatched[(size_t)i].y = prev[2 * i + 1]; }
+    t.mvIniMatches.assign(matches, matches + n1);
+    t.mpInitializer.reset(new Initializer(t.mInitialFrame, 1.0, 200));
+    const int r = t.MonocularInitializationMatches();
+    for (int i = 0; i < n1; i++) { prev[2 * i] = t.mvbPrevMatched[(size_t)i].x; prev[2 * i + 1] = t.mvbPrevMatched[(size_t)i].y; }
+    for (int i = 0; i < n1 && (size_t)i < t.mvIniMatches.size(); i++) matches[i] = t.mvIniMatches[(size_t)i];
+    *alive = t.mpInitializer ? 1 : 0;
+    *init_ret = -1;
+    if (!t.mpInitializer || !do_initialize) return r;
+    Initializer* I = t.mpInitializer.get();
+    std::array<float, 9> R{};
+    std::array<float, 3> tt{};
+    std::vector<Point3f> P3D;
+    std::vector<bool> tri;
+    const bool ok = I->Initialize(t.mCurrentFrame, t.mvIniMatches, R, tt, P3D, tri);
+    if (ok) {
+        std::memcpy(R21, R.data(), 36);
+        std::memcpy(t21, tt.data(), 12);
+        for (size_t i = 0; i < P3D.size(); i++) { vP3D[3 * i] = P3D[i].x; vP3D[3 * i + 1] = P3D[i].y; vP3D[3 * i + 2] = P3D[i].z; vbTriangulated[i] = tri[i] ? 1 : 0; }
+    }
+    for (size_t it = 0; it < I->mvSets.size(); it++)
+        for (int j = 0; j < 8; j++) sets[8 * it + j] = (int32_t)I->mvSets[it][j];
+    const vba_two_view_result& L = I->mLast;
+    const int32_t v[10] = {L.ok, L.model, L.reason, L.best_hyp_h, L.best_hyp_f, L.n_inliers_h, L.n_inliers_f, L.n_rt, L.best_rt, (int32_t)I->mvMatches12.size()};
+    std::memcpy(info, v, sizeof v);
+    *init_ret = ok ? 1 : 0;
+    return r;
+}
 // ---- new map points (LocalMapping::CreateNewMapPoints, LocalMapping.cpp) ----
 // The matcher is a table: neighbour i of `neigh` gets matches [begin[i], begin[i + 1]) of `matches` ([..][2] keypoint indices in kf /
 // in the neighbour).  seen[i]: how many keypoints of kf had a map point when the matcher was called for neighbour i, -1 where it was

@@ -1300,3 +1300,81 @@ def search_bow_scene(seed, mode, n_keys1=1500, n_keys2=1500, n_nodes=100, twins=
                                 node_id1=id1, node_begin1=b1, node_feat1=ft1, node_id2=id2, node_begin2=b2, node_feat2=ft2,
                                 angle1=ang1[p1] if check_orientation else None, angle2=ang2[p2] if check_orientation else None, th_low=th_low,
                                 nn_ratio=nn_ratio, check_orientation=check_orientation, truth=dict(pair=np.stack([inv1[:nt], inv2[:nt]], axis=1)))
+
+
+# ---------------------------------------------------------------- matching for the monocular initialisation (vba_search_for_initialization)
+def search_init_scene(seed, n_keys1=1500, n_keys2=1500, size=(640, 480), cols=64, rows=48, window_size=100.0, level0=0.6, matched=0.7, twins=0.2,
+                      crowd=0.3, flip_bits=24, spread=0.6, th_low=50, nn_ratio=0.9, check_orientation=True, rotation=20.0, angle_noise=3.0,
+                      angle_outliers=0.1):
+    """One ORBmatcher::SearchForInitialization call (abi.SearchInitProblem), every input as the reference holds it (float32 pixels).
+      pixels      off the integer lattice: a keypoint of frame 2 lies on (integer + an odd multiple of 1/8), a vbPrevMatched entry on
+                  (integer + an odd multiple of 1/4), so with an integer window no |dx| sits on r and no floor or ceil argument on an integer
+      level0      the share of the keypoints of either frame at octave 0; the others are spread over the octaves 1 .. 7
+      matched     the first share `matched` of min(n_keys1, n_keys2) keypoints of frame 1 are views of keypoint i of frame 2: the
+                  descriptor 0 .. flip_bits bits off, vbPrevMatched within spread * window_size of it, the same octave
+      twins       the last share of the keypoints of frame 2 are moved beside keypoint 0, 1, ...: up to 3 pixels away, the same octave,
+                  the descriptor 2 .. 10 bits off: best and second best lie close, and the ratio test decides
+      crowd       the last share of the keypoints of frame 1 are second views of the keypoints 0, 1, ... of frame 1 (the descriptor up
+                  to 6 bits off theirs, vbPrevMatched drawn anew around the same keypoint of frame 2): queries compete for a keypoint, and
+                  the later one steals it when it is strictly nearer
+      angles      uniform in frame 2; a view's angle1 is its keypoint's plus `rotation` plus angle_noise degrees of noise, a share
+                  angle_outliers of the views and every other keypoint has a random one
+    Both frames are shuffled at the end.  truth: key1 [n_keys1], the keypoint of frame 2 a keypoint of frame 1 is a view of, -1 for none."""
+    r = np.random.default_rng(seed)
+    f32 = lambda a: np.asarray(a, dtype=np.float32)
+    w, h = size
+    bounds = np.array([0.0, float(w), 0.0, float(h)])
+
+    def octaves(n):
+        return np.where(r.random(n) < level0, 0, r.integers(1, 8, n)).astype(np.uint8)
+
+    def flipped(d, lo, hi):
+        bits = np.unpackbits(d)
+        bits[r.permutation(256)[:int(r.integers(lo, hi + 1))]] ^= 1
+        return np.packbits(bits)
+
+    lat8 = lambda n, top: r.integers(0, max(int(top) - 1, 1), n) + (2 * r.integers(0, 4, n) + 1) / 8.0
+    uv2 = np.stack([lat8(n_keys2, w), lat8(n_keys2, h)], axis=1).reshape(-1, 2)
+    oct2 = octaves(n_keys2)
+    d2 = r.integers(0, 256, (n_keys2, 32), dtype=np.uint8)
+    m2 = min(int(n_keys2 * twins), n_keys2 // 2)
+    for j in range(m2):
+        k = n_keys2 - m2 + j
+        uv2[k] = np.clip(uv2[j] + r.integers(-3, 4, 2), 0.125, [w - 0.125, h - 0.125])
+        oct2[k] = oct2[j]
+        d2[k] = flipped(d2[j], 2, 10)
+    ang2 = r.uniform(0.0, 360.0, n_keys2)
+
+    def around(k):
+        reach = max(int(abs(window_size) * spread), 1)
+        c = np.floor(uv2[k]) + r.integers(-reach, reach + 1, 2) + (2 * r.integers(0, 2, 2) + 1) / 4.0
+        return np.clip(c, 0.25, [w - 0.25, h - 0.25])
+
+    key1 = np.full(n_keys1, -1, dtype=np.int64)
+    oct1 = octaves(n_keys1)
+    d1 = r.integers(0, 256, (n_keys1, 32), dtype=np.uint8)
+    prev = np.stack([r.integers(0, max(w - 1, 1), n_keys1), r.integers(0, max(h - 1, 1), n_keys1)], axis=1).reshape(-1, 2) + (2 * r.integers(0, 2, (n_keys1, 2)) + 1) / 4.0
+    ang1 = r.uniform(0.0, 360.0, n_keys1)
+    nm = int(min(n_keys1, n_keys2 - m2) * matched)
+    for i in range(nm):
+        key1[i], oct1[i], d1[i], prev[i] = i, oct2[i], flipped(d2[i], 0, flip_bits), around(i)
+    mc = min(int(n_keys1 * crowd), n_keys1 - nm, nm)
+    for j in range(mc):
+        i, src = n_keys1 - mc + j, j % max(nm, 1)
+        key1[i], oct1[i], d1[i], prev[i] = key1[src], oct1[src], flipped(d1[src], 0, 6), around(key1[src])
+    for i in np.nonzero(key1 >= 0)[0]:
+        if r.random() >= angle_outliers:
+            ang1[i] = np.mod(ang2[key1[i]] + rotation + r.normal() * angle_noise, 360.0)
+    ang1, ang2 = f32(ang1), f32(ang2)
+    ang1[ang1 >= 360] = 0; ang2[ang2 >= 360] = 0
+    p1, p2 = r.permutation(n_keys1), r.permutation(n_keys2)          # new index -> old index
+    inv2 = np.argsort(p2)
+    uv2 = f32(uv2[p2]).astype(np.float64).reshape(-1, 2)
+    inv_w, inv_h = float(np.float32(cols) / np.float32(w)), float(np.float32(rows) / np.float32(h))
+    cell_begin, cell_feat = abi.grid_csr(uv2, bounds, cols, rows, inv_w, inv_h)
+    k1 = key1[p1]
+    return abi.SearchInitProblem(desc1=d1[p1], oct1=oct1[p1], prev_matched=f32(prev[p1]), desc2=d2[p2], uv2=uv2, oct2=oct2[p2], bounds=bounds, grid_cols=cols,
+                                 grid_rows=rows, grid_inv_w=inv_w, grid_inv_h=inv_h, cell_begin=cell_begin, cell_feat=cell_feat,
+                                 angle1=ang1[p1] if check_orientation else None, angle2=ang2[p2] if check_orientation else None,
+                                 window_size=window_size, th_low=th_low, nn_ratio=nn_ratio, check_orientation=check_orientation,
+                                 truth=dict(key1=np.where(k1 >= 0, inv2[np.maximum(k1, 0)], -1) if n_keys2 else k1))
