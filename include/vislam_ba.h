@@ -1102,6 +1102,77 @@ typedef struct vba_search_init_result {
  * A pair's outputs do not depend on where it stands in the batch. */
 int vba_search_for_initialization(void *handle, int32_t n_pairs, vba_search_init_problem *const *in, vba_search_init_result *const *out);
 
+/* ---- map-point refresh: representative descriptor, mean viewing direction, scale-invariance range ----
+ * MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cpp:336-413) and MapPoint::UpdateNormalAndDepth (:450-501), which
+ * LocalMapping calls as a pair for every map point of the current keyframe (src/LocalMapping.cpp:1144-1171, :1532-1534, :1635-1650)
+ * and every BA write-back calls for every local map point (src/Optimizer.cpp:605, :3328, :4213, :4545).  They produce what the
+ * matchers read: pt_desc, normal, dist_min, dist_max of vba_fuse and its siblings.  One problem is one list of points over one table
+ * of keyframes; one call takes any number of problems, ragged, in one kernel launch.  The reference is restated as it stands:
+ *   descriptor  the observations in the order of mObservations, ascending keyframe id (:19-22); an observation whose keyframe isBad()
+ *               contributes no descriptor (:360); with no observation (:349) or none from a good keyframe (:364) nothing is written.
+ *               Otherwise N descriptors remain, Distances[i][j] is the 256-bit Hamming distance with a diagonal of 0, row i is sorted
+ *               and its median is the entry (int)(0.5 * (N - 1)) (:394): the LOWER median, for N = 2 the 0 of the diagonal.  The first
+ *               row with a strictly smaller median wins (:397); N = 1 gives median 0 and row 0
+ *   normal      with no observation, return (:467).  normal = the sum over ALL observations, bad keyframes included (:472-481 has no
+ *               isBad test), of (Pos - Ow_i) / |Pos - Ow_i|, divided by their count (:498); dist = |Pos - Ow_ref| (:484-485);
+ *               mfMaxDistance = dist * mvScaleFactors[level] (:494), mfMinDistance = mfMaxDistance / mvScaleFactors[nLevels - 1] (:496),
+ *               level the octave of the reference keyframe's keypoint observations[pRefKF] (:486).  `observations` is a local std::map:
+ *               when the reference keyframe is no observer, operator[] inserts 0 and keypoint 0 is read.  The two scale factors are
+ *               per-point inputs here, so that lookup stays with the caller
+ * FP64 where the reference computes in float32 (cv::Mat CV_32F, cv::norm accumulating in double); a caller narrows to float32 when it
+ * writes back.  One declared deviation: a point that coincides exactly with an observer's camera centre (|Pos - Ow_i| = 0), where the
+ * reference divides by zero and stores NaN: the normal part leaves with normal_state 3 and writes nothing for the point.
+ * desc_state / normal_state say where a part left:
+ *   0  done
+ *   1  not asked (its bit of `what` is clear)
+ *   2  no observations (:349 / :467)
+ *   3  descriptor: no observation from a good keyframe (:364); normal: the point lies in an observer's camera centre */
+#define VBA_MAPPOINT_MAX_OBS 1024   /* observations of one point: its descriptors live in LDS */
+#define VBA_MAPPOINT_DESC 1         /* bit of `what`: ComputeDistinctiveDescriptors */
+#define VBA_MAPPOINT_NORMAL 2       /* bit of `what`: UpdateNormalAndDepth */
+typedef struct vba_mappoint_problem {
+    int32_t n_kf;                    /* keyframes of the table */
+    const double *kf_center;         /* [n_kf][3] KeyFrame::GetCameraCenter (:476, :484); read when a point asks for the normal part */
+    const uint8_t *kf_bad;           /* [n_kf] KeyFrame::isBad (:360); read when a point asks for the descriptor part */
+    int32_t n_pt;                    /* points */
+    const uint8_t *what;             /* [n_pt] VBA_MAPPOINT_DESC | VBA_MAPPOINT_NORMAL; 0 is legal */
+    const double *pos;               /* [n_pt][3] mWorldPos (:464); may be NULL when no point asks for the normal part, like the next three */
+    const int32_t *ref_kf;           /* [n_pt] mpRefKF as an index into the table (:463) */
+    const double *ref_scale;         /* [n_pt] pRefKF->mvScaleFactors[level] (:486-487); > 0 */
+    const double *ref_top_scale;     /* [n_pt] pRefKF->mvScaleFactors[nLevels - 1] (:496); > 0 */
+    const int32_t *obs_begin;        /* [n_pt + 1] CSR: the observations of point i are obs_begin[i] .. obs_begin[i + 1], in the order of
+                                        mObservations; at most VBA_MAPPOINT_MAX_OBS of them */
+    const int32_t *obs_kf;           /* [obs_begin[n_pt]] the observing keyframe as an index into the table */
+    const uint8_t *obs_desc;         /* [obs_begin[n_pt]][32] pKF->mDescriptors.row(mit->second) (:361), gathered by the caller; may be NULL
+                                        when no point asks for the descriptor part */
+} vba_mappoint_problem;
+
+typedef struct vba_mappoint_result {
+    int32_t status;           /* VBA_OK */
+    int32_t n_desc_done;      /* points with desc_state 0 */
+    int32_t n_normal_done;    /* points with normal_state 0 */
+    int32_t *best_obs;        /* [n_pt] caller-allocated: BestIdx (:400) as an index INTO THE POINT'S OBSERVATION LIST, bad keyframes counted;
+                                 -1 where the descriptor part did not run to its end */
+    int32_t *best_median;     /* [n_pt] caller-allocated: BestMedian (:399); -1 likewise */
+    int32_t *n_desc;          /* [n_pt] caller-allocated: N (:368); 0 where the part was not asked */
+    uint8_t *desc;            /* [n_pt][32] caller-allocated: the winning row (:410), ready to be pt_desc of vba_fuse; zeros where none */
+    double *normal;           /* [n_pt][3] caller-allocated: mNormalVector (:498); 0.0 where the normal part did not run to its end */
+    double *dist_max;         /* [n_pt] caller-allocated: mfMaxDistance (:494); 0.0 likewise */
+    double *dist_min;         /* [n_pt] caller-allocated: mfMinDistance (:496); 0.0 likewise */
+    uint8_t *desc_state;      /* [n_pt] caller-allocated: the codes above */
+    uint8_t *normal_state;    /* [n_pt] caller-allocated: the codes above */
+} vba_mappoint_result;
+
+/* Synchronous, like vba_fuse; -1 while asynchronous tickets are pending.  n_problems == 0 returns 0; a problem with n_pt == 0 or
+ * n_kf == 0 is legal (a point of a table without keyframes can have no observation).  A bad problem fails the whole call before any
+ * GPU work, with nothing written, as "vba_mappoint_update: problem K: <why>" through vba_last_error: a NULL problem or result, a
+ * negative count, with n_pt > 0 a NULL what, obs_begin or result array, an obs_begin that does not start at 0 or decreases, a list
+ * above VBA_MAPPOINT_MAX_OBS, a bit of `what` outside the two, a NULL array that a requested part needs (obs_kf with observations;
+ * kf_bad and obs_desc for the descriptor part; kf_center, pos, ref_kf and both scale arrays for the normal part), and for the points
+ * that ask for the part that reads them: an obs_kf or ref_kf out of range, a non-finite position or scale, a scale <= 0; with a
+ * normal part in the problem a non-finite centre.  A point's outputs do not depend on where it stands in the batch. */
+int vba_mappoint_update(void *handle, int32_t n_problems, vba_mappoint_problem *const *in, vba_mappoint_result *const *out);
+
 /* ---- essential-graph optimisation (Sim3 pose graph) ----
  * Optimizer::OptimizeEssentialGraph(Map*, KeyFrame* pLoopKF, KeyFrame* pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections,
  * bFixScale, LoopClosing*)   src/Optimizer.cpp:4243-4552

@@ -1868,6 +1868,123 @@ class SearchInitResultBuf:
                                 self.st[:n].copy(), self.pm[:n].copy(), self.m21[:self.n2].copy(), self.md[:self.n2].copy())
 
 
+# ---- map-point refresh (include/vislam_ba.h: vba_mappoint_problem / vba_mappoint_result) ----
+MAPPOINT_MAX_OBS = 1024
+MAPPOINT_DESC, MAPPOINT_NORMAL = 1, 2
+
+
+class vba_mappoint_problem(C.Structure):
+    _fields_ = [("n_kf", C.c_int32), ("kf_center", _pd), ("kf_bad", _pu8), ("n_pt", C.c_int32), ("what", _pu8), ("pos", _pd), ("ref_kf", _pi),
+                ("ref_scale", _pd), ("ref_top_scale", _pd), ("obs_begin", _pi), ("obs_kf", _pi), ("obs_desc", _pu8)]
+
+
+class vba_mappoint_result(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_desc_done", C.c_int32), ("n_normal_done", C.c_int32), ("best_obs", _pi), ("best_median", _pi), ("n_desc", _pi),
+                ("desc", _pu8), ("normal", _pd), ("dist_max", _pd), ("dist_min", _pd), ("desc_state", _pu8), ("normal_state", _pu8)]
+
+
+(MP_DONE, MP_NOT_ASKED, MP_NO_OBSERVATIONS, MP_NO_INPUT) = range(4)   # MP_NO_INPUT: no good keyframe / the point in an observer's centre
+
+
+@dataclass
+class MapPointProblem:
+    """One list of map points over one table of keyframes, for MapPoint::ComputeDistinctiveDescriptors and
+    MapPoint::UpdateNormalAndDepth (src/MapPoint.cpp:336-413, :450-501): the observations in CSR form, in the order of mObservations.
+    obs_desc may stay None when no point asks for the descriptor part; pos, ref_kf and the scales when none asks for the normal part."""
+    kf_center: np.ndarray          # [n_kf,3]
+    kf_bad: np.ndarray             # [n_kf] uint8
+    what: np.ndarray               # [n_pt] uint8: MAPPOINT_DESC | MAPPOINT_NORMAL
+    obs_begin: np.ndarray          # [n_pt + 1] int32
+    obs_kf: np.ndarray             # [n_obs] int32
+    obs_desc: np.ndarray = None    # [n_obs,32] uint8
+    pos: np.ndarray = None         # [n_pt,3]
+    ref_kf: np.ndarray = None      # [n_pt] int32
+    ref_scale: np.ndarray = None   # [n_pt]
+    ref_top_scale: np.ndarray = None   # [n_pt]
+    truth: dict = field(default_factory=dict)
+
+    def __post_init__(self):
+        u8 = lambda a, *shape: np.ascontiguousarray(a, dtype=np.uint8).reshape(shape)
+        opt = lambda a, f, *s: None if a is None else f(a, *s)
+        self.kf_center = _f64(self.kf_center, (-1, 3)); self.kf_bad = u8(self.kf_bad, -1)
+        self.what = u8(self.what, -1)
+        self.obs_begin = _i32(self.obs_begin).reshape(-1); self.obs_kf = _i32(self.obs_kf).reshape(-1)
+        self.obs_desc = opt(self.obs_desc, u8, -1, 32)
+        self.pos = opt(self.pos, _f64, (-1, 3)); self.ref_kf = opt(self.ref_kf, lambda a: _i32(a).reshape(-1))
+        self.ref_scale = opt(self.ref_scale, _f64, (-1,)); self.ref_top_scale = opt(self.ref_top_scale, _f64, (-1,))
+
+    n_kf = property(lambda self: self.kf_center.shape[0])
+    n_pt = property(lambda self: self.what.shape[0])
+    n_obs = property(lambda self: self.obs_kf.shape[0])
+
+    def copy(self, **changes):
+        import copy as _c
+        q = _c.copy(self)
+        for k, v in changes.items():
+            setattr(q, k, v)
+        q.__post_init__()
+        return q
+
+    def as_struct(self) -> vba_mappoint_problem:
+        s = vba_mappoint_problem()
+        p = lambda a, t: None if a is None else a.ctypes.data_as(t)
+        s.n_kf, s.n_pt = self.n_kf, self.n_pt
+        s.kf_center, s.kf_bad, s.what = p(self.kf_center, _pd), p(self.kf_bad, _pu8), p(self.what, _pu8)
+        s.pos, s.ref_kf, s.ref_scale, s.ref_top_scale = p(self.pos, _pd), p(self.ref_kf, _pi), p(self.ref_scale, _pd), p(self.ref_top_scale, _pd)
+        s.obs_begin, s.obs_kf, s.obs_desc = p(self.obs_begin, _pi), p(self.obs_kf, _pi), p(self.obs_desc, _pu8)
+        return s
+
+
+@dataclass
+class MapPointResult:
+    status: int
+    n_desc_done: int
+    n_normal_done: int
+    best_obs: np.ndarray            # [n_pt] int32
+    best_median: np.ndarray         # [n_pt] int32
+    n_desc: np.ndarray              # [n_pt] int32
+    desc: np.ndarray                # [n_pt,32] uint8
+    normal: np.ndarray              # [n_pt,3]
+    dist_max: np.ndarray            # [n_pt]
+    dist_min: np.ndarray            # [n_pt]
+    desc_state: np.ndarray          # [n_pt] uint8
+    normal_state: np.ndarray        # [n_pt] uint8
+
+
+class MapPointResultBuf:
+    """Caller-allocated result storage of one problem."""
+
+    def __init__(self, p: MapPointProblem):
+        self.n = p.n_pt
+        m = max(self.n, 1)
+        self.bo = np.full(m, -7, dtype=np.int32)
+        self.bm = np.full(m, -7, dtype=np.int32)
+        self.nd = np.full(m, -7, dtype=np.int32)
+        self.de = np.full((m, 32), 77, dtype=np.uint8)
+        self.no = np.full((m, 3), -7.0)
+        self.dx = np.full(m, -7.0)
+        self.dn = np.full(m, -7.0)
+        self.ds = np.full(m, 255, dtype=np.uint8)
+        self.ns = np.full(m, 255, dtype=np.uint8)
+        s = self.s = vba_mappoint_result()
+        s.status, s.n_desc_done, s.n_normal_done = -7, -7, -7
+        s.best_obs, s.best_median, s.n_desc, s.desc = self.bo.ctypes.data_as(_pi), self.bm.ctypes.data_as(_pi), self.nd.ctypes.data_as(_pi), self.de.ctypes.data_as(_pu8)
+        s.normal, s.dist_max, s.dist_min = self.no.ctypes.data_as(_pd), self.dx.ctypes.data_as(_pd), self.dn.ctypes.data_as(_pd)
+        s.desc_state, s.normal_state = self.ds.ctypes.data_as(_pu8), self.ns.ctypes.data_as(_pu8)
+
+    def untouched(self):
+        """nothing was written since construction"""
+        s = self.s
+        return ((s.status, s.n_desc_done, s.n_normal_done) == (-7, -7, -7) and (self.bo == -7).all() and (self.bm == -7).all() and (self.nd == -7).all() and
+                (self.de == 77).all() and (self.no == -7.0).all() and (self.dx == -7.0).all() and (self.dn == -7.0).all() and (self.ds == 255).all() and
+                (self.ns == 255).all())
+
+    def get(self) -> MapPointResult:
+        s, n = self.s, self.n
+        return MapPointResult(s.status, s.n_desc_done, s.n_normal_done, self.bo[:n].copy(), self.bm[:n].copy(), self.nd[:n].copy(), self.de[:n].copy(),
+                              self.no[:n].copy(), self.dx[:n].copy(), self.dn[:n].copy(), self.ds[:n].copy(), self.ns[:n].copy())
+
+
 # ---- essential-graph optimisation (include/vislam_ba.h: vba_posegraph_problem / vba_posegraph_result) ----
 class vba_posegraph_problem(C.Structure):
     _fields_ = [

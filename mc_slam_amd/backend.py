@@ -21,7 +21,7 @@ EXPORTS = ["vba_create", "vba_destroy", "vba_last_error", "vba_solve", "vba_batc
            "vba_batch_set_depth", "vba_batch_submit", "vba_batch_submit_b", "vba_batch_poll", "vba_batch_wait", "vba_sim3_optimize",
            "vba_posegraph_optimize", "vba_sim3_ransac", "vba_triangulate", "vba_two_view_init", "vba_search_triangulation", "vba_fuse",
            "vba_search_by_sim3", "vba_search_by_projection", "vba_search_by_bow", "vba_search_by_projection_kf",
-           "vba_search_for_initialization"]
+           "vba_search_for_initialization", "vba_mappoint_update"]
 
 # The small-problem entry points, all of the shape fn(handle, n, problems, results).  kind -> (library function, problem struct,
 # result struct, result buffer of one problem -- called with the problem and the extra arguments of its pack --, whether the call
@@ -41,6 +41,7 @@ _SMALL = {
     "search_by_bow": ("vba_search_by_bow", abi.vba_search_bow_problem, abi.vba_search_bow_result, abi.SearchBowResultBuf, False),
     "search_for_initialization": ("vba_search_for_initialization", abi.vba_search_init_problem, abi.vba_search_init_result, abi.SearchInitResultBuf,
                                   False),
+    "mappoint_update": ("vba_mappoint_update", abi.vba_mappoint_problem, abi.vba_mappoint_result, abi.MapPointResultBuf, False),
     "posegraph": ("vba_posegraph_optimize", abi.vba_posegraph_problem, abi.vba_posegraph_result, lambda p: abi.vba_posegraph_result(), True),
 }
 
@@ -443,6 +444,19 @@ class LocalBA:
         """vba_search_for_initialization on a list of abi.SearchInitProblem: list of abi.SearchInitResult"""
         packed = self.search_for_initialization_pack(problems)
         self.search_for_initialization_call(packed)
+        return [b.get() for b in packed[2]]
+
+    # map-point refresh (vba_mappoint_update): abi.MapPointProblem, one point list over one keyframe table each
+    def mappoint_update_pack(self, problems):
+        return self._small_pack("mappoint_update", problems)
+
+    def mappoint_update_call(self, packed):
+        self._small_call("mappoint_update", packed)
+
+    def mappoint_update(self, problems):
+        """vba_mappoint_update on a list of abi.MapPointProblem: list of abi.MapPointResult"""
+        packed = self.mappoint_update_pack(problems)
+        self.mappoint_update_call(packed)
         return [b.get() for b in packed[2]]
 
     # essential-graph optimisation (vba_posegraph_optimize): abi.PoseGraphProblem, independent Sim3 pose graphs.  The call updates

@@ -85,8 +85,8 @@ struct SideArena {
 };
 // vba_preintegrate (dev only), vba_pose_optimize, vba_sim3_optimize, vba_sim3_ransac, vba_triangulate, vba_two_view_init,
 // vba_search_triangulation, vba_fuse, vba_posegraph_optimize, vba_search_by_sim3, vba_search_by_projection, vba_search_by_bow,
-// vba_search_by_projection_kf, vba_search_for_initialization
-enum Side { SIDE_PREINT, SIDE_POSE, SIDE_SIM3, SIDE_RANSAC, SIDE_TRI, SIDE_TWO_VIEW, SIDE_SEARCH_TRI, SIDE_FUSE, SIDE_POSEGRAPH, SIDE_SEARCH_SIM3, SIDE_SEARCH_PROJ, SIDE_SEARCH_BOW, SIDE_SEARCH_PROJ_KF, SIDE_SEARCH_INIT, SIDE_N };
+// vba_search_by_projection_kf, vba_search_for_initialization, vba_mappoint_update
+enum Side { SIDE_PREINT, SIDE_POSE, SIDE_SIM3, SIDE_RANSAC, SIDE_TRI, SIDE_TWO_VIEW, SIDE_SEARCH_TRI, SIDE_FUSE, SIDE_POSEGRAPH, SIDE_SEARCH_SIM3, SIDE_SEARCH_PROJ, SIDE_SEARCH_BOW, SIDE_SEARCH_PROJ_KF, SIDE_SEARCH_INIT, SIDE_MAPPOINT, SIDE_N };
 
 // Growable array in pinned host memory with the few std::vector members the upload / download code uses.  The staging
 // arrays of a handle persist from call to call, so the H2D / D2H copies are true DMA transfers (no pageable bounce

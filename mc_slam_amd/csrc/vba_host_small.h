@@ -1,5 +1,5 @@
 // vba_host_small.h -- host side of the library, part 5: the small-problem entry points.  vba_preintegrate copies straight from and
-// to the caller's arrays.  The other thirteen are one driver, run_small, over the call object of their topic (PoseCall, Sim3Call, ...:
+// to the caller's arrays.  The other fourteen are one driver, run_small, over the call object of their topic (PoseCall, Sim3Call, ...:
 // plain C++, vba_host_<topic>.h), which knows what is refused, the arena, the packing, the kernel's argument and the write-back;
 // what an entry point adds here is the launch of its kernel.  No entry point shares its arena (Handle::side) with another.
 #pragma once
@@ -15,6 +15,7 @@
 #include "vba_host_search_proj_kf.h"
 #include "vba_host_search_bow.h"
 #include "vba_host_search_init.h"
+#include "vba_host_mappoint.h"
 #include "vba_host_posegraph.h"
 
 namespace {
@@ -193,6 +194,15 @@ int search_for_initialization(Handle* h, int32_t n_pairs, vba_search_init_proble
     return run_small(h, SIDE_SEARCH_INIT, "vba_search_for_initialization", C, n_pairs, in, out, [h, &C](const SiBatch& B, unsigned g) {
         VBA_LAUNCH(k_search_init, dim3(g), dim3(SI_NT), C.lds_bytes(), h->stream, B);
     });
+}
+
+// MapPoint::ComputeDistinctiveDescriptors and MapPoint::UpdateNormalAndDepth (src/MapPoint.cpp:336-413, :450-501) for a batch of
+// point lists: the host sorts the points of the whole call into the item table while it describes the call, a workgroup takes one
+// point of more than 256 observations or four smaller ones; the winner's descriptor is copied in the write-back
+int mappoint_update(Handle* h, int32_t n_problems, vba_mappoint_problem* const* in, vba_mappoint_result* const* out) {
+    vba_host::MapPointCall C;
+    return run_small(h, SIDE_MAPPOINT, "vba_mappoint_update", C, n_problems, in, out,
+                     [h](const MpBatch& B, unsigned g) { VBA_LAUNCH(k_mappoint_update, dim3(g), dim3(MP_NT), 0, h->stream, B); });
 }
 
 // what vba_debug_posegraph_system asks of a run: graph 0 stops after the solve of its first trial, and H, b, x come back

@@ -488,6 +488,32 @@ struct SiBatch {
     int* next;                   // [total queries] device only: the next claimer of the same keypoint, -1 at the end of a list
     int* cdist;                  // [total queries] device only: the distance of the query's claim as the last rebuild saw it
 };
+// vba_mappoint_update (vba_mappoint.h)
+#define VBA_MP_NT 256          // lanes of a workgroup: four wave items or one workgroup item
+#define VBA_MP_MAX_OBS 1024    // observations of a point: 1024 descriptors of 32 bytes are the 32 KB of LDS of a workgroup
+#define VBA_MP_WAVE_OBS 256    // a point of at most so many observations is one wave's item (8 KB of LDS)
+#define VBA_MP_ROWS 4          // rows a lane owns at most: VBA_MP_WAVE_OBS / 64 = VBA_MP_MAX_OBS / VBA_MP_NT
+struct alignas(16) MpItem {    // one point with device work, 80 bytes
+    long long desc0, obs0;     // its rows in the descriptor region; its entries in the observer region
+    int n_desc;                // N: descriptors of good keyframes, 0 without a descriptor part
+    int n_obs;                 // observations, bad keyframes counted, 0 without a normal part
+    int ref;                   // the reference keyframe's row in the centre region
+    int pad;
+    double pos[3];             // mWorldPos
+    double ref_scale, ref_top_scale;
+    double pad2;
+};
+static_assert(sizeof(MpItem) == 80, "scripts/mappoint_bench.py derives the copied bytes from this size");
+struct MpBatch {
+    const MpItem* item;          // [items] workgroup items first, then the wave items, four to a workgroup
+    const double* center;        // [total keyframes][3]
+    const int* obs;              // observers of the points with a normal part, as rows of center
+    const unsigned int* desc;    // [total N][8] the descriptors of good keyframes of the points with a descriptor part
+    int n_items, n_big;          // n_big: the workgroup items
+    int* best;                   // [items] (median << 16) | row, -1 without a descriptor part
+    double* nrm;                 // [items][5] normal, dist_max, dist_min
+    unsigned char* nstate;       // [items] 0 done, 3 the point lies in an observer's centre, 1 no normal part
+};
 // vba_posegraph_optimize (vba_posegraph.h)
 struct PgDesc {
     int nv, ne, nf, npair;

@@ -6,7 +6,7 @@
 //                 download / solve*, vba_batch_set_depth / submit* / poll / wait
 //   small problems  vba_host_small.h: one driver over the plain-C++ call object of each topic (vba_host_<topic>.h).  Tracking:
 //                 vba_preintegrate, vba_search_by_projection and vba_search_by_bow (the matchers in front of) vba_pose_optimize.  Initialisation: vba_search_for_initialization (the matcher in front of) vba_two_view_init.  Local mapping:
-//                 vba_search_triangulation (the matcher in front of) vba_triangulate, vba_fuse.  Loop closing: vba_search_by_bow, vba_sim3_ransac,
+//                 vba_search_triangulation (the matcher in front of) vba_triangulate, vba_fuse, vba_mappoint_update (what refreshes the points between them and the BA).  Loop closing: vba_search_by_bow, vba_sim3_ransac,
 //                 vba_search_by_sim3, vba_sim3_optimize, vba_search_by_projection_kf (the matcher behind it), vba_posegraph_optimize.
 //                 Relocalisation: vba_search_by_bow, vba_search_by_projection_kf between two vba_pose_optimize calls
 //   the rest      vba_host_hooks.h (vba_debug_*, hooks flavour), vba_host_threads, vba_set_profile / get_profile
@@ -33,6 +33,7 @@
 #include "vba_search_proj_kf.h"
 #include "vba_search_bow.h"
 #include "vba_search_init.h"
+#include "vba_mappoint.h"
 #include "vba_posegraph.h"
 #include "vba_structure.h"
 #include "vba_pcg.h"
@@ -228,6 +229,10 @@ int vba_search_by_bow(void* handle, int32_t n_pairs, vba_search_bow_problem* con
 int vba_search_for_initialization(void* handle, int32_t n_pairs, vba_search_init_problem* const* in, vba_search_init_result* const* out) {
     Handle* h = idle_handle(handle);
     return h ? search_for_initialization(h, n_pairs, in, out) : -1;
+}
+int vba_mappoint_update(void* handle, int32_t n_problems, vba_mappoint_problem* const* in, vba_mappoint_result* const* out) {
+    Handle* h = idle_handle(handle);
+    return h ? mappoint_update(h, n_problems, in, out) : -1;
 }
 int vba_posegraph_optimize(void* handle, int32_t n_graphs, vba_posegraph_problem* const* inout, vba_posegraph_result* const* out) {
     Handle* h = idle_handle(handle);

@@ -84,7 +84,7 @@ int create_new_map_points(KeyFrame* pKF, const std::vector<KeyFrame*>& vpNeighKF
             pMP->AddObservation(pKF2, idx2);
             pKF->AddMapPoint(pMP, idx1);
             pKF2->AddMapPoint(pMP, idx2);
-            pMP->UpdateNormalAndDepth();   // ComputeDistinctiveDescriptors / UpdateNormalAndDepth: bookkeeping of the map, out of scope
+            pMP->UpdateNormalAndDepth();   // a counter here (existing tests pin it); the batched form of the pair is UpdateMapPoints
             pMap->AddMapPoint(pMP);
             lpRecentAddedMapPoints.push_back(pMP);
             nnew++;

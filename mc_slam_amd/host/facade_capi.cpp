@@ -702,6 +702,35 @@ int fc_mp_fuse_state(void* m, long mp, long* out5) {
     out5[4] = (long)std::count(M->map.mspMapPoints.begin(), M->map.mspMapPoints.end(), p);
     return 0;
 }
+// ---- map-point refresh (UpdateMapPoints, the two LocalMapping loops; MapPointUpdate.cpp) ----
+// UpdateMapPoints(the points `ids`, what); an id of -1 is a NULL entry
+int fc_update_map_points(void* m, const long* mp_ids, int n, int what) { return UpdateMapPoints(point_list(reinterpret_cast<FcMap*>(m), mp_ids, n), what); }
+// LocalMapping::ProcessNewKeyFramePoints(kf, list): recent [cap] receives the ids the call appended to an empty mlpRecentAddedMapPoints,
+// in order (n_recent: how many)
+int fc_process_new_keyframe_points(void* m, long kf, long* recent, int cap, int* n_recent) {
+    FcMap* M = reinterpret_cast<FcMap*>(m);
+    std::list<MapPoint*> l;
+    const int r = M->lm.ProcessNewKeyFramePoints(M->kfs.at(kf).get(), l);
+    *n_recent = (int)l.size();
+    int k = 0;
+    for (MapPoint* p : l)
+        if (k < cap) recent[k++] = (long)p->mnId;
+    return r;
+}
+int fc_update_current_keyframe_points(void* m, long kf) {
+    FcMap* M = reinterpret_cast<FcMap*>(m);
+    return M->lm.UpdateCurrentKeyFramePoints(M->kfs.at(kf).get());
+}
+// what the refresh writes and what it must leave alone: mNormalVector, (mfMinDistance, mfMaxDistance), mDescriptor; counters: the
+// UpdateNormalAndDepth stub's, the ComputeDistinctiveDescriptors stub's, the size of mObservations, nObs
+int fc_mp_attributes(void* m, long mp, float* normal3, float* minmax2, unsigned char* desc32, int* counters4) {
+    MapPoint* p = reinterpret_cast<FcMap*>(m)->mps.at(mp).get();
+    std::memcpy(normal3, p->mNormalVector, 12);
+    minmax2[0] = p->mfMinDistance; minmax2[1] = p->mfMaxDistance;
+    std::memcpy(desc32, p->mDescriptor, 32);
+    counters4[0] = p->nNormalUpdates; counters4[1] = p->nDescriptorUpdates; counters4[2] = (int)p->mObservations.size(); counters4[3] = p->nObs;
+    return 0;
+}
 // ---- projection matching for tracking (both ORBmatcher::SearchByProjection overloads, the Tracking slice) ----
 // what the tracking matchers read of a frame beside the keypoints fc_frame_add_obs gave it: the id, N x 32 descriptor bytes, the
 // keypoint angles, the image bounds and the grid, which is assigned here; eight levels of factor 1.2; mvKeys = mvKeysUn; the pose

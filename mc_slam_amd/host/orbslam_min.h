@@ -152,6 +152,14 @@ public:
     // into pKF, one vba_fuse call per Fuse call, in order (LocalMapping.cpp).  Returns the fused points of all calls, -1 when the
     // backend failed (the Fuse calls in front of the failing one stay applied)
     int SearchInNeighbors(KeyFrame* pKF, const std::vector<KeyFrame*>& vpTargetKFs);
+    // src/LocalMapping.cpp:1144-1171, the map-point loop of ProcessNewKeyFrame for pKF (= mpCurrentKeyFrame): a good point that pKF does
+    // not observe yet gets its AddObservation, in keypoint order, a point already in the keyframe goes to the recent list; then the
+    // UpdateNormalAndDepth / ComputeDistinctiveDescriptors pairs of the new observers as ONE vba_mappoint_update call
+    // (MapPointUpdate.cpp).  Returns the points refreshed, -1 when the backend failed (the observations stay added)
+    int ProcessNewKeyFramePoints(KeyFrame* pKF, std::list<MapPoint*>& lpRecentAddedMapPoints);
+    // src/LocalMapping.cpp:1635-1650, the end of SearchInNeighbors: both refreshes for every good map point of pKF, ONE call.  Returns
+    // the points refreshed, -1 when the backend failed
+    int UpdateCurrentKeyFramePoints(KeyFrame* pKF);
 };
 
 class KeyFrame {
@@ -415,6 +423,13 @@ public:
         }
     }
 };
+
+// MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cpp:336-413; bit VBA_MAPPOINT_DESC = 1 of `what`) and / or
+// MapPoint::UpdateNormalAndDepth (:450-501; bit VBA_MAPPOINT_NORMAL = 2) for every point of the list that is neither NULL nor bad
+// (:344, :458), as ONE vba_mappoint_update call (MapPointUpdate.cpp): mDescriptor, mNormalVector, mfMaxDistance and mfMinDistance are
+// written as float32 where the reference writes them.  The counters of the per-point stubs above are not touched.  Returns the points
+// handed to the backend, -1 when the backend failed or an input cannot be gathered (a message on std::cerr; nothing is written)
+int UpdateMapPoints(const std::vector<MapPoint*>& vpMPs, int what);
 
 inline bool cmpKeyFrameId::operator()(const KeyFrame* a, const KeyFrame* b) const { return a->mnId < b->mnId; }
 inline Quaterniond MatrixToQuat(const Matrix3d& m) {   // Eigen::Quaterniond(Matrix3d)
